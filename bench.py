@@ -8,9 +8,12 @@ B=1024, T=10000, d=6, m=1 (per GPU; weak scaling: every rank owns its own 1024 s
 collective is one RCCL all-reduce of the scalar log-likelihood).
 
 A "step" of the driver contract = one full ``log_likelihood()`` evaluation over the resident batch.
-Prints ONE JSON line on rank 0 with `roofline` (HBM roofline of the dominant kernel, timed live with
-HIP events on the launch stream) and `cpu_baseline` (the C restatement of the reference algorithm,
-oracle/c/mf_oracle.c, timed on the host cores on a bounded sample of the same workload).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps and prints the headline only.
+With --full the line also carries `roofline` (HBM roofline of the dominant kernel, timed live with HIP events on the
+launch stream), `cpu_baseline` (the C restatement of the reference algorithm, oracle/c/mf_oracle.c, timed on the host
+cores on a bounded sample of the same workload), `smoother_and_backward` and `other_configs` (the other BASELINE configs).
+--dump-outputs DIR writes what the last timed step returned (the scalar log-likelihood) as DIR/<name>.npy; the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes
@@ -39,8 +42,14 @@ def parse():
                     help="target: the headline (KalmanFilter.log_likelihood, B=1024/GPU, T=10000, d=6); config4: BASELINE config 4's "
                          "per-GPU shard (512 series, T=1000, 3 x Matern-5/2 with 3 outputs, d=9) - log-likelihood + KL(q || prior), "
                          "one scalar all-reduce (sharded_elbo)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the brief timing of BASELINE configs 2-5")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the dominant kernel's roofline, the CPU baseline, the smoother / backward at the "
+                         "headline shape and the brief timing of BASELINE configs 2-5 (a plain run does none of these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true",
+                    help="with --full: skip the smoother / backward and the brief timing of BASELINE configs 2-5")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the baseline sample")
     ap.add_argument("--dry-launch", action="store_true",
                     help="exercise the multi-rank launch only: ranks join a gloo group, shard the batch, all-reduce a probe and "
@@ -563,6 +572,46 @@ def smoother_and_backward(kf, inputs, bsz, tn, d, m, esz):
     return out
 
 
+def headline_roofline(args, bsz, tn, d, m, esz, kern_avg_ms):
+    """HBM roofline of the dominant kernel at the headline shape (--full): its duration by the HIP events around it."""
+    from markovflow_amd import synthetic
+
+    bytes_per_step = synthetic.loglik_bytes_per_step(d, m, esz)
+    units_per_launch = bsz * tn
+    achieved_gbs = units_per_launch * bytes_per_step / (kern_avg_ms * 1e-3) / 1e9
+    # HBM-side bytes per launch measured with rocprofv3 PMC passes (cannot be collected from inside this
+    # process): quoted from profiles/hbm_traffic.json when it holds this exact workload, else null
+    traffic, traffic_src = None, None
+    try:
+        with open(os.path.join(ROOT, "profiles", "hbm_traffic.json")) as fh:
+            entry = json.load(fh).get(f"kf_loglik B={bsz} T={tn} d={d} m={m} {args.dtype}")
+        # only when the counters were collected on exactly THESE library sources (sha256 over markovflow_amd/csrc + the header,
+        # scripts/csrc_hash.py): a stale figure is worse than none
+        from scripts.csrc_hash import csrc_hash
+
+        if entry and args.chunks == 0 and entry.get("csrc_sha256") == csrc_hash(ROOT):
+            traffic, traffic_src = entry["traffic_bytes"], entry["source"]
+    except OSError:
+        pass
+    return {
+        "bound": "hbm", "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+        "kernel": "mf::kf_chunk_lds_kernel (level 0 of the partitioned elimination)", "kernel_ms": kern_avg_ms,
+        "algorithmic_bytes_per_launch": units_per_launch * bytes_per_step,
+    }
+
+
+def dump_outputs(out_dir, arrays) -> None:
+    """What the last timed step returned, one ``<name>.npy`` per array in its own float dtype (float32 / float64)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, tensor in arrays.items():
+        arr = tensor.detach().cpu().numpy()
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+
+
 def config4_rank(args, dev, dist, rank, world, dtype) -> int:
     """BASELINE config 4's per-GPU shard as the timed step (so that a scaling run measures it too): 512 series x 1000 points,
     IndependentMultiOutput(3 x Matern-5/2) with 3 outputs (d = 9); step = log-likelihood of the shard + KL(q || prior) of the
@@ -602,6 +651,8 @@ def config4_rank(args, dev, dist, rank, world, dtype) -> int:
         ones = torch.ones(1, dtype=torch.float64, device=dev)
         dist.all_reduce(ones, op=dist.ReduceOp.SUM)
         ranks_seen = int(ones.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"elbo": val})
     if rank == 0:
         print(json.dumps({
             "metric": "config 4 shard: log-lik + KL steps/sec (BxT) at d=9, m=3", "value": world * bsz * tn * args.steps / elapsed,
@@ -744,8 +795,9 @@ def main():
     inputs = synthetic.make_ssm(bsz, tn, (5, 5), dtype=dtype, device=dev, seed=synthetic.DEFAULT_SEED + rank)
     kf = synthetic.kalman_filter_from(inputs)
     kf._chunks = args.chunks
-    ev = HipEvents()
-    kf._prof_events = (ev.start, ev.stop)
+    if args.full:
+        ev = HipEvents()
+        kf._prof_events = (ev.start, ev.stop)
 
     def step():
         # this rank's series + the path's only exchange: one all-reduce of the scalar (a no-op at N=1)
@@ -770,12 +822,15 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
-    # dominant-kernel duration: separate short loop so that reading the events does not perturb the timed region
-    kernel_ms = []
-    for _ in range(min(args.steps, 10)):
-        step()
-        kernel_ms.append(ev.elapsed_ms())
-    kern_avg_ms = sum(kernel_ms) / len(kernel_ms)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"log_likelihood": ll})
+    if args.full:
+        # dominant-kernel duration: separate short loop so that reading the events does not perturb the timed region
+        kernel_ms = []
+        for _ in range(min(args.steps, 10)):
+            step()
+            kernel_ms.append(ev.elapsed_ms())
+        kern_avg_ms = sum(kernel_ms) / len(kernel_ms)
 
     if dist is not None:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -788,25 +843,7 @@ def main():
         ranks_seen = 1
 
     esz = 8 if dtype == torch.float64 else 4
-    bytes_per_step = synthetic.loglik_bytes_per_step(d, m, esz)
-    units_per_launch = bsz * tn
-    achieved_gbs = units_per_launch * bytes_per_step / (kern_avg_ms * 1e-3) / 1e9
     value = world * bsz * tn * args.steps / elapsed
-
-    # HBM-side bytes per launch measured with rocprofv3 PMC passes (cannot be collected from inside this
-    # process): quoted from profiles/hbm_traffic.json when it holds this exact workload, else null
-    traffic, traffic_src = None, None
-    try:
-        with open(os.path.join(ROOT, "profiles", "hbm_traffic.json")) as fh:
-            entry = json.load(fh).get(f"kf_loglik B={bsz} T={tn} d={d} m={m} {args.dtype}")
-        # only when the counters were collected on exactly THESE library sources (sha256 over markovflow_amd/csrc + the header,
-        # scripts/csrc_hash.py): a stale figure is worse than none
-        from scripts.csrc_hash import csrc_hash
-
-        if entry and args.chunks == 0 and entry.get("csrc_sha256") == csrc_hash(ROOT):
-            traffic, traffic_src = entry["traffic_bytes"], entry["source"]
-    except OSError:
-        pass
 
     result = {
         "metric": "Kalman log-lik steps/sec (BxT) at d=6",
@@ -829,15 +866,11 @@ def main():
             "series_per_gpu": bsz, "time_points": tn, "state_dim": d, "output_dim": m,
             "parallelism": f"batch-sharded x{world}, one scalar RCCL all-reduce",
         },
-        "roofline": {
-            "bound": "hbm", "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-            "kernel": "mf::kf_chunk_lds_kernel (level 0 of the partitioned elimination)", "kernel_ms": kern_avg_ms,
-            "algorithmic_bytes_per_launch": units_per_launch * bytes_per_step,
-        },
         "log_likelihood": float(ll.item()),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        result["roofline"] = headline_roofline(args, bsz, tn, d, m, esz, kern_avg_ms)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         base, cpu_out = cpu_baseline(inputs, args.cpu_seconds)
         result["cpu_baseline"] = base
         # the checker, not the thing measured: GPU per-series values agree with the CPU port on the sample
@@ -847,7 +880,7 @@ def main():
         cst = -0.5 * np.log(2 * np.pi) * tn + 0.5 * tn * np.log(1.0 / 0.1)
         rel = float(np.max(np.abs(per + cst - cpu_out) / np.abs(cpu_out)))
         result["cpu_baseline"]["max_rel_diff_vs_gpu"] = rel
-    if rank == 0 and world == 1 and not args.no_other_configs:
+    if args.full and rank == 0 and world == 1 and not args.no_other_configs:
         try:
             result["smoother_and_backward"] = smoother_and_backward(kf, inputs, bsz, tn, d, m, esz)
         except Exception as exc:

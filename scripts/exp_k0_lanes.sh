@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$R/gpurun_out/${1:-exp_lanes}; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for LANES in 65536 49152 32768 16384; do
   CH=$((LANES / 1024))
-  python3 $R/bench.py --steps 20 --warmup 3 --chunks $CH --no-cpu-baseline --no-other-configs > $OUT/bench_$LANES.json 2> $OUT/bench_$LANES.err
+  python3 $R/bench.py --full --steps 20 --warmup 3 --chunks $CH --no-cpu-baseline --no-other-configs > $OUT/bench_$LANES.json 2> $OUT/bench_$LANES.err
   python3 - $OUT/bench_$LANES.json $LANES <<'PY'
 import json, sys
 j = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

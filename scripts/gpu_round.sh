@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd $R
 python3 -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/pytest_gpu.log
 tail -3 $OUT/pytest_gpu.log
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json
 cd /tmp && export TMPDIR=/tmp
 BENCH="python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs"
 rm -rf /tmp/prof_stats

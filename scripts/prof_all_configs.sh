@@ -5,7 +5,7 @@
 # usage: bash scripts/prof_all_configs.sh <tag>  ->  gpurun_out/<tag>_all_configs_kernel_stats.csv
 TAG=${1:-r05}; R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/pall; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pall -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline > /dev/null 2>&1
+rm -rf $TMPDIR/pall; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/pall -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > /dev/null 2>&1
 f=$(find /tmp/pall -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && { head -1 $f; grep "mf::" $f; } > $R/gpurun_out/${TAG}_all_configs_kernel_stats.csv
 wc -l $R/gpurun_out/${TAG}_all_configs_kernel_stats.csv; head -12 $R/gpurun_out/${TAG}_all_configs_kernel_stats.csv | cut -c1-170
