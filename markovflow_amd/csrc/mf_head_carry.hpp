@@ -1,0 +1,150 @@
+// Head carry of a streamed row-major tensor whose rows do not start on 128-B lines (mf_kf_lds.hpp, chol Q).
+//
+// A row of ROWB bytes is fetched as the UNIT-byte units that Keep flags.  When a row starts inside a line, that line was already
+// touched by the fetch of the previous row (whose last unit ends where this row starts).  If ALL kept units of the row that lie in
+// this first line belong to a small fixed set - the "tail units", at most MAXT of them - the previous row's fetch brings them
+// along (as extra units past its own end, out of a line it moves anyway), the consumer keeps their values in registers across
+// the step boundary, and the row's own fetch leaves the first line alone: one line less on the fabric for that row.
+//
+// Everything here is integer arithmetic on BYTE ADDRESSES modulo 128 (base offsets, batch slices and chunk starts all shift the
+// phase, differently for every lane), shared by the two sides that have to agree:
+//   * the consumer: lane r, reading row r of the LDS image at the top of a step, decides per tail unit "carried or in the image";
+//   * the producer: the DMA lane that fetches a unit of some OTHER row decides "fetch or leave out" for head and tail units.
+// Both derive their decision from carried(address of the row whose head is in question, t): they agree by construction.
+// Plain constexpr functions: used by the kernel and, compiled for the host, by tests/host_sim/head_carry_sim.cpp.
+#pragma once
+
+namespace mf {
+
+template <int ROWB, int UNIT, typename Keep> struct HeadCarry {
+    static constexpr int LINE = 128;
+    static constexpr int MAXT = 2;                                  // tail units per row (each costs 64 x UNIT bytes of LDS)
+    static constexpr int UG = (ROWB + UNIT - 1) / UNIT;             // units per row in global memory
+    static constexpr int STEP = ROWB % LINE;                        // the phase advances by this much from one row to the next
+    // the t-th candidate: kept units, in order, that can lie wholly inside a first line shared with the previous row
+    static constexpr int cand(int t) {
+        int n = 0;
+        for (int u = 0; u < UG; ++u)
+            if (Keep::keep(u, UNIT) && (u + 1) * UNIT <= LINE - 4) { if (n == t) return u; ++n; }
+        return -1;
+    }
+    static constexpr int count_cand() { int n = 0; while (n < MAXT && cand(n) >= 0) ++n; return n; }
+    static constexpr int tail_index(int u) { for (int t = 0; t < count_cand(); ++t) if (cand(t) == u) return t; return -1; }
+    // Tail units (bit t = unit cand(t)) that a row at byte address r (mod 128) takes from the previous row's fetch.  Empty unless
+    // every kept unit that touches the row's first line is a tail unit and lies wholly inside that line: otherwise the row's own
+    // fetch moves the line anyway and carrying buys nothing.
+    static constexpr unsigned carried_units(int r) {
+        r &= LINE - 1;
+        if (r == 0) return 0u;                                      // the row starts a line of its own
+        const int room = LINE - r;                                  // bytes of the row inside its first line
+        unsigned m = 0u;
+        for (int u = 0; u < UG; ++u) {
+            if (!Keep::keep(u, UNIT) || u * UNIT >= room) continue;
+            const int t = tail_index(u);
+            if (t < 0 || (u + 1) * UNIT > room) return 0u;
+            m |= 1u << t;
+        }
+        return m;
+    }
+    // the same as a 32-entry bit table over (r / 4) per tail unit
+    static constexpr unsigned table(int t) {
+        unsigned m = 0u;
+        for (int g = 0; g < 32; ++g) if ((carried_units(4 * g) >> t) & 1u) m |= 1u << g;
+        return m;
+    }
+    static constexpr unsigned TAB0 = table(0), TAB1 = table(1);
+    // the decisions repeat with this period in the step index (a power of two, at most 32 for rows of whole dwords)
+    static constexpr int period() { int p = 1, r = STEP; while (r % LINE) { r += STEP; ++p; } return p; }
+    static constexpr int PERIOD = (ROWB % 4 == 0) ? period() : 0;
+    // Usable: rows of whole dwords that span at least a line (the line before a row then belongs to the previous row alone) but
+    // not a whole number of lines (such rows share no line unless the base is misaligned), whose last unit is fetched (so the
+    // previous row's fetch does touch the shared line), and some phase that carries at all.
+    static constexpr bool USABLE = ROWB % 4 == 0 && ROWB >= LINE && STEP != 0 && Keep::keep(UG - 1, UNIT) && (TAB0 | TAB1) != 0u;
+    static constexpr int NT = USABLE ? count_cand() : 0;
+    static constexpr int tail_unit(int t) { return cand(t); }
+
+    // THE decision: is tail unit t of the row at byte address `addr` (its low 7 bits matter) carried from the previous row's fetch?
+    static constexpr bool carried(unsigned addr, int t) { return (((t == 0 ? TAB0 : TAB1) >> ((addr & (LINE - 1)) >> 2)) & 1u) != 0u; }
+
+    // Consumer schedule of a lane whose row of step 0 is at addr0: bit (t PERIOD + j % PERIOD) = tail unit t of step j's row is
+    // carried (j >= 1; step 0 of a chunk is fetched whole).
+    static constexpr unsigned consumer_bits(unsigned addr0) {
+        unsigned m = 0u;
+        for (int t = 0; t < NT; ++t)
+            for (int p = 0; p < PERIOD; ++p) if (carried(addr0 + (unsigned)(p * STEP), t)) m |= 1u << (t * PERIOD + p);
+        return m;
+    }
+    // Producer schedule of a DMA lane that moves one unit of the row whose step-0 address is addr0: bit (jn % PERIOD) = fetch the
+    // unit when the rows of step jn >= 1 are fetched.  kind 0: an ordinary unit; 1 + t: the row's own (head) unit tail_unit(t);
+    // 1 + MAXT + t: the NEXT row's unit tail_unit(t), fetched into this row's tail slot t.
+    static constexpr unsigned producer_bits(unsigned addr0, int kind) {
+        unsigned m = 0u;
+        for (int p = 0; p < PERIOD; ++p) {
+            bool f = true;
+            if (kind >= 1 + MAXT) f = carried(addr0 + (unsigned)((p + 1) * STEP), kind - 1 - MAXT);
+            else if (kind >= 1) f = !carried(addr0 + (unsigned)(p * STEP), kind - 1);
+            if (f) m |= 1u << p;
+        }
+        return m;
+    }
+};
+
+// One streamed array: ROWB bytes per (row, step), of which only the units flagged by Keep are fetched.
+// UNIT is the DMA granule (16 when ROWB is a multiple of 16, else 4).  The LDS image of a stream is
+// row-major [64 rows][U units], filled by U wave-instructions: instruction i, lane l carries unit
+// p = 64 i + l, i.e. (row, unit) = divmod(p, U) - consecutive lanes read consecutive 16-B pieces of a row.
+// (Rows are NOT padded to an odd stride: the per-lane row reads then take a 2..4-way LDS bank conflict, but
+// the kernel reads ~600 B per lane per step, nowhere near LDS bandwidth, while padding would push the
+// fp64 d=6 image over a quarter of the CU's 160 KB and cost a wave of occupancy.)
+// TAIL: the row's image ends with tail slots that hold the NEXT row's head units (mf_head_carry.hpp; chol Q only).
+template <int ROWB, typename Keep, bool TAIL = false> struct Stream {
+    // 16-B granules whenever a row holds at least one; a row that is not a whole number of them (odd d) is fetched up
+    // to the next 16-B boundary: the extra 4..12 bytes belong to the next row (or lie past the end of the tensor, where
+    // the buffer range check returns zeros) and are never read.  Rows then start 4- or 8-byte aligned, which the DMA
+    // (dword-aligned dwordx4) accepts.
+    static constexpr int UNIT = (ROWB >= 16) ? 16 : 4;
+    static constexpr int UG = (ROWB + UNIT - 1) / UNIT;          // units per row in global memory
+    static constexpr int count_kept() { int n = 0; for (int u = 0; u < UG; ++u) n += Keep::keep(u, UNIT) ? 1 : 0; return n; }
+    using HC = HeadCarry<ROWB, UNIT, Keep>;
+    static constexpr int UB = count_kept();                       // the row's own units kept in LDS
+    static constexpr int NT = TAIL ? HC::NT : 0;                  // tail slots: the next row's units HC::tail_unit(t)
+    static constexpr int U = UB + NT;                             // units per row of the LDS image
+    static constexpr int NI = U;                                  // DMA wave-instructions per step
+    static constexpr int LDS_BYTES = 64 * U * UNIT;
+    static constexpr bool ALL = (UB == UG) && NT == 0;
+    // global unit index of the c-th kept unit
+    static constexpr int global_unit(int c) {
+        int n = 0;
+        for (int u = 0; u < UG; ++u) if (Keep::keep(u, UNIT)) { if (n == c) return u; ++n; }
+        return -1;
+    }
+    // global byte offset (from the row's start) of the c-th unit of the image: a tail slot reads past the row's end
+    static constexpr int global_offset(int c) { return c < UB ? global_unit(c) * UNIT : ROWB + HC::tail_unit(c - UB) * UNIT; }
+    // producer kind (HC::producer_bits) of the c-th unit of the image
+    static constexpr int unit_kind(int c) {
+        if (c >= UB) return 1 + HC::MAXT + (c - UB);
+        for (int t = 0; t < NT; ++t) if (global_unit(c) == HC::tail_unit(t)) return 1 + t;
+        return 0;
+    }
+    // compact index of global unit u (must be kept)
+    static constexpr int compact_unit(int gu) {
+        int n = 0;
+        for (int u = 0; u < gu; ++u) n += Keep::keep(u, UNIT) ? 1 : 0;
+        return n;
+    }
+};
+
+struct KeepAll { static constexpr bool keep(int, int) { return true; } };
+// keep the units of a row-major D x D matrix (element size S) that contain an entry of the lower triangle
+template <int D, int S> struct KeepLower {
+    static constexpr bool keep(int u, int unit) {
+        const int lo = u * unit, hi = lo + unit;                 // byte range of the unit
+        for (int i = 0; i < D; ++i) {
+            const int a = (i * D) * S, b = (i * D + i + 1) * S;   // bytes of row i's lower part
+            if (a < hi && lo < b) return true;
+        }
+        return false;
+    }
+};
+
+}  // namespace mf

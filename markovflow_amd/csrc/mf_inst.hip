@@ -174,7 +174,7 @@ int reduce_levels_row(RedSys<T> cur, long B, char* p, T add_const, T* out, int* 
 // The LDS-DMA streaming kernel (mf_kf_lds.hpp) covers: up to 4 outputs with a shared observation precision,
 // or one output with per-step precisions (sites); matrix rows that are a whole number of 16-B units; 16-B aligned
 // tensors; at least one transition.  Everything else takes kf_chunk_kernel (direct loads).
-template <typename T, int M, bool RSTEP> constexpr bool lds_supported() { return KfLdsCfg<T, D, M, RSTEP>::SUPPORTED; }
+template <typename T, int M, bool RSTEP> constexpr bool lds_supported() { return KfChunkCfg<T, D, M, RSTEP>::SUPPORTED; }
 template <typename T> bool use_lds_kernel(long Tn, int m, int rinv_per_step) {
     static const bool force_direct = [] {
         const char* e = mf_knob("MF_KF_IMPL");
@@ -194,10 +194,10 @@ template <typename T> bool use_lds_kernel(long Tn, int m, int rinv_per_step) {
 template <typename T> long lds_target_lanes(int m, int rinv_per_step) {
     auto waves = [](int lds_bytes) { const int w = (160 * 1024) / lds_bytes; return w > 4 ? 4 : (w < 1 ? 1 : w); };
     int w = 4;
-    if (rinv_per_step) w = waves(KfLdsCfg<T, D, 1, true>::LDS_TOTAL);
-    else if (m == 2) w = waves(KfLdsCfg<T, D, 2, false>::LDS_TOTAL);
-    else if (m == 3) w = waves(KfLdsCfg<T, D, 3, false>::LDS_TOTAL);
-    else if (m == 4) w = waves(KfLdsCfg<T, D, 4, false>::LDS_TOTAL);
+    if (rinv_per_step) w = waves(KfChunkCfg<T, D, 1, true>::LDS_TOTAL);
+    else if (m == 2) w = waves(KfChunkCfg<T, D, 2, false>::LDS_TOTAL);
+    else if (m == 3) w = waves(KfChunkCfg<T, D, 3, false>::LDS_TOTAL);
+    else if (m == 4) w = waves(KfChunkCfg<T, D, 4, false>::LDS_TOTAL);
     long lanes = 256L * 64 * w;
     // Small blocks: every lane keeps a few partially used 128-B lines alive between two steps, and with one wave on every
     // SIMD (65 536 lanes x 5 streams x 128 B = 42 MB) they no longer fit the 32 MB of L2 - each line is then fetched twice.
@@ -369,8 +369,8 @@ int kf_loglik(long B, long Tn, int m, const T* mu0, const T* cholP0, const T* A,
         auto launch = [&](auto mtag, auto rtag) {
             constexpr int M = decltype(mtag)::value;
             constexpr bool RS = decltype(rtag)::value;
-            if constexpr (KfLdsCfg<T, D, M, RS>::SUPPORTED) {
-                constexpr int lds = KfLdsCfg<T, D, M, RS>::LDS_TOTAL;
+            if constexpr (KfChunkCfg<T, D, M, RS>::SUPPORTED) {
+                constexpr int lds = KfChunkCfg<T, D, M, RS>::LDS_TOTAL;
                 if (P > 1) MF_LANE_LAUNCH((kf_chunk_lds_kernel<T, D, M, true, RS>), grid, block, lds, st, a, L, lvl0);
                 else MF_LANE_LAUNCH((kf_chunk_lds_kernel<T, D, M, false, RS>), grid, block, lds, st, a, L, lvl0);
             }

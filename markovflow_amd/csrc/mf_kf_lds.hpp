@@ -22,6 +22,8 @@
 // chunk leaves behind is the block its last transition leads to.
 #pragma once
 #include "mf_kernels.hpp"
+#include "mf_head_carry.hpp"
+#include <type_traits>
 #ifndef MF_PUMPMASK
 #define MF_PUMPMASK 63   // bit k: DMA batch k of the next step is issued between arithmetic phases (else up front)
 #endif
@@ -97,54 +99,14 @@ template <int N> MF_DEV void dma_b32_group(mf_v4i srd, unsigned lds_addr, const 
                      : "=&s"(keep) : "s"(srd), "s"(lds_addr), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]) : "memory", "scc");
 }
 
-// One streamed array: ROWB bytes per (row, step), of which only the units flagged by Keep are fetched.
-// UNIT is the DMA granule (16 when ROWB is a multiple of 16, else 4).  The LDS image of a stream is
-// row-major [64 rows][U units], filled by U wave-instructions: instruction i, lane l carries unit
-// p = 64 i + l, i.e. (row, unit) = divmod(p, U) - consecutive lanes read consecutive 16-B pieces of a row.
-// (Rows are NOT padded to an odd stride: the per-lane row reads then take a 2..4-way LDS bank conflict, but
-// the kernel reads ~600 B per lane per step, nowhere near LDS bandwidth, while padding would push the
-// fp64 d=6 image over a quarter of the CU's 160 KB and cost a wave of occupancy.)
-template <int ROWB, typename Keep> struct Stream {
-    // 16-B granules whenever a row holds at least one; a row that is not a whole number of them (odd d) is fetched up
-    // to the next 16-B boundary: the extra 4..12 bytes belong to the next row (or lie past the end of the tensor, where
-    // the buffer range check returns zeros) and are never read.  Rows then start 4- or 8-byte aligned, which the DMA
-    // (dword-aligned dwordx4) accepts.
-    static constexpr int UNIT = (ROWB >= 16) ? 16 : 4;
-    static constexpr int UG = (ROWB + UNIT - 1) / UNIT;          // units per row in global memory
-    static constexpr int count_kept() { int n = 0; for (int u = 0; u < UG; ++u) n += Keep::keep(u, UNIT) ? 1 : 0; return n; }
-    static constexpr int U = count_kept();                        // units per row kept in LDS
-    static constexpr int NI = U;                                  // DMA wave-instructions per step
-    static constexpr int LDS_BYTES = 64 * U * UNIT;
-    static constexpr bool ALL = (U == UG);
-    // global unit index of the c-th kept unit
-    static constexpr int global_unit(int c) {
-        int n = 0;
-        for (int u = 0; u < UG; ++u) if (Keep::keep(u, UNIT)) { if (n == c) return u; ++n; }
-        return -1;
-    }
-    // compact index of global unit u (must be kept)
-    static constexpr int compact_unit(int gu) {
-        int n = 0;
-        for (int u = 0; u < gu; ++u) n += Keep::keep(u, UNIT) ? 1 : 0;
-        return n;
-    }
-};
-
-struct KeepAll { static constexpr bool keep(int, int) { return true; } };
-// keep the units of a row-major D x D matrix (element size S) that contain an entry of the lower triangle
-template <int D, int S> struct KeepLower {
-    static constexpr bool keep(int u, int unit) {
-        const int lo = u * unit, hi = lo + unit;                 // byte range of the unit
-        for (int i = 0; i < D; ++i) {
-            const int a = (i * D) * S, b = (i * D + i + 1) * S;   // bytes of row i's lower part
-            if (a < hi && lo < b) return true;
-        }
-        return false;
-    }
-};
+// (Stream, KeepAll, KeepLower: the layout of a streamed array and of its LDS image, in mf_head_carry.hpp.)
 
 constexpr unsigned MF_DMA_INVALID = 0xF0000000u;   // row offset of an invalid row: lands out of range
 constexpr unsigned long long MF_DMA_MAXREC = 0xE0000000ull;
+
+// tail slots and schedule period of a stream type (0 / 1 for the types that know nothing of tails)
+template <typename St, typename = void> struct StreamTail { static constexpr int NT = 0, PERIOD = 1; };
+template <typename St> struct StreamTail<St, std::enable_if_t<(St::NT > 0)>> { static constexpr int NT = St::NT, PERIOD = St::HC::PERIOD; };
 
 // DMA source addressing of one stream.  The per-row byte offsets (relative to the wave's descriptor
 // base) live in a 64-entry LDS table; each lane derives its (row, unit) for instruction i from two
@@ -152,11 +114,19 @@ constexpr unsigned long long MF_DMA_MAXREC = 0xE0000000ull;
 // registers (a register table per instruction was spilled to scratch, and every scratch reload waits
 // `vmcnt(0)`, i.e. for every DMA in flight).
 template <typename St> struct DmaStream {
+    using TL = StreamTail<St>;
     unsigned vo[St::NI];           // this lane's source byte offset for DMA instruction i (registers / AGPRs)
+    // head carry (streams with tail slots): PB bits per instruction, bit (jn % PB) = this lane's unit is fetched with the rows of
+    // step jn >= 1 (HeadCarry::producer_bits), packed in instruction order
+    static constexpr int PB = TL::PERIOD;
+    static constexpr int FW = TL::NT > 0 ? (St::NI * PB + 31) / 32 : 1;
+    unsigned fm[FW];
     // rel_tab: LDS byte address of this stream's row-offset table; gtab: LDS byte address of the
     // compact-unit -> global byte offset table (only read when the stream drops units)
-    MF_DEV void init(const char* smem, int lane, int rel_tab, int gtab) {
+    // base_lo: low 32 bits of the address the row offsets are relative to (streams with tail slots only: the phase of a row)
+    MF_DEV void init(const char* smem, int lane, int rel_tab, int gtab, unsigned base_lo = 0u) {
         const int q0 = lane / St::U, c0 = lane - q0 * St::U;
+        if constexpr (TL::NT > 0) { MF_UNROLL for (int w = 0; w < FW; ++w) fm[w] = 0u; }
         MF_UNROLL for (int i = 0; i < St::NI; ++i) {
             const int a = (64 * i) / St::U, b = (64 * i) % St::U;
             int cu = c0 + b;
@@ -168,6 +138,15 @@ template <typename St> struct DmaStream {
             if (St::ALL) off = (unsigned)cu * St::UNIT;
             else off = *reinterpret_cast<const unsigned*>(smem + gtab + cu * 4);
             vo[i] = rel + off;
+            if constexpr (TL::NT > 0) {
+                static_assert(PB < 32 && 32 % PB == 0, "an instruction's schedule bits do not straddle two words");
+                int kind = 0;
+                MF_UNROLL for (int cc = 0; cc < St::U; ++cc) if (St::unit_kind(cc) != 0 && cu == cc) kind = St::unit_kind(cc);
+                unsigned bits = (1u << PB) - 1u;
+                MF_UNROLL for (int kk = 1; kk <= 2 * St::HC::MAXT; ++kk)
+                    if (kind == kk) bits = St::HC::producer_bits(base_lo + rel, kk);
+                fm[(i * PB) / 32] |= bits << ((i * PB) % 32);
+            }
 #ifdef MF_EXPERIMENT
             // ablation "what would a line ring buy" (MF_KF_DEBUG bit 3): bits 24..28 carry the unit's index in its row, bits
             // 29..30 the 32-byte phase of the row's first step (valid offsets stay below 2^24)
@@ -189,8 +168,10 @@ template <typename St> struct DmaStream {
         return carried ? MF_DMA_INVALID : off;
     }
 #endif
-    // issue DMA instructions [i0, i1) of this stream, up to four per asm statement
-    template <int I0, int I1> MF_DEV void issue(mf_v4i srd, unsigned lds_base) const {
+    // issue DMA instructions [i0, i1) of this stream, up to four per asm statement.  SCHED (streams with tail slots, every fetch
+    // but a chunk's first): phase = jn % PB of the step jn being fetched; a unit the schedule leaves out gets the out-of-range
+    // offset, i.e. zeros in its own slot, which nothing reads.
+    template <int I0, int I1, bool SCHED = false> MF_DEV void issue(mf_v4i srd, unsigned lds_base, unsigned phase = 0u) const {
         constexpr int HI = I1 < St::NI ? I1 : St::NI;
         if constexpr (I0 < HI) {
             constexpr int N = (HI - I0) < 4 ? (HI - I0) : 4;
@@ -201,10 +182,12 @@ template <typename St> struct DmaStream {
 #else
                 voff[k] = vo[I0 + k];
 #endif
+                if constexpr (SCHED && TL::NT > 0)
+                    voff[k] = ((fm[((I0 + k) * PB) / 32] >> (((I0 + k) * PB) % 32 + phase)) & 1u) ? voff[k] : MF_DMA_INVALID;
             }
             if (St::UNIT == 16) dma_b128_group<(St::UG >= 8), N>(srd, lds_base + I0 * 1024, voff);
             else dma_b32_group<N>(srd, lds_base + I0 * 256, voff);
-            issue<I0 + N, I1>(srd, lds_base);
+            issue<I0 + N, I1, SCHED>(srd, lds_base, phase);
         }
     }
 };
@@ -240,6 +223,8 @@ template <typename T, typename St> struct RowReader {
         const int off = St::compact_unit(gu) * St::UNIT + (byte - gu * St::UNIT);
         return *reinterpret_cast<const T*>(row + off);
     }
+    // element k of tail slot t: the next row's unit HC::tail_unit(t)
+    MF_DEV T tail_at(int t, int k) const { return *reinterpret_cast<const T*>(row + (St::UB + t) * St::UNIT + k * (int)sizeof(T)); }
 };
 
 // RSTEP: the observation precision is a per-step stream [B, T, M, M] (KalmanFilterWithSites / WithSparseSites) instead of
@@ -247,11 +232,17 @@ template <typename T, typename St> struct RowReader {
 // BG: rows of b and H fetched per DMA batch (the same remedy as YG below, for kernels that have the LDS: the passes of the streamed
 // backward, mf_post_lds.hpp MODE 2 and mf_grad_lds.hpp, run two wavefronts per CU and take pairs - a 48-B row touches 1.375 lines,
 // a 96-B pair 1.5).
-template <typename T, int D, int M, bool RSTEP = false, int BG = 1> struct KfLdsCfg {
+// CARRY (kf_chunk_lds_kernel only): chol Q's image gets tail slots and the kernel carries the shared head of the next row in
+// registers (mf_head_carry.hpp) - wherever that set is not empty, the stream already drops units, the schedule bits fit two
+// registers and the image still fits FOUR wavefronts per CU (a quarter of 160 KB = 40 960 B).  To make room the offset tables,
+// which only DmaStream::init reads (before the first DMA is issued), then lie OVER the image.  Everywhere else, and in the sibling
+// kernels that reuse this layout (mf_post_lds.hpp, mf_grad_lds.hpp), the streams and the layout are what they were.
+template <typename T, int D, int M, bool RSTEP = false, int BG = 1, bool CARRY = false> struct KfLdsCfg {
     static constexpr int S = sizeof(T);
     static constexpr int BGRP = BG;
     using StA = Stream<D * D * S, KeepAll>;
-    using StC = Stream<D * D * S, KeepLower<D, S>>;
+    using StC0 = Stream<D * D * S, KeepLower<D, S>>;
+    using StCT = Stream<D * D * S, KeepLower<D, S>, true>;
     using Stb = Stream<BG * D * S, KeepAll>;
     using StH = Stream<BG * M * D * S, KeepAll>;
     // y rows are tiny (M S bytes): with one output they are fetched YG steps at a time, so a 128-B line of y is
@@ -260,25 +251,37 @@ template <typename T, int D, int M, bool RSTEP = false, int BG = 1> struct KfLds
     using Sty = Stream<YG * M * S, KeepAll>;
     using StR = Stream<M * M * S, KeepAll>;
     static constexpr bool RS = RSTEP;
+    static constexpr int QUARTER_CU = (160 * 1024) / 4;
+    static constexpr int TABLE_BYTES = 5 * 256 + ((StCT::U * 4 + 15) / 16) * 16;
+    static constexpr int IMAGE_T = StA::LDS_BYTES + StCT::LDS_BYTES + Stb::LDS_BYTES + StH::LDS_BYTES + ((Sty::LDS_BYTES + 15) / 16) * 16 +
+                                   (RSTEP ? ((StR::LDS_BYTES + 15) / 16) * 16 : 0);
+    static constexpr bool TAIL = CARRY && StCT::NT > 0 && !StC0::ALL && StCT::NI * StCT::HC::PERIOD <= 64 &&
+                                 StCT::NT * StCT::HC::PERIOD <= 32 && IMAGE_T <= QUARTER_CU && TABLE_BYTES <= IMAGE_T &&
+                                 (StA::NI + StCT::NI + Stb::NI + StH::NI + Sty::NI + (RSTEP ? StR::NI : 0)) < 64;
+    using StC = Stream<D * D * S, KeepLower<D, S>, TAIL>;
     static constexpr int OFF_A = 0;
     static constexpr int OFF_C = OFF_A + StA::LDS_BYTES;
     static constexpr int OFF_b = OFF_C + StC::LDS_BYTES;
     static constexpr int OFF_H = OFF_b + Stb::LDS_BYTES;
     static constexpr int OFF_y = OFF_H + StH::LDS_BYTES;
     static constexpr int OFF_R = OFF_y + ((Sty::LDS_BYTES + 15) / 16) * 16;
-    static constexpr int OFF_relA = OFF_R + (RSTEP ? ((StR::LDS_BYTES + 15) / 16) * 16 : 0);   // row offsets of A and cholQ
+    static constexpr int IMAGE_END = OFF_R + (RSTEP ? ((StR::LDS_BYTES + 15) / 16) * 16 : 0);
+    static constexpr int OFF_relA = TAIL ? 0 : IMAGE_END;                                       // row offsets of A and cholQ
     static constexpr int OFF_relb = OFF_relA + 256;
     static constexpr int OFF_relH = OFF_relb + 256;
     static constexpr int OFF_rely = OFF_relH + 256;
     static constexpr int OFF_relR = OFF_rely + 256;
     static constexpr int OFF_gtabC = OFF_relR + 256;
-    static constexpr int LDS_TOTAL = OFF_gtabC + ((StC::U * 4 + 15) / 16) * 16;
+    static constexpr int LDS_TOTAL = TAIL ? IMAGE_END : OFF_gtabC + ((StC::U * 4 + 15) / 16) * 16;
     // the streaming kernel is instantiated only where matrix rows are whole 16-B units, the per-step DMA count
     // fits the 6-bit vm counter and the image fits 64 KB of LDS
     static constexpr bool SUPPORTED =
                                       (StA::NI + StC::NI + Stb::NI + StH::NI + Sty::NI + (RSTEP ? StR::NI : 0)) < 64 &&
                                       LDS_TOTAL <= 64 * 1024;
 };
+
+template <typename T, int D, int M, bool RSTEP = false> using KfChunkCfg = KfLdsCfg<T, D, M, RSTEP, 1, true>;
+static_assert(KfChunkCfg<double, 6, 1>::TAIL && KfChunkCfg<double, 6, 1>::LDS_TOTAL <= 40960, "fp64 d = 6: four wavefronts per CU");
 
 // DMA batches of one step.  All of a step's data is pulled into registers at the top of the step behind ONE
 // `s_waitcnt vmcnt(0)`; the batches of the next step are then issued between the arithmetic phases.
@@ -294,6 +297,7 @@ template <typename Cfg> struct KfPump {
     unsigned lds0;
     bool more;
     bool yfetch = true;     // this step's batch includes the next group of y rows
+    unsigned cphase = 0;    // head carry: (index of the step being fetched) % period
     template <int K> MF_DEV void small() const {
         if (!((MF_PUMPMASK >> K) & 1)) return;
         small_do<K>();
@@ -301,15 +305,16 @@ template <typename Cfg> struct KfPump {
     template <int K> MF_DEV void small_do() const {
         if (!more) return;
         constexpr int HC = (Cfg::StC::NI + 1) / 2;
-        if (K == 0) dC.template issue<0, HC>(sC, lds0 + Cfg::OFF_C);
+        if (K == 0) dC.template issue<0, HC, true>(sC, lds0 + Cfg::OFF_C, cphase);
         else {
-            dC.template issue<HC, 64>(sC, lds0 + Cfg::OFF_C);
+            dC.template issue<HC, 64, true>(sC, lds0 + Cfg::OFF_C, cphase);
             db.template issue<0, 64>(sb, lds0 + Cfg::OFF_b);
             dH.template issue<0, 64>(sH, lds0 + Cfg::OFF_H);
             if (yfetch) dy.template issue<0, 64>(sy, lds0 + Cfg::OFF_y);
             if (Cfg::RS) dR.template issue<0, 64>(sR, lds0 + Cfg::OFF_R);
         }
     }
+    // a chunk's first fetch: every unit, tail slots included (step 0 consumes no carry)
     template <int K> MF_DEV void all() const {
         dC.template issue<0, 64>(sC, lds0 + Cfg::OFF_C);
         db.template issue<0, 64>(sb, lds0 + Cfg::OFF_b);
@@ -406,7 +411,7 @@ MF_DEV void kf_lds_step(Elim<T, D, SPIKE>& E, LogAcc<T>& laC, T& acc_yry, T& acc
 // KfArgs::P = chunks per series, L = transitions per chunk.
 template <typename T, int D, int M, bool SPIKE, bool RSTEP = false>
 __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, RedSys<T> out) {
-    using Cfg = KfLdsCfg<T, D, M, RSTEP>;
+    using Cfg = KfChunkCfg<T, D, M, RSTEP>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x;
     const long total = a.B * a.P;
@@ -439,8 +444,8 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
         tab[Cfg::OFF_relR / 4 + lane] = rowok ? (unsigned)(offR - offR0) : MF_DMA_INVALID;
         if (lane < Cfg::StC::U) {
             unsigned g = 0;
-            MF_UNROLL for (int cc = 0; cc < Cfg::StC::U; ++cc) if (lane == cc) g = (unsigned)Cfg::StC::global_unit(cc);
-            tab[Cfg::OFF_gtabC / 4 + lane] = g * Cfg::StC::UNIT;
+            MF_UNROLL for (int cc = 0; cc < Cfg::StC::U; ++cc) if (lane == cc) g = (unsigned)Cfg::StC::global_offset(cc);
+            tab[Cfg::OFF_gtabC / 4 + lane] = g;
         }
     }
     DmaStream<typename Cfg::StA> dA;
@@ -499,11 +504,19 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
     }
 #endif
     dA.init(smem, lane, Cfg::OFF_relA, 0);
-    dC.init(smem, lane, Cfg::OFF_relA, Cfg::OFF_gtabC);
+    dC.init(smem, lane, Cfg::OFF_relA, Cfg::OFF_gtabC, (unsigned)pC);
     db.init(smem, lane, Cfg::OFF_relb, 0);
     dH.init(smem, lane, Cfg::OFF_relH, 0);
     dy.init(smem, lane, Cfg::OFF_rely, 0);
     if (RSTEP) dR.init(smem, lane, Cfg::OFF_relR, 0);
+    // (with the head carry the tables lie over the image: the last table read is done before the first DMA writes there)
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    // head carry: this lane's consumer schedule, and the carried entries of the next row's chol Q (tail slot t, element k)
+    using HC = typename Cfg::StC::HC;
+    constexpr int NTAIL = Cfg::StC::NT, CPER = NTAIL > 0 ? HC::PERIOD : 1, UEL = Cfg::StC::UNIT / S;
+    const unsigned cbits = NTAIL > 0 ? HC::consumer_bits((unsigned)((unsigned long long)a.cholQ + offA)) : 0u;
+    T cv[NTAIL > 0 ? NTAIL : 1][UEL];
+    MF_UNROLL for (int t = 0; t < (NTAIL > 0 ? NTAIL : 1); ++t) MF_UNROLL for (int k = 0; k < UEL; ++k) cv[t][k] = T(0);
 
     const RowReader<T, typename Cfg::StA> rA(smem, Cfg::OFF_A, lane);
     const RowReader<T, typename Cfg::StC> rC(smem, Cfg::OFF_C, lane);
@@ -557,6 +570,17 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
         if (yfetch) py += Cfg::YG * M * S;                                                                            \
         T C[D][D], mvec[D], hk[M * D], yk[M];                                                                         \
         MF_UNROLL for (int i = 0; i < D; ++i) MF_UNROLL for (int jj = 0; jj <= i; ++jj) C[i][jj] = rC.at(i * D + jj); \
+        if constexpr (NTAIL > 0) {                                                                                    \
+            /* entries of the row's head units that the previous step carried come from registers; then pick up  */   \
+            /* the next row's from the tail slots (zeros where this step's fetch left them out: not used then)   */   \
+            MF_UNROLL for (int t = 0; t < NTAIL; ++t) {                                                               \
+                const bool got = !(FIRST) && ((cbits >> (t * CPER + (int)(j & (CPER - 1)))) & 1u) != 0u;              \
+                MF_UNROLL for (int i = 0; i < D; ++i) MF_UNROLL for (int jj = 0; jj <= i; ++jj)                       \
+                    if (((i * D + jj) * S) / Cfg::StC::UNIT == HC::tail_unit(t))                                      \
+                        C[i][jj] = got ? cv[t][(i * D + jj) - HC::tail_unit(t) * UEL] : C[i][jj];                     \
+                MF_UNROLL for (int k = 0; k < UEL; ++k) cv[t][k] = rC.tail_at(t, k);                                  \
+            }                                                                                                         \
+        }                                                                                                             \
         MF_UNROLL for (int i = 0; i < D; ++i) mvec[i] = rb.at(i);                                                     \
         MF_UNROLL for (int i = 0; i < M * D; ++i) hk[i] = rH.at(i);                                                   \
         MF_UNROLL for (int i = 0; i < M; ++i)                                                                         \
@@ -572,7 +596,8 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
                         make_srd(pb, eb, a.debug | ((a.debug >> 1) & 1)),                                             \
                         make_srd(pH, eH, a.debug | ((a.debug >> 1) & 1)),                                             \
                         make_srd(py, ey, a.debug | ((a.debug >> 1) & 1)),                                             \
-                        make_srd(pR, eR, a.debug | ((a.debug >> 1) & 1)), lds0, more, yfetch};                        \
+                        make_srd(pR, eR, a.debug | ((a.debug >> 1) & 1)), lds0, more, yfetch,                         \
+                        (unsigned)((j + 1) & (CPER - 1))};                                                            \
         MF_EXP_STEP_NEXT                                                                                              \
         MF_NOPUMP_ISSUE                                                                                               \
         const bool active = j < len;                                                                                  \
