@@ -381,9 +381,9 @@ int mf_sde_conditional_statistics_f32(int64_t n, int d, const float* A_mt, const
  *   mf_btd_diag_of_inverse_grad: sigma = the forward's diagonal blocks of (L L^T)^-1; (g_diag | NULL, g_sub | NULL) = gradients
  *     w.r.t. the diagonal / sub-diagonal blocks of the inverse -> (g_ldiag lower, g_lsub).  The block Takahashi recursion run
  *     forward in reverse mode, A_{k+1} = Qbar_{k+1} + G_k A_k G_k^T, between two local kernels.
- * lsub == NULL: block-diagonal factor.  Workspace: mf_btd_grad_workspace_bytes (0: state dimension without these kernels,
- * the entry points then return -100).  d <= 9 (register kernels) and 10 <= d <= 15 where the row scan takes the recursion;
- * 10 <= d <= 32 otherwise (round 6, csrc/mf_adj.hip, 16 x 16 MFMA register tiles; the reference differentiates these operators at
+ * lsub == NULL: block-diagonal factor, B T independent blocks (every d <= 32).  Workspace: mf_btd_grad_workspace_bytes (0: state
+ * dimension without these kernels, the entry points then return -100).  d <= 9: register kernels (the workspace is required);
+ * 10 <= d <= 32 (round 6, csrc/mf_adj.hip, 16 x 16 MFMA register tiles; the reference differentiates these operators at
  * d = 30, T = 1001): with a workspace of mf_btd_grad_workspace_bytes and at least 32 blocks, terms local in time (a wavefront per
  * block) around one congruence recursion per adjoint, partitioned in time; otherwise (shorter chains, ws == NULL) one wavefront
  * per series walks the block recurrences.

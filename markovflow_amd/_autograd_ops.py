@@ -285,7 +285,9 @@ class BtdInverseBlocks(torch.autograd.Function):
         # silently, so that case takes the torch expressions below, which are recorded)
         plan = None if torch.is_grad_enabled() else _hip_grad_ws(ldiag)
         if plan is None:
-            if _scan_pays(ldiag):
+            # (with the tape on - create_graph=True - the scan form for any n and device: the block loop below detaches its inputs
+            # and would drop the second-order terms, or leave nothing to differentiate)
+            if _scan_pays(ldiag) or torch.is_grad_enabled():
                 g_chol, g_w = _inverse_blocks_backward_scan(ldiag, lsub, odiag, g_diag, g_sub)
             else:
                 g_chol, g_w = _inverse_blocks_backward_torch(ldiag, lsub, g_diag, g_sub)

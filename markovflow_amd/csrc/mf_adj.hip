@@ -693,7 +693,8 @@ template <typename T>
 int adj_cholesky_grad(long B, long n, int d, const T* ldiag, const T* lsub, const T* g_ldiag, const T* g_lsub, T* g_diag, T* g_sub,
                       void* ws, size_t ws_bytes, hipStream_t st) {
     if (!adj_covers(d)) return -100;
-    if (n > 1 && !lsub) return -100;
+    // block-diagonal factor: B n independent blocks - local terms only, every block a series of its own
+    if (n > 1 && !lsub) return adj_cholesky_grad<T>(B * n, 1, d, ldiag, lsub, g_ldiag, nullptr, g_diag, nullptr, ws, ws_bytes, st);
     {
         AdjWs<T> w;
         if (n > 1 && adj_carve<T>(ws, ws_bytes, B, n, d, w)) {
@@ -715,7 +716,9 @@ template <typename T>
 int adj_diag_of_inverse_grad(long B, long n, int d, const T* ldiag, const T* lsub, const T* sigma, const T* g_diag, const T* g_sub,
                              T* g_ldiag, T* g_lsub, void* ws, size_t ws_bytes, hipStream_t st) {
     if (!adj_covers(d)) return -100;
-    if (n > 1 && !lsub) return -100;
+    // block-diagonal factor: B n independent blocks (Sigma_k = L_k^-T L_k^-1) - every block a series of its own
+    if (n > 1 && !lsub)
+        return adj_diag_of_inverse_grad<T>(B * n, 1, d, ldiag, lsub, sigma, g_diag, nullptr, g_ldiag, nullptr, ws, ws_bytes, st);
     {
         AdjWs<T> w;
         if (n > 1 && adj_carve<T>(ws, ws_bytes, B, n, d, w)) {

@@ -747,11 +747,12 @@ size_t mf_btd_diag_of_inverse_workspace_bytes(int64_t B, int64_t T, int d, int e
 // differentiable torch route there)
 size_t mf_btd_grad_workspace_bytes(int64_t B, int64_t T, int d, int elem_size) {
     if (B < 1 || T < 1) return 0;
+    // 10 <= d <= 32: the parallel-in-time adjoints on register tiles (mf_adj.hip) - also for 10 <= d <= 15, where the row tables
+    // hand both adjoints over (their own size lacks the chunk maps of the tile scans: the call would take the sequential form)
+    if (mf::adj_covers(d)) return mf::adj_grad_ws(B, T, d, elem_size);
     size_t ws = 0;
     if (elem_size == 4) { if (const auto* t = table_for<float>(d)) ws = t->btd_grad_ws(B, T); }
     else if (const auto* t = table_for<double>(d)) ws = t->btd_grad_ws(B, T);
-    // 10 <= d <= 32: the parallel-in-time adjoints on register tiles (mf_adj.hip)
-    if (ws == 0 && mf::adj_covers(d)) ws = mf::adj_grad_ws(B, T, d, elem_size);
     return ws;
 }
 

@@ -844,6 +844,7 @@ template <typename T> size_t btd_grad_ws(long B, long n) {
 template <typename T>
 int btd_cholesky_grad(long B, long n, const T* ldiag, const T* lsub, const T* g_ldiag, const T* g_lsub, T* g_diag, T* g_sub, void* ws,
                       size_t ws_bytes, hipStream_t st) {
+    if constexpr (!LANE) return -100;      // 10 <= d <= 15: mf_adj.hip's (before the workspace check: its sequential form needs none)
     if (ws == nullptr || ws_bytes < btd_grad_ws<T>(B, n)) return -9;
     const size_t blk = align_up(size_t(B) * n * D * D * sizeof(T));
     char* p = static_cast<char*>(ws);
@@ -866,6 +867,7 @@ int btd_cholesky_grad(long B, long n, const T* ldiag, const T* lsub, const T* g_
 template <typename T>
 int btd_diag_of_inverse_grad(long B, long n, const T* ldiag, const T* lsub, const T* sigma, const T* g_diag, const T* g_sub,
                              T* g_ldiag, T* g_lsub, void* ws, size_t ws_bytes, hipStream_t st) {
+    if constexpr (!LANE) return -100;      // 10 <= d <= 15: mf_adj.hip's
     if (ws == nullptr || ws_bytes < btd_grad_ws<T>(B, n)) return -11;
     const size_t blk = align_up(size_t(B) * n * D * D * sizeof(T));
     char* p = static_cast<char*>(ws);

@@ -33,10 +33,59 @@ def blocks_of(m, n, d, want_sub=True):
     return diag, sub
 
 
-def random_spd(rng, batch, n, d):
+def random_factor(rng, batch, n, d, scaled=False):
+    """A lower block-bidiagonal factor ``(ldiag [.., n, d, d], lsub [.., n - 1, d, d])`` in fp64 on the CPU: the one generator of the
+    adjoint tests here and in tests/test_gpu_autograd_ops.py.  ``scaled``: the couplings times 2 / d and the strict lower triangles
+    times 4 / d - ``G_k = W_k L_k^-1`` has to stay a contraction for the recurrences to be evaluable over hundreds of blocks at all, in
+    any implementation; unscaled (entries of ordinary size, ``|G_k|`` well above one from d = 10 on) is for a handful of blocks."""
     ld = np.tril(0.3 * rng.normal(size=batch + (n, d, d)), k=-1) + (1.0 + np.abs(0.3 * rng.normal(size=batch + (n, d))))[..., None] * np.eye(d)
     ls = 0.3 * rng.normal(size=batch + (n - 1, d, d))
     ldt, lst = torch.tensor(ld, dtype=F64), torch.tensor(ls, dtype=F64)
+    if scaled:
+        lst = lst * (2.0 / d)
+        ldt = torch.tril(ldt, -1) * (4.0 / d) + torch.diag_embed(torch.diagonal(ldt, dim1=-2, dim2=-1))
+    return ldt, lst
+
+
+def adjoint_case(seed, batch, n, d, scaled):
+    """``(ldiag, lsub | None, g1, g2 | None)``: a factor of ``random_factor`` and incoming gradients of its blocks' shapes."""
+    rng = np.random.default_rng(seed)
+    ld, ls = random_factor(rng, batch, n, d, scaled)
+    g1 = torch.tensor(rng.normal(size=tuple(ld.shape)), dtype=F64)
+    g2 = torch.tensor(rng.normal(size=tuple(ls.shape)), dtype=F64) if n > 1 else None
+    return ld, (ls if n > 1 else None), g1, g2
+
+
+def spd_blocks_of_factor(ld, ls):
+    """The blocks ``(diag, sub)`` of ``L L^T`` from the blocks of ``L`` (block products: no dense matrix)."""
+    low = torch.tril(ld)
+    diag = low @ low.transpose(-1, -2)
+    if ls is None:
+        return diag, None
+    diag = torch.cat([diag[..., :1, :, :], diag[..., 1:, :, :] + ls @ ls.transpose(-1, -2)], dim=-3)
+    return diag, ls @ low[..., :-1, :, :].transpose(-1, -2)
+
+
+def dense_cholesky_blocks(diag, sub):
+    """Differentiable dense reference of ``SymmetricBlockTriDiagonal.cholesky``: the blocks of ``chol`` of the dense matrix; the
+    symmetric blocks enter through their symmetrised form, as torch.linalg.cholesky's adjoint assumes."""
+    n, d = diag.shape[-3], diag.shape[-1]
+    chol = torch.linalg.cholesky(dense_of(0.5 * (diag + diag.transpose(-1, -2)), sub, True))
+    return blocks_of(chol, n, d, want_sub=sub is not None)
+
+
+def dense_inverse_blocks(ldiag, lsub):
+    """Differentiable dense reference of the diagonal / sub-diagonal blocks of ``(L L^T)^-1``: one triangular solve against the
+    identity (no LU-based inverse), ``L^-T L^-1``."""
+    n, d = ldiag.shape[-3], ldiag.shape[-1]
+    full = dense_of(ldiag, lsub, False)
+    eye = torch.eye(n * d, dtype=full.dtype, device=full.device).expand(full.shape)
+    linv = torch.linalg.solve_triangular(full, eye, upper=False)
+    return blocks_of(linv.transpose(-1, -2) @ linv, n, d, want_sub=lsub is not None)
+
+
+def random_spd(rng, batch, n, d):
+    ldt, lst = random_factor(rng, batch, n, d)
     full = dense_of(ldt, lst, False)
     return blocks_of(full @ full.transpose(-1, -2), n, d), (ldt, lst)
 
@@ -190,3 +239,84 @@ def test_scan_forms_of_the_operator_adjoints_against_the_block_loops(batch, n, d
     torch.testing.assert_close(e[0], c[0], rtol=1e-11, atol=1e-12)
     if ls is not None:
         torch.testing.assert_close(e[1], c[1], rtol=1e-11, atol=1e-12)
+
+
+# ---- the recursions at the state dimensions of the register-tile adjoint kernels (10 <= d <= 32) ----------------------------
+# tests/test_gpu_autograd_ops.py compares the HIP adjoints of long chains with the block loops: here the loops (and the scan
+# forms) are themselves pinned on dense autograd at those d, with the generator the GPU file uses - scaled as for long chains and
+# unscaled (a handful of blocks: |G_k| is well above one there and the gradients grow by orders of magnitude per block).
+@pytest.mark.parametrize("d", [10, 16, 17, 24, 32])
+@pytest.mark.parametrize("n,scaled", [(1, True), (12, True), (2, False), (5, False), (12, False)])
+def test_recursions_against_dense_autograd_at_tile_kernel_sizes(d, n, scaled):
+    rng = np.random.default_rng(21)
+    ld, ls = random_factor(rng, (2,), n, d, scaled)
+    if n == 1:
+        ls = None
+    g1 = torch.tensor(rng.normal(size=ld.shape), dtype=F64)
+    g2 = None if ls is None else torch.tensor(rng.normal(size=ls.shape), dtype=F64)
+    # cholesky: dense reverse mode through chol of the dense matrix; the recursions get that factor's blocks
+    dg, sb = spd_blocks_of_factor(ld, ls)
+    a = dg.clone().requires_grad_(True)
+    b = None if sb is None else sb.clone().requires_grad_(True)
+    cd, cs = dense_cholesky_blocks(a, b)
+    (torch.sum(torch.tril(cd) * g1) + (0 if cs is None else torch.sum(cs * g2))).backward()
+    for fn in (ag._cholesky_backward_torch, ag._cholesky_backward_scan):
+        gd, gs = fn(cd.detach(), None if cs is None else cs.detach(), g1, g2)
+        np.testing.assert_allclose(gd.numpy(), a.grad.numpy(), rtol=1e-9, atol=1e-11, err_msg=fn.__name__)
+        if ls is not None:
+            np.testing.assert_allclose(gs.numpy(), b.grad.numpy(), rtol=1e-9, atol=1e-11, err_msg=fn.__name__)
+    # the blocks of the inverse
+    a = ld.clone().requires_grad_(True)
+    b = None if ls is None else ls.clone().requires_grad_(True)
+    od, osub = dense_inverse_blocks(a, b)
+    (torch.sum(od * g1) + (0 if osub is None else torch.sum(osub * g2))).backward()
+    for name, (gl, gw) in (("loop", ag._inverse_blocks_backward_torch(ld, ls, g1, g2)),
+                           ("scan", ag._inverse_blocks_backward_scan(ld, ls, od.detach(), g1, g2))):
+        np.testing.assert_allclose(gl.numpy(), torch.tril(a.grad).numpy(), rtol=1e-8, atol=1e-10, err_msg=name)
+        if ls is not None:
+            np.testing.assert_allclose(gw.numpy(), b.grad.numpy(), rtol=1e-8, atol=1e-10, err_msg=name)
+
+
+# ---- second order ---------------------------------------------------------------------------------------------------------------
+def _hvp(loss, leaves, vs):
+    grads = torch.autograd.grad(loss, leaves, create_graph=True)
+    return torch.autograd.grad(sum(torch.sum(g * v) for g, v in zip(grads, vs)), leaves)
+
+
+@pytest.mark.parametrize("n", [3, 12])
+def test_hessian_vector_products_through_cholesky_and_inverse_blocks(n):
+    """Under ``create_graph=True`` the backward of the operators is recorded: Hessian-vector products of ``cholesky`` and of the
+    blocks of the inverse, through the dense stand-ins, against torch's double reverse mode through the dense matrices.  (The
+    inverse blocks' loop form detaches its inputs: with the tape on, the scan form takes the call for any n and device.)"""
+    d = 3
+    rng = np.random.default_rng(8)
+    (dg, sb), (ld, ls) = random_spd(rng, (2,), n, d)
+    g1 = torch.tensor(rng.normal(size=dg.shape), dtype=F64)
+    g2 = torch.tensor(rng.normal(size=sb.shape), dtype=F64)
+    vd = torch.tensor(rng.normal(size=dg.shape), dtype=F64)
+    vd = vd + vd.transpose(-1, -2)                                  # a direction within the symmetric blocks
+    vs = torch.tensor(rng.normal(size=sb.shape), dtype=F64)
+
+    def chol_loss(fn, a, b):
+        cd, cs = fn(a, b)
+        return torch.sum(torch.tril(cd) ** 2 * g1) + torch.sum(cs ** 2 * g2)
+
+    outs = []
+    for fn in (lambda a, b: ag.BtdCholesky.apply(chol_run, a, b), dense_cholesky_blocks):
+        a, b = dg.clone().requires_grad_(True), sb.clone().requires_grad_(True)
+        outs.append(_hvp(chol_loss(fn, a, b), (a, b), (vd, vs)))
+    for x1, x2 in zip(*outs):
+        np.testing.assert_allclose(x1.numpy(), x2.numpy(), rtol=1e-8, atol=1e-10)
+
+    def inv_loss(fn, a, b):
+        od, osub = fn(a, b)
+        return torch.sum(od ** 2 * g1) + torch.sum(osub ** 2 * g2)
+
+    vl = torch.tril(torch.tensor(rng.normal(size=ld.shape), dtype=F64))
+    outs = []
+    for fn in (lambda a, b: ag.BtdInverseBlocks.apply(inv_run, a, b, True), dense_inverse_blocks):
+        a, b = ld.clone().requires_grad_(True), ls.clone().requires_grad_(True)
+        h = _hvp(inv_loss(fn, a, b), (a, b), (vl, vs))
+        outs.append((torch.tril(h[0]), h[1]))
+    for x1, x2 in zip(*outs):
+        np.testing.assert_allclose(x1.numpy(), x2.numpy(), rtol=1e-8, atol=1e-10)

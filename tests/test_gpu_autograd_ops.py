@@ -5,13 +5,18 @@ reference's CVI models differentiate - ``dist_p.precision -> naturals_to_ssm_par
 (/root/reference/markovflow/models/variational_cvi.py:105-136,402; the operators' gradients there come from banded_matrices,
 block_tri_diag.py:22-31) - against central differences of the same (forward-only, oracle-checked) kernels.  fp64.
 """
+import collections
+
 import numpy as np
 import pytest
 import torch
 
 import markovflow_amd as mfa
+from markovflow_amd import _autograd_ops as ag
+from markovflow_amd import _lib
 from markovflow_amd import ssm_gaussian_transformations as G
-from test_autograd_ops import blocks_of, dense_of, random_spd
+from test_autograd_ops import (adjoint_case, blocks_of, dense_cholesky_blocks, dense_inverse_blocks, dense_of, random_factor,
+                               random_spd, spd_blocks_of_factor)
 from test_gpu_kalman import DEV, nn, random_ssm, tt
 
 pytestmark = pytest.mark.gpu
@@ -118,10 +123,26 @@ def test_cvi_shaped_gradient_through_precision_and_naturals(rng):
 
 
 # ---- the HIP adjoints of cholesky / block_diagonal_of_inverse (mf_btd_cholesky_grad_*, mf_btd_diag_of_inverse_grad_*) -------------
-def _random_factor(rng, batch, n, d, dtype=F64):
-    ld = np.tril(0.3 * rng.normal(size=batch + (n, d, d)), k=-1) + (1.0 + np.abs(0.3 * rng.normal(size=batch + (n, d))))[..., None] * np.eye(d)
-    ls = 0.3 * rng.normal(size=batch + (n - 1, d, d))
-    return torch.tensor(ld, dtype=dtype, device=DEV), torch.tensor(ls, dtype=dtype, device=DEV)
+CHOL_GRAD, INV_GRAD = "mf_btd_cholesky_grad", "mf_btd_diag_of_inverse_grad"
+
+
+@pytest.fixture
+def abi_calls(monkeypatch):
+    """Counts the entry points that go through ``_lib.call`` (``_autograd_ops`` reaches the adjoint kernels as ``_lib.call``): a
+    parity test that can pass without the kernel having run proves nothing about the kernel."""
+    counts = collections.Counter()
+    real = _lib.call
+
+    def spy(base, *args, **kwargs):
+        counts[base] += 1
+        return real(base, *args, **kwargs)
+
+    monkeypatch.setattr(_lib, "call", spy)
+    return counts
+
+
+class Ctx:
+    pass
 
 
 @pytest.mark.parametrize("batch,n,d,with_sub,which", [
@@ -136,19 +157,19 @@ def _random_factor(rng, batch, n, d, dtype=F64):
     ((1,), 12, 32, True, "both"), ((2,), 9, 17, False, "both"), ((3,), 1, 20, False, "both"), ((1,), 1001, 30, True, "both"),
     ((2,), 77, 16, True, "both"), ((3,), 100, 20, True, "diag"), ((2,), 64, 32, True, "sub"), ((5,), 33, 10, True, "both"),
     ((2,), 130, 24, True, "both"), ((70,), 45, 15, True, "both"),
+    # one incoming gradient missing (NULL) in the sequential kernels (n < 32) of both tile counts and in the scans at d <= 16
+    ((2,), 12, 16, True, "diag"), ((2,), 12, 10, True, "sub"), ((2,), 5, 31, True, "sub"), ((2,), 31, 17, True, "diag"),
+    ((1,), 40, 15, True, "diag"), ((2,), 33, 16, True, "sub"), ((3,), 40, 12, False, "diag"), ((2,), 1, 32, False, "diag"),
 ])
-def test_hip_operator_adjoints_against_the_torch_recursions(batch, n, d, with_sub, which):
+def test_hip_operator_adjoints_against_the_torch_recursions(batch, n, d, with_sub, which, abi_calls):
     """The kernels against the block-by-block torch recursions (which tests/test_autograd_ops.py pins on dense autograd): few long
     series (recursion parallel in time), many short ones (a lane per series), no coupling, a single block, only one of the two
-    output gradients given."""
-    from markovflow_amd import _autograd_ops as ag
+    output gradients given (a NULL pointer at the C ABI: through ``loss.backward()`` autograd hands zeros instead).  ``backward`` is
+    called directly, with the tape OFF as under ``loss.backward()`` - with the tape on it takes the torch route (create_graph)."""
     rng = np.random.default_rng(11)
-    ldiag, lsub = _random_factor(rng, batch, n, d)
-    if d >= 10:
-        # (G_k = W_k L_k^-1 has to stay a contraction for the recurrences to be evaluable over a thousand blocks at all - in any
-        # implementation: scale the couplings and the strict lower triangles with the state dimension)
-        lsub = lsub * (2.0 / d)
-        ldiag = torch.tril(ldiag, -1) * (4.0 / d) + torch.diag_embed(torch.diagonal(ldiag, dim1=-2, dim2=-1))
+    # (d >= 10: G_k = W_k L_k^-1 has to stay a contraction for the recurrences to be evaluable over a thousand blocks at all - in any
+    # implementation: the couplings and the strict lower triangles are scaled with the state dimension, random_factor)
+    ldiag, lsub = (x.to(DEV) for x in random_factor(rng, batch, n, d, scaled=d >= 10))
     if not with_sub or n == 1:
         lsub = None
     g1 = torch.tensor(rng.normal(size=tuple(ldiag.shape)), dtype=F64, device=DEV) if which in ("both", "diag") else None
@@ -156,14 +177,12 @@ def test_hip_operator_adjoints_against_the_torch_recursions(batch, n, d, with_su
           if (lsub is not None and which in ("both", "sub")) else None)
     assert ag._hip_grad_ws(ldiag) is not None
     # cholesky: gradients w.r.t. the factor's blocks -> gradients w.r.t. the matrix' blocks
-
-    class Ctx:
-        pass
-
     ctx = Ctx()
     ctx.has_sub = lsub is not None
     ctx.saved_tensors = (ldiag, lsub if lsub is not None else ldiag.new_zeros(0))
-    _, gd, gs = ag.BtdCholesky.backward(ctx, g1, g2)
+    with torch.no_grad():
+        _, gd, gs = ag.BtdCholesky.backward(ctx, g1, g2)
+    assert (abi_calls[CHOL_GRAD], abi_calls[INV_GRAD]) == (1, 0), "the cholesky adjoint kernel has to take this call"
     want_d, want_s = ag._cholesky_backward_torch(ldiag, lsub, g1, g2)
     scale = float(want_d.abs().max())
     assert float((gd - want_d).abs().max()) <= 1e-9 * scale
@@ -175,7 +194,9 @@ def test_hip_operator_adjoints_against_the_torch_recursions(batch, n, d, with_su
     ctx = Ctx()
     ctx.has_sub, ctx.want_sub = lsub is not None, lsub is not None
     ctx.saved_tensors = (ldiag, lsub if lsub is not None else ldiag.new_zeros(0), odiag.contiguous())
-    _, gl, gw, _ = ag.BtdInverseBlocks.backward(ctx, g1, g2)
+    with torch.no_grad():
+        _, gl, gw, _ = ag.BtdInverseBlocks.backward(ctx, g1, g2)
+    assert (abi_calls[CHOL_GRAD], abi_calls[INV_GRAD]) == (1, 1), "the inverse blocks' adjoint kernel has to take this call"
     want_l, want_w = ag._inverse_blocks_backward_torch(ldiag, lsub, g1, g2)
     if want_l is None:
         want_l = torch.zeros_like(ldiag)
@@ -187,20 +208,17 @@ def test_hip_operator_adjoints_against_the_torch_recursions(batch, n, d, with_su
         assert float((gw - want_w).abs().max()) <= 1e-9 * max(float(want_w.abs().max()), scale)
 
 
-def test_hip_operator_adjoints_fp32():
-    from markovflow_amd import _autograd_ops as ag
+def test_hip_operator_adjoints_fp32(abi_calls):
     rng = np.random.default_rng(12)
-    ldiag, lsub = _random_factor(rng, (3,), 120, 5, dtype=torch.float32)
+    ldiag, lsub = (x.to(device=DEV, dtype=torch.float32) for x in random_factor(rng, (3,), 120, 5))
     g1 = torch.tensor(rng.normal(size=tuple(ldiag.shape)), dtype=torch.float32, device=DEV)
     g2 = torch.tensor(rng.normal(size=tuple(lsub.shape)), dtype=torch.float32, device=DEV)
-
-    class Ctx:
-        pass
-
     ctx = Ctx()
     ctx.has_sub = True
     ctx.saved_tensors = (ldiag, lsub)
-    _, gd, gs = ag.BtdCholesky.backward(ctx, g1, g2)
+    with torch.no_grad():
+        _, gd, gs = ag.BtdCholesky.backward(ctx, g1, g2)
+    assert abi_calls[CHOL_GRAD] == 1
     want_d, want_s = ag._cholesky_backward_torch(ldiag.double(), lsub.double(), g1.double(), g2.double())
     assert float((gd.double() - want_d).abs().max()) <= 2e-4 * float(want_d.abs().max())
     assert float((gs.double() - want_s).abs().max()) <= 2e-4 * float(want_s.abs().max())
@@ -211,7 +229,6 @@ def test_operator_adjoints_beyond_the_kernels_take_the_scan_forms(d, n, bsz):
     """d > 32 (fp32 operators on the panel / tile engine): no adjoint kernel; a GPU tensor takes the scan forms of
     markovflow_amd/_autograd_ops.py (local terms + a Hillis-Steele congruence scan, no Python loop over the blocks) - checked
     against the block loops in float32 arithmetic on the same device."""
-    from markovflow_amd import _autograd_ops as ag
     gen = torch.Generator(device=DEV).manual_seed(5)
     f32 = torch.float32
     ld = torch.tril((4.0 / d) * 0.3 * torch.randn(bsz, n, d, d, dtype=f32, device=DEV, generator=gen), -1) + torch.diag_embed(
@@ -235,3 +252,331 @@ def test_operator_adjoints_beyond_the_kernels_take_the_scan_forms(d, n, bsz):
     assert float((got_d - want_d).abs().max()) <= 2e-3 * scale
     assert float((got_s - want_s).abs().max()) <= 2e-3 * max(float(want_s.abs().max()), scale)
 
+
+
+# ---- 10 <= d <= 32: the register-tile adjoints (csrc/mf_adj.hip) through the public API and a real loss.backward() ----------------
+# Every case asserts the ROUTE (abi_calls: the adjoint entry point was called exactly once) and compares with plain fp64 that is not
+# the code under test: torch reverse mode through the dense n d x n d matrix where that fits (n d <= 2500), else the block loops of
+# _autograd_ops.py, which tests/test_autograd_ops.py pins on dense autograd at these d.  The cases follow the branches of mf_adj.hip /
+# mf_api.hip: the row tables' hand-over (10 <= d <= 15), one tile (d <= 16) or four (d > 16), identity padding (d = 10 ... 15, 17 ... 31),
+# the sequential kernel (n < 32) or local terms + scan (n >= 32: ragged chunk partitions at n = 77, 130, 1001), one wavefront per
+# series / per block with few series and with more than there are compute units, a block-diagonal factor.
+DENSE_LIMIT = 2500
+TILE_D = (10, 12, 15, 16, 17, 20, 24, 31, 32)
+
+
+def _dev_case(seed, batch, n, d, scaled, with_sub=True, dtype=F64):
+    ld, ls, g1, g2 = adjoint_case(seed, batch, n, d, scaled)
+    if not with_sub:
+        ls = g2 = None
+    return tuple(None if x is None else x.to(device=DEV, dtype=dtype) for x in (ld, ls, g1, g2))
+
+
+def _leaf(x):
+    return None if x is None else x.clone().requires_grad_(True)
+
+
+def _assert_close(got, want, ref):
+    """fp64 tolerances of this file: against dense autograd 1e-8 x the reference's largest entry, tensor by tensor (as in
+    test_cholesky_solve_inverse_blocks_and_products_vs_dense_autograd); against the block loops 1e-9 x the largest entry (the
+    couplings' gradient on the scale of the larger of the two, as in test_hip_operator_adjoints_against_the_torch_recursions)."""
+    scale = max(float(want[0].abs().max()), 1e-30)
+    errs = [float((got[0] - want[0]).abs().max()) / scale]
+    if want[1] is not None:
+        s1 = float(want[1].abs().max())
+        errs.append(float((got[1] - want[1]).abs().max()) / (s1 if ref == "dense" else max(s1, scale)))
+    print(f"  relative error ({ref}): " + ", ".join(f"{e:.3g}" for e in errs))
+    for e in errs:
+        assert e <= (1e-8 if ref == "dense" else 1e-9)
+    return errs
+
+
+def _cholesky_through_backward(calls, ld, ls, g1, g2, which="both"):
+    """``SymmetricBlockTriDiagonal(diag, sub).cholesky`` of ``L L^T`` under a real ``loss.backward()``: (gradients w.r.t. the
+    matrix' blocks, the factor the forward kernel produced)."""
+    dg, sb = spd_blocks_of_factor(ld, ls)
+    a, b = _leaf(dg), _leaf(sb)
+    before = (calls[CHOL_GRAD], calls[INV_GRAD])
+    chol = mfa.SymmetricBlockTriDiagonal(a, b).cholesky
+    loss = 0.0
+    if which in ("both", "diag"):
+        loss = loss + torch.sum(chol.block_diagonal * g1)
+    if which in ("both", "sub") and b is not None:
+        loss = loss + torch.sum(chol.block_sub_diagonal * g2)
+    loss.backward()
+    assert (calls[CHOL_GRAD] - before[0], calls[INV_GRAD] - before[1]) == (1, 0), "mf_btd_cholesky_grad has to take this backward"
+    cs = chol.block_sub_diagonal
+    return (a.grad, None if b is None else b.grad), (chol.block_diagonal.detach(), None if cs is None else cs.detach()), (dg, sb)
+
+
+def _cholesky_dense_reference(dg, sb, g1, g2, which="both"):
+    a, b = _leaf(dg), _leaf(sb)
+    cd, cs = dense_cholesky_blocks(a, b)
+    loss = 0.0
+    if which in ("both", "diag"):
+        loss = loss + torch.sum(torch.tril(cd) * g1)
+    if which in ("both", "sub") and b is not None:
+        loss = loss + torch.sum(cs * g2)
+    loss.backward()
+    return a.grad, None if b is None else b.grad
+
+
+def _inverse_through_backward(calls, ld, ls, g1, g2, which="both", want_sub=True):
+    a, b = _leaf(ld), _leaf(ls)
+    before = (calls[CHOL_GRAD], calls[INV_GRAD])
+    op = mfa.LowerTriangularBlockTriDiagonal(a, b)
+    if want_sub:
+        od, osub = op._diag_and_sub_of_inverse(want_sub=True)
+    else:
+        od, osub = op.block_diagonal_of_inverse(), None
+    loss = 0.0
+    if which in ("both", "diag"):
+        loss = loss + torch.sum(od * g1)
+    if which in ("both", "sub") and osub is not None:
+        loss = loss + torch.sum(osub * g2)
+    loss.backward()
+    assert (calls[CHOL_GRAD] - before[0], calls[INV_GRAD] - before[1]) == (0, 1), "mf_btd_diag_of_inverse_grad has to take this backward"
+    return a.grad, None if b is None else b.grad
+
+
+def _inverse_dense_reference(ld, ls, g1, g2, which="both", want_sub=True):
+    a, b = _leaf(ld), _leaf(ls)
+    od, osub = dense_inverse_blocks(a, b)
+    loss = 0.0
+    if which in ("both", "diag"):
+        loss = loss + torch.sum(od * g1)
+    if which in ("both", "sub") and osub is not None and want_sub:
+        loss = loss + torch.sum(osub * g2)
+    loss.backward()
+    return torch.tril(a.grad), None if b is None else b.grad
+
+
+def _both_operators(calls, batch, n, d, scaled, ref, with_sub=True, which="both", want_sub=True):
+    ld, ls, g1, g2 = _dev_case(21, batch, n, d, scaled, with_sub)
+    assert ref == "loop" or n * d <= DENSE_LIMIT
+    assert ag._hip_grad_ws(ld) is not None
+    only = lambda g, name: g if which in ("both", name) else None                       # noqa: E731
+    got, (cd, cs), (dg, sb) = _cholesky_through_backward(calls, ld, ls, g1, g2, which)
+    if ref == "dense":
+        want = _cholesky_dense_reference(dg, sb, g1, g2, which)
+    else:
+        want = ag._cholesky_backward_torch(cd, cs, only(g1, "diag"), None if cs is None else only(g2, "sub"))
+    _assert_close(got, want, ref)
+    got = _inverse_through_backward(calls, ld, ls, g1, g2, which, want_sub)
+    if ref == "dense":
+        want = _inverse_dense_reference(ld, ls, g1, g2, which, want_sub)
+    else:
+        gl, gw = ag._inverse_blocks_backward_torch(ld, ls, only(g1, "diag"), only(g2, "sub") if (ls is not None and want_sub) else None)
+        want = (gl if gl is not None else torch.zeros_like(ld), None if ls is None else (gw if gw is not None else torch.zeros_like(ls)))
+    _assert_close(got, want, ref)
+
+
+@pytest.mark.parametrize("n", [1, 2, 31, 32, 33])
+@pytest.mark.parametrize("d", TILE_D + (30,))
+def test_tile_adjoints_around_the_hand_over_to_the_scans_vs_dense_autograd(abi_calls, n, d):
+    """Every state dimension of the tile kernels, either side of ADJ_PAR_MIN_BLOCKS = 32 (sequential kernel below, local terms + scan
+    from there on), a single block, a single coupling; the scaling of long chains."""
+    _both_operators(abi_calls, (2,), n, d, True, "dense")
+
+
+# Unscaled, n = 12, d >= 24 takes the block loops as its reference, evaluated at the factor the forward kernel produced.  There
+# ``L L^T`` is ill-conditioned (the gradients reach 1e9 at d = 32) and dense autograd linearises at ITS OWN Cholesky factor, which
+# differs from the kernel's by cond x eps: measured against dense autograd, ``cholesky``'s gradients differ by 8e-10 (d = 24), 2.0e-6
+# (d = 31) and 3.4e-6 (d = 32) of the largest entry, while the inverse blocks' adjoint of the same factors - no factorisation in front
+# of it - agrees with dense autograd to 1e-15, and so does the cholesky adjoint with the loops at a common factor.  The 1e-8 bound
+# is beyond the dense reference itself there; tests/test_autograd_ops.py pins the loops on dense autograd for these very inputs.
+@pytest.mark.parametrize("d,n,ref", [(d, n, "dense") for d in TILE_D for n in (2, 5)] + [(d, 12, "dense") for d in TILE_D if d < 24]
+                         + [(d, 12, "loop") for d in TILE_D if d >= 24])
+def test_tile_adjoints_on_unscaled_factors(abi_calls, d, n, ref):
+    """Short chains with the unscaled factor: the tiles see entries of ordinary size (and gradients that grow by an order of
+    magnitude per block at d = 32: the bounds are relative to the largest entry)."""
+    _both_operators(abi_calls, (3,), n, d, False, ref)
+
+
+@pytest.mark.parametrize("batch,n,d,ref", [
+    # ragged chunk partitions of the scans
+    ((1,), 77, 10, "dense"), ((1,), 77, 16, "dense"), ((1,), 77, 17, "dense"), ((1,), 77, 32, "dense"), ((3,), 77, 24, "loop"),
+    ((1,), 130, 10, "dense"), ((1,), 130, 12, "dense"), ((1,), 130, 15, "dense"), ((1,), 130, 16, "dense"), ((1,), 130, 17, "dense"),
+    ((2,), 130, 20, "loop"), ((2,), 130, 31, "loop"), ((1,), 130, 32, "loop"),
+    # the reference's largest tested operator shape (tests/unit/test_ssm_gaussian_transformations.py:40-46) and its neighbours
+    ((1,), 1001, 30, "loop"), ((2,), 1001, 10, "loop"), ((1,), 1001, 16, "loop"), ((1,), 1001, 17, "loop"),
+    # many series: a wavefront each (sequential) / per block (local terms); more series than compute units
+    ((70,), 45, 15, "loop"), ((70,), 33, 17, "dense"), ((70,), 12, 32, "dense"), ((600,), 2, 16, "dense"), ((600,), 5, 24, "loop"),
+    ((600,), 33, 10, "loop"), ((600,), 31, 20, "loop"),
+    # two leading batch dimensions
+    ((2, 3), 33, 12, "dense"), ((2, 2), 7, 20, "dense"), ((3, 2), 40, 31, "dense"),
+])
+def test_tile_adjoints_long_chains_and_many_series(abi_calls, batch, n, d, ref):
+    _both_operators(abi_calls, batch, n, d, True, ref)
+
+
+@pytest.mark.parametrize("batch,n,d", [((2,), 9, 17), ((3,), 1, 10), ((3,), 1, 20), ((2,), 1, 32), ((3,), 40, 12), ((2,), 33, 32),
+                                       ((1,), 5, 15), ((2, 2), 31, 16), ((70,), 4, 24)])
+def test_tile_adjoints_of_a_block_diagonal_factor(abi_calls, batch, n, d):
+    """``lsub is None``: B n independent blocks (n = 1 and n > 1).  d = 17, n = 9 raised NotImplementedError inside backward()
+    before the entry points re-entered with every block as a series of its own."""
+    _both_operators(abi_calls, batch, n, d, True, "dense", with_sub=False)
+    _both_operators(abi_calls, batch, n, d, False, "dense", with_sub=False)
+
+
+@pytest.mark.parametrize("which", ["diag", "sub"])
+@pytest.mark.parametrize("batch,n,d", [((2,), 12, 10), ((2,), 40, 16), ((2,), 12, 24), ((2,), 40, 31)])
+def test_tile_adjoints_with_one_output_in_the_loss(abi_calls, batch, n, d, which):
+    """Only the diagonal or only the sub-diagonal blocks enter the loss (autograd hands the kernel zeros for the other)."""
+    _both_operators(abi_calls, batch, n, d, True, "dense", which=which)
+
+
+@pytest.mark.parametrize("batch,n,d", [((2,), 12, 10), ((2,), 40, 10), ((3,), 12, 17), ((2,), 40, 17), ((2,), 12, 32), ((1,), 40, 32),
+                                       ((2,), 33, 16)])
+def test_tile_adjoint_of_block_diagonal_of_inverse_without_the_sub_diagonal_output(abi_calls, batch, n, d):
+    """``block_diagonal_of_inverse()`` (``want_sub=False``) of a factor WITH couplings: no incoming gradient for the sub-diagonal
+    blocks of the inverse (NULL at the C ABI), still a gradient for the couplings."""
+    ld, ls, g1, g2 = _dev_case(22, batch, n, d, True)
+    got = _inverse_through_backward(abi_calls, ld, ls, g1, g2, want_sub=False)
+    _assert_close(got, _inverse_dense_reference(ld, ls, g1, g2, want_sub=False), "dense")
+    assert float(got[1].abs().max()) > 0
+
+
+# fp32 at d >= 10.  The yardstick is the error of the block loops evaluated in float32 against the same loops in float64 on identical
+# (float32-representable) inputs, adjoint_case(12, ...), measured on the CPU with the metric of _fp32_error below:
+#     case (batch, n, d, scaled)      cholesky adjoint    inverse blocks' adjoint
+FP32_LOOP_ERROR = {
+    ((3,), 5, 10, False): (3.2e-07, 9.3e-08),
+    ((3,), 12, 10, True): (1.9e-07, 2.6e-07),
+    ((2,), 200, 10, True): (2e-07, 1.6e-07),
+    ((3,), 5, 16, False): (4.5e-07, 1.8e-07),
+    ((3,), 12, 16, True): (2e-07, 2.5e-07),
+    ((2,), 200, 16, True): (3.1e-07, 2.2e-07),
+    ((3,), 5, 24, False): (1.8e-07, 2.7e-07),
+    ((3,), 12, 24, True): (2.3e-07, 1.5e-07),
+    ((2,), 200, 24, True): (3.3e-07, 2.8e-07),
+    ((3,), 5, 32, False): (7.5e-07, 6e-07),
+    ((3,), 12, 32, True): (2.6e-07, 2.2e-07),
+    ((2,), 200, 32, True): (4.5e-07, 3.2e-07),
+}
+# The kernels are allowed FP32_FACTOR x the per-case figure: the MFMA accumulation order and the scans' reassociation differ from
+# the loops'; nothing else justifies more.
+FP32_FACTOR = 4.0
+
+
+def _fp32_error(got, want):
+    sd = float(want[0].abs().max())
+    ss = max(float(want[1].abs().max()), sd)
+    return max(float((got[0].double() - want[0]).abs().max()) / sd, float((got[1].double() - want[1]).abs().max()) / ss)
+
+
+@pytest.mark.parametrize("case", list(FP32_LOOP_ERROR), ids=lambda c: "B%s-n%d-d%d-%s" % ("x".join(map(str, c[0])), c[1], c[2], "scaled" if c[3] else "plain"))
+def test_tile_adjoints_fp32(abi_calls, case):
+    """float32 through backward(), short and long chains: against the block loops in float64 on the inputs the kernel saw (for
+    ``cholesky``: the factor its float32 forward produced)."""
+    batch, n, d, scaled = case
+    f32 = torch.float32
+    ld, ls, g1, g2 = _dev_case(12, batch, n, d, scaled, dtype=f32)
+    assert ag._hip_grad_ws(ld) is not None
+    up = lambda x: x.double()                                                            # noqa: E731
+    got, (cd, cs), _ = _cholesky_through_backward(abi_calls, ld, ls, g1, g2)
+    assert got[0].dtype == f32
+    e_chol = _fp32_error(got, ag._cholesky_backward_torch(up(cd), up(cs), up(g1), up(g2)))
+    got = _inverse_through_backward(abi_calls, ld, ls, g1, g2)
+    e_inv = _fp32_error(got, ag._inverse_blocks_backward_torch(up(ld), up(ls), up(g1), up(g2)))
+    print(f"  fp32 relative error: cholesky {e_chol:.3g} (loops {FP32_LOOP_ERROR[case][0]:.3g}), inverse blocks {e_inv:.3g} "
+          f"(loops {FP32_LOOP_ERROR[case][1]:.3g})")
+    assert e_chol <= FP32_FACTOR * FP32_LOOP_ERROR[case][0]
+    assert e_inv <= FP32_FACTOR * FP32_LOOP_ERROR[case][1]
+
+
+# ---- robustness: no further reference needed ---------------------------------------------------------------------------------------
+def _direct_backwards(calls, ld, ls, sigma, g_ldiag, g1, g2):
+    """Both ``backward``s called directly with the tape off (a saved factor cannot be given junk through the public API);
+    ``g_ldiag``: the cholesky adjoint's incoming gradient of the factor's diagonal blocks, ``g1``: the inverse blocks' adjoint's
+    incoming gradient of the diagonal blocks of the inverse (a full matrix: nothing to ignore there)."""
+    before = (calls[CHOL_GRAD], calls[INV_GRAD])
+    none = ld.new_zeros(0)
+    with torch.no_grad():
+        ctx = Ctx()
+        ctx.has_sub = ls is not None
+        ctx.saved_tensors = (ld, ls if ls is not None else none)
+        _, gd, gs = ag.BtdCholesky.backward(ctx, g_ldiag, g2)
+        ctx = Ctx()
+        ctx.has_sub = ctx.want_sub = ls is not None
+        ctx.saved_tensors = (ld, ls if ls is not None else none, sigma)
+        _, gl, gw, _ = ag.BtdInverseBlocks.backward(ctx, g1, g2)
+    assert (calls[CHOL_GRAD] - before[0], calls[INV_GRAD] - before[1]) == (1, 1)
+    return [x for x in (gd, gs, gl, gw) if x is not None]
+
+
+@pytest.mark.parametrize("scaled", [True, False])
+@pytest.mark.parametrize("batch,n,d", [((2,), 12, 10), ((2,), 40, 15), ((2,), 12, 16), ((2,), 40, 17), ((2,), 12, 31), ((2,), 40, 32),
+                                       ((2,), 1, 24)])
+def test_tile_adjoints_ignore_the_strict_upper_triangles(abi_calls, batch, n, d, scaled):
+    """Finite junk in the strict upper triangles of ``ldiag`` and of the incoming ``g_ldiag`` must not change a result."""
+    if not scaled and n > 12:
+        n = 7
+    ld, ls, g1, g2 = _dev_case(23, batch, n, d, scaled)
+    sigma = mfa.LowerTriangularBlockTriDiagonal(ld, ls)._diag_and_sub_of_inverse(want_sub=False)[0].contiguous()
+    junk = torch.triu(torch.tensor(np.random.default_rng(5).normal(size=tuple(ld.shape)), dtype=F64, device=DEV) * 3.0 + 1.0, 1)
+    clean = _direct_backwards(abi_calls, ld, ls, sigma, torch.tril(g1), g1, g2)
+    dirty = _direct_backwards(abi_calls, ld + junk, ls, sigma, torch.tril(g1) + 2.0 * junk, g1, g2)
+    assert len(clean) == len(dirty) == (4 if ls is not None else 2)
+    for x, y in zip(clean, dirty):
+        assert float((x - y).abs().max()) <= 1e-12 * float(x.abs().max())
+    # ... and the factor's junk reaches neither the forward kernel nor its adjoint through the public API
+    got = _inverse_through_backward(abi_calls, ld + junk, ls, g1, g2)
+    gl = clean[2 if ls is not None else 1]
+    assert float((got[0] - gl).abs().max()) <= 1e-12 * float(gl.abs().max())
+
+
+def _abi_adjoints(ld, ls, g1, g2, with_ws):
+    """Both entry points through the raw C ABI, output buffers filled with NaN beforehand; ``with_ws`` False: ``ws = NULL,
+    ws_bytes = 0`` (the sequential kernels, whatever the length of the chain)."""
+    d, n = ld.shape[-1], ld.shape[-3]
+    flat = lambda t: None if t is None else t.reshape((-1, t.shape[-3], d, d)).contiguous()            # noqa: E731
+    ld, ls, g1, g2 = flat(ld), flat(ls), flat(g1), flat(g2)
+    bsz = ld.shape[0]
+    sigma = mfa.LowerTriangularBlockTriDiagonal(ld, ls)._diag_and_sub_of_inverse(want_sub=False)[0].contiguous()
+    wsb = int(_lib.load().mf_btd_grad_workspace_bytes(bsz, n, d, ld.element_size())) if with_ws else 0
+    assert wsb > 0 or not with_ws
+    ws = _lib.workspace(wsb, ld.device)
+    nan = lambda t: None if t is None else torch.full_like(t, float("nan"))             # noqa: E731
+    gd, gs, gl, gw = nan(ld), nan(ls), nan(ld), nan(ls)
+    st = _lib.stream_ptr(ld.device)
+    rc = _lib.call_rc(CHOL_GRAD, ld.dtype, bsz, n, d, _lib.ptr(ld), _lib.ptr(ls), _lib.ptr(g1), _lib.ptr(g2), _lib.ptr(gd),
+                      _lib.ptr(gs), _lib.ptr(ws), wsb, st)
+    assert rc == 0, rc
+    rc = _lib.call_rc(INV_GRAD, ld.dtype, bsz, n, d, _lib.ptr(ld), _lib.ptr(ls), _lib.ptr(sigma), _lib.ptr(g1), _lib.ptr(g2),
+                      _lib.ptr(gl), _lib.ptr(gw), _lib.ptr(ws), wsb, st)
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    return [x for x in (gd, gs, gl, gw) if x is not None]
+
+
+@pytest.mark.parametrize("with_ws", [True, False])
+@pytest.mark.parametrize("with_sub", [True, False])
+@pytest.mark.parametrize("n,d", [(1, 10), (31, 15), (33, 12), (77, 16), (2, 17), (33, 20), (31, 31), (77, 31), (33, 32), (1, 32)])
+def test_tile_adjoints_write_every_promised_element(n, d, with_sub, with_ws):
+    """Every element of ``g_diag`` / ``g_sub`` / ``g_ldiag`` / ``g_lsub`` is written (the Python layer hands ``torch.empty``
+    buffers over and returns them as the gradients), the strict upper triangle of ``g_ldiag`` with zeros."""
+    ld, ls, g1, g2 = _dev_case(24, (3,), n, d, True, with_sub)
+    outs = _abi_adjoints(ld, ls, g1, g2, with_ws)
+    for x in outs:
+        assert bool(torch.isfinite(x).all()), "an element was left unwritten"
+    gl = outs[2 if ls is not None else 1]
+    assert float(torch.triu(gl, 1).abs().max()) == 0.0
+    gd = outs[0]
+    assert float((gd - gd.transpose(-1, -2)).abs().max()) <= 1e-13 * float(gd.abs().max())
+
+
+@pytest.mark.parametrize("which", ["both", "diag", "sub"])
+@pytest.mark.parametrize("batch,n,d", [((1,), 32, 10), ((3,), 77, 12), ((2,), 130, 15), ((3,), 33, 16), ((1,), 130, 16), ((3,), 32, 17),
+                                       ((2,), 77, 20), ((1,), 130, 24), ((3,), 33, 31), ((2,), 77, 32), ((70,), 33, 32)])
+def test_tile_adjoints_scan_form_against_sequential_form(batch, n, d, which):
+    """The two implementations of each recurrence: with the full workspace (n >= 32: local terms + congruence scan, parallel in
+    time) and with ``ws = NULL`` (``adj_carve`` declines: one wavefront per series walks the chain).  Same inputs, fp64 tolerance
+    of the loop comparisons."""
+    ld, ls, g1, g2 = _dev_case(25, batch, n, d, True)
+    g1, g2 = (g1 if which != "sub" else None), (g2 if which != "diag" else None)
+    par = _abi_adjoints(ld, ls, g1, g2, True)
+    seq = _abi_adjoints(ld, ls, g1, g2, False)
+    scale_c, scale_i = float(seq[0].abs().max()), float(seq[2].abs().max())
+    for x, y, scale in zip(par, seq, (scale_c, scale_c, scale_i, scale_i)):
+        assert float((x - y).abs().max()) <= 1e-9 * max(float(y.abs().max()), scale)
