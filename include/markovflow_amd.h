@@ -295,6 +295,36 @@ int mf_sde_matern_prior_chol_grad_f32(int64_t B, int ncomp, const int* orders, c
                                       float jitter, const float* g_cholP0, float* out, void* stream);
 
 /*
+ * The generator for generalised components (markovflow/kernels/constant.py, periodic.py, sde_kernel.py:691-822): as
+ * mf_sde_matern_transitions_*, with
+ *   orders[c] in {0, 1, 3, 5}: order 0 is the constant component, A = [1], Pinf = [var], Q = jitter I exactly (lam[c] is ignored);
+ *   osc[c] (HOST array of ncomp ints): 0 = no oscillator, 1 = A = A^M (x) R(omega dt), Pinf = Pinf^M (x) I2,
+ *                                      2 = A = R(omega dt) (x) A^M, Pinf = I2 (x) Pinf^M,
+ *     R(th) = [[cos th, -sin th], [sin th, cos th]]; an oscillator doubles the component's state size (1, 2, 3 -> 2, 4, 6);
+ *   omega: device array shaped like lam / var ([ncomp] or [B, ncomp]), angular frequency 2 pi / period, ignored where osc[c] = 0
+ *     (may be NULL when no component has an oscillator); var is the product of the factors' variances.
+ * With every osc[c] = 0 and no order 0 the outputs are bit-identical to mf_sde_matern_transitions_*.
+ * Errors: the negative position of the offending argument; -100 when the 64 d x d staging images exceed the LDS limit.
+ */
+int mf_sde_transitions_f64(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, const double* lam, const double* var,
+                           const double* omega, int per_series, const double* dt, double jitter, double* A, double* cholQ, double* Q,
+                           void* stream);
+int mf_sde_transitions_f32(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, const float* lam, const float* var,
+                           const float* omega, int per_series, const float* dt, float jitter, float* A, float* cholQ, float* Q,
+                           void* stream);
+/*
+ * Reverse mode of mf_sde_transitions_*: out[b, k, c, 0 / 1 / 2] = d/d lam_c, d/d var_c, d/d omega_c of
+ * <g_A[b,k], A_k> + <g_cholQ[b,k], chol Q_k> (g_A, g_cholQ [B,n,d,d], either may be NULL; out [B,n,ncomp,3]); d/d lam is zero
+ * for order 0 and d/d omega where osc[c] = 0.  The same closed forms in forward mode with three tangents (csrc/mf_sde.hip: Dual3).
+ */
+int mf_sde_transitions_grad_f64(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, const double* lam,
+                                const double* var, const double* omega, int per_series, const double* dt, double jitter,
+                                const double* g_A, const double* g_cholQ, double* out, void* stream);
+int mf_sde_transitions_grad_f32(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, const float* lam,
+                                const float* var, const float* omega, int per_series, const float* dt, float jitter,
+                                const float* g_A, const float* g_cholQ, float* out, void* stream);
+
+/*
  * GaussianProcessRegression.log_likelihood (markovflow/models/gaussian_process_regression.py:150-160) for a Matern kernel or
  * a Sum of two, with the kernel -> state-space-model step FUSED into the Kalman sweep: A_k and chol(Q_k) are generated in
  * registers from dt_k = t_{k+1} - t_k, so a step reads 16 bytes (t, y) instead of the materialised tensors.  One output,

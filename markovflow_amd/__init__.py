@@ -18,7 +18,8 @@ from .kalman_filter import (
 )
 from .state_space_model import StateSpaceModel, state_space_model_from_covariances
 from . import conditionals, distributed, kernels, models, ssm_gaussian_transformations
-from .kernels import IndependentMultiOutput, Matern12, Matern32, Matern52, SDEKernel, StationaryKernel, Sum
+from .kernels import (Constant, HarmonicOscillator, IndependentMultiOutput, Matern12, Matern32, Matern52, Product, SDEKernel,
+                      StationaryKernel, Sum)
 from .models import GaussianProcessRegression
 from .posterior import AnalyticPosteriorProcess, ConditionalProcess
 from ._lib import MarkovflowAmdError, check_errors, errors_as_nan, set_synchronous_checks
@@ -28,6 +29,6 @@ __all__ = [
     "GaussMarkovDistribution", "check_compatible", "BaseKalmanFilter", "GaussianSites", "KalmanFilter",
     "KalmanFilterWithSites", "KalmanFilterWithSparseSites", "UnivariateGaussianSitesNat", "StateSpaceModel",
     "state_space_model_from_covariances", "conditionals", "distributed", "kernels", "models", "ssm_gaussian_transformations", "SDEKernel", "StationaryKernel", "Matern12", "Matern32",
-    "Matern52", "Sum", "IndependentMultiOutput", "GaussianProcessRegression", "AnalyticPosteriorProcess", "ConditionalProcess",
+    "Matern52", "Sum", "IndependentMultiOutput", "Constant", "HarmonicOscillator", "Product", "GaussianProcessRegression", "AnalyticPosteriorProcess", "ConditionalProcess",
     "MarkovflowAmdError", "check_errors", "errors_as_nan", "set_synchronous_checks",
 ]

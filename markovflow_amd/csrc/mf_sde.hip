@@ -7,6 +7,8 @@
 //   markovflow/kernels/sde_kernel.py:592-610,644-658 (ConcatKernel: block-diagonal A and Pinf),
 //   markovflow/state_space_model.py:634-656 (cholesky_or_zero: an all-zero covariance passes through as zero).
 // One lane per (series, transition); every component is at most 3 x 3, so everything is register resident.
+// mf_sde_transitions_* (further down) adds the order-0 component (Constant) and an oscillator factor (HarmonicOscillator,
+// Matern * HarmonicOscillator: blocks up to 6 x 6) in a kernel of its own; the Matern entry points are untouched by it.
 #include "../../include/markovflow_amd.h"
 
 // No fused-multiply-add contraction in this file: Q = Pinf - A Pinf A^T must come out EXACTLY zero for a zero time gap
@@ -395,6 +397,300 @@ int run_grad(int64_t B, int64_t n, int ncomp, const int* orders, const T* lam, c
     return hipGetLastError() == hipSuccess ? 0 : -1000;
 }
 
+// ---- generalised components: order 0 (Constant) and an oscillator factor (HarmonicOscillator, Matern * HarmonicOscillator) ----------
+// (markovflow/kernels/constant.py, periodic.py, sde_kernel.py:691-822 (Product): A = A^M (x) R(omega dt) or R (x) A^M,
+// Pinf = Pinf^M (x) I2 or I2 (x) Pinf^M, with R(th) = [[cos th, -sin th], [sin th, cos th]].)  Order 0 is the Matern-1/2 form at
+// lam = 0: A = [1], Pinf = [var]; its Q is jitter I EXACTLY (constant.py:86-102, periodic.py:135-154), not the rounding noise of
+// var (I - R R^T).  The Matern factor comes from Comp::build and Q / chol Q from comp_chol, so a component without an oscillator is
+// computed by the very instructions of matern_transitions_kernel.
+struct GSpec {
+    int ncomp, d;
+    int order[MAXC];       // 0, 1, 3 or 5
+    int osc[MAXC];         // 0 = no oscillator, 1 = Matern (x) R, 2 = R (x) Matern
+    int off[MAXC];
+};
+
+// accurate sin / cos (not the fast intrinsics): cos 0 = 1 and sin 0 = 0 exactly, which the zero-gap pass-through relies on
+template <typename T> __device__ __forceinline__ T t_sin(T x);
+template <> __device__ __forceinline__ float t_sin<float>(float x) { return sinf(x); }
+template <> __device__ __forceinline__ double t_sin<double>(double x) { return sin(x); }
+template <typename T> __device__ __forceinline__ T t_cos(T x);
+template <> __device__ __forceinline__ float t_cos<float>(float x) { return cosf(x); }
+template <> __device__ __forceinline__ double t_cos<double>(double x) { return cos(x); }
+
+// Dual2 with a third tangent (d/d lam, d/d var, d/d omega): the carrier of the generalised generator's reverse mode
+template <typename T> struct Dual3 {
+    T v, a, b, c;
+    __device__ __forceinline__ Dual3() {}
+    __device__ __forceinline__ Dual3(T x) : v(x), a(T(0)), b(T(0)), c(T(0)) {}
+    __device__ __forceinline__ Dual3(T x, T da, T db, T dc) : v(x), a(da), b(db), c(dc) {}
+};
+template <typename T> __device__ __forceinline__ Dual3<T> operator+(Dual3<T> x, Dual3<T> y) { return {x.v + y.v, x.a + y.a, x.b + y.b, x.c + y.c}; }
+template <typename T> __device__ __forceinline__ Dual3<T> operator-(Dual3<T> x, Dual3<T> y) { return {x.v - y.v, x.a - y.a, x.b - y.b, x.c - y.c}; }
+template <typename T> __device__ __forceinline__ Dual3<T> operator-(Dual3<T> x) { return {-x.v, -x.a, -x.b, -x.c}; }
+template <typename T> __device__ __forceinline__ Dual3<T> operator*(Dual3<T> x, Dual3<T> y) {
+    return {x.v * y.v, x.a * y.v + x.v * y.a, x.b * y.v + x.v * y.b, x.c * y.v + x.v * y.c};
+}
+template <typename T> __device__ __forceinline__ Dual3<T> operator/(Dual3<T> x, Dual3<T> y) {
+    const T r = T(1) / y.v, q = x.v * r;
+    return {q, (x.a - q * y.a) * r, (x.b - q * y.b) * r, (x.c - q * y.c) * r};
+}
+template <typename T> __device__ __forceinline__ Dual3<T>& operator+=(Dual3<T>& x, Dual3<T> y) { x = x + y; return x; }
+template <typename T> __device__ __forceinline__ Dual3<T>& operator-=(Dual3<T>& x, Dual3<T> y) { x = x - y; return x; }
+template <typename T> __device__ __forceinline__ bool operator==(Dual3<T> x, Dual3<T> y) { return x.v == y.v; }
+template <> __device__ __forceinline__ Dual3<float> t_exp<Dual3<float>>(Dual3<float> x) { const float e = expf(x.v); return {e, e * x.a, e * x.b, e * x.c}; }
+template <> __device__ __forceinline__ Dual3<double> t_exp<Dual3<double>>(Dual3<double> x) { const double e = exp(x.v); return {e, e * x.a, e * x.b, e * x.c}; }
+template <> __device__ __forceinline__ Dual3<float> t_sqrt_<Dual3<float>>(Dual3<float> x) {
+    const float r = sqrtf(x.v), h = 0.5f / r;
+    return {r, h * x.a, h * x.b, h * x.c};
+}
+template <> __device__ __forceinline__ Dual3<double> t_sqrt_<Dual3<double>>(Dual3<double> x) {
+    const double r = sqrt(x.v), h = 0.5 / r;
+    return {r, h * x.a, h * x.b, h * x.c};
+}
+template <> __device__ __forceinline__ Dual3<float> t_sin<Dual3<float>>(Dual3<float> x) {
+    const float s = sinf(x.v), c = cosf(x.v);
+    return {s, c * x.a, c * x.b, c * x.c};
+}
+template <> __device__ __forceinline__ Dual3<double> t_sin<Dual3<double>>(Dual3<double> x) {
+    const double s = sin(x.v), c = cos(x.v);
+    return {s, c * x.a, c * x.b, c * x.c};
+}
+template <> __device__ __forceinline__ Dual3<float> t_cos<Dual3<float>>(Dual3<float> x) {
+    const float s = -sinf(x.v), c = cosf(x.v);
+    return {c, s * x.a, s * x.b, s * x.c};
+}
+template <> __device__ __forceinline__ Dual3<double> t_cos<Dual3<double>>(Dual3<double> x) {
+    const double s = -sin(x.v), c = cos(x.v);
+    return {c, s * x.a, s * x.b, s * x.c};
+}
+
+// A and Pinf of (a Matern factor of KM states) x (the oscillator): RF = false: Matern (x) R, true: R (x) Matern
+template <typename T, int KM, bool RF>
+__device__ __forceinline__ void build_osc(T lam, T var, T omega, T dt, Comp<T, 2 * KM>& out) {
+    Comp<T, KM> m;
+    m.build(lam, var, dt);
+    const T th = omega * dt;
+    const T c = t_cos<T>(th), s = t_sin<T>(th);
+    const T R[2][2] = {{c, -s}, {s, c}};
+    for (int i = 0; i < KM; ++i)
+        for (int j = 0; j < KM; ++j)
+            for (int p = 0; p < 2; ++p)
+                for (int q = 0; q < 2; ++q) {
+                    const int row = RF ? p * KM + i : i * 2 + p, col = RF ? q * KM + j : j * 2 + q;
+                    out.A[row][col] = m.A[i][j] * R[p][q];
+                    out.P[row][col] = p == q ? m.P[i][j] : T(0);
+                }
+}
+
+// emit() for a component that may be of order 0, whose Q is jitter I exactly
+template <typename T, int K>
+__device__ __forceinline__ void emit_g(const Comp<T, K>& c, bool order0, T jitter, int d, int off, int which, T* __restrict__ blk) {
+    if (which == 0 || !order0) { emit<T, K>(c, jitter, d, off, which, blk); return; }
+    const T v = which == 2 ? jitter : t_sqrt_<T>(jitter);
+    for (int i = 0; i < K; ++i) for (int j = 0; j < K; ++j) blk[(off + i) * d + off + j] = i == j ? v : T(0);
+}
+
+// matern_transitions_kernel for generalised components: the same staging and stores, the component's block up to 6 x 6
+template <typename T>
+__global__ void __launch_bounds__(64) sde_transitions_kernel(long B, long n, GSpec sp, const T* __restrict__ lam,
+                                                             const T* __restrict__ var, const T* __restrict__ omega, long hstride,
+                                                             const T* __restrict__ dt, T jitter, T* __restrict__ A,
+                                                             T* __restrict__ cholQ, T* __restrict__ Q) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    T* buf = reinterpret_cast<T*>(smem_raw);
+    const long base = (long)blockIdx.x * 64, total = B * n;
+    const long id = base + threadIdx.x;
+    const bool valid = id < total;
+    const int d = sp.d, dd = d * d, stride = dd | 1;
+    const long s = valid ? id / n : 0;
+    const T delta = valid ? dt[id] : T(1);
+    T* mine = buf + threadIdx.x * stride;
+    T* outs[3] = {A, cholQ, Q};
+    for (int which = 0; which < 3; ++which) {
+        T* dst = outs[which];
+        if (!dst) continue;
+        for (int e = 0; e < dd; ++e) mine[e] = T(0);
+        for (int c = 0; c < sp.ncomp; ++c) {
+            const int order = sp.order[c], osc = sp.osc[c], off = sp.off[c];
+            const T l = order == 0 ? T(0) : lam[s * hstride + c], v = var[s * hstride + c];
+            if (osc == 0) {
+                if (order <= 1) { Comp<T, 1> k; k.build(l, v, delta); emit_g<T, 1>(k, order == 0, jitter, d, off, which, mine); }
+                else if (order == 3) { Comp<T, 2> k; k.build(l, v, delta); emit<T, 2>(k, jitter, d, off, which, mine); }
+                else { Comp<T, 3> k; k.build(l, v, delta); emit<T, 3>(k, jitter, d, off, which, mine); }
+                continue;
+            }
+            const T w = omega[s * hstride + c];
+            if (order <= 1) {          // (one Matern state: both Kronecker orders coincide)
+                Comp<T, 2> k;
+                build_osc<T, 1, false>(l, v, w, delta, k);
+                emit_g<T, 2>(k, order == 0, jitter, d, off, which, mine);
+            } else if (order == 3) {
+                Comp<T, 4> k;
+                if (osc == 1) build_osc<T, 2, false>(l, v, w, delta, k); else build_osc<T, 2, true>(l, v, w, delta, k);
+                emit<T, 4>(k, jitter, d, off, which, mine);
+            } else {
+                Comp<T, 6> k;
+                if (osc == 1) build_osc<T, 3, false>(l, v, w, delta, k); else build_osc<T, 3, true>(l, v, w, delta, k);
+                emit<T, 6>(k, jitter, d, off, which, mine);
+            }
+        }
+        __syncthreads();
+        long nvalid = total - base;
+        if (nvalid > 64) nvalid = 64;
+        const long count = nvalid * dd;
+        T* gdst = dst + base * dd;
+        for (long e = threadIdx.x; e < count; e += 64) gdst[e] = buf[(e / dd) * stride + (e % dd)];
+        __syncthreads();
+    }
+}
+
+// argument checks shared by the two generalised entry points: 0, or the (negative) position of the offending argument
+inline int g_spec(int ncomp, const int* orders, const int* osc, GSpec& sp, bool& any_osc) {
+    if (ncomp < 1 || ncomp > MAXC) return -3;
+    if (!orders) return -4;
+    if (!osc) return -5;
+    sp.ncomp = ncomp;
+    any_osc = false;
+    int off = 0;
+    for (int c = 0; c < ncomp; ++c) {
+        if (orders[c] != 0 && orders[c] != 1 && orders[c] != 3 && orders[c] != 5) return -4;
+        if (osc[c] < 0 || osc[c] > 2) return -5;
+        sp.order[c] = orders[c];
+        sp.osc[c] = osc[c];
+        sp.off[c] = off;
+        off += (orders[c] == 0 ? 1 : (orders[c] + 1) / 2) * (osc[c] ? 2 : 1);
+        any_osc |= osc[c] != 0;
+    }
+    sp.d = off;
+    return 0;
+}
+
+template <typename T>
+int run_g(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, const T* lam, const T* var, const T* omega,
+          int per_series, const T* dt, T jitter, T* A, T* cholQ, T* Q, void* stream) {
+    if (B < 0) return -1;
+    if (n < 0) return -2;
+    GSpec sp;
+    bool any_osc;
+    const int bad = g_spec(ncomp, orders, osc, sp, any_osc);
+    if (bad) return bad;
+    if (B == 0 || n == 0) return 0;
+    if (!lam) return -6;
+    if (!var) return -7;
+    if (any_osc && !omega) return -8;
+    if (!dt) return -10;
+    if (!A) return -12;
+    const long total = B * n;
+    const size_t lds = size_t(64) * size_t((sp.d * sp.d) | 1) * sizeof(T);
+    if (lds > size_t(160) * 1024) return -100;              // (the limit of run(): d <= 17 in fp64)
+    if (lds > size_t(64) * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&sde_transitions_kernel<T>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return -100;
+    hipLaunchKernelGGL((sde_transitions_kernel<T>), dim3((unsigned)((total + 63) / 64)), dim3(64), lds,
+                       static_cast<hipStream_t>(stream), (long)B, (long)n, sp, lam, var, omega, per_series ? (long)ncomp : 0L, dt,
+                       jitter, A, cholQ, Q);
+    return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
+// reverse mode: grad_component with the third tangent.  g[0..2] = d/d (lam, var, omega) of <gA, A> + <gC, chol Q> over the
+// component's K x K block of the dense [.., d, d] gradients (row stride ld)
+template <typename T, int K>
+__device__ void contract3(const Comp<Dual3<T>, K>& c, bool order0, T jitter, int ld, const T* __restrict__ gA,
+                          const T* __restrict__ gC, T (&g)[3]) {
+    using Du = Dual3<T>;
+    g[0] = g[1] = g[2] = T(0);
+    if (gA) {
+        for (int i = 0; i < K; ++i)
+            for (int j = 0; j < K; ++j) {
+                const T w = gA[i * ld + j];
+                g[0] += w * c.A[i][j].a;
+                g[1] += w * c.A[i][j].b;
+                g[2] += w * c.A[i][j].c;
+            }
+    }
+    if (gC && !order0) {               // (order 0: chol Q = sqrt(jitter) I does not depend on the hyper-parameters)
+        Du Q[K][K], L[K][K];
+        bool zero;
+        comp_chol<Du, K>(c, Du(jitter), Q, L, zero, true);
+        if (!zero) {
+            for (int i = 0; i < K; ++i)
+                for (int j = 0; j <= i; ++j) {
+                    const T w = gC[i * ld + j];
+                    g[0] += w * L[i][j].a;
+                    g[1] += w * L[i][j].b;
+                    g[2] += w * L[i][j].c;
+                }
+        }
+    }
+}
+template <typename T>
+__global__ void __launch_bounds__(64) sde_transitions_grad_kernel(long B, long n, GSpec sp, const T* __restrict__ lam,
+                                                                  const T* __restrict__ var, const T* __restrict__ omega, long hstride,
+                                                                  const T* __restrict__ dt, T jitter, const T* __restrict__ gA,
+                                                                  const T* __restrict__ gC, T* __restrict__ out) {
+    using Du = Dual3<T>;
+    const long id = (long)blockIdx.x * 64 + threadIdx.x;
+    if (id >= B * n) return;
+    const long s = id / n;
+    const int d = sp.d;
+    const Du delta(dt[id]);
+    for (int c = 0; c < sp.ncomp; ++c) {
+        const int order = sp.order[c], osc = sp.osc[c], off = sp.off[c];
+        const Du l(order == 0 ? T(0) : lam[s * hstride + c], T(1), T(0), T(0)), v(var[s * hstride + c], T(0), T(1), T(0));
+        const T* ga = gA ? gA + id * d * d + off * d + off : nullptr;
+        const T* gc = gC ? gC + id * d * d + off * d + off : nullptr;
+        T g[3];
+        if (osc == 0) {
+            if (order <= 1) { Comp<Du, 1> k; k.build(l, v, delta); contract3<T, 1>(k, order == 0, jitter, d, ga, gc, g); }
+            else if (order == 3) { Comp<Du, 2> k; k.build(l, v, delta); contract3<T, 2>(k, false, jitter, d, ga, gc, g); }
+            else { Comp<Du, 3> k; k.build(l, v, delta); contract3<T, 3>(k, false, jitter, d, ga, gc, g); }
+        } else {
+            const Du w(omega[s * hstride + c], T(0), T(0), T(1));
+            if (order <= 1) {
+                Comp<Du, 2> k;
+                build_osc<Du, 1, false>(l, v, w, delta, k);
+                contract3<T, 2>(k, order == 0, jitter, d, ga, gc, g);
+            } else if (order == 3) {
+                Comp<Du, 4> k;
+                if (osc == 1) build_osc<Du, 2, false>(l, v, w, delta, k); else build_osc<Du, 2, true>(l, v, w, delta, k);
+                contract3<T, 4>(k, false, jitter, d, ga, gc, g);
+            } else {
+                Comp<Du, 6> k;
+                if (osc == 1) build_osc<Du, 3, false>(l, v, w, delta, k); else build_osc<Du, 3, true>(l, v, w, delta, k);
+                contract3<T, 6>(k, false, jitter, d, ga, gc, g);
+            }
+        }
+        T* o = out + (id * sp.ncomp + c) * 3;
+        o[0] = order == 0 ? T(0) : g[0];      // (order 0 has no lam)
+        o[1] = g[1];
+        o[2] = osc == 0 ? T(0) : g[2];
+    }
+}
+
+template <typename T>
+int run_g_grad(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, const T* lam, const T* var, const T* omega,
+               int per_series, const T* dt, T jitter, const T* gA, const T* gC, T* out, void* stream) {
+    if (B < 0) return -1;
+    if (n < 0) return -2;
+    GSpec sp;
+    bool any_osc;
+    const int bad = g_spec(ncomp, orders, osc, sp, any_osc);
+    if (bad) return bad;
+    if (B == 0 || n == 0) return 0;
+    if (!lam) return -6;
+    if (!var) return -7;
+    if (any_osc && !omega) return -8;
+    if (!dt) return -10;
+    if (!out) return -14;
+    const long total = B * n;
+    hipLaunchKernelGGL((sde_transitions_grad_kernel<T>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0,
+                       static_cast<hipStream_t>(stream), (long)B, (long)n, sp, lam, var, omega, per_series ? (long)ncomp : 0L, dt,
+                       jitter, gA, gC, out);
+    return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
 // R^-1 = (L L^T)^-1 from the Cholesky factor of the observation covariance (KalmanFilter._r_inv, kalman_filter.py:341-348: a
 // tf.linalg.cholesky_solve against the identity).  m <= 32: one wavefront, thread j solves column j of L^-1 by forward
 // substitution, then the threads share the m^2 entries of L^-T L^-1.  ONE launch instead of the eleven small torch / rocBLAS
@@ -451,6 +747,27 @@ int mf_sde_matern_transitions_f32(int64_t B, int64_t n, int ncomp, const int* or
                                   int per_series, const float* dt, float jitter, float* A, float* cholQ, float* Q,
                                   void* stream) {
     return run<float>(B, n, ncomp, orders, lam, var, per_series, dt, jitter, A, cholQ, Q, stream);
+}
+
+int mf_sde_transitions_f64(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, const double* lam, const double* var,
+                           const double* omega, int per_series, const double* dt, double jitter, double* A, double* cholQ, double* Q,
+                           void* stream) {
+    return run_g<double>(B, n, ncomp, orders, osc, lam, var, omega, per_series, dt, jitter, A, cholQ, Q, stream);
+}
+int mf_sde_transitions_f32(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, const float* lam, const float* var,
+                           const float* omega, int per_series, const float* dt, float jitter, float* A, float* cholQ, float* Q,
+                           void* stream) {
+    return run_g<float>(B, n, ncomp, orders, osc, lam, var, omega, per_series, dt, jitter, A, cholQ, Q, stream);
+}
+int mf_sde_transitions_grad_f64(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, const double* lam,
+                                const double* var, const double* omega, int per_series, const double* dt, double jitter,
+                                const double* g_A, const double* g_cholQ, double* out, void* stream) {
+    return run_g_grad<double>(B, n, ncomp, orders, osc, lam, var, omega, per_series, dt, jitter, g_A, g_cholQ, out, stream);
+}
+int mf_sde_transitions_grad_f32(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, const float* lam,
+                                const float* var, const float* omega, int per_series, const float* dt, float jitter,
+                                const float* g_A, const float* g_cholQ, float* out, void* stream) {
+    return run_g_grad<float>(B, n, ncomp, orders, osc, lam, var, omega, per_series, dt, jitter, g_A, g_cholQ, out, stream);
 }
 
 int mf_sde_matern_transitions_grad_f64(int64_t B, int64_t n, int ncomp, const int* orders, const double* lam, const double* var,

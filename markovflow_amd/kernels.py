@@ -6,8 +6,15 @@ Mirror of the part of ``markovflow/kernels`` (reference) that generates the BASE
 (``kernels/matern.py``), ``ConcatKernel`` / ``Sum`` / ``IndependentMultiOutput`` (``sde_kernel.py:540-690,826-878``), with
 the same method names and shapes.  The transition matrices ``A_k = exp(F Δt_k)`` and the Cholesky factors of
 ``Q_k = P∞ − A_k P∞ A_kᵀ`` are produced by one HIP kernel (``mf_sde_matern_transitions_*``) directly in the
-``[batch, T−1, d, d]`` layout ``StateSpaceModel`` takes; nothing else of the reference's kernels package (Product, Stack,
-Periodic, piecewise, latent-exp kernels) is mirrored.
+``[batch, T−1, d, d]`` layout ``StateSpaceModel`` takes.
+
+Periodic and quasi-periodic kernels: ``Constant`` (``kernels/constant.py``), ``HarmonicOscillator`` (``kernels/periodic.py``),
+``Product`` (``sde_kernel.py:691-822``) and ``SDEKernel.__mul__`` (``:347-350``).  A product of at most one Matérn factor, at most
+one ``HarmonicOscillator`` and any number of ``Constant`` factors is ONE generalised component - an order in {0, 1, 3, 5} (0: the
+constant), an optional oscillator ``ω = 2π / period`` and the Kronecker order - whose ``A_k = A_k^M ⊗ R(ωΔt_k)`` (or ``R ⊗ A_k^M``)
+and ``chol Q_k`` come from ``mf_sde_transitions_*``; ``Sum`` / ``IndependentMultiOutput`` concatenate such components like Matérn
+ones.  Plain Matérn kernels keep the Matérn generator.  Nothing else of the reference's kernels package (Stack, FactorAnalysis,
+piecewise, latent-exp kernels, products of two Matérns) is mirrored.
 
 Hyper-parameters are plain tensors / floats (the reference wraps them in ``gpflow.Parameter``); a hyper-parameter may also
 carry ``batch_shape`` (one value per series), which the reference expresses with ``StackKernel``.
@@ -31,6 +38,12 @@ Hyper = Union[float, torch.Tensor]
 def to_delta_time(time_points: torch.Tensor) -> torch.Tensor:
     """``Δt_k = t_{k+1} − t_k`` (markovflow/utils.py ``to_delta_time``)."""
     return time_points[..., 1:] - time_points[..., :-1]
+
+
+def _kron(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """Kronecker product of the trailing matrices; leading dims broadcast (markovflow/utils.py ``kronecker_product``)."""
+    out = a[..., :, None, :, None] * b[..., None, :, None, :]
+    return out.reshape(tuple(out.shape[:-4]) + (out.shape[-4] * out.shape[-3], out.shape[-2] * out.shape[-1]))
 
 
 def _block_diag(blocks: Sequence[torch.Tensor]) -> torch.Tensor:
@@ -69,8 +82,10 @@ class SDEKernel(abc.ABC):
 
     # -- what a concrete kernel provides -----------------------------------------------------------------------------
     @abc.abstractmethod
-    def _components(self) -> List["_MaternBase"]:
-        """The Matérn components whose block-diagonal concatenation is this kernel's state."""
+    def _components(self) -> List["SDEKernel"]:
+        """The components whose block-diagonal concatenation is this kernel's state.  A component has an ``order`` in {0, 1, 3, 5}
+        (0: constant; otherwise Matérn-order/2), ``_osc`` (0: no oscillator, 1: Matérn ⊗ R, 2: R ⊗ Matérn), the tensors ``_lambda``,
+        ``_variance_t`` and ``_omega`` (None without an oscillator) and ``_leaves()``, the hyper-parameter tensors behind them."""
 
     @abc.abstractmethod
     def initial_mean(self, batch_shape) -> torch.Tensor:
@@ -88,8 +103,7 @@ class SDEKernel(abc.ABC):
         return self._jitter * torch.eye(self.state_dim, dtype=ref.dtype, device=ref.device)
 
     def _needs_grad(self) -> bool:
-        return torch.is_grad_enabled() and any(
-            c._lengthscale_t.requires_grad or c._variance_t.requires_grad for c in self._components())
+        return torch.is_grad_enabled() and any(x.requires_grad for c in self._components() for x in c._leaves())
 
     def _torch_transitions(self, time_deltas: torch.Tensor, want_chol: bool, want_cov: bool):
         """The same closed forms in differentiable torch ops: used only while a hyper-parameter requires a gradient (the
@@ -97,7 +111,13 @@ class SDEKernel(abc.ABC):
         last link being the Fisher-identity kernel of ``KalmanFilter``."""
         blocks_a, blocks_q = [], []
         dtm = time_deltas[..., None, None]
-        for c in self._components():
+        comps = self._components()
+        for c in comps:
+            if not isinstance(c, _MaternBase):
+                a, q = _general_transitions(c, time_deltas)
+                blocks_a.append(a)
+                blocks_q.append(q)
+                continue
             lam = c._lambda.to(dtype=time_deltas.dtype, device=time_deltas.device)
             lam_b = lam[..., None, None, None] if lam.dim() > 0 else lam
             k = c.state_dim
@@ -115,7 +135,16 @@ class SDEKernel(abc.ABC):
             blocks_q.append(0.5 * (q + q.transpose(-1, -2)))
         a_s = _block_diag(blocks_a)
         q_s = _block_diag(blocks_q) + self.jitter_matrix.to(time_deltas)
-        chol = torch.linalg.cholesky(q_s) if want_chol else None
+        if want_chol and any(c.order == 0 for c in comps):
+            # an order-0 block is jitter I exactly: its factor is sqrt(jitter) I, zero for a zero jitter (the all-zero pass-through
+            # of cholesky_or_zero) - block by block, since a Cholesky of the whole matrix would stop at the zero block
+            facs = []
+            for c, q in zip(comps, blocks_q):
+                eye = torch.eye(c.state_dim, dtype=time_deltas.dtype, device=time_deltas.device)
+                facs.append(math.sqrt(self._jitter) * eye if c.order == 0 else torch.linalg.cholesky(q + self._jitter * eye))
+            chol = _block_diag([f.expand(tuple(time_deltas.shape) + tuple(f.shape[-2:])) for f in facs])
+        else:
+            chol = torch.linalg.cholesky(q_s) if want_chol else None
         return a_s, chol, (q_s if want_cov else None)
 
     def _device_transitions(self, time_deltas: torch.Tensor, want_chol: bool, want_cov: bool):
@@ -130,6 +159,8 @@ class SDEKernel(abc.ABC):
             return self._torch_transitions(time_deltas, want_chol, want_cov)
         dt = time_deltas.reshape(-1, n).contiguous()
         bsz = dt.shape[0]
+        if not all(c._osc == 0 and c.order != 0 for c in comps):
+            return self._general_device_transitions(comps, dt, batch, needs_grad, want_chol, want_cov)
         lam = [c._lambda.to(dtype=dt.dtype, device=dt.device) for c in comps]
         var = [c._variance_t.to(dtype=dt.dtype, device=dt.device) for c in comps]
         per_series = any(x.dim() > 0 for x in lam + var)
@@ -155,6 +186,34 @@ class SDEKernel(abc.ABC):
         shape = batch + (n, d, d)
         return (a_s.reshape(shape), None if chol is None else chol.reshape(shape),
                 None if cov is None else cov.reshape(shape))
+
+    def _general_device_transitions(self, comps, dt, batch, needs_grad, want_chol, want_cov):
+        """``_device_transitions`` when a component is of order 0 or has an oscillator: ``mf_sde_transitions_*``, and under a
+        gradient ``_SdeTransitions`` (its backward is ``mf_sde_transitions_grad_*``)."""
+        bsz, n = dt.shape
+        d = self.state_dim
+        zero = torch.zeros((), dtype=dt.dtype, device=dt.device)
+        hyper = [[c._lambda.to(dtype=dt.dtype, device=dt.device) for c in comps],
+                 [c._variance_t.to(dtype=dt.dtype, device=dt.device) for c in comps],
+                 [zero if c._omega is None else c._omega.to(dtype=dt.dtype, device=dt.device) for c in comps]]
+        per_series = any(x.dim() > 0 for group in hyper for x in group)
+        if per_series:
+            lam_t, var_t, om_t = (torch.stack([x.expand(batch).reshape(-1) for x in group], dim=-1).contiguous() for group in hyper)
+        else:
+            lam_t, var_t, om_t = (torch.stack(group).contiguous() for group in hyper)
+        orders, oscs = tuple(c.order for c in comps), tuple(c._osc for c in comps)
+        shape = batch + (n, d, d)
+        if needs_grad:
+            a_s, chol = _SdeTransitions.apply(dt, lam_t, var_t, om_t, orders, oscs, bool(per_series), float(self._jitter),
+                                              bool(want_chol))
+            return a_s.reshape(shape), (chol.reshape(shape) if want_chol else None), None
+        a_s = torch.empty((bsz, n, d, d), dtype=dt.dtype, device=dt.device)
+        chol = torch.empty_like(a_s) if want_chol else None
+        cov = torch.empty_like(a_s) if want_cov else None
+        _lib.call("mf_sde_transitions", dt.dtype, bsz, n, len(comps), (ctypes.c_int * len(comps))(*orders),
+                  (ctypes.c_int * len(comps))(*oscs), _lib.ptr(lam_t), _lib.ptr(var_t), _lib.ptr(om_t), int(per_series), _lib.ptr(dt),
+                  self._jitter, _lib.ptr(a_s), _lib.ptr(chol), _lib.ptr(cov), _lib.stream_ptr(dt.device))
+        return (a_s.reshape(shape), None if chol is None else chol.reshape(shape), None if cov is None else cov.reshape(shape))
 
     def state_transitions(self, transition_times: torch.Tensor, time_deltas: torch.Tensor) -> torch.Tensor:
         """``A_k = exp(F Δt_k)``, ``batch_shape + [num_transitions, state_dim, state_dim]`` (sde_kernel.py:299-310)."""
@@ -261,6 +320,10 @@ class SDEKernel(abc.ABC):
         assert self.output_dim == other.output_dim                         # sde_kernel.py:342-345
         return Sum([self, other])
 
+    def __mul__(self, other: "SDEKernel") -> "Product":
+        assert self.output_dim == other.output_dim                         # sde_kernel.py:347-350
+        return Product([self, other])
+
 
 class _MaternTransitions(torch.autograd.Function):
     """``(A [B,n,d,d], chol Q [B,n,d,d])`` of a concatenation of Matern components as a differentiable function of the stacked
@@ -303,6 +366,92 @@ class _MaternTransitions(torch.autograd.Function):
             if not per_series:
                 g = torch.sum(g, dim=0)                                  # shared hyper-parameters: [ncomp, 2]
         return None, g[..., 0].contiguous(), g[..., 1].contiguous(), None, None, None, None
+
+
+class _SdeTransitions(torch.autograd.Function):
+    """``_MaternTransitions`` for generalised components: ``(A, chol Q)`` as a differentiable function of the stacked ``lam``, ``var``
+    and ``omega`` (= 2π / period) - forward ``mf_sde_transitions_*``, backward ``mf_sde_transitions_grad_*`` (the same closed forms
+    with three tangents), summed over the transitions here."""
+
+    @staticmethod
+    def forward(ctx, dt, lam_t, var_t, om_t, orders, oscs, per_series, jitter, want_chol):
+        bsz, n = dt.shape
+        d = sum((1 if o == 0 else (o + 1) // 2) * (2 if r else 1) for o, r in zip(orders, oscs))
+        a_s = torch.empty((bsz, n, d, d), dtype=dt.dtype, device=dt.device)
+        chol = torch.empty_like(a_s) if want_chol else None
+        lam_c, var_c, om_c = lam_t.detach().contiguous(), var_t.detach().contiguous(), om_t.detach().contiguous()
+        _lib.call("mf_sde_transitions", dt.dtype, bsz, n, len(orders), (ctypes.c_int * len(orders))(*orders),
+                  (ctypes.c_int * len(orders))(*oscs), _lib.ptr(lam_c), _lib.ptr(var_c), _lib.ptr(om_c), int(per_series),
+                  _lib.ptr(dt.detach()), jitter, _lib.ptr(a_s), _lib.ptr(chol), None, _lib.stream_ptr(dt.device))
+        ctx.save_for_backward(dt.detach(), lam_c, var_c, om_c)
+        ctx.meta = (orders, oscs, per_series, jitter)
+        if not want_chol:
+            chol = a_s.new_zeros(())
+            ctx.mark_non_differentiable(chol)
+        return a_s, chol
+
+    @staticmethod
+    def backward(ctx, g_a, g_chol):
+        dt, lam_c, var_c, om_c = ctx.saved_tensors
+        orders, oscs, per_series, jitter = ctx.meta
+        bsz, n = dt.shape
+        part = torch.empty((bsz, n, len(orders), 3), dtype=dt.dtype, device=dt.device)
+        with torch.no_grad():
+            ga = None if g_a is None else g_a.contiguous()
+            gc = None if (g_chol is None or g_chol.dim() == 0) else g_chol.contiguous()
+            _lib.call("mf_sde_transitions_grad", dt.dtype, bsz, n, len(orders), (ctypes.c_int * len(orders))(*orders),
+                      (ctypes.c_int * len(orders))(*oscs), _lib.ptr(lam_c), _lib.ptr(var_c), _lib.ptr(om_c), int(per_series),
+                      _lib.ptr(dt), jitter, _lib.ptr(ga), _lib.ptr(gc), _lib.ptr(part), _lib.stream_ptr(dt.device))
+            g = torch.sum(part, dim=1)                                   # [B, ncomp, 3]
+            if not per_series:
+                g = torch.sum(g, dim=0)                                  # shared hyper-parameters: [ncomp, 3]
+        return None, g[..., 0].contiguous(), g[..., 1].contiguous(), g[..., 2].contiguous(), None, None, None, None, None
+
+
+def _general_transitions(c: "SDEKernel", time_deltas: torch.Tensor):
+    """``(A, Q − jitter)`` of ONE generalised component in differentiable torch ops - the closed forms of ``mf_sde_transitions_*``
+    (csrc/mf_sde.hip): the Matérn factor ``e^{−λΔt}(I + NΔt + N²Δt²/2)`` (order 0: ``[1]``), Kronecker-multiplied with the rotation
+    ``R(ωΔt)`` when there is an oscillator; ``Q = P∞ − A P∞ Aᵀ``, symmetrised - and exactly zero for order 0."""
+    x = time_deltas
+    one, zero = torch.ones_like(x), torch.zeros_like(x)
+
+    def hyper(h):                                       # [] or batch_shape -> broadcastable against batch_shape + [n]
+        h = h.to(dtype=x.dtype, device=x.device)
+        return h[..., None] if h.dim() > 0 else h
+
+    def mat(rows):
+        return torch.stack([torch.stack([e * one for e in row], dim=-1) for row in rows], dim=-2)
+
+    lam, var = hyper(c._lambda), hyper(c._variance_t)
+    if c.order == 0:
+        a, p = mat([[one]]), mat([[var]])
+    else:
+        e = torch.exp(-lam * x)[..., None, None]
+        l2 = lam * lam
+        if c.order == 1:
+            nil, p = mat([[zero]]), mat([[var]])
+        elif c.order == 3:
+            nil = mat([[lam, one], [-l2, -lam]])
+            p = mat([[var, zero], [zero, var * l2]])
+        else:
+            nil = mat([[lam, one, zero], [zero, lam, one], [-l2 * lam, -3.0 * l2, -2.0 * lam]])
+            l23 = l2 / 3.0
+            p = mat([[var, zero, -var * l23], [zero, var * l23, zero], [-var * l23, zero, var * l2 * l2]])
+        xm = x[..., None, None]
+        a = torch.eye(nil.shape[-1], dtype=x.dtype, device=x.device) + nil * xm
+        if c.order == 5:
+            a = a + (nil @ nil) * (0.5 * xm ** 2)
+        a = a * e
+    if c._osc:
+        th = hyper(c._omega) * x
+        cos, sin = torch.cos(th), torch.sin(th)
+        rot = mat([[cos, -sin], [sin, cos]])
+        eye2 = torch.eye(2, dtype=x.dtype, device=x.device)
+        a, p = (_kron(a, rot), _kron(p, eye2)) if c._osc == 1 else (_kron(rot, a), _kron(eye2, p))
+    if c.order == 0:
+        return a, torch.zeros_like(a)
+    q = p - a @ p @ a.transpose(-1, -2)
+    return a, 0.5 * (q + q.transpose(-1, -2))
 
 
 class StationaryKernel(SDEKernel, abc.ABC):
@@ -378,6 +527,8 @@ def _known_positive(*tensors: torch.Tensor) -> bool:
 
 class _MaternBase(StationaryKernel):
     order = 0   # Matérn-order/2
+    _osc = 0    # a component without an oscillator
+    _omega = None
 
     def __init__(self, lengthscale: Hyper, variance: Hyper, output_dim: int = 1, jitter: float = 0.0, device=None,
                  dtype=torch.float64) -> None:
@@ -422,6 +573,9 @@ class _MaternBase(StationaryKernel):
 
     def _components(self):
         return [self]
+
+    def _leaves(self):
+        return (self._lengthscale_t, self._variance_t)
 
 
 class Matern12(_MaternBase):
@@ -485,6 +639,205 @@ class Matern52(_MaternBase):
         p[..., 1, 1] = var * l23
         p[..., 2, 2] = var * lam ** 4
         return p
+
+
+class Constant(StationaryKernel):
+    """Constant kernel ``C(x, x') = σ²`` (constant.py:27-153): one state, ``F = [0]``, ``A_k = [1]``, ``P∞ = [σ²]`` - the order-0
+    component.  ``Q_k = jitter·I`` exactly: the precision-form Kalman filter therefore needs ``jitter > 0`` on the kernel that
+    builds the state space model (the ``Sum`` around it).  With ``jitter = 0`` the zero factor passes through as in the reference
+    and the filter reports the non-positive pivot through ``MarkovflowAmdError``."""
+    order = 0
+    _osc = 0
+    _omega = None
+
+    def __init__(self, variance: Hyper, output_dim: int = 1, jitter: float = 0.0, device=None, dtype=torch.float64) -> None:
+        super().__init__(output_dim, jitter)
+        dev = device if device is not None else (variance.device if isinstance(variance, torch.Tensor) else "cpu")
+        self._variance_t = torch.as_tensor(variance, dtype=dtype, device=dev)
+        if not _known_positive(self._variance_t):
+            raise ValueError("variance must be positive.")                   # constant.py:54-55
+
+    @property
+    def state_dim(self) -> int:
+        return 1
+
+    @property
+    def variance(self) -> torch.Tensor:
+        return self._variance_t
+
+    @property
+    def _lambda(self) -> torch.Tensor:
+        return torch.zeros((), dtype=self._variance_t.dtype, device=self._variance_t.device)
+
+    @property
+    def feedback_matrix(self) -> torch.Tensor:
+        return torch.zeros((1, 1), dtype=self._variance_t.dtype, device=self._variance_t.device)
+
+    @property
+    def steady_state_covariance(self) -> torch.Tensor:
+        return self._variance_t[..., None, None].clone()
+
+    def invalidate_cache(self) -> None:
+        """Forget the positivity check of the variance (see ``_MaternBase.invalidate_cache``)."""
+        for t in self._leaves():
+            _POSITIVE.pop(id(t), None)
+
+    def _components(self):
+        return [self]
+
+    def _leaves(self):
+        return (self._variance_t,)
+
+
+class HarmonicOscillator(Constant):
+    """Periodic kernel ``C(x, x') = σ² cos(2π (x − x') / period)`` (periodic.py:27-203): two states, ``F = [[0, −ω], [ω, 0]]``,
+    ``A_k = R(ωΔt_k) = [[cos, −sin], [sin, cos]]``, ``P∞ = σ² I``, ``ω = 2π / period`` - the order-0 component with an oscillator.
+    ``Q_k = jitter·I`` exactly (a rotation adds no noise), so what ``Constant`` says about ``jitter`` holds here too."""
+    _osc = 1
+
+    def __init__(self, variance: Hyper, period: Hyper, output_dim: int = 1, jitter: float = 0.0, device=None,
+                 dtype=torch.float64) -> None:
+        dev = device if device is not None else next((x.device for x in (variance, period) if isinstance(x, torch.Tensor)), "cpu")
+        super().__init__(variance, output_dim, jitter, device=dev, dtype=dtype)
+        self._period_t = torch.as_tensor(period, dtype=dtype, device=dev)
+        if not _known_positive(self._period_t):
+            raise ValueError("period must be positive.")                     # periodic.py:84-85
+
+    @property
+    def state_dim(self) -> int:
+        return 2
+
+    @property
+    def period(self) -> torch.Tensor:
+        return self._period_t
+
+    @property
+    def _omega(self) -> torch.Tensor:
+        return (2.0 * math.pi) / self._period_t
+
+    @property
+    def feedback_matrix(self) -> torch.Tensor:
+        om = self._omega
+        zero = torch.zeros_like(om)
+        return torch.stack([torch.stack([zero, -om], dim=-1), torch.stack([om, zero], dim=-1)], dim=-2)
+
+    @property
+    def steady_state_covariance(self) -> torch.Tensor:
+        var = self._variance_t
+        return var[..., None, None] * torch.eye(2, dtype=var.dtype, device=var.device)
+
+    def _leaves(self):
+        return (self._variance_t, self._period_t)
+
+
+class Product(StationaryKernel):
+    """Product of kernels (sde_kernel.py:691-822): ``A_k``, ``P∞`` and the emission matrix are the Kronecker products of the
+    children's, in the order of ``kernels`` (``kronecker_product`` of the reference).
+
+    Supported: at most one Matérn factor, at most one ``HarmonicOscillator`` and any number of ``Constant`` factors (which only
+    scale the variance) - a decaying oscillation ``Matern * HarmonicOscillator`` with ``σ² k_Matérn(r) cos(ωr)``, state dimension
+    2, 4 or 6.  Anything else (Matérn × Matérn, two oscillators, a ``Sum`` or ``Product`` as a child) raises ``NotImplementedError``.
+    The whole product is ONE generalised component of the HIP generator ``mf_sde_transitions_*``.  Without a Matérn factor it is of
+    order 0 and ``Q_k = jitter·I`` exactly: see ``Constant`` on what that asks of ``jitter``.
+
+    ``feedback_matrix`` is the Kronecker SUM ``F₁ ⊗ I + I ⊗ F₂``, for which ``A_k = exp(F Δt_k)`` holds as ``StationaryKernel``
+    documents.  The reference returns the Kronecker PRODUCT of the children's feedback matrices (sde_kernel.py:783-793), for which
+    that identity is false; nothing on the path consumes either."""
+
+    def __init__(self, kernels: List[SDEKernel], jitter: float = 0.0):
+        self._kernels = list(kernels)
+        assert self._kernels, "There must be at least one child kernel."    # sde_kernel.py:745-749
+        if not all(isinstance(k, SDEKernel) for k in self._kernels):
+            raise TypeError("can only combine Kernel instances")
+        assert len({k.output_dim for k in self._kernels}) == 1, "All kernels must have the same output dimension"
+        matern = [k for k in self._kernels if isinstance(k, _MaternBase)]
+        osc = [k for k in self._kernels if isinstance(k, HarmonicOscillator)]
+        rest = [k for k in self._kernels if not isinstance(k, (_MaternBase, Constant))]
+        if rest or len(matern) > 1 or len(osc) > 1:
+            raise NotImplementedError(
+                "Product supports at most one Matern12 / Matern32 / Matern52 factor, at most one HarmonicOscillator and any number "
+                "of Constant factors; got " + " * ".join(type(k).__name__ for k in self._kernels))
+        self._matern = matern[0] if matern else None
+        self._oscillator = osc[0] if osc else None
+        self.order = self._matern.order if matern else 0
+        if not osc:
+            self._osc = 0
+        elif not matern or self._matern.state_dim == 1:
+            self._osc = 1                                                    # (a 1 x 1 factor: both Kronecker orders coincide)
+        else:
+            self._osc = 1 if self._kernels.index(self._matern) < self._kernels.index(self._oscillator) else 2
+        super().__init__(self._kernels[0].output_dim, jitter)
+
+    @property
+    def kernels(self) -> List[SDEKernel]:
+        return self._kernels
+
+    @property
+    def state_dim(self) -> int:
+        return math.prod(k.state_dim for k in self._kernels)
+
+    @property
+    def variance(self) -> torch.Tensor:
+        """The product of the factors' variances."""
+        return self._variance_t
+
+    @property
+    def _variance_t(self) -> torch.Tensor:
+        out = self._kernels[0]._variance_t
+        for k in self._kernels[1:]:
+            out = out * k._variance_t
+        return out
+
+    @property
+    def _lambda(self) -> torch.Tensor:
+        if self._matern is not None:
+            return self._matern._lambda
+        ref = self._kernels[0]._variance_t
+        return torch.zeros((), dtype=ref.dtype, device=ref.device)
+
+    @property
+    def _omega(self):
+        return None if self._oscillator is None else self._oscillator._omega
+
+    @property
+    def feedback_matrix(self) -> torch.Tensor:
+        out = None
+        for k in self._kernels:
+            f = k.feedback_matrix
+            if out is None:
+                out = f
+                continue
+            eye_l = torch.eye(out.shape[-1], dtype=f.dtype, device=f.device)
+            eye_r = torch.eye(f.shape[-1], dtype=f.dtype, device=f.device)
+            out = _kron(out, eye_r) + _kron(eye_l, f)
+        return out
+
+    @property
+    def steady_state_covariance(self) -> torch.Tensor:
+        out = None
+        for k in self._kernels:
+            p = k.steady_state_covariance
+            out = p if out is None else _kron(out, p)
+        return out
+
+    def generate_emission_model(self, time_points: torch.Tensor) -> EmissionModel:
+        """The Kronecker product of the children's emission matrices (sde_kernel.py:808-822); for the supported products that
+        is the base class's ``[1, 0, …]``."""
+        out = None
+        for k in self._kernels:
+            h = k.generate_emission_model(time_points).emission_matrix
+            out = h if out is None else _kron(out, h)
+        return EmissionModel(out.contiguous())
+
+    def invalidate_cache(self) -> None:
+        for k in self._kernels:
+            k.invalidate_cache()
+
+    def _components(self):
+        return [self]
+
+    def _leaves(self):
+        return tuple(x for k in self._kernels for x in k._leaves())
 
 
 class ConcatKernel(StationaryKernel, abc.ABC):

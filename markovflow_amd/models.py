@@ -14,10 +14,15 @@ import torch
 
 from . import _lib
 from .kalman_filter import KalmanFilter
-from .kernels import IndependentMultiOutput, SDEKernel
+from .kernels import IndependentMultiOutput, SDEKernel, _MaternBase
 from .posterior import AnalyticPosteriorProcess
 from .state_space_model import StateSpaceModel
 
+
+def _all_matern(comps) -> bool:
+    """True when every component is a plain Matérn kernel - what the fused ``mf_gpr_matern_*`` kernels generate.  A component of
+    order 0 or with an oscillator (``Constant``, ``HarmonicOscillator``, ``Product``) takes the materialised route."""
+    return all(isinstance(c, _MaternBase) for c in comps)
 
 
 def _gpr_partition(bsz: int, nt: int, chunks: int, lanes: int = 65536):
@@ -169,7 +174,10 @@ class GaussianProcessRegression:
         invisible to that check: call this after such a write."""
         self._fused_cache = None
         for comp in self._kernel._components():
-            comp._lambda_cached = None          # (the components keep sqrt(order) / lengthscale per lengthscale version)
+            if isinstance(comp, _MaternBase):
+                comp._lambda_cached = None      # (the components keep sqrt(order) / lengthscale per lengthscale version)
+            else:
+                comp.invalidate_cache()         # (a Product hands it on to its Matérn factor)
 
     fused_backward = True    # set False to force the materialised route whenever a gradient is required
 
@@ -178,6 +186,8 @@ class GaussianProcessRegression:
         kernel -> state space model step fused; d <= 6: one or two components, one output, chains of more than 64 points).  ``None``:
         the materialised, differentiable route runs (row signatures, observations that require a gradient, short chains)."""
         n = self._time_points.shape[-1]
+        if not _all_matern(comps):
+            return None
         if (not self.fused_backward or rows or multi or m != 1 or d > 6 or n <= 64 or self._observations.requires_grad
                 or self._time_points.requires_grad):
             return None
@@ -212,6 +222,8 @@ class GaussianProcessRegression:
         multi = isinstance(self._kernel, IndependentMultiOutput)
         m = self._observations.shape[-1]
         d = self._kernel.state_dim
+        if not _all_matern(comps):
+            return None
         # register kernels (d <= 6): one or two components, one output; row kernels (7 <= d <= 15): any concatenation, one
         # output (Sum) or one per component (IndependentMultiOutput, up to four; eight for d >= 10) - BASELINE config 4 is 3 x Matern-5/2, 3 outputs
         rows = 7 <= d <= 15 and len(comps) <= 15 and (m == len(comps) <= (8 if d >= 10 else 4) if multi else m == 1)
@@ -301,6 +313,8 @@ class GaussianProcessRegression:
         kernels do not apply (row signatures, several outputs, d > 6, short chains, gradients required)."""
         comps = self._kernel._components()
         d, m, n = self._kernel.state_dim, self._observations.shape[-1], self._time_points.shape[-1]
+        if not _all_matern(comps):
+            return None
         if (not self.fused or not self.fused_backward or not self._observations.is_cuda or isinstance(self._kernel, IndependentMultiOutput)
                 or len(comps) > 2 or m != 1 or d > 6 or n <= 64):
             return None
