@@ -692,6 +692,42 @@ int mf_ssm_marginals_grad_f32(int64_t B, int64_t T, int d, const float* cholP0, 
  * (M_k, lambda_k) of the adjoint recursion - (2 d^2 + 2 d) elements. */
 size_t mf_ssm_adjoint_workspace_bytes(int64_t B, int64_t T, int d, int elem_size);
 
+/*
+ * Likelihoods of the CVI model (markovflow/models/variational_cvi.py:321-368 over gpflow's likelihoods; csrc/mf_lik.hip).  One
+ * lane per data point, N points (a batch of series flattened).  `lik`: 0 Gaussian, params [variance]; 1 Bernoulli with gpflow's
+ * probit link  p = 0.5 (1 + erf(f / sqrt 2)) (1 - 2e-3) + 1e-3, y in {0, 1}, no params; 2 Poisson with exp link and bin size 1,
+ * no params; 3 Student-t, params [scale, df, lgamma((df + 1) / 2) - lgamma(df / 2) - log(df pi) / 2 - log(scale)].
+ * `params`, `nodes` and `weights` are HOST arrays of doubles in both precisions (as `orders` / `osc` of mf_sde_transitions):
+ * the nq <= 32 nodes and weights of a Gauss-Hermite rule (numpy.polynomial.hermite.hermgauss; weights sum to sqrt pi), which
+ * travel by value in the kernel arguments.  Gaussian and Poisson expectations are closed forms; Bernoulli and Student-t are
+ *   VE = sum w_i l(f_i),  dVE/dmu = sum w_i l'(f_i),  dVE/dvar = sum w_i l'(f_i) x_i / sqrt(2 var),   f_i = mu + sqrt(2 var) x_i,
+ * w_i = weights_i / sqrt pi: the exact derivatives of the discretised sum.  A point with fvar <= 0 or NaN gets NaN in its own
+ * outputs.  Returns 0, -(position of the offending argument) - unknown lik, nq outside 1..32, a missing or non-positive
+ * parameter, a NULL array - or -1000 (launch failed); N = 0 returns 0 without a launch.
+ *
+ * mf_lik_variational_expectations: ve, g_mu, g_var [N], any of them may be NULL.
+ * mf_lik_cvi_site_update: nat1, nat2 [N] updated IN PLACE with the gradient in the expectation parameters [mu, var + mu^2],
+ *   g2 = dVE/dvar, g1 = dVE/dmu - 2 g2 mu, nat <- (1 - lr) nat + lr g  (0 <= lr <= 1); ve [N] optional.
+ * mf_lik_predict_log_density: out [N] = log int p(y | f) N(f | mu, var) df - Gaussian in closed form, the others as a
+ *   log-sum-exp over the nodes shifted by its maximum.
+ */
+int mf_lik_variational_expectations_f64(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                                        const double* fmu, const double* fvar, const double* y, double* ve, double* g_mu,
+                                        double* g_var, void* stream);
+int mf_lik_variational_expectations_f32(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                                        const float* fmu, const float* fvar, const float* y, float* ve, float* g_mu, float* g_var,
+                                        void* stream);
+int mf_lik_cvi_site_update_f64(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                               const double* fmu, const double* fvar, const double* y, double lr, double* nat1, double* nat2,
+                               double* ve, void* stream);
+int mf_lik_cvi_site_update_f32(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                               const float* fmu, const float* fvar, const float* y, float lr, float* nat1, float* nat2, float* ve,
+                               void* stream);
+int mf_lik_predict_log_density_f64(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                                   const double* fmu, const double* fvar, const double* y, double* out, void* stream);
+int mf_lik_predict_log_density_f32(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                                   const float* fmu, const float* fvar, const float* y, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,10 +17,11 @@ from .kalman_filter import (
     UnivariateGaussianSitesNat,
 )
 from .state_space_model import StateSpaceModel, state_space_model_from_covariances
-from . import conditionals, distributed, kernels, models, ssm_gaussian_transformations
+from . import conditionals, distributed, kernels, likelihoods, models, ssm_gaussian_transformations
 from .kernels import (Constant, HarmonicOscillator, IndependentMultiOutput, Matern12, Matern32, Matern52, Product, SDEKernel,
                       StationaryKernel, Sum)
-from .models import GaussianProcessRegression
+from .likelihoods import Bernoulli, Gaussian, Likelihood, Poisson, StudentT
+from .models import CVIGaussianProcess, GaussianProcessRegression
 from .posterior import AnalyticPosteriorProcess, ConditionalProcess
 from ._lib import MarkovflowAmdError, check_errors, errors_as_nan, set_synchronous_checks
 
@@ -31,4 +32,5 @@ __all__ = [
     "state_space_model_from_covariances", "conditionals", "distributed", "kernels", "models", "ssm_gaussian_transformations", "SDEKernel", "StationaryKernel", "Matern12", "Matern32",
     "Matern52", "Sum", "IndependentMultiOutput", "Constant", "HarmonicOscillator", "Product", "GaussianProcessRegression", "AnalyticPosteriorProcess", "ConditionalProcess",
     "MarkovflowAmdError", "check_errors", "errors_as_nan", "set_synchronous_checks",
+    "likelihoods", "Likelihood", "Gaussian", "Bernoulli", "Poisson", "StudentT", "CVIGaussianProcess",
 ]

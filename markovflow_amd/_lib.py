@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MF_LIB_PATH", os.path.join(_HERE, "libmarkovflow_amd.so"))   # override: A/B builds
 
 _i64, _int, _vp, _sz = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t
+_hd = ctypes.POINTER(ctypes.c_double)        # a HOST array of doubles (likelihood parameters, quadrature rule)
 
 # name -> (restype, argtypes with the scalar type written as "T" / "Tp")
 _SIGS = {
@@ -68,6 +69,9 @@ _SIGS = {
                                   _int, "Tp", "T", "Tp", "Tp", "Tp", _vp]),
     "mf_sde_transitions_grad": (_int, [_i64, _i64, _int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), "Tp", "Tp", "Tp",
                                        _int, "Tp", "T", "Tp", "Tp", "Tp", _vp]),
+    "mf_lik_variational_expectations": (_int, [_i64, _int, _hd, _int, _hd, _hd, "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
+    "mf_lik_cvi_site_update": (_int, [_i64, _int, _hd, _int, _hd, _hd, "Tp", "Tp", "Tp", "T", "Tp", "Tp", "Tp", _vp]),
+    "mf_lik_predict_log_density": (_int, [_i64, _int, _hd, _int, _hd, _hd, "Tp", "Tp", "Tp", "Tp", _vp]),
 }
 _PLAIN = {
     "mf_version": (_int, []),

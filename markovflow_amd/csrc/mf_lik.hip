@@ -1,0 +1,303 @@
+// Likelihoods for the CVI model (markovflow/models/variational_cvi.py:321-368 with gpflow's likelihoods underneath): per data
+// point the expectation of log p(y | f) under N(f | mu, s2), its derivatives with respect to mu and s2, the natural-parameter
+// site update built from them, and the log predictive density log E[p(y | f)].
+//   lik 0  Gaussian            params [variance]             closed forms
+//   lik 1  Bernoulli, probit   gpflow's inv_probit: p = 0.5 (1 + erf(f / sqrt 2)) (1 - 2e-3) + 1e-3
+//   lik 2  Poisson, exp link   bin size 1                    closed forms (VE); quadrature (predictive density)
+//   lik 3  Student-t           params [scale, df, const]     const = lgamma((df+1)/2) - lgamma(df/2) - log(df pi)/2 - log scale
+// Bernoulli and Student-t use an nq-point Gauss-Hermite rule: f_i = mu + sqrt(2 s2) x_i,
+//   VE = sum w_i l(f_i),  dVE/dmu = sum w_i l'(f_i),  dVE/ds2 = sum w_i l'(f_i) x_i / sqrt(2 s2)        (w_i = weight_i / sqrt pi)
+// - the exact derivatives of the discretised sum, which is what the reference's tape through ndiagquad yields.
+// One lane per data point; the rule travels by value in the kernel arguments and the loop over its nodes is wavefront-uniform, so
+// nodes and weights are scalar loads; no LDS, no cross-lane traffic, no temporaries in memory.
+#include "../../include/markovflow_amd.h"
+
+#include <cmath>
+#include <hip/hip_runtime.h>
+
+namespace {
+
+constexpr int MAXQ = 32;
+
+template <typename T> struct Rule {
+    int nq;
+    T x[MAXQ];     // nodes
+    T w[MAXQ];     // weights / sqrt(pi)  (variational expectations)  or  log(weights / sqrt(pi))  (predictive density)
+};
+template <typename T> struct Par { T p0, p1, p2; };
+
+__device__ __forceinline__ float m_exp(float x) { return expf(x); }
+__device__ __forceinline__ double m_exp(double x) { return exp(x); }
+__device__ __forceinline__ float m_log(float x) { return logf(x); }
+__device__ __forceinline__ double m_log(double x) { return log(x); }
+__device__ __forceinline__ float m_log1p(float x) { return log1pf(x); }
+__device__ __forceinline__ double m_log1p(double x) { return log1p(x); }
+__device__ __forceinline__ float m_erf(float x) { return erff(x); }
+__device__ __forceinline__ double m_erf(double x) { return erf(x); }
+__device__ __forceinline__ float m_sqrt(float x) { return sqrtf(x); }
+__device__ __forceinline__ double m_sqrt(double x) { return sqrt(x); }
+__device__ __forceinline__ float m_lgamma(float x) { return lgammaf(x); }
+__device__ __forceinline__ double m_lgamma(double x) { return lgamma(x); }
+
+template <typename T> __device__ __forceinline__ T nan_of() { return T(NAN); }
+
+// log p(y | f) and, when asked, its derivative in f.  Poisson: WITHOUT - lgamma(y + 1), which does not depend on f; the caller
+// subtracts it once per point, outside its loop over the nodes.
+template <typename T, int LIK, bool DERIV>
+__device__ __forceinline__ T log_prob(T f, T y, const Par<T>& p, T& dl) {
+    constexpr T LOG_2PI = T(1.8378770664093454835606594728112);
+    if (LIK == 0) {
+        const T r = y - f, iv = T(1) / p.p0;
+        if (DERIV) dl = r * iv;
+        return T(-0.5) * (LOG_2PI + m_log(p.p0)) - T(0.5) * r * r * iv;
+    } else if (LIK == 1) {
+        constexpr T JIT = T(1e-3), INV_SQRT2 = T(0.70710678118654752440084436210485), INV_SQRT_2PI = T(0.3989422804014326779399460599343);
+        const T pr = T(0.5) * (T(1) + m_erf(f * INV_SQRT2)) * (T(1) - T(2) * JIT) + JIT;
+        if (DERIV) {
+            const T dp = (T(1) - T(2) * JIT) * INV_SQRT_2PI * m_exp(T(-0.5) * f * f);
+            dl = dp * (y / pr - (T(1) - y) / (T(1) - pr));
+        }
+        return y * m_log(pr) + (T(1) - y) * m_log1p(-pr);
+    } else if (LIK == 2) {
+        const T e = m_exp(f);
+        if (DERIV) dl = y - e;
+        return y * f - e;
+    } else {
+        const T r = y - f, a = p.p1 * p.p0 * p.p0, r2 = r * r;      // a = df scale^2
+        if (DERIV) dl = (p.p1 + T(1)) * r / (a + r2);
+        return p.p2 - T(0.5) * (p.p1 + T(1)) * m_log1p(r2 / a);
+    }
+}
+
+// the expectation and its two derivatives at one point (fvar > 0)
+template <typename T, int LIK>
+__device__ __forceinline__ void expectations(const Rule<T>& q, const Par<T>& p, T mu, T s2, T y, T& ve, T& gm, T& gv) {
+    if (LIK == 0) {
+        constexpr T LOG_2PI = T(1.8378770664093454835606594728112);
+        const T r = y - mu, iv = T(1) / p.p0;
+        ve = T(-0.5) * (LOG_2PI + m_log(p.p0)) - T(0.5) * (r * r + s2) * iv;
+        gm = r * iv;
+        gv = T(-0.5) * iv;
+    } else if (LIK == 2) {
+        const T e = m_exp(mu + T(0.5) * s2);
+        ve = y * mu - e - m_lgamma(y + T(1));
+        gm = y - e;
+        gv = T(-0.5) * e;
+    } else {
+        const T sd = m_sqrt(T(2) * s2);
+        T a0 = T(0), a1 = T(0), a2 = T(0);
+        for (int i = 0; i < q.nq; ++i) {          // wavefront-uniform: q lives in the kernel arguments
+            const T x = q.x[i], w = q.w[i];
+            T dl;
+            const T l = log_prob<T, LIK, true>(mu + sd * x, y, p, dl);             // (Poisson never gets here)
+            a0 += w * l;
+            a1 += w * dl;
+            a2 += w * dl * x;
+        }
+        ve = a0;
+        gm = a1;
+        gv = a2 / sd;
+    }
+}
+
+// Variational expectations (nat1 == NULL) or the CVI site update (nat1, nat2 given): any of ve / g_mu / g_var may be NULL.
+template <typename T, int LIK>
+__global__ void __launch_bounds__(256) lik_ve_kernel(long N, Rule<T> q, Par<T> p, const T* __restrict__ fmu, const T* __restrict__ fvar,
+                                                     const T* __restrict__ yobs, T lr, T* __restrict__ nat1, T* __restrict__ nat2,
+                                                     T* __restrict__ out_ve, T* __restrict__ out_gm, T* __restrict__ out_gv) {
+    const long id = (long)blockIdx.x * 256 + threadIdx.x;
+    if (id >= N) return;
+    const T mu = fmu[id], s2 = fvar[id], y = yobs[id];
+    T ve, gm, gv;
+    if (s2 > T(0)) {
+        expectations<T, LIK>(q, p, mu, s2, y, ve, gm, gv);
+    } else {                                       // outside the domain (non-positive or NaN variance): NaN for this point only
+        ve = gm = gv = nan_of<T>();
+    }
+    if (out_ve) out_ve[id] = ve;
+    if (out_gm) out_gm[id] = gm;
+    if (out_gv) out_gv[id] = gv;
+    if (nat1) {
+        // gradient with respect to the expectation parameters [mu, s2 + mu^2] (variational_cvi.py:448-460), then
+        // theta <- (1 - lr) theta + lr g (:351-368)
+        const T g1 = gm - T(2) * gv * mu;
+        nat1[id] = (T(1) - lr) * nat1[id] + lr * g1;
+        nat2[id] = (T(1) - lr) * nat2[id] + lr * gv;
+    }
+}
+
+// log of the predictive density  log int p(y | f) N(f | mu, s2) df
+template <typename T, int LIK>
+__global__ void __launch_bounds__(256) lik_pld_kernel(long N, Rule<T> q, Par<T> p, const T* __restrict__ fmu, const T* __restrict__ fvar,
+                                                      const T* __restrict__ yobs, T* __restrict__ out) {
+    const long id = (long)blockIdx.x * 256 + threadIdx.x;
+    if (id >= N) return;
+    const T mu = fmu[id], s2 = fvar[id], y = yobs[id];
+    T res;
+    if (!(s2 > T(0))) {
+        res = nan_of<T>();
+    } else if (LIK == 0) {
+        constexpr T LOG_2PI = T(1.8378770664093454835606594728112);
+        const T v = s2 + p.p0, r = y - mu;
+        res = T(-0.5) * (LOG_2PI + m_log(v)) - T(0.5) * r * r / v;
+    } else {
+        // log-sum-exp over the nodes, shifted by the running maximum (q.w holds the LOG weights here)
+        const T sd = m_sqrt(T(2) * s2);
+        T m = -INFINITY, s = T(0), dl;
+        for (int i = 0; i < q.nq; ++i) {
+            const T v = log_prob<T, LIK, false>(mu + sd * q.x[i], y, p, dl) + q.w[i];
+            if (v > m) {
+                s = s * m_exp(m - v) + T(1);
+                m = v;
+            } else {
+                s += v == -INFINITY ? T(0) : m_exp(v - m);      // (a NaN term lands here and makes the sum NaN)
+            }
+        }
+        res = m + m_log(s);
+        if (LIK == 2) res -= m_lgamma(y + T(1));       // the node-independent term of the Poisson log density, once
+    }
+    out[id] = res;
+}
+
+// argument checks shared by the three entry points: 0, or the (negative) position of the offending argument
+template <typename T>
+int prepare(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights, bool log_weights,
+            Rule<T>& q, Par<T>& p) {
+    if (N < 0 || (N + 255) / 256 > int64_t(0x7fffffff)) return -1;
+    if (lik < 0 || lik > 3) return -2;
+    p.p0 = p.p1 = p.p2 = T(0);
+    if (lik == 0) {
+        if (!params || !(params[0] > 0.0)) return -3;
+        p.p0 = T(params[0]);
+    } else if (lik == 3) {
+        if (!params || !(params[0] > 0.0) || !(params[1] > 0.0) || !std::isfinite(params[2])) return -3;
+        p.p0 = T(params[0]);
+        p.p1 = T(params[1]);
+        p.p2 = T(params[2]);
+    }
+    if (nq < 1 || nq > MAXQ) return -4;
+    if (!nodes) return -5;
+    if (!weights) return -6;
+    const double inv_sqrt_pi = 0.56418958354775628694807945156077;
+    q.nq = nq;
+    for (int i = 0; i < MAXQ; ++i) {
+        const double w = i < nq ? weights[i] * inv_sqrt_pi : 0.0;
+        if (i < nq && !(weights[i] > 0.0)) return -6;
+        q.x[i] = i < nq ? T(nodes[i]) : T(0);
+        q.w[i] = i < nq ? T(log_weights ? std::log(w) : w) : T(0);
+    }
+    return 0;
+}
+
+template <typename T, int LIK>
+int launch_ve(int64_t N, const Rule<T>& q, const Par<T>& p, const T* fmu, const T* fvar, const T* y, T lr, T* nat1, T* nat2, T* ve,
+              T* g_mu, T* g_var, void* stream) {
+    hipLaunchKernelGGL((lik_ve_kernel<T, LIK>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       (long)N, q, p, fmu, fvar, y, lr, nat1, nat2, ve, g_mu, g_var);
+    return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
+template <typename T>
+int dispatch_ve(int64_t N, int lik, const Rule<T>& q, const Par<T>& p, const T* fmu, const T* fvar, const T* y, T lr, T* nat1,
+                T* nat2, T* ve, T* g_mu, T* g_var, void* stream) {
+    switch (lik) {
+        case 0: return launch_ve<T, 0>(N, q, p, fmu, fvar, y, lr, nat1, nat2, ve, g_mu, g_var, stream);
+        case 1: return launch_ve<T, 1>(N, q, p, fmu, fvar, y, lr, nat1, nat2, ve, g_mu, g_var, stream);
+        case 2: return launch_ve<T, 2>(N, q, p, fmu, fvar, y, lr, nat1, nat2, ve, g_mu, g_var, stream);
+        default: return launch_ve<T, 3>(N, q, p, fmu, fvar, y, lr, nat1, nat2, ve, g_mu, g_var, stream);
+    }
+}
+
+template <typename T>
+int run_ve(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights, const T* fmu, const T* fvar,
+           const T* y, T* ve, T* g_mu, T* g_var, void* stream) {
+    Rule<T> q;
+    Par<T> p;
+    const int bad = prepare<T>(N, lik, params, nq, nodes, weights, false, q, p);
+    if (bad) return bad;
+    if (N == 0) return 0;
+    if (!fmu) return -7;
+    if (!fvar) return -8;
+    if (!y) return -9;
+    if (!ve && !g_mu && !g_var) return 0;          // nothing asked for
+    return dispatch_ve<T>(N, lik, q, p, fmu, fvar, y, T(0), nullptr, nullptr, ve, g_mu, g_var, stream);
+}
+
+template <typename T>
+int run_site(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights, const T* fmu, const T* fvar,
+             const T* y, T lr, T* nat1, T* nat2, T* ve, void* stream) {
+    Rule<T> q;
+    Par<T> p;
+    const int bad = prepare<T>(N, lik, params, nq, nodes, weights, false, q, p);
+    if (bad) return bad;
+    if (!(lr >= T(0)) || !(lr <= T(1))) return -10;
+    if (N == 0) return 0;
+    if (!fmu) return -7;
+    if (!fvar) return -8;
+    if (!y) return -9;
+    if (!nat1) return -11;
+    if (!nat2) return -12;
+    return dispatch_ve<T>(N, lik, q, p, fmu, fvar, y, lr, nat1, nat2, ve, nullptr, nullptr, stream);
+}
+
+template <typename T, int LIK>
+int launch_pld(int64_t N, const Rule<T>& q, const Par<T>& p, const T* fmu, const T* fvar, const T* y, T* out, void* stream) {
+    hipLaunchKernelGGL((lik_pld_kernel<T, LIK>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       (long)N, q, p, fmu, fvar, y, out);
+    return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
+template <typename T>
+int run_pld(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights, const T* fmu, const T* fvar,
+            const T* y, T* out, void* stream) {
+    Rule<T> q;
+    Par<T> p;
+    const int bad = prepare<T>(N, lik, params, nq, nodes, weights, true, q, p);
+    if (bad) return bad;
+    if (N == 0) return 0;
+    if (!fmu) return -7;
+    if (!fvar) return -8;
+    if (!y) return -9;
+    if (!out) return -10;
+    switch (lik) {
+        case 0: return launch_pld<T, 0>(N, q, p, fmu, fvar, y, out, stream);
+        case 1: return launch_pld<T, 1>(N, q, p, fmu, fvar, y, out, stream);
+        case 2: return launch_pld<T, 2>(N, q, p, fmu, fvar, y, out, stream);
+        default: return launch_pld<T, 3>(N, q, p, fmu, fvar, y, out, stream);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int mf_lik_variational_expectations_f64(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                                        const double* fmu, const double* fvar, const double* y, double* ve, double* g_mu,
+                                        double* g_var, void* stream) {
+    return run_ve<double>(N, lik, params, nq, nodes, weights, fmu, fvar, y, ve, g_mu, g_var, stream);
+}
+int mf_lik_variational_expectations_f32(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                                        const float* fmu, const float* fvar, const float* y, float* ve, float* g_mu, float* g_var,
+                                        void* stream) {
+    return run_ve<float>(N, lik, params, nq, nodes, weights, fmu, fvar, y, ve, g_mu, g_var, stream);
+}
+int mf_lik_cvi_site_update_f64(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                               const double* fmu, const double* fvar, const double* y, double lr, double* nat1, double* nat2,
+                               double* ve, void* stream) {
+    return run_site<double>(N, lik, params, nq, nodes, weights, fmu, fvar, y, lr, nat1, nat2, ve, stream);
+}
+int mf_lik_cvi_site_update_f32(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                               const float* fmu, const float* fvar, const float* y, float lr, float* nat1, float* nat2, float* ve,
+                               void* stream) {
+    return run_site<float>(N, lik, params, nq, nodes, weights, fmu, fvar, y, lr, nat1, nat2, ve, stream);
+}
+int mf_lik_predict_log_density_f64(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                                   const double* fmu, const double* fvar, const double* y, double* out, void* stream) {
+    return run_pld<double>(N, lik, params, nq, nodes, weights, fmu, fvar, y, out, stream);
+}
+int mf_lik_predict_log_density_f32(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                                   const float* fmu, const float* fvar, const float* y, float* out, void* stream) {
+    return run_pld<float>(N, lik, params, nq, nodes, weights, fmu, fvar, y, out, stream);
+}
+
+}  // extern "C"

@@ -620,14 +620,16 @@ class UnivariateGaussianSitesNat(GaussianSites):
     """Univariate Gaussian sites in natural parameters (kalman_filter.py:382-433)."""
 
     def __init__(self, nat1: torch.Tensor, nat2: torch.Tensor, log_norm: Optional[torch.Tensor] = None):
-        """:param nat1: ``[N, 1]``; :param nat2: ``[N, 1, 1]``; :param log_norm: ``[N, 1]`` or None."""
-        if nat1.dim() != 2 or nat1.shape[-1] != 1:
+        """:param nat1: ``batch + [N, 1]``; :param nat2: ``batch + [N, 1, 1]``; :param log_norm: ``batch + [N, 1]`` or None.
+        (The reference takes ``[N, 1]`` only; the leading batch dimensions - a batch of series, as ``CVIGaussianProcess`` holds -
+        are an extension: ``BaseKalmanFilter._expanded`` takes per-step precisions with a batch shape.)"""
+        if nat1.dim() < 2 or nat1.shape[-1] != 1:
             raise ValueError(f"nat1 must have shape [N, 1], got {tuple(nat1.shape)}")
-        if tuple(nat2.shape) != (nat1.shape[0], 1, 1):
+        if tuple(nat2.shape) != tuple(nat1.shape) + (1,):
             raise ValueError(f"nat2 must have shape [N, 1, 1], got {tuple(nat2.shape)}")
-        if log_norm is not None and tuple(log_norm.shape) != (nat1.shape[0], 1):
+        if log_norm is not None and tuple(log_norm.shape) != tuple(nat1.shape):
             raise ValueError(f"log_norm must have shape [N, 1], got {tuple(log_norm.shape)}")
-        self.num_data, self.output_dim = nat1.shape
+        self.num_data, self.output_dim = nat1.shape[-2:]
         self.nat1 = nat1
         self.nat2 = nat2
         self.log_norm = log_norm
