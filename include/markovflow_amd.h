@@ -728,6 +728,35 @@ int mf_lik_predict_log_density_f64(int64_t N, int lik, const double* params, int
 int mf_lik_predict_log_density_f32(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
                                    const float* fmu, const float* fvar, const float* y, float* out, void* stream);
 
+/*
+ * The segmented site update of the sparse CVI model (markovflow/models/sparse_variational_cvi.py:176-221; csrc/mf_lik.hip): B
+ * series of N data points, S = M + 1 sites per series on the pairs of neighbouring inducing states, two_d = 2 d in 2, 4, ..., 18.
+ *   seg_offsets [B, S + 1] int64  the points seg_offsets[b, s] <= k < seg_offsets[b, s + 1] of series b belong to site s
+ *                                 (ascending, 0 first and N last; built by the caller, not validated on the device)
+ *   w [B, N, 2d]                  H P_k, the projection of the pair [u_-, u_+] onto f_k
+ *   c [B, N]                      H T_k H^T, the conditional variance of f_k given the pair
+ *   y [B, N]                      observations
+ *   pair_mean [B, S, 2d], pair_cov [B, S, 2d, 2d]   marginals of q on the pairs (conditionals.pairwise_marginals)
+ *   nat1 [B, S, 2d], nat2 [B, S, 2d, 2d]            the sites, updated IN PLACE; BOTH NULL: projection only
+ *   fmu, fvar, ve [B, N]          optional outputs, any of them may be NULL
+ * Per point k of segment s:  fmu = w_k . m_s,  fvar = c_k + w_k^T S_s w_k,  (ve, gm, gv) as mf_lik_variational_expectations,
+ * g2 = gv, g1 = gm - 2 gv fmu;  per segment  nat1_s <- (1 - lr) nat1_s + lr sum_k g1 w_k,
+ * nat2_s <- (1 - lr) nat2_s + lr sum_k g2 w_k w_k^T  (an empty segment decays).  The sums run over the points in ascending order:
+ * no floating-point atomics, the same bits on every launch and for a series alone or inside a batch.  A point with fvar <= 0 or
+ * NaN gets NaN in its own fmu / fvar / ve and makes its segment's sites NaN; every other segment is untouched by it.
+ * Returns 0, -(position of the offending argument in THIS signature: 1 B, 2 N, 3 S, 5 lik, 6 params, 7 nq, 8 nodes, 9 weights,
+ * 10 ... 15 a NULL input, 16 lr outside [0, 1], 17 / 18 one of nat1 / nat2 NULL without the other), -100 for a two_d that is
+ * odd, < 2 or > 18, or -1000 (launch failed).  Nothing is launched on an error, for B = 0, or when nothing is asked for.
+ */
+int mf_lik_sparse_cvi_site_update_f64(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq,
+                                      const double* nodes, const double* weights, const int64_t* seg_offsets, const double* w,
+                                      const double* c, const double* y, const double* pair_mean, const double* pair_cov, double lr,
+                                      double* nat1, double* nat2, double* fmu, double* fvar, double* ve, void* stream);
+int mf_lik_sparse_cvi_site_update_f32(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq,
+                                      const double* nodes, const double* weights, const int64_t* seg_offsets, const float* w,
+                                      const float* c, const float* y, const float* pair_mean, const float* pair_cov, float lr,
+                                      float* nat1, float* nat2, float* fmu, float* fvar, float* ve, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,7 @@ from . import conditionals, distributed, kernels, likelihoods, models, ssm_gauss
 from .kernels import (Constant, HarmonicOscillator, IndependentMultiOutput, Matern12, Matern32, Matern52, Product, SDEKernel,
                       StationaryKernel, Sum)
 from .likelihoods import Bernoulli, Gaussian, Likelihood, Poisson, StudentT
-from .models import CVIGaussianProcess, GaussianProcessRegression
+from .models import CVIGaussianProcess, GaussianProcessRegression, SparseCVIGaussianProcess
 from .posterior import AnalyticPosteriorProcess, ConditionalProcess
 from ._lib import MarkovflowAmdError, check_errors, errors_as_nan, set_synchronous_checks
 
@@ -33,4 +33,5 @@ __all__ = [
     "Matern52", "Sum", "IndependentMultiOutput", "Constant", "HarmonicOscillator", "Product", "GaussianProcessRegression", "AnalyticPosteriorProcess", "ConditionalProcess",
     "MarkovflowAmdError", "check_errors", "errors_as_nan", "set_synchronous_checks",
     "likelihoods", "Likelihood", "Gaussian", "Bernoulli", "Poisson", "StudentT", "CVIGaussianProcess",
+    "SparseCVIGaussianProcess",
 ]

@@ -126,6 +126,128 @@ __global__ void __launch_bounds__(256) lik_ve_kernel(long N, Rule<T> q, Par<T> p
     }
 }
 
+// ---- sparse CVI: the segmented site update (markovflow/models/sparse_variational_cvi.py:176-221) ------------------------------
+// One wavefront per (series, segment); the segment's points are walked in tiles of 64.
+//   phase 1, a lane per point: the tile's rows of w travel through LDS (coalesced global loads, row stride 2d + 1 elements - odd,
+//            so the lanes' rows start on distinct banks); the segment's pair marginal (m_s, S_s) sits in LDS and is read as
+//            broadcasts.  fmu = w . m_s, fvar = c + w^T S_s w, the expectations, then g2 = gv and g1 = gm - 2 gv fmu are left in LDS.
+//   phase 2, a lane per few entries of the accumulator - the lower triangle of nat2 and nat1, 2d (2d + 1) / 2 + 2d entries (90 at
+//            2d = 12: two per lane, 189 at 2d = 18: three) - looping over the tile's points in ascending order with broadcast LDS
+//            reads: entry (i, j) += (g2_k w_kj) w_ki; a nat1 entry reads g1_k and the column of ones that pads every row of w.
+//            A tile's sum is formed on its own and then added to the segment's running sum.
+// The sums run over the points in ascending order whatever the grid: the same bits on every launch, alone or inside a batch, and no
+// floating-point atomics.  A point outside the domain (fvar <= 0 or NaN) leaves NaN in its own outputs and in its segment's sites.
+template <typename T, int LIK, int D2>
+__global__ void __launch_bounds__(64) sparse_site_kernel(long N, int S, Rule<T> q, Par<T> p, const long long* __restrict__ seg,
+                                                         const T* __restrict__ w, const T* __restrict__ cvar,
+                                                         const T* __restrict__ yobs, const T* __restrict__ pair_mean,
+                                                         const T* __restrict__ pair_cov, T lr, T* __restrict__ nat1,
+                                                         T* __restrict__ nat2, T* __restrict__ out_fmu, T* __restrict__ out_fvar,
+                                                         T* __restrict__ out_ve) {
+    constexpr int W = D2 + 1, TRI = D2 * (D2 + 1) / 2, E = TRI + D2, R = (E + 63) / 64;
+    __shared__ T lw[64 * W];
+    __shared__ T ls[D2 * D2];
+    __shared__ T lm[D2];
+    __shared__ T lg[2 * 64];           // g2 of the tile's points, then g1
+    const int lane = threadIdx.x;
+    const long bs = blockIdx.x;        // series * S + segment
+    const long b = bs / S;
+    const long s = bs - b * S;
+    long k_lo = (long)seg[b * (S + 1) + s], k_hi = (long)seg[b * (S + 1) + s + 1];
+    k_lo = k_lo < 0 ? 0 : (k_lo > N ? N : k_lo);                   // (the caller builds the offsets; a bad one reads nothing)
+    k_hi = k_hi < k_lo ? k_lo : (k_hi > N ? N : k_hi);
+    // this lane's entries: e < TRI is (i, j <= i) of nat2, the rest are nat1's (j = D2: the column of ones)
+    int ei[R], ej[R], es[R];
+    T acc[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        int e = lane + 64 * r;
+        acc[r] = T(0);
+        if (e >= E) e = 0;
+        if (e < TRI) {
+            int i = 0;
+            while ((i + 1) * (i + 2) / 2 <= e) ++i;
+            ei[r] = i;
+            ej[r] = e - i * (i + 1) / 2;
+            es[r] = 0;
+        } else {
+            ei[r] = e - TRI;
+            ej[r] = D2;
+            es[r] = 64;
+        }
+    }
+    if (k_hi > k_lo) {
+        for (int idx = lane; idx < D2 * D2; idx += 64) ls[idx] = pair_cov[bs * (D2 * D2) + idx];
+        if (lane < D2) lm[lane] = pair_mean[bs * D2 + lane];
+        lw[lane * W + D2] = T(1);
+    }
+    for (long k0 = k_lo; k0 < k_hi; k0 += 64) {
+        const int npts = k_hi - k0 < 64 ? int(k_hi - k0) : 64;
+        __syncthreads();               // the previous tile's phase 2 has read lw and lg
+        const T* wt = w + (b * N + k0) * D2;
+        for (int idx = lane; idx < npts * D2; idx += 64) lw[(idx / D2) * W + idx % D2] = wt[idx];
+        __syncthreads();
+        if (lane < npts) {
+            const long id = b * N + k0 + lane;
+            T wr[D2];
+#pragma unroll
+            for (int i = 0; i < D2; ++i) wr[i] = lw[lane * W + i];
+            T mu = T(0), s2 = cvar[id];
+#pragma unroll
+            for (int i = 0; i < D2; ++i) {
+                T t = T(0);
+#pragma unroll
+                for (int j = 0; j < D2; ++j) t += ls[i * D2 + j] * wr[j];
+                s2 += wr[i] * t;
+                mu += wr[i] * lm[i];
+            }
+            const T y = yobs[id];
+            T ve, gm, gv;
+            if (s2 > T(0)) {
+                expectations<T, LIK>(q, p, mu, s2, y, ve, gm, gv);
+            } else {
+                ve = gm = gv = mu = s2 = nan_of<T>();
+            }
+            if (out_fmu) out_fmu[id] = mu;
+            if (out_fvar) out_fvar[id] = s2;
+            if (out_ve) out_ve[id] = ve;
+            if (nat1) {
+                lg[lane] = gv;
+                lg[64 + lane] = gm - T(2) * gv * mu;
+            }
+        }
+        if (nat1) {
+            __syncthreads();
+            T part[R];                 // the tile's own sum first, then onto the running one: the rounding error grows with
+#pragma unroll                         // 64 + the number of tiles, not with the length of the segment
+            for (int r = 0; r < R; ++r) part[r] = T(0);
+            for (int k = 0; k < npts; ++k) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) part[r] += (lg[es[r] + k] * lw[k * W + ej[r]]) * lw[k * W + ei[r]];
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) acc[r] += part[r];
+        }
+    }
+    if (nat1) {
+        // theta <- (1 - lr) theta + lr sum_k g_k (:215-218); an empty segment just decays
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int e = lane + 64 * r;
+            if (e >= E) continue;
+            if (e < TRI) {
+                T* blk = nat2 + bs * (D2 * D2);
+                const int a = ei[r] * D2 + ej[r], t = ej[r] * D2 + ei[r];
+                blk[a] = (T(1) - lr) * blk[a] + lr * acc[r];
+                if (a != t) blk[t] = (T(1) - lr) * blk[t] + lr * acc[r];
+            } else {
+                T* v = nat1 + bs * D2 + ei[r];
+                *v = (T(1) - lr) * *v + lr * acc[r];
+            }
+        }
+    }
+}
+
 // log of the predictive density  log int p(y | f) N(f | mu, s2) df
 template <typename T, int LIK>
 __global__ void __launch_bounds__(256) lik_pld_kernel(long N, Rule<T> q, Par<T> p, const T* __restrict__ fmu, const T* __restrict__ fvar,
@@ -267,6 +389,62 @@ int run_pld(int64_t N, int lik, const double* params, int nq, const double* node
     }
 }
 
+template <typename T, int LIK, int D2>
+int launch_sparse(int64_t B, int64_t N, int64_t S, const Rule<T>& q, const Par<T>& p, const int64_t* seg, const T* w, const T* c,
+                  const T* y, const T* pm, const T* pc, T lr, T* nat1, T* nat2, T* fmu, T* fvar, T* ve, void* stream) {
+    hipLaunchKernelGGL((sparse_site_kernel<T, LIK, D2>), dim3((unsigned)(B * S)), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       (long)N, (int)S, q, p, reinterpret_cast<const long long*>(seg), w, c, y, pm, pc, lr, nat1, nat2, fmu, fvar, ve);
+    return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
+template <typename T, int D2>
+int dispatch_sparse(int lik, int64_t B, int64_t N, int64_t S, const Rule<T>& q, const Par<T>& p, const int64_t* seg, const T* w,
+                    const T* c, const T* y, const T* pm, const T* pc, T lr, T* nat1, T* nat2, T* fmu, T* fvar, T* ve, void* stream) {
+    switch (lik) {
+        case 0: return launch_sparse<T, 0, D2>(B, N, S, q, p, seg, w, c, y, pm, pc, lr, nat1, nat2, fmu, fvar, ve, stream);
+        case 1: return launch_sparse<T, 1, D2>(B, N, S, q, p, seg, w, c, y, pm, pc, lr, nat1, nat2, fmu, fvar, ve, stream);
+        case 2: return launch_sparse<T, 2, D2>(B, N, S, q, p, seg, w, c, y, pm, pc, lr, nat1, nat2, fmu, fvar, ve, stream);
+        default: return launch_sparse<T, 3, D2>(B, N, S, q, p, seg, w, c, y, pm, pc, lr, nat1, nat2, fmu, fvar, ve, stream);
+    }
+}
+
+// the sparse site update's argument checks: the (negative) position of the offending argument in ITS signature, -100 for a
+// two_d outside 2, 4, ..., 18
+template <typename T>
+int run_sparse(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq, const double* nodes,
+               const double* weights, const int64_t* seg, const T* w, const T* c, const T* y, const T* pm, const T* pc, T lr,
+               T* nat1, T* nat2, T* fmu, T* fvar, T* ve, void* stream) {
+    if (B < 0) return -1;
+    if (N < 0) return -2;
+    if (S < 1 || (B > 0 && S > int64_t(0x7fffffff) / B)) return -3;
+    if (two_d < 2 || two_d > 18 || (two_d & 1)) return -100;
+    Rule<T> q;
+    Par<T> p;
+    const int bad = prepare<T>(0, lik, params, nq, nodes, weights, false, q, p);      // -2 ... -6 there are arguments 5 ... 9 here
+    if (bad) return bad - 3;
+    if (!(lr >= T(0)) || !(lr <= T(1))) return -16;
+    if (!nat1 && nat2) return -17;
+    if (nat1 && !nat2) return -18;
+    if (B == 0) return 0;
+    if (!nat1 && (N == 0 || (!fmu && !fvar && !ve))) return 0;      // nothing asked for
+    if (!seg) return -10;
+    if (N > 0) {
+        if (!w) return -11;
+        if (!c) return -12;
+        if (!y) return -13;
+        if (!pm) return -14;
+        if (!pc) return -15;
+    }
+#define MF_SPARSE_CASE(D2) \
+    case D2: return dispatch_sparse<T, D2>(lik, B, N, S, q, p, seg, w, c, y, pm, pc, lr, nat1, nat2, fmu, fvar, ve, stream);
+    switch (two_d) {
+        MF_SPARSE_CASE(2) MF_SPARSE_CASE(4) MF_SPARSE_CASE(6) MF_SPARSE_CASE(8) MF_SPARSE_CASE(10) MF_SPARSE_CASE(12)
+        MF_SPARSE_CASE(14) MF_SPARSE_CASE(16) MF_SPARSE_CASE(18)
+        default: return -100;
+    }
+#undef MF_SPARSE_CASE
+}
+
 }  // namespace
 
 extern "C" {
@@ -298,6 +476,20 @@ int mf_lik_predict_log_density_f64(int64_t N, int lik, const double* params, int
 int mf_lik_predict_log_density_f32(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
                                    const float* fmu, const float* fvar, const float* y, float* out, void* stream) {
     return run_pld<float>(N, lik, params, nq, nodes, weights, fmu, fvar, y, out, stream);
+}
+int mf_lik_sparse_cvi_site_update_f64(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq,
+                                      const double* nodes, const double* weights, const int64_t* seg_offsets, const double* w,
+                                      const double* c, const double* y, const double* pair_mean, const double* pair_cov, double lr,
+                                      double* nat1, double* nat2, double* fmu, double* fvar, double* ve, void* stream) {
+    return run_sparse<double>(B, N, S, two_d, lik, params, nq, nodes, weights, seg_offsets, w, c, y, pair_mean, pair_cov, lr, nat1,
+                              nat2, fmu, fvar, ve, stream);
+}
+int mf_lik_sparse_cvi_site_update_f32(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq,
+                                      const double* nodes, const double* weights, const int64_t* seg_offsets, const float* w,
+                                      const float* c, const float* y, const float* pair_mean, const float* pair_cov, float lr,
+                                      float* nat1, float* nat2, float* fmu, float* fvar, float* ve, void* stream) {
+    return run_sparse<float>(B, N, S, two_d, lik, params, nq, nodes, weights, seg_offsets, w, c, y, pair_mean, pair_cov, lr, nat1,
+                             nat2, fmu, fvar, ve, stream);
 }
 
 }  // extern "C"

@@ -9,6 +9,11 @@ Only what drives the hot path is mirrored: construction from ``(time_points, obs
 ``CVIGaussianProcess`` with a zero mean function) is the site-based model for non-Gaussian likelihoods
 (``markovflow_amd/likelihoods.py``): its ``update_sites`` is the filter route's posterior chain followed by ONE launch of
 ``mf_lik_cvi_site_update_*``.
+
+``SparseCVIGaussianProcess`` (mirror of ``markovflow/models/sparse_variational_cvi.py:38-313``, zero mean function) carries
+``M + 1`` multivariate sites on the pairs of neighbouring inducing states instead of one site per data point: the chain has ``M``
+blocks, and the ``N`` data points enter ``update_sites`` through ONE launch of ``mf_lik_sparse_cvi_site_update_*`` (projection onto
+the bracketing pair, expectations, back-projection and the segmented sum).
 """
 from typing import Optional, Tuple
 
@@ -17,9 +22,9 @@ import math
 
 import torch
 
-from . import _lib
+from . import _lib, conditionals
 from .kalman_filter import KalmanFilter, KalmanFilterWithSites, UnivariateGaussianSitesNat
-from .kernels import IndependentMultiOutput, SDEKernel, _MaternBase
+from .kernels import IndependentMultiOutput, SDEKernel, _MaternBase, _version_key
 from .likelihoods import Likelihood
 from .posterior import AnalyticPosteriorProcess, ConditionalProcess
 from .ssm_gaussian_transformations import naturals_to_ssm_params
@@ -537,6 +542,288 @@ class CVIGaussianProcess:
     def predict_log_density(self, input_data: Tuple[torch.Tensor, torch.Tensor], full_output_cov: bool = False) -> torch.Tensor:
         """Log density of new data ``(time_points, observations)`` under the posterior, ``batch + [num_new]``
         (variational_cvi.py:406-420)."""
+        if full_output_cov:
+            raise NotImplementedError("predict_log_density: the likelihoods are univariate (marginal variances only)")
+        new_times, new_obs = input_data
+        f_mean, f_var = self.posterior.predict_f(new_times)
+        return self._likelihood.predict_log_density(f_mean, f_var, new_obs)
+
+
+SPARSE_SITE_MAX_TWO_D = 18      # mf_lik_sparse_cvi_site_update_*: 2 d <= 18, the range of the lane-per-point conditional kernels
+
+
+def sparse_site_projections(kernel: SDEKernel, time_points: torch.Tensor, inducing_points: torch.Tensor
+                            ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """What the sparse site update needs of every data point, none of it depending on the sites: ``w_k = H P_k``
+    (``batch + [N, 2d]``), ``c_k = H T_k H^T`` (``batch + [N]``) from ``conditional_statistics`` (sparse_variational_cvi.py:192-194),
+    the index of the pair that brackets the point (``batch + [N]``; ``z_{m-1} < x <= z_m`` belongs to pair ``m``) and the segment
+    offsets ``batch + [M + 2]`` (offset ``m`` counts the ``x <= z_{m-1}``; 0 and ``N`` at the ends).  Both sets of time points must
+    be sorted."""
+    proj, cov, indices = conditionals._conditional_statistics(time_points, inducing_points, kernel)
+    h = kernel.generate_emission_model(time_points).emission_matrix                         # [.., N, 1, d]
+    w = (h @ proj)[..., 0, :]
+    c = (h @ cov @ h.transpose(-1, -2))[..., 0, 0]
+    x = time_points.to(inducing_points.dtype).contiguous()
+    inner = torch.searchsorted(x, inducing_points.contiguous(), right=True)
+    zero = torch.zeros_like(inner[..., :1])
+    offsets = torch.cat([zero, inner, torch.full_like(zero, x.shape[-1])], dim=-1)
+    return w.contiguous(), c.contiguous(), indices, offsets.contiguous()
+
+
+def sparse_cvi_site_update_torch(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor, indices: torch.Tensor,
+                                 pair_mean: torch.Tensor, pair_cov: torch.Tensor, learning_rate: float, nat1: torch.Tensor,
+                                 nat2: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The sparse CVI step as a torch composition (sparse_variational_cvi.py:176-221), IN PLACE on ``nat1 [.., M+1, 2d]`` and
+    ``nat2 [.., M+1, 2d, 2d]``: per point ``fmu = w . m_s``, ``fvar = c + w^T S_s w`` with ``(m_s, S_s)`` the marginal of the pair the
+    point belongs to, the gradients of the variational expectations in ``[mu, var + mu^2]``, ``back_project_nats`` through ``w`` and
+    ``index_add_`` over the segment index; ``nat <- (1 - lr) nat + lr sum``.  What ``mf_lik_sparse_cvi_site_update_*`` fuses: it
+    runs on CPU tensors as a function (the model itself needs the HIP chain kernels, as every model here), it is the model's route
+    for ``2d > 18``, and it is what the kernel is measured against.  ``w [.., N, 2d]``, ``c``, ``y``, ``indices``
+    ``[.., N]``.  Returns ``(fmu, fvar, ve)``, ``[.., N]`` each."""
+    two_d, segs = w.shape[-1], nat1.shape[-2]
+    lr = float(learning_rate)
+    with torch.no_grad():
+        m = torch.gather(pair_mean, -2, indices[..., None].expand(tuple(indices.shape) + (two_d,)))
+        cov = torch.gather(pair_cov, -3, indices[..., None, None].expand(tuple(indices.shape) + (two_d, two_d)))
+        fmu = torch.sum(w * m, dim=-1)
+        fvar = c + torch.sum(w * torch.sum(cov * w[..., None, :], dim=-1), dim=-1)
+        ve, g_mu, g_var = likelihood._expectations(fmu[..., None], fvar[..., None], y[..., None])
+        bad = ~(fvar > 0)
+        fmu, fvar = (torch.where(bad, torch.full_like(v, float("nan")), v) for v in (fmu, fvar))
+        g1, g2 = gradient_transformation_mean_var_to_expectation((fmu[..., None], fvar[..., None]), (g_mu, g_var))
+        theta1, theta2 = back_project_nats(g1, g2, w[..., None, :])
+        # one flat segment index over the batch: series * (M + 1) + pair
+        series = torch.arange(math.prod(indices.shape[:-1]), device=indices.device).reshape(tuple(indices.shape[:-1]) + (1,))
+        flat = (indices + series * segs).reshape(-1)
+        sum1 = torch.zeros_like(nat1).reshape(-1, two_d).index_add_(0, flat, theta1.reshape(-1, two_d))
+        sum2 = torch.zeros_like(nat2).reshape(-1, two_d, two_d).index_add_(0, flat, theta2.reshape(-1, two_d, two_d))
+        nat1.mul_(1.0 - lr).add_(lr * sum1.reshape(nat1.shape))
+        nat2.mul_(1.0 - lr).add_(lr * sum2.reshape(nat2.shape))
+    return fmu, fvar, ve[..., 0]
+
+
+def sparse_cvi_site_update_hip(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor, offsets: torch.Tensor,
+                               pair_mean: torch.Tensor, pair_cov: torch.Tensor, learning_rate: float, nat1: Optional[torch.Tensor],
+                               nat2: Optional[torch.Tensor], want_outputs: bool = False):
+    """ONE launch of ``mf_lik_sparse_cvi_site_update_*`` on HIP tensors (``2d <= 18``): what ``sparse_cvi_site_update_torch``
+    computes, with the segment ``offsets [.., M + 2]`` in place of the per-point index; ``nat1`` / ``nat2`` (contiguous) are updated
+    IN PLACE, or both ``None``: projection only.  ``want_outputs``: return ``(fmu, fvar, ve)``, ``[.., N]`` each (else three Nones)."""
+    dtype, dev = w.dtype, w.device
+    n, two_d, segs = w.shape[-2], w.shape[-1], offsets.shape[-1] - 1
+    bsz = offsets.numel() // (segs + 1)
+    if nat1 is not None and not (nat1.is_contiguous() and nat2.is_contiguous()):
+        raise ValueError("sparse_cvi_site_update_hip: nat1 and nat2 must be contiguous")
+    outs = tuple(torch.empty(tuple(w.shape[:-1]), dtype=dtype, device=dev) for _ in range(3)) if want_outputs else (None, None, None)
+    lik = likelihood
+    _lib.call("mf_lik_sparse_cvi_site_update", dtype, bsz, n, segs, two_d, lik._id, lik._c_params(), lik.num_gauss_hermite_points,
+              lik._c_nodes, lik._c_weights, _lib.ptr(offsets.contiguous()), _lib.ptr(w.contiguous()), _lib.ptr(c.contiguous()),
+              _lib.ptr(y.contiguous()), _lib.ptr(pair_mean.contiguous()), _lib.ptr(pair_cov.contiguous()), float(learning_rate),
+              _lib.ptr(nat1), _lib.ptr(nat2), *[_lib.ptr(o) for o in outs], _lib.stream_ptr(dev))
+    if nat1 is not None:
+        # the kernel wrote through raw pointers: tell torch, so that whatever keys a cache on (tensor, version) sees the write
+        torch.autograd.graph.increment_version(nat1)
+        torch.autograd.graph.increment_version(nat2)
+    return outs
+
+
+class SparseCVIGaussianProcess:
+    """GP prior, general likelihood, Gaussian posterior on the states ``u = s(z)`` at ``M`` inducing points, parameterised by
+    ``M + 1`` Gaussian sites in natural form on the pairs ``v_m = [u_{m-1}, u_m]`` of neighbouring inducing states,
+    ``q(s) = p(s) prod_m t_m(v_m)``; pairs ``0`` and ``M`` have the stationary prior as their outer neighbour.  A data point with
+    ``z_{m-1} < x <= z_m`` contributes to site ``m`` through the conditional ``p(f(x) | v_m)`` (sparse_variational_cvi.py:38-313;
+    zero mean function, plain float likelihood parameters, a batch of series as leading dimensions)."""
+
+    def __init__(self, kernel: SDEKernel, inducing_points: torch.Tensor, likelihood: Likelihood, learning_rate: float = 0.1) -> None:
+        """
+        :param inducing_points: ``batch + [num_inducing]``, sorted.
+        :param likelihood: a ``markovflow_amd.likelihoods.Likelihood``.
+        :param learning_rate: the step ``rho`` of ``update_sites``, in [0, 1].
+        """
+        if not isinstance(kernel, SDEKernel):
+            raise TypeError("kernel must be a markovflow_amd.kernels.SDEKernel")
+        if not isinstance(likelihood, Likelihood):
+            raise TypeError("likelihood must be a markovflow_amd.likelihoods.Likelihood")
+        if not 0.0 <= float(learning_rate) <= 1.0:
+            raise ValueError(f"learning_rate must lie in [0, 1], got {learning_rate}")
+        if not isinstance(inducing_points, torch.Tensor) or inducing_points.dim() < 1 or inducing_points.shape[-1] < 1:
+            raise ValueError("inducing_points must be a tensor of shape batch + [num_inducing] with at least one point")
+        if inducing_points.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"markovflow_amd supports float32 and float64 tensors, got {inducing_points.dtype}")
+        if bool((inducing_points[..., 1:] < inducing_points[..., :-1]).any()):
+            raise ValueError("inducing_points must be sorted")
+        self._kernel = kernel
+        self._likelihood = likelihood
+        self.learning_rate = float(learning_rate)
+        self.inducing_inputs = inducing_points
+        # sparse_variational_cvi.py:131-137
+        batch, two_d = tuple(inducing_points.shape[:-1]), 2 * kernel.state_dim
+        shape = batch + (inducing_points.shape[-1] + 1, two_d)
+        self.nat1 = torch.zeros(shape, dtype=inducing_points.dtype, device=inducing_points.device)
+        self.nat2 = torch.zeros(shape + (two_d,), dtype=inducing_points.dtype, device=inducing_points.device)
+        self._projection_cache = None
+        self._sorted_data = None           # the data tensor last found sorted, and its (data pointer, version)
+
+    @property
+    def kernel(self) -> SDEKernel:
+        return self._kernel
+
+    @property
+    def likelihood(self) -> Likelihood:
+        return self._likelihood
+
+    @property
+    def _chain_points(self) -> torch.Tensor:
+        """The time points of ``dist_p`` / ``dist_q``: the inducing points - and for ``M = 1``, since a ``StateSpaceModel`` needs a
+        transition (as the reference's, state_space_model.py:111-116), a second state ``APPROX_INF`` to the right of the only one:
+        the stationary prior, independent of everything (``A = 0``, ``Q = P_inf``), which no site touches and which adds nothing to
+        the KL divergence.  The pair ``(u_0, that state)`` IS pair ``M``, whose outer neighbour is the stationary prior."""
+        z = self.inducing_inputs
+        if z.shape[-1] > 1:
+            return z
+        return torch.cat([z, z + conditionals.APPROX_INF], dim=-1)
+
+    @property
+    def dist_p(self) -> StateSpaceModel:
+        """The prior chain on the inducing points (sparse_variational_cvi.py:301-306; ``M = 1``: see ``_chain_points``)."""
+        return self._kernel.state_space_model(self._chain_points)
+
+    @property
+    def dist_q(self) -> StateSpaceModel:
+        """The posterior chain on the inducing points: the sites' diagonal halves of neighbouring pairs summed onto the prior
+        naturals, the off-diagonal block times two, then ``naturals_to_ssm_params`` (sparse_variational_cvi.py:139-174)."""
+        prec = self.dist_p.precision
+        sd = self._kernel.state_dim
+        nat1, nat2 = self.nat1, self.nat2
+        lik_nat1 = nat1[..., 1:, :sd] + nat1[..., :-1, sd:]
+        lik_nat2_diag = nat2[..., 1:, :sd, :sd] + nat2[..., :-1, sd:, sd:]
+        lik_nat2_sub = nat2[..., 1:-1, sd:, :sd]
+        if self.inducing_inputs.shape[-1] == 1:           # the second state of ``_chain_points`` carries no site
+            lik_nat1 = torch.cat([lik_nat1, torch.zeros_like(lik_nat1)], dim=-2)
+            lik_nat2_diag = torch.cat([lik_nat2_diag, torch.zeros_like(lik_nat2_diag)], dim=-3)
+            lik_nat2_sub = torch.zeros_like(lik_nat2_diag[..., :1, :, :])
+        theta_diag = -0.5 * prec.block_diagonal + lik_nat2_diag
+        theta_sub = -prec.block_sub_diagonal + 2.0 * lik_nat2_sub
+        a_s, offsets, chol_p0, chol_q, mu0 = naturals_to_ssm_params(lik_nat1, theta_diag, theta_sub)
+        return StateSpaceModel(initial_mean=mu0, chol_initial_covariance=chol_p0, state_transitions=a_s, state_offsets=offsets,
+                               chol_process_covariances=chol_q)
+
+    @property
+    def posterior(self) -> ConditionalProcess:
+        """Posterior process for prediction at any time points (sparse_variational_cvi.py:232-239)."""
+        return ConditionalProcess(posterior_dist=self.dist_q, kernel=self._kernel, conditioning_time_points=self._chain_points)
+
+    # ---- data --------------------------------------------------------------------------------------------------------------------
+    def _check_data(self, input_data: Tuple[torch.Tensor, torch.Tensor], what: str) -> Tuple[torch.Tensor, torch.Tensor]:
+        time_points, observations = input_data
+        if observations.dim() < 2 or observations.shape[-1] != 1:
+            raise ValueError(f"{what}: observations must have shape batch + [num_data, 1], got {tuple(observations.shape)}")
+        if tuple(time_points.shape) != tuple(observations.shape[:-1]):
+            raise ValueError(f"{what}: time_points must have shape observations.shape[:-1]")
+        if tuple(time_points.shape[:-1]) != tuple(self.inducing_inputs.shape[:-1]):
+            raise ValueError(f"{what}: the data must carry the batch shape of the inducing points, "
+                             f"{tuple(self.inducing_inputs.shape[:-1])}, got {tuple(time_points.shape[:-1])}")
+        _lib.same_dtype_device(self.inducing_inputs, f"SparseCVIGaussianProcess.{what}", time_points=time_points,
+                               observations=observations)
+        # (one pass over the data and one read-back: once per data tensor and version, not once per step)
+        key = _version_key(time_points)
+        known = self._sorted_data
+        if known is None or known[0] is not time_points or key is None or known[1] != key:
+            if bool((time_points[..., 1:] < time_points[..., :-1]).any()):
+                raise ValueError(f"{what}: time_points must be sorted")
+            self._sorted_data = (time_points, key)
+        return time_points, observations
+
+    def _fused(self, time_points: torch.Tensor) -> bool:
+        return time_points.is_cuda and 2 * self._kernel.state_dim <= SPARSE_SITE_MAX_TWO_D
+
+    def _projections(self, time_points: torch.Tensor):
+        """``sparse_site_projections`` of the data, kept until the data, the inducing points or a hyper-parameter of the kernel is
+        replaced or written in place (tensor identity, data pointer and version counter, as the filter caches)."""
+        sources = [time_points, self.inducing_inputs] + [x for comp in self._kernel._components() for x in comp._leaves()]
+        key = tuple(_version_key(x) for x in sources)
+        cached = self._projection_cache
+        if (cached is not None and None not in key and cached[0] == key and len(cached[1]) == len(sources)
+                and all(a is b for a, b in zip(cached[1], sources))):          # (the cache holds the tensors: ids are not reused)
+            return cached[2]
+        with torch.no_grad():
+            out = sparse_site_projections(self._kernel, time_points, self.inducing_inputs)
+        self._projection_cache = (key, sources, out)
+        return out
+
+    def _pair_marginals(self, dist_q: StateSpaceModel) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(m_pair [.., M+1, 2d], S_pair [.., M+1, 2d, 2d])`` of ``dist_q``, the stationary prior beyond both ends."""
+        z = self.inducing_inputs
+        batch = tuple(z.shape[:-1])
+        m0 = self._kernel.initial_mean(batch).to(dtype=z.dtype, device=z.device)
+        p0 = self._kernel.initial_covariance(z[..., :1]).to(dtype=z.dtype, device=z.device)
+        pair_mean, pair_cov = conditionals.pairwise_marginals(dist_q, m0, p0)
+        segs = z.shape[-1] + 1                             # (``M = 1``: the pairs of the real state only, see ``_chain_points``)
+        return pair_mean[..., :segs, :], pair_cov[..., :segs, :, :]
+
+    def _site_kernel(self, time_points, observations, dist_q, update: bool):
+        """ONE launch of ``mf_lik_sparse_cvi_site_update_*``: the in-place site update, or (``update`` False) its projection-only
+        mode, which returns ``(fmu, fvar, ve)``, ``batch + [N]`` each."""
+        w, c, _, offsets = self._projections(time_points)
+        pair_mean, pair_cov = self._pair_marginals(dist_q)
+        if update:
+            return sparse_cvi_site_update_hip(self._likelihood, w, c, observations[..., 0], offsets, pair_mean, pair_cov,
+                                              self.learning_rate, self.nat1, self.nat2)
+        return sparse_cvi_site_update_hip(self._likelihood, w, c, observations[..., 0], offsets, pair_mean, pair_cov, 0.0, None, None,
+                                          want_outputs=True)
+
+    # ---- inference ---------------------------------------------------------------------------------------------------------------
+    def local_objective(self, Fmu: torch.Tensor, Fvar: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
+        """The variational expectations, ``[..., 1] -> [...]`` (sparse_variational_cvi.py:260-268)."""
+        return self._likelihood.variational_expectations(Fmu, Fvar, Y)
+
+    def local_objective_and_gradients(self, Fmu: torch.Tensor, Fvar: torch.Tensor, Y: torch.Tensor
+                                      ) -> Tuple[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
+        """The summed local objective and its gradients with respect to ``[mu, var + mu^2]`` (sparse_variational_cvi.py:241-258;
+        the reference's tape is the derivative pair the likelihood computes with the value)."""
+        fmu, fvar = Fmu.detach(), Fvar.detach()
+        with torch.no_grad():
+            ve, g_mu, g_var = self._likelihood._expectations(fmu, fvar, Y)
+        return torch.sum(ve), gradient_transformation_mean_var_to_expectation((fmu, fvar), (g_mu, g_var))
+
+    def update_sites(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> None:
+        """One joint CVI step on the sites, in place: ``theta_m <- (1 - rho) theta_m + rho g_m`` with ``g_m`` the gradients of the
+        variational expectations of the segment's points, projected back onto the pair through ``p(f_k | v_m)``
+        (sparse_variational_cvi.py:176-221).  HIP tensors with ``2d <= 18``: the pair marginals of ``dist_q``, the cached per-point
+        projections and ONE launch of ``mf_lik_sparse_cvi_site_update_*``; ``2d > 18``: ``sparse_cvi_site_update_torch``."""
+        time_points, observations = self._check_data(input_data, "update_sites")
+        with torch.no_grad():
+            if self._fused(time_points):
+                self._site_kernel(time_points, observations, self.dist_q, update=True)
+                return
+            w, c, indices, _ = self._projections(time_points)
+            pair_mean, pair_cov = self._pair_marginals(self.dist_q)
+            sparse_cvi_site_update_torch(self._likelihood, w, c, observations[..., 0], indices, pair_mean, pair_cov,
+                                         self.learning_rate, self.nat1, self.nat2)
+
+    def classic_elbo(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+        """``sum_i E_q log p(y_i | f_i) - KL[q(u) || p(u)]`` (sparse_variational_cvi.py:270-292).  Without a gradient on HIP tensors
+        the expectations come from the site kernel's projection-only mode; with a kernel hyper-parameter that requires a gradient
+        every piece takes its differentiable route (pair marginals under the tape, ``conditional_predict``'s torch branch, the
+        likelihood's autograd function, the KL adjoints): ``loss(...).backward()`` gives the hyper-parameter gradients with the
+        sites held fixed."""
+        time_points, observations = self._check_data(input_data, "classic_elbo")
+        dist_q = self.dist_q
+        if self._fused(time_points) and not self._kernel._needs_grad():
+            with torch.no_grad():
+                ve = self._site_kernel(time_points, observations, dist_q, update=False)[2]
+        else:
+            pair_mean, pair_cov = self._pair_marginals(dist_q)
+            s_mean, s_cov = conditionals.conditional_predict(time_points, self.inducing_inputs, self._kernel, pair_mean, pair_cov)
+            fmu, fvar = self._kernel.generate_emission_model(time_points).project_state_marginals_to_f(s_mean, s_cov)
+            ve = self._likelihood.variational_expectations(fmu, fvar, observations)
+        return torch.sum(ve) - torch.sum(dist_q.kl_divergence(self.dist_p))
+
+    def loss(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+        """``-classic_elbo`` (sparse_variational_cvi.py:223-230)."""
+        return -self.classic_elbo(input_data)
+
+    def predict_log_density(self, input_data: Tuple[torch.Tensor, torch.Tensor], full_output_cov: bool = False) -> torch.Tensor:
+        """Log density of new data ``(time_points, observations)`` under the posterior, ``batch + [num_new]``."""
         if full_output_cov:
             raise NotImplementedError("predict_log_density: the likelihoods are univariate (marginal variances only)")
         new_times, new_obs = input_data
