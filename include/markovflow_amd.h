@@ -757,6 +757,43 @@ int mf_lik_sparse_cvi_site_update_f32(int64_t B, int64_t N, int64_t S, int two_d
                                       const float* c, const float* y, const float* pair_mean, const float* pair_cov, float lr,
                                       float* nat1, float* nat2, float* fmu, float* fvar, float* ve, void* stream);
 
+/*
+ * The data term of the SVGP ELBO and its adjoint onto the pair marginals (markovflow/models/sparse_variational.py:149-192;
+ * csrc/mf_lik.hip): B, N, S, two_d, the likelihood, the rule, seg_offsets, w, c, y, pair_mean and pair_cov as for
+ * mf_lik_sparse_cvi_site_update_*.  Per point k of segment s:  fmu = w_k . m_s,  fvar = c_k + w_k^T S_s w_k,  (ve, gm, gv) as
+ * mf_lik_variational_expectations;  per segment
+ *   ve_sum [B, S]           sum_k ve_k
+ *   g_mean [B, S, 2d]       sum_k gm_k w_k            d ve_sum_s / d m_s
+ *   g_cov  [B, S, 2d, 2d]   sum_k gv_k w_k w_k^T      d ve_sum_s / d S_s for an unconstrained S_s (symmetric, both triangles written)
+ * g_mean and g_cov BOTH NULL: the value only (the same bits); ve_sum may be NULL beside the gradients.
+ * Two passes.  Pass 1 runs one wavefront per TILE - at most 64 consecutive points of one segment, tile j of a segment starting at
+ * the segment's first point + 64 j - and leaves the tile's 2d (2d + 1) / 2 + 2d + 1 partial sums as one row of the workspace; pass
+ * 2 adds a segment's rows in ascending tile order.  The caller supplies the tile table (int64, built from seg_offsets):
+ *   num_tiles               sum over the segments of ceil(length / 64)
+ *   tile_seg [num_tiles]    series * S + segment of every tile, ascending
+ *   seg_tile [B S + 1]      the first tile of every segment (exclusive prefix sum; the last entry is num_tiles)
+ * and the workspace, mf_lik_sparse_expectations_workspace_bytes(num_tiles, two_d, sizeof(T)) bytes (0 for num_tiles = 0).  The
+ * table is clamped on the device, not validated: a wrong one gives wrong numbers and no access outside the buffers.
+ * No floating-point atomics: every sum runs over the points in ascending order, the same bits on every launch and for a series
+ * alone or inside a batch.  A point with fvar <= 0 or NaN makes the three outputs of ITS segment NaN; no other segment is touched.
+ * An empty segment, and every segment for N = 0, gets zeros.  No allocation, no synchronisation.
+ * Returns 0, -(position of the offending argument in THIS signature: 1 B, 2 N, 3 S, 5 lik, 6 params, 7 nq, 8 nodes, 9 weights,
+ * 10 ... 15 a NULL input, 16 num_tiles negative, above 2^31 - 1 or non-zero for N = 0, 17 / 18 a NULL table, 19 a NULL workspace,
+ * 20 a workspace that is too small, 22 / 23 one of g_mean / g_cov NULL without the other), -100 for a two_d that is odd, < 2 or
+ * > 18, or -1000 (launch failed).  Nothing is launched on an error, for B = 0, or when every output is NULL.
+ */
+size_t mf_lik_sparse_expectations_workspace_bytes(int64_t num_tiles, int two_d, int elem_size);
+int mf_lik_sparse_expectations_f64(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq,
+                                   const double* nodes, const double* weights, const int64_t* seg_offsets, const double* w,
+                                   const double* c, const double* y, const double* pair_mean, const double* pair_cov,
+                                   int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile, void* workspace,
+                                   size_t workspace_bytes, double* ve_sum, double* g_mean, double* g_cov, void* stream);
+int mf_lik_sparse_expectations_f32(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq,
+                                   const double* nodes, const double* weights, const int64_t* seg_offsets, const float* w,
+                                   const float* c, const float* y, const float* pair_mean, const float* pair_cov,
+                                   int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile, void* workspace,
+                                   size_t workspace_bytes, float* ve_sum, float* g_mean, float* g_cov, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,11 +17,13 @@ from .kalman_filter import (
     UnivariateGaussianSitesNat,
 )
 from .state_space_model import StateSpaceModel, state_space_model_from_covariances
-from . import conditionals, distributed, kernels, likelihoods, models, ssm_gaussian_transformations
+from . import conditionals, distributed, kernels, likelihoods, models, ssm_gaussian_transformations, ssm_natgrad
 from .kernels import (Constant, HarmonicOscillator, IndependentMultiOutput, Matern12, Matern32, Matern52, Product, SDEKernel,
                       StationaryKernel, Sum)
 from .likelihoods import Bernoulli, Gaussian, Likelihood, Poisson, StudentT
-from .models import CVIGaussianProcess, GaussianProcessRegression, SparseCVIGaussianProcess
+from .models import (CVIGaussianProcess, GaussianProcessRegression, SparseCVIGaussianProcess,
+                     SparseVariationalGaussianProcess)
+from .ssm_natgrad import SSMNaturalGradient
 from .posterior import AnalyticPosteriorProcess, ConditionalProcess
 from ._lib import MarkovflowAmdError, check_errors, errors_as_nan, set_synchronous_checks
 
@@ -33,5 +35,5 @@ __all__ = [
     "Matern52", "Sum", "IndependentMultiOutput", "Constant", "HarmonicOscillator", "Product", "GaussianProcessRegression", "AnalyticPosteriorProcess", "ConditionalProcess",
     "MarkovflowAmdError", "check_errors", "errors_as_nan", "set_synchronous_checks",
     "likelihoods", "Likelihood", "Gaussian", "Bernoulli", "Poisson", "StudentT", "CVIGaussianProcess",
-    "SparseCVIGaussianProcess",
+    "SparseCVIGaussianProcess", "SparseVariationalGaussianProcess", "SSMNaturalGradient", "ssm_natgrad",
 ]

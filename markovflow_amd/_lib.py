@@ -74,6 +74,8 @@ _SIGS = {
     "mf_lik_predict_log_density": (_int, [_i64, _int, _hd, _int, _hd, _hd, "Tp", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_sparse_cvi_site_update": (_int, [_i64, _i64, _i64, _int, _int, _hd, _int, _hd, _hd, _vp, "Tp", "Tp", "Tp", "Tp", "Tp", "T",
                                       "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
+    "mf_lik_sparse_expectations": (_int, [_i64, _i64, _i64, _int, _int, _hd, _int, _hd, _hd, _vp, "Tp", "Tp", "Tp", "Tp", "Tp", _i64,
+                                   _vp, _vp, _vp, _sz, "Tp", "Tp", "Tp", _vp]),
 }
 _PLAIN = {
     "mf_version": (_int, []),
@@ -102,6 +104,7 @@ _PLAIN = {
     "mf_btd_diag_of_inverse_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
     "mf_btd_udl_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
     "mf_btd_grad_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
+    "mf_lik_sparse_expectations_workspace_bytes": (_sz, [_i64, _int, _int]),
 }
 
 _lib = None

@@ -248,6 +248,151 @@ __global__ void __launch_bounds__(64) sparse_site_kernel(long N, int S, Rule<T> 
     }
 }
 
+// ---- SVGP: the segmented expected log-likelihood and its adjoint onto the pair marginals (markovflow/models/sparse_variational.py
+// :149-192, the data term of the ELBO) -----------------------------------------------------------------------------------------
+// Two passes, tile-parallel: the grid of pass 1 is the number of TILES, so one long segment spreads over the whole device.
+//   pass 1, one wavefront per tile: a tile is at most 64 consecutive points of one segment, tile j of a segment starting at the
+//            segment's first point + 64 j (the tiling of a segment depends on nothing but the segment).  Phase 1 is
+//            sparse_site_kernel's (w rows through LDS with the odd stride 2d + 1, the pair marginal in LDS read as broadcasts, a lane
+//            per point); it leaves gv, gm and ve of the tile's points in LDS.  Phase 2, a lane per few entries of the accumulator -
+//            the lower triangle of g_cov, g_mean and ONE more entry, sum ve: 2d (2d + 1) / 2 + 2d + 1 entries - loops over the
+//            tile's points in ascending order: entry (i, j) += (gv_k w_kj) w_ki, a g_mean entry reads gm_k and the column of ones
+//            that pads every row of w, the last entry reads ve_k and the ones twice.  The tile's sums go to the workspace as one
+//            contiguous row (coalesced stores).
+//   pass 2, one block per (series, segment), a lane per entry: the segment's rows are added in ascending tile order, the outputs
+//            are written and the triangle mirrored.  An empty segment writes zeros.
+// The tile table comes from the caller: tile_seg[t] = series * S + segment of tile t, seg_tile[series * S + segment] = the first
+// tile of the segment (a prefix sum, B S + 1 entries).  It is clamped here, not trusted: a wrong table gives wrong numbers and no
+// access outside the buffers.  No floating-point atomics; every sum's order is fixed by the point order alone.
+template <typename T, int LIK, int D2>
+__global__ void __launch_bounds__(64) sparse_expect_tile_kernel(long N, int S, long BS, Rule<T> q, Par<T> p,
+                                                                const long long* __restrict__ seg,
+                                                                const long long* __restrict__ tile_seg,
+                                                                const long long* __restrict__ seg_tile, const T* __restrict__ w,
+                                                                const T* __restrict__ cvar, const T* __restrict__ yobs,
+                                                                const T* __restrict__ pair_mean, const T* __restrict__ pair_cov,
+                                                                int grads, T* __restrict__ ws) {
+    constexpr int W = D2 + 1, TRI = D2 * (D2 + 1) / 2, E = TRI + D2 + 1, R = (E + 63) / 64;
+    __shared__ T lw[64 * W];
+    __shared__ T ls[D2 * D2];
+    __shared__ T lm[D2];
+    __shared__ T lg[3 * 64];           // gv of the tile's points, then gm, then ve
+    const int lane = threadIdx.x;
+    const long t = blockIdx.x;
+    long bs = (long)tile_seg[t];
+    bs = bs < 0 ? 0 : (bs >= BS ? BS - 1 : bs);
+    const long b = bs / S;
+    const long s = bs - b * S;
+    long k_lo = (long)seg[b * (S + 1) + s], k_hi = (long)seg[b * (S + 1) + s + 1];
+    k_lo = k_lo < 0 ? 0 : (k_lo > N ? N : k_lo);
+    k_hi = k_hi < k_lo ? k_lo : (k_hi > N ? N : k_hi);
+    const long j = t - (long)seg_tile[bs];                          // this tile's number within its segment
+    const long k0 = (j >= 0 && j <= (k_hi - k_lo) / 64) ? k_lo + 64 * j : k_hi;
+    const int npts = k_hi - k0 < 64 ? int(k_hi - k0) : 64;          // (0 only for a table that disagrees with the offsets)
+    // this lane's entries: e < TRI is (i, j <= i) of g_cov, then g_mean's (j = D2: the column of ones), then sum ve (i = j = D2)
+    int ei[R], ej[R], es[R];
+    T part[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        int e = lane + 64 * r;
+        part[r] = T(0);
+        if (e >= E) e = 0;
+        if (e < TRI) {
+            int i = 0;
+            while ((i + 1) * (i + 2) / 2 <= e) ++i;
+            ei[r] = i;
+            ej[r] = e - i * (i + 1) / 2;
+            es[r] = 0;
+        } else if (e < TRI + D2) {
+            ei[r] = e - TRI;
+            ej[r] = D2;
+            es[r] = 64;
+        } else {
+            ei[r] = D2;
+            ej[r] = D2;
+            es[r] = 128;
+        }
+    }
+    if (npts > 0) {
+        for (int idx = lane; idx < D2 * D2; idx += 64) ls[idx] = pair_cov[bs * (D2 * D2) + idx];
+        if (lane < D2) lm[lane] = pair_mean[bs * D2 + lane];
+        lw[lane * W + D2] = T(1);
+        const T* wt = w + (b * N + k0) * D2;
+        for (int idx = lane; idx < npts * D2; idx += 64) lw[(idx / D2) * W + idx % D2] = wt[idx];
+        __syncthreads();
+        if (lane < npts) {
+            const long id = b * N + k0 + lane;
+            T wr[D2];
+#pragma unroll
+            for (int i = 0; i < D2; ++i) wr[i] = lw[lane * W + i];
+            T mu = T(0), s2 = cvar[id];
+#pragma unroll
+            for (int i = 0; i < D2; ++i) {
+                T u = T(0);
+#pragma unroll
+                for (int c = 0; c < D2; ++c) u += ls[i * D2 + c] * wr[c];
+                s2 += wr[i] * u;
+                mu += wr[i] * lm[i];
+            }
+            const T y = yobs[id];
+            T ve, gm, gv;
+            if (s2 > T(0)) {
+                expectations<T, LIK>(q, p, mu, s2, y, ve, gm, gv);
+            } else {                               // outside the domain: NaN in all three sums of this point's segment
+                ve = gm = gv = nan_of<T>();
+            }
+            lg[lane] = gv;
+            lg[64 + lane] = gm;
+            lg[128 + lane] = ve;
+        }
+        __syncthreads();
+        if (grads) {
+            for (int k = 0; k < npts; ++k) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) part[r] += (lg[es[r] + k] * lw[k * W + ej[r]]) * lw[k * W + ei[r]];
+            }
+        } else if (lane == (E - 1) % 64) {         // value only: the one entry, with the bits it has beside the gradients
+            for (int k = 0; k < npts; ++k) part[R - 1] += lg[128 + k];
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int e = lane + 64 * r;
+        if (e < E) ws[t * E + e] = part[r];
+    }
+}
+
+template <typename T, int D2>
+__global__ void __launch_bounds__(256) sparse_expect_reduce_kernel(long num_tiles, const long long* __restrict__ seg_tile,
+                                                                   const T* __restrict__ ws, T* __restrict__ ve_sum,
+                                                                   T* __restrict__ g_mean, T* __restrict__ g_cov) {
+    constexpr int TRI = D2 * (D2 + 1) / 2, E = TRI + D2 + 1;
+    const long bs = blockIdx.x;
+    long t_lo = 0, t_hi = 0;
+    if (seg_tile) {                                // (NULL: no points at all)
+        t_lo = (long)seg_tile[bs];
+        t_hi = (long)seg_tile[bs + 1];
+        t_lo = t_lo < 0 ? 0 : (t_lo > num_tiles ? num_tiles : t_lo);
+        t_hi = t_hi < t_lo ? t_lo : (t_hi > num_tiles ? num_tiles : t_hi);
+    }
+    for (int e = threadIdx.x; e < E; e += 256) {
+        if (e < E - 1 ? !g_mean : !ve_sum) continue;
+        T acc = T(0);
+        for (long t = t_lo; t < t_hi; ++t) acc += ws[t * E + e];
+        if (e < TRI) {
+            int i = 0;
+            while ((i + 1) * (i + 2) / 2 <= e) ++i;
+            const int c = e - i * (i + 1) / 2;
+            g_cov[bs * (D2 * D2) + i * D2 + c] = acc;
+            g_cov[bs * (D2 * D2) + c * D2 + i] = acc;
+        } else if (e < E - 1) {
+            g_mean[bs * D2 + (e - TRI)] = acc;
+        } else {
+            ve_sum[bs] = acc;
+        }
+    }
+}
+
 // log of the predictive density  log int p(y | f) N(f | mu, s2) df
 template <typename T, int LIK>
 __global__ void __launch_bounds__(256) lik_pld_kernel(long N, Rule<T> q, Par<T> p, const T* __restrict__ fmu, const T* __restrict__ fvar,
@@ -445,9 +590,102 @@ int run_sparse(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double
 #undef MF_SPARSE_CASE
 }
 
+constexpr size_t expect_row(int two_d) { return size_t(two_d) * (two_d + 1) / 2 + two_d + 1; }
+
+template <typename T, int LIK, int D2>
+int launch_expect(int64_t B, int64_t N, int64_t S, const Rule<T>& q, const Par<T>& p, const int64_t* seg, const T* w, const T* c,
+                  const T* y, const T* pm, const T* pc, int64_t tiles, const int64_t* tile_seg, const int64_t* seg_tile, T* ws,
+                  T* ve_sum, T* g_mean, T* g_cov, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const long long* table = reinterpret_cast<const long long*>(seg_tile);
+    if (tiles > 0) {
+        hipLaunchKernelGGL((sparse_expect_tile_kernel<T, LIK, D2>), dim3((unsigned)tiles), dim3(64), 0, st, (long)N, (int)S,
+                           (long)(B * S), q, p, reinterpret_cast<const long long*>(seg),
+                           reinterpret_cast<const long long*>(tile_seg), table, w, c, y, pm, pc, g_mean ? 1 : 0, ws);
+        if (hipGetLastError() != hipSuccess) return -1000;
+    }
+    hipLaunchKernelGGL((sparse_expect_reduce_kernel<T, D2>), dim3((unsigned)(B * S)), dim3(256), 0, st, (long)tiles,
+                       tiles > 0 ? table : nullptr, ws, ve_sum, g_mean, g_cov);
+    return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
+template <typename T, int D2>
+int dispatch_expect(int lik, int64_t B, int64_t N, int64_t S, const Rule<T>& q, const Par<T>& p, const int64_t* seg, const T* w,
+                    const T* c, const T* y, const T* pm, const T* pc, int64_t tiles, const int64_t* tile_seg,
+                    const int64_t* seg_tile, T* ws, T* ve_sum, T* g_mean, T* g_cov, void* stream) {
+    switch (lik) {
+        case 0: return launch_expect<T, 0, D2>(B, N, S, q, p, seg, w, c, y, pm, pc, tiles, tile_seg, seg_tile, ws, ve_sum, g_mean, g_cov, stream);
+        case 1: return launch_expect<T, 1, D2>(B, N, S, q, p, seg, w, c, y, pm, pc, tiles, tile_seg, seg_tile, ws, ve_sum, g_mean, g_cov, stream);
+        case 2: return launch_expect<T, 2, D2>(B, N, S, q, p, seg, w, c, y, pm, pc, tiles, tile_seg, seg_tile, ws, ve_sum, g_mean, g_cov, stream);
+        default: return launch_expect<T, 3, D2>(B, N, S, q, p, seg, w, c, y, pm, pc, tiles, tile_seg, seg_tile, ws, ve_sum, g_mean, g_cov, stream);
+    }
+}
+
+// the segmented expected log-likelihood's argument checks: the (negative) position of the offending argument in ITS signature
+template <typename T>
+int run_expect(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq, const double* nodes,
+               const double* weights, const int64_t* seg, const T* w, const T* c, const T* y, const T* pm, const T* pc,
+               int64_t tiles, const int64_t* tile_seg, const int64_t* seg_tile, void* ws, size_t ws_bytes, T* ve_sum, T* g_mean,
+               T* g_cov, void* stream) {
+    if (B < 0) return -1;
+    if (N < 0) return -2;
+    if (S < 1 || (B > 0 && S > int64_t(0x7fffffff) / B)) return -3;
+    if (two_d < 2 || two_d > 18 || (two_d & 1)) return -100;
+    Rule<T> q;
+    Par<T> p;
+    const int bad = prepare<T>(0, lik, params, nq, nodes, weights, false, q, p);      // -2 ... -6 there are arguments 5 ... 9 here
+    if (bad) return bad - 3;
+    if (tiles < 0 || tiles > int64_t(0x7fffffff) || (N == 0 && tiles != 0)) return -16;
+    if (!g_mean && g_cov) return -22;
+    if (g_mean && !g_cov) return -23;
+    if (B == 0 || (!ve_sum && !g_mean)) return 0;      // nothing asked for
+    if (tiles > 0) {
+        if (!seg) return -10;
+        if (!w) return -11;
+        if (!c) return -12;
+        if (!y) return -13;
+        if (!pm) return -14;
+        if (!pc) return -15;
+        if (!tile_seg) return -17;
+        if (!seg_tile) return -18;
+        if (!ws) return -19;
+        if (ws_bytes < size_t(tiles) * expect_row(two_d) * sizeof(T)) return -20;
+    }
+#define MF_EXPECT_CASE(D2) \
+    case D2: return dispatch_expect<T, D2>(lik, B, N, S, q, p, seg, w, c, y, pm, pc, tiles, tile_seg, seg_tile, static_cast<T*>(ws), \
+                                           ve_sum, g_mean, g_cov, stream);
+    switch (two_d) {
+        MF_EXPECT_CASE(2) MF_EXPECT_CASE(4) MF_EXPECT_CASE(6) MF_EXPECT_CASE(8) MF_EXPECT_CASE(10) MF_EXPECT_CASE(12)
+        MF_EXPECT_CASE(14) MF_EXPECT_CASE(16) MF_EXPECT_CASE(18)
+        default: return -100;
+    }
+#undef MF_EXPECT_CASE
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t mf_lik_sparse_expectations_workspace_bytes(int64_t num_tiles, int two_d, int elem_size) {
+    if (num_tiles <= 0 || two_d < 2 || two_d > 18 || (two_d & 1) || elem_size < 1) return 0;
+    return size_t(num_tiles) * expect_row(two_d) * size_t(elem_size);
+}
+int mf_lik_sparse_expectations_f64(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq,
+                                   const double* nodes, const double* weights, const int64_t* seg_offsets, const double* w,
+                                   const double* c, const double* y, const double* pair_mean, const double* pair_cov,
+                                   int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile, void* workspace,
+                                   size_t workspace_bytes, double* ve_sum, double* g_mean, double* g_cov, void* stream) {
+    return run_expect<double>(B, N, S, two_d, lik, params, nq, nodes, weights, seg_offsets, w, c, y, pair_mean, pair_cov, num_tiles,
+                              tile_seg, seg_tile, workspace, workspace_bytes, ve_sum, g_mean, g_cov, stream);
+}
+int mf_lik_sparse_expectations_f32(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq,
+                                   const double* nodes, const double* weights, const int64_t* seg_offsets, const float* w,
+                                   const float* c, const float* y, const float* pair_mean, const float* pair_cov,
+                                   int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile, void* workspace,
+                                   size_t workspace_bytes, float* ve_sum, float* g_mean, float* g_cov, void* stream) {
+    return run_expect<float>(B, N, S, two_d, lik, params, nq, nodes, weights, seg_offsets, w, c, y, pair_mean, pair_cov, num_tiles,
+                             tile_seg, seg_tile, workspace, workspace_bytes, ve_sum, g_mean, g_cov, stream);
+}
 
 int mf_lik_variational_expectations_f64(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
                                         const double* fmu, const double* fvar, const double* y, double* ve, double* g_mu,

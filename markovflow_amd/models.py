@@ -14,6 +14,10 @@ Only what drives the hot path is mirrored: construction from ``(time_points, obs
 ``M + 1`` multivariate sites on the pairs of neighbouring inducing states instead of one site per data point: the chain has ``M``
 blocks, and the ``N`` data points enter ``update_sites`` through ONE launch of ``mf_lik_sparse_cvi_site_update_*`` (projection onto
 the bracketing pair, expectations, back-projection and the segmented sum).
+
+``SparseVariationalGaussianProcess`` (mirror of ``markovflow/models/sparse_variational.py:31-270``, zero mean function) holds ``q`` on
+the inducing points as a trainable ``StateSpaceModel``; the data term of its ELBO and the adjoint onto the pair marginals of ``q`` are
+ONE call of ``mf_lik_sparse_expectations_*`` (two passes, tile-parallel), the KL term is ``StateSpaceModel.kl_divergence``.
 """
 from typing import Optional, Tuple
 
@@ -828,4 +832,294 @@ class SparseCVIGaussianProcess:
             raise NotImplementedError("predict_log_density: the likelihoods are univariate (marginal variances only)")
         new_times, new_obs = input_data
         f_mean, f_var = self.posterior.predict_f(new_times)
+        return self._likelihood.predict_log_density(f_mean, f_var, new_obs)
+
+
+# ---- SVGP: the ELBO's data term ----------------------------------------------------------------------------------------------------
+SPARSE_EXPECT_TILE = 64         # mf_lik_sparse_expectations_*: points per tile of pass 1
+
+
+def sparse_expectation_tiles(offsets: torch.Tensor) -> Tuple[int, torch.Tensor, torch.Tensor]:
+    """The tile table of ``mf_lik_sparse_expectations_*`` from the segment ``offsets [.., S + 1]``: the number of tiles (ONE read-back:
+    callers cache the table with the projections), ``tile_seg [num_tiles]`` - the flat segment ``series * S + segment`` of every tile
+    - and ``seg_tile [B S + 1]``, the first tile of every segment; flat int64 tensors on the offsets' device."""
+    lengths = (offsets[..., 1:] - offsets[..., :-1]).reshape(-1)
+    per_segment = (lengths + (SPARSE_EXPECT_TILE - 1)) // SPARSE_EXPECT_TILE
+    seg_tile = torch.cat([torch.zeros_like(per_segment[:1]), torch.cumsum(per_segment, dim=0)]).contiguous()
+    num_tiles = int(seg_tile[-1])
+    tile_seg = torch.repeat_interleave(torch.arange(per_segment.numel(), device=offsets.device), per_segment, output_size=num_tiles)
+    return num_tiles, tile_seg.contiguous(), seg_tile
+
+
+def _sparse_expectations_launch(likelihood: Likelihood, w, c, y, offsets, tiles, pair_mean, pair_cov, want_grads: bool):
+    """ONE call of ``mf_lik_sparse_expectations_*``: ``(ve_sum [.., S], g_mean [.., S, 2d] | None, g_cov [.., S, 2d, 2d] | None)``."""
+    dtype, dev = w.dtype, w.device
+    n, two_d, segs = w.shape[-2], w.shape[-1], offsets.shape[-1] - 1
+    batch = tuple(offsets.shape[:-1])
+    bsz = offsets.numel() // (segs + 1)
+    num_tiles, tile_seg, seg_tile = tiles
+    ve_sum = torch.empty(batch + (segs,), dtype=dtype, device=dev)
+    g_mean = torch.empty(batch + (segs, two_d), dtype=dtype, device=dev) if want_grads else None
+    g_cov = torch.empty(batch + (segs, two_d, two_d), dtype=dtype, device=dev) if want_grads else None
+    ws_bytes = int(_lib.load().mf_lik_sparse_expectations_workspace_bytes(num_tiles, two_d, w.element_size()))
+    ws = _lib.workspace(ws_bytes, dev)
+    lik = likelihood
+    _lib.call("mf_lik_sparse_expectations", dtype, bsz, n, segs, two_d, lik._id, lik._c_params(), lik.num_gauss_hermite_points,
+              lik._c_nodes, lik._c_weights, _lib.ptr(offsets.contiguous()), _lib.ptr(w.contiguous()), _lib.ptr(c.contiguous()),
+              _lib.ptr(y.contiguous()), _lib.ptr(pair_mean.contiguous()), _lib.ptr(pair_cov.contiguous()), num_tiles,
+              _lib.ptr(tile_seg), _lib.ptr(seg_tile), _lib.ptr(ws), ws_bytes, _lib.ptr(ve_sum), _lib.ptr(g_mean), _lib.ptr(g_cov),
+              _lib.stream_ptr(dev))
+    return ve_sum, g_mean, g_cov
+
+
+class _SparseExpectedLogLikelihood(torch.autograd.Function):
+    """Value ``batch + [M + 1]``; the adjoints onto the pair marginals come out of the same launch and wait for the backward."""
+
+    @staticmethod
+    def forward(ctx, pair_mean, pair_cov, likelihood, w, c, y, offsets, tiles):
+        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        with torch.no_grad():
+            ve_sum, g_mean, g_cov = _sparse_expectations_launch(likelihood, w.detach(), c.detach(), y.detach(), offsets, tiles,
+                                                                pair_mean.detach(), pair_cov.detach(), want)
+        if want:
+            ctx.save_for_backward(g_mean, g_cov)
+        return ve_sum
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if torch.is_grad_enabled():
+            raise RuntimeError("sparse_expected_log_likelihood is differentiable once: its backward uses the adjoints computed in "
+                               "the forward and has no second-order support (create_graph=True)")
+        g_mean, g_cov = ctx.saved_tensors
+        return (grad_out[..., None] * g_mean if ctx.needs_input_grad[0] else None,
+                grad_out[..., None, None] * g_cov if ctx.needs_input_grad[1] else None, None, None, None, None, None, None)
+
+
+def sparse_expected_log_likelihood(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor, offsets: torch.Tensor,
+                                   pair_mean: torch.Tensor, pair_cov: torch.Tensor, tiles=None) -> torch.Tensor:
+    """``sum_k E_q log p(y_k | f_k)`` per pair of neighbouring inducing states, ``batch + [M + 1]``, with ``fmu = w_k . m_s`` and
+    ``fvar = c_k + w_k^T S_s w_k`` for the points ``offsets[s] <= k < offsets[s + 1]`` of pair ``s`` (``w [.., N, 2d]``, ``c``, ``y``
+    ``[.., N]``, ``offsets [.., M + 2]``, ``pair_mean [.., M + 1, 2d]``, ``pair_cov [.., M + 1, 2d, 2d]``): ONE call of
+    ``mf_lik_sparse_expectations_*`` on HIP tensors, ``2d <= 18``.  Differentiable ONCE in ``pair_mean`` and ``pair_cov`` (an
+    unconstrained matrix: the gradient is symmetric) - the backward multiplies the adjoints the forward computed beside the value,
+    there is no second launch; not differentiable in ``w`` and ``c``.  ``tiles``: ``sparse_expectation_tiles(offsets)`` when the
+    caller keeps it."""
+    if not isinstance(likelihood, Likelihood):
+        raise TypeError("likelihood must be a markovflow_amd.likelihoods.Likelihood")
+    two_d, segs = w.shape[-1], offsets.shape[-1] - 1
+    batch = tuple(offsets.shape[:-1])
+    if two_d > SPARSE_SITE_MAX_TWO_D or two_d % 2:
+        raise NotImplementedError(f"sparse_expected_log_likelihood: 2d = {two_d} is outside 2, 4, ..., {SPARSE_SITE_MAX_TWO_D}; "
+                                  "use sparse_expected_log_likelihood_torch")
+    expect = dict(w=(w, batch + (w.shape[-2], two_d)), c=(c, batch + (w.shape[-2],)), y=(y, batch + (w.shape[-2],)),
+                  pair_mean=(pair_mean, batch + (segs, two_d)), pair_cov=(pair_cov, batch + (segs, two_d, two_d)))
+    for name, (t, shape) in expect.items():
+        if tuple(t.shape) != shape:
+            raise ValueError(f"sparse_expected_log_likelihood: {name} has shape {tuple(t.shape)}, expected {shape}")
+    _lib.same_dtype_device(w, "sparse_expected_log_likelihood", c=c, y=y, pair_mean=pair_mean, pair_cov=pair_cov)
+    if torch.is_grad_enabled() and (w.requires_grad or c.requires_grad):
+        raise NotImplementedError("sparse_expected_log_likelihood has no adjoint onto w and c (a kernel hyper-parameter under the "
+                                  "tape): use sparse_expected_log_likelihood_torch")
+    if tiles is None:
+        tiles = sparse_expectation_tiles(offsets)
+    return _SparseExpectedLogLikelihood.apply(pair_mean, pair_cov, likelihood, w, c, y, offsets, tiles)
+
+
+def sparse_expected_log_likelihood_torch(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor,
+                                         indices: torch.Tensor, pair_mean: torch.Tensor, pair_cov: torch.Tensor) -> torch.Tensor:
+    """The same quantity as a torch composition, differentiable by autograd in ``pair_mean``, ``pair_cov``, ``w`` and ``c``: gathers
+    of the pair marginals by the per-point pair index (``indices [.., N]``), ``likelihood.variational_expectations`` and
+    ``index_add_`` over the segments.  It runs on CPU tensors, it is the models' route for ``2d > 18`` and for a kernel
+    hyper-parameter under the tape, and it is what ``mf_lik_sparse_expectations_*`` is measured against."""
+    two_d, segs = w.shape[-1], pair_mean.shape[-2]
+    m = torch.gather(pair_mean, -2, indices[..., None].expand(tuple(indices.shape) + (two_d,)))
+    cov = torch.gather(pair_cov, -3, indices[..., None, None].expand(tuple(indices.shape) + (two_d, two_d)))
+    fmu = torch.sum(w * m, dim=-1)
+    fvar = c + torch.sum(w * torch.sum(cov * w[..., None, :], dim=-1), dim=-1)
+    ve = likelihood.variational_expectations(fmu[..., None], fvar[..., None], y[..., None])
+    series = torch.arange(math.prod(indices.shape[:-1]), device=indices.device).reshape(tuple(indices.shape[:-1]) + (1,))
+    flat = (indices + series * segs).reshape(-1)
+    out = torch.zeros(math.prod(pair_mean.shape[:-1]), dtype=ve.dtype, device=ve.device).index_add(0, flat, ve.reshape(-1))
+    return out.reshape(pair_mean.shape[:-1])
+
+
+def _sorted_series(time_points: torch.Tensor) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+    """``(order, sorted time points)``: the stable permutation that sorts every series, or ``(None, time_points)`` for sorted data."""
+    if not bool((time_points[..., 1:] < time_points[..., :-1]).any()):
+        return None, time_points
+    order = torch.argsort(time_points, dim=-1, stable=True)
+    return order, torch.gather(time_points, -1, order)
+
+
+class SparseVariationalGaussianProcess:
+    """GP prior, general likelihood, a free-form Gaussian posterior ``q(s(z))`` on the states at ``M`` inducing points held as a
+    trainable ``StateSpaceModel`` (markovflow/models/sparse_variational.py:31-270; zero mean function, plain float likelihood
+    parameters, a batch of series as leading dimensions).  The ELBO is ``scale sum_i E_q log p(y_i | f_i) - KL[q(s(z)) || p(s(z))]``;
+    ``q`` is trained with any torch optimiser on ``trainable_variables`` or with ``ssm_natgrad.SSMNaturalGradient`` on ``dist_q``."""
+
+    def __init__(self, kernel: SDEKernel, likelihood: Likelihood, inducing_points: torch.Tensor, num_data: Optional[int] = None,
+                 initial_distribution: Optional[StateSpaceModel] = None) -> None:
+        """
+        :param inducing_points: ``batch + [num_inducing]``, sorted, at least two (a ``StateSpaceModel`` needs a transition).
+        :param num_data: the total number of observations per series when ``elbo`` is fed minibatches.
+        :param initial_distribution: the initial ``q`` on the inducing points; the prior by default.
+        """
+        if not isinstance(kernel, SDEKernel):
+            raise TypeError("kernel must be a markovflow_amd.kernels.SDEKernel")
+        if not isinstance(likelihood, Likelihood):
+            raise TypeError("likelihood must be a markovflow_amd.likelihoods.Likelihood")
+        if not isinstance(inducing_points, torch.Tensor) or inducing_points.dim() < 1 or inducing_points.shape[-1] < 2:
+            raise ValueError("inducing_points must be a tensor of shape batch + [num_inducing] with at least two points")
+        if inducing_points.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"markovflow_amd supports float32 and float64 tensors, got {inducing_points.dtype}")
+        if bool((inducing_points[..., 1:] < inducing_points[..., :-1]).any()):
+            raise ValueError("inducing_points must be sorted")
+        if num_data is not None and not num_data > 0:
+            raise ValueError(f"num_data must be positive, got {num_data}")
+        self._kernel = kernel
+        self._likelihood = likelihood
+        self.inducing_inputs = inducing_points
+        self.num_data = num_data
+        if initial_distribution is None:
+            initial_distribution = kernel.state_space_model(inducing_points)
+        elif not isinstance(initial_distribution, StateSpaceModel):
+            raise TypeError("initial_distribution must be a StateSpaceModel")
+        if (tuple(initial_distribution.batch_shape) != tuple(inducing_points.shape[:-1])
+                or initial_distribution.num_transitions + 1 != inducing_points.shape[-1]
+                or initial_distribution.state_dim != kernel.state_dim):
+            raise ValueError("initial_distribution must be a chain on the inducing points: batch shape "
+                             f"{tuple(inducing_points.shape[:-1])}, {inducing_points.shape[-1]} states of dimension {kernel.state_dim}")
+        self._dist_q = initial_distribution.create_trainable_copy()
+        self._posterior = ConditionalProcess(posterior_dist=self._dist_q, kernel=kernel, conditioning_time_points=inducing_points)
+        self._projection_cache = None
+
+    @property
+    def time_points(self) -> torch.Tensor:
+        """The inducing points (sparse_variational.py:194-202)."""
+        return self.inducing_inputs
+
+    @property
+    def kernel(self) -> SDEKernel:
+        return self._kernel
+
+    @property
+    def likelihood(self) -> Likelihood:
+        return self._likelihood
+
+    @property
+    def dist_p(self) -> StateSpaceModel:
+        """The prior chain on the inducing points, rebuilt on every access (sparse_variational.py:225-230)."""
+        return self._kernel.state_space_model(self.inducing_inputs)
+
+    @property
+    def dist_q(self) -> StateSpaceModel:
+        """The variational chain, a trainable copy: its leaves are ``trainable_variables``."""
+        return self._dist_q
+
+    @property
+    def posterior(self) -> ConditionalProcess:
+        return self._posterior
+
+    @property
+    def trainable_variables(self) -> Tuple[torch.Tensor, ...]:
+        """The leaves of ``dist_q``: ``(mu0, chol_P0, As, offsets, chol_Qs)``."""
+        return self._dist_q.trainable_variables
+
+    # ---- data --------------------------------------------------------------------------------------------------------------------
+    def _check_data(self, input_data: Tuple[torch.Tensor, torch.Tensor], what: str) -> Tuple[torch.Tensor, torch.Tensor]:
+        time_points, observations = input_data
+        if observations.dim() < 2 or observations.shape[-1] != 1:
+            raise ValueError(f"{what}: observations must have shape batch + [num_data, 1], got {tuple(observations.shape)}")
+        if tuple(time_points.shape) != tuple(observations.shape[:-1]):
+            raise ValueError(f"{what}: time_points must have shape observations.shape[:-1]")
+        if tuple(time_points.shape[:-1]) != tuple(self.inducing_inputs.shape[:-1]):
+            raise ValueError(f"{what}: the data must carry the batch shape of the inducing points, "
+                             f"{tuple(self.inducing_inputs.shape[:-1])}, got {tuple(time_points.shape[:-1])}")
+        _lib.same_dtype_device(self.inducing_inputs, f"SparseVariationalGaussianProcess.{what}", time_points=time_points,
+                               observations=observations)
+        return time_points, observations
+
+    def _fused(self, time_points: torch.Tensor) -> bool:
+        return (time_points.is_cuda and 2 * self._kernel.state_dim <= SPARSE_SITE_MAX_TWO_D and not self._kernel._needs_grad())
+
+    def _projections(self, time_points: torch.Tensor):
+        """``(order | None, w, c, indices, offsets, tiles)`` of the data: the permutation that sorts each series (None for sorted
+        data), ``sparse_site_projections`` of the sorted points and the tile table, kept until the data, the inducing points or a
+        hyper-parameter of the kernel is replaced or written in place (keyed as ``SparseCVIGaussianProcess._projections``)."""
+        sources = [time_points, self.inducing_inputs] + [x for comp in self._kernel._components() for x in comp._leaves()]
+        key = tuple(_version_key(x) for x in sources)
+        cached = self._projection_cache
+        if (cached is not None and None not in key and cached[0] == key and len(cached[1]) == len(sources)
+                and all(a is b for a, b in zip(cached[1], sources))):          # (the cache holds the tensors: ids are not reused)
+            return cached[2]
+        with torch.no_grad():
+            order, time_points = _sorted_series(time_points)
+            w, c, indices, offsets = sparse_site_projections(self._kernel, time_points, self.inducing_inputs)
+            tiles = sparse_expectation_tiles(offsets) if time_points.is_cuda else None
+        out = (order, w, c, indices, offsets, tiles)
+        self._projection_cache = (key, sources, out)
+        return out
+
+    def _pair_marginals(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(m_pair [.., M+1, 2d], S_pair [.., M+1, 2d, 2d])`` of ``dist_q`` - under the tape when its leaves require a gradient -
+        with the stationary prior beyond both ends."""
+        z = self.inducing_inputs
+        batch = tuple(z.shape[:-1])
+        m0 = self._kernel.initial_mean(batch).to(dtype=z.dtype, device=z.device)
+        p0 = self._kernel.initial_covariance(z[..., :1]).to(dtype=z.dtype, device=z.device)
+        return conditionals.pairwise_marginals(self._dist_q, m0, p0)
+
+    def _expected_log_likelihood(self, time_points: torch.Tensor, observations: torch.Tensor) -> torch.Tensor:
+        """``sum_i E_q log p(y_i | f_i)`` per pair, ``batch + [M + 1]``."""
+        pair_mean, pair_cov = self._pair_marginals()
+        if self._fused(time_points):
+            order, w, c, _, offsets, tiles = self._projections(time_points)
+            y = observations[..., 0]
+            if order is not None:
+                y = torch.gather(y, -1, order)
+            return sparse_expected_log_likelihood(self._likelihood, w, c, y, offsets, pair_mean, pair_cov, tiles=tiles)
+        if self._kernel._needs_grad():
+            # a hyper-parameter under the tape: w and c are part of the graph
+            order, time_points = _sorted_series(time_points)
+            proj, cov, indices = conditionals._conditional_statistics(time_points, self.inducing_inputs, self._kernel)
+            h = self._kernel.generate_emission_model(time_points).emission_matrix
+            w, c = (h @ proj)[..., 0, :], (h @ cov @ h.transpose(-1, -2))[..., 0, 0]
+        else:
+            order, w, c, indices, _, _ = self._projections(time_points)
+        y = observations[..., 0]
+        if order is not None:
+            y = torch.gather(y, -1, order)
+        return sparse_expected_log_likelihood_torch(self._likelihood, w, c, y, indices, pair_mean, pair_cov)
+
+    # ---- inference ---------------------------------------------------------------------------------------------------------------
+    def elbo(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+        """``scale sum_i E_q log p(y_i | f_i) - KL[q(s(z)) || p(s(z))]``, summed over the batch; ``scale = num_data / minibatch size``
+        when ``num_data`` is set (sparse_variational.py:149-192).  The data need not be sorted: a minibatch is a random subset; each
+        series is sorted on a copy (a stable argsort, cached with the projections), so the ELBO of shuffled data has the bits of the
+        sorted data's.  HIP tensors with ``2d <= 18`` and no kernel hyper-parameter under the tape: the pair marginals of ``dist_q``
+        under the tape, ONE call of ``mf_lik_sparse_expectations_*`` whose adjoints the backward reuses, and the KL adjoints;
+        otherwise ``sparse_expected_log_likelihood_torch``."""
+        time_points, observations = self._check_data(input_data, "elbo")
+        ve = torch.sum(self._expected_log_likelihood(time_points, observations))
+        kl = torch.sum(self._dist_q.kl_divergence(self.dist_p))
+        if self.num_data is not None:
+            ve = ve * (float(self.num_data) / time_points.shape[-1])
+        return ve - kl
+
+    def loss(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+        """``-elbo`` (sparse_variational.py:250-260)."""
+        return -self.elbo(input_data)
+
+    def predict_f(self, new_time_points: torch.Tensor, full_output_cov: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Posterior mean and variance of ``f`` at ``new_time_points`` (sorted), ``batch + [num_new, 1]`` each."""
+        with torch.no_grad():
+            return self._posterior.predict_f(new_time_points, full_output_cov)
+
+    def predict_log_density(self, input_data: Tuple[torch.Tensor, torch.Tensor], full_output_cov: bool = False) -> torch.Tensor:
+        """Log density of new data ``(time_points, observations)`` under the posterior, ``batch + [num_new]``
+        (sparse_variational.py:262-270)."""
+        if full_output_cov:
+            raise NotImplementedError("predict_log_density: the likelihoods are univariate (marginal variances only)")
+        new_times, new_obs = input_data
+        f_mean, f_var = self.predict_f(new_times)
         return self._likelihood.predict_log_density(f_mean, f_var, new_obs)
