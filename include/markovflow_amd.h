@@ -729,6 +729,37 @@ int mf_lik_predict_log_density_f32(int64_t N, int lik, const double* params, int
                                    const float* fmu, const float* fvar, const float* y, float* out, void* stream);
 
 /*
+ * Power expectation propagation (markovflow/models/pep.py:99-215; csrc/mf_lik.hip).  N, lik, params, nq, nodes and weights as above;
+ * alpha in (0, 1] is the power, lr in [0, 1] the damping.
+ *
+ * mf_lik_log_expected_density: led [N] = I(mu, var; alpha) = log int p(y | f)^alpha N(f | mu, var) df,  g1 = dI/dmu,  g2 = d2I/dmu2;
+ *   any of the three may be NULL.  Gaussian in closed form, the others on the rule: with v_i = alpha l(f_i) + log w_i and
+ *   p_i = softmax_i v_i,  I = logsumexp_i v_i,  g1 = sum p_i alpha l'(f_i),  g2 = sum p_i (alpha l''(f_i) + alpha^2 l'(f_i)^2) - g1^2
+ *   - the exact derivatives of the discretised sum, accumulated in one pass under the running maximum.  Poisson's - lgamma(y + 1)
+ *   enters multiplied by alpha.  At alpha = 1, led is mf_lik_predict_log_density's out.
+ * mf_lik_pep_site_update: one step on the sites t(f) = exp(nat1 f + nat2 f^2 + log_norm), [N] each, IN PLACE, from the posterior
+ *   marginals fmu, fvar of f:  cavity 1 / v_c = 1 / fvar + 2 alpha nat2,  mu_c = v_c (fmu / fvar - alpha nat1);  I, g1, g2 at the
+ *   cavity;  den = 1 + v_c g2,  L2 = g2 / (2 den),  L1 = (g1 - mu_c g2) / den;  normaliser I + G(mu_c, v_c) - G(fmu, fvar) with
+ *   G(mu, v) = (log v + mu^2 / v) / 2;  pep = (1 - alpha) old + (L1, L2, normaliser),  new = (1 - lr) old + lr pep.
+ *   `update` [N] (bytes, may be NULL = every point): a point whose flag is 0 is left as it is, and so - all three numbers, bit for
+ *   bit - is a point where fvar, 1 / v_c or den is not > 0 or a new value is not finite.  cav_mu, cav_var [N] (may be NULL) get the
+ *   cavity of EVERY point, NaN where it does not exist.
+ */
+int mf_lik_log_expected_density_f64(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                                    double alpha, const double* fmu, const double* fvar, const double* y, double* led, double* g1,
+                                    double* g2, void* stream);
+int mf_lik_log_expected_density_f32(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                                    float alpha, const float* fmu, const float* fvar, const float* y, float* led, float* g1, float* g2,
+                                    void* stream);
+int mf_lik_pep_site_update_f64(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                               double alpha, double lr, const double* fmu, const double* fvar, const double* y,
+                               const unsigned char* update, double* nat1, double* nat2, double* log_norm, double* cav_mu,
+                               double* cav_var, void* stream);
+int mf_lik_pep_site_update_f32(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                               float alpha, float lr, const float* fmu, const float* fvar, const float* y, const unsigned char* update,
+                               float* nat1, float* nat2, float* log_norm, float* cav_mu, float* cav_var, void* stream);
+
+/*
  * The segmented site update of the sparse CVI model (markovflow/models/sparse_variational_cvi.py:176-221; csrc/mf_lik.hip): B
  * series of N data points, S = M + 1 sites per series on the pairs of neighbouring inducing states, two_d = 2 d in 2, 4, ..., 18.
  *   seg_offsets [B, S + 1] int64  the points seg_offsets[b, s] <= k < seg_offsets[b, s + 1] of series b belong to site s

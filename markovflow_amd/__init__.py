@@ -21,7 +21,7 @@ from . import conditionals, distributed, kernels, likelihoods, models, ssm_gauss
 from .kernels import (Constant, HarmonicOscillator, IndependentMultiOutput, Matern12, Matern32, Matern52, Product, SDEKernel,
                       StationaryKernel, Sum)
 from .likelihoods import Bernoulli, Gaussian, Likelihood, Poisson, StudentT
-from .models import (CVIGaussianProcess, GaussianProcessRegression, SparseCVIGaussianProcess,
+from .models import (CVIGaussianProcess, GaussianProcessRegression, PowerExpectationPropagation, SparseCVIGaussianProcess,
                      SparseVariationalGaussianProcess)
 from .ssm_natgrad import SSMNaturalGradient
 from .posterior import AnalyticPosteriorProcess, ConditionalProcess
@@ -34,6 +34,6 @@ __all__ = [
     "state_space_model_from_covariances", "conditionals", "distributed", "kernels", "models", "ssm_gaussian_transformations", "SDEKernel", "StationaryKernel", "Matern12", "Matern32",
     "Matern52", "Sum", "IndependentMultiOutput", "Constant", "HarmonicOscillator", "Product", "GaussianProcessRegression", "AnalyticPosteriorProcess", "ConditionalProcess",
     "MarkovflowAmdError", "check_errors", "errors_as_nan", "set_synchronous_checks",
-    "likelihoods", "Likelihood", "Gaussian", "Bernoulli", "Poisson", "StudentT", "CVIGaussianProcess",
+    "likelihoods", "Likelihood", "Gaussian", "Bernoulli", "Poisson", "StudentT", "CVIGaussianProcess", "PowerExpectationPropagation",
     "SparseCVIGaussianProcess", "SparseVariationalGaussianProcess", "SSMNaturalGradient", "ssm_natgrad",
 ]

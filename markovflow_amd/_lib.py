@@ -72,6 +72,8 @@ _SIGS = {
     "mf_lik_variational_expectations": (_int, [_i64, _int, _hd, _int, _hd, _hd, "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_cvi_site_update": (_int, [_i64, _int, _hd, _int, _hd, _hd, "Tp", "Tp", "Tp", "T", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_predict_log_density": (_int, [_i64, _int, _hd, _int, _hd, _hd, "Tp", "Tp", "Tp", "Tp", _vp]),
+    "mf_lik_log_expected_density": (_int, [_i64, _int, _hd, _int, _hd, _hd, "T", "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
+    "mf_lik_pep_site_update": (_int, [_i64, _int, _hd, _int, _hd, _hd, "T", "T", "Tp", "Tp", "Tp", _vp, "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_sparse_cvi_site_update": (_int, [_i64, _i64, _i64, _int, _int, _hd, _int, _hd, _hd, _vp, "Tp", "Tp", "Tp", "Tp", "Tp", "T",
                                       "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_sparse_expectations": (_int, [_i64, _i64, _i64, _int, _int, _hd, _int, _hd, _hd, _vp, "Tp", "Tp", "Tp", "Tp", "Tp", _i64,

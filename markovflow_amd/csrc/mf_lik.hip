@@ -8,6 +8,8 @@
 // Bernoulli and Student-t use an nq-point Gauss-Hermite rule: f_i = mu + sqrt(2 s2) x_i,
 //   VE = sum w_i l(f_i),  dVE/dmu = sum w_i l'(f_i),  dVE/ds2 = sum w_i l'(f_i) x_i / sqrt(2 s2)        (w_i = weight_i / sqrt pi)
 // - the exact derivatives of the discretised sum, which is what the reference's tape through ndiagquad yields.
+// Power expectation propagation (markovflow/models/pep.py) adds the log of the expected alpha-power density with its first two
+// derivatives in the mean, and the fused site update built on it (cavity, gradient correction, site normaliser, power / damping step).
 // One lane per data point; the rule travels by value in the kernel arguments and the loop over its nodes is wavefront-uniform, so
 // nodes and weights are scalar loads; no LDS, no cross-lane traffic, no temporaries in memory.
 #include "../../include/markovflow_amd.h"
@@ -41,32 +43,46 @@ __device__ __forceinline__ double m_lgamma(double x) { return lgamma(x); }
 
 template <typename T> __device__ __forceinline__ T nan_of() { return T(NAN); }
 
-// log p(y | f) and, when asked, its derivative in f.  Poisson: WITHOUT - lgamma(y + 1), which does not depend on f; the caller
-// subtracts it once per point, outside its loop over the nodes.
-template <typename T, int LIK, bool DERIV>
-__device__ __forceinline__ T log_prob(T f, T y, const Par<T>& p, T& dl) {
+// log p(y | f) and, when asked, its first (DERIV) and second (DERIV2, which implies the first) derivative in f.  Poisson: WITHOUT
+// - lgamma(y + 1), which does not depend on f; the caller subtracts it once per point, outside its loop over the nodes.
+//   Bernoulli: with p' = (1 - 2e-3) phi(f) and p'' = -f p',  l'' = -f l' - p'^2 (y / p^2 + (1 - y) / (1 - p)^2)
+//   Student-t: l'' = -(df + 1) (a - r^2) / (a + r^2)^2,  a = df scale^2,  r = y - f
+template <typename T, int LIK, bool DERIV, bool DERIV2 = false>
+__device__ __forceinline__ T log_prob(T f, T y, const Par<T>& p, T& dl, T& d2l) {
     constexpr T LOG_2PI = T(1.8378770664093454835606594728112);
     if (LIK == 0) {
         const T r = y - f, iv = T(1) / p.p0;
-        if (DERIV) dl = r * iv;
+        if (DERIV || DERIV2) dl = r * iv;
+        if (DERIV2) d2l = -iv;
         return T(-0.5) * (LOG_2PI + m_log(p.p0)) - T(0.5) * r * r * iv;
     } else if (LIK == 1) {
         constexpr T JIT = T(1e-3), INV_SQRT2 = T(0.70710678118654752440084436210485), INV_SQRT_2PI = T(0.3989422804014326779399460599343);
         const T pr = T(0.5) * (T(1) + m_erf(f * INV_SQRT2)) * (T(1) - T(2) * JIT) + JIT;
-        if (DERIV) {
+        if (DERIV || DERIV2) {
             const T dp = (T(1) - T(2) * JIT) * INV_SQRT_2PI * m_exp(T(-0.5) * f * f);
             dl = dp * (y / pr - (T(1) - y) / (T(1) - pr));
+            if (DERIV2) {
+                const T q1 = T(1) - pr;
+                d2l = -f * dl - dp * dp * (y / (pr * pr) + (T(1) - y) / (q1 * q1));
+            }
         }
         return y * m_log(pr) + (T(1) - y) * m_log1p(-pr);
     } else if (LIK == 2) {
         const T e = m_exp(f);
-        if (DERIV) dl = y - e;
+        if (DERIV || DERIV2) dl = y - e;
+        if (DERIV2) d2l = -e;
         return y * f - e;
     } else {
         const T r = y - f, a = p.p1 * p.p0 * p.p0, r2 = r * r;      // a = df scale^2
-        if (DERIV) dl = (p.p1 + T(1)) * r / (a + r2);
+        if (DERIV || DERIV2) dl = (p.p1 + T(1)) * r / (a + r2);
+        if (DERIV2) d2l = -(p.p1 + T(1)) * (a - r2) / ((a + r2) * (a + r2));
         return p.p2 - T(0.5) * (p.p1 + T(1)) * m_log1p(r2 / a);
     }
+}
+template <typename T, int LIK, bool DERIV>
+__device__ __forceinline__ T log_prob(T f, T y, const Par<T>& p, T& dl) {
+    T unused;
+    return log_prob<T, LIK, DERIV, false>(f, y, p, dl, unused);
 }
 
 // the expectation and its two derivatives at one point (fvar > 0)
@@ -426,7 +442,110 @@ __global__ void __launch_bounds__(256) lik_pld_kernel(long N, Rule<T> q, Par<T> 
     out[id] = res;
 }
 
-// argument checks shared by the three entry points: 0, or the (negative) position of the offending argument
+// ---- power expectation propagation (markovflow/models/pep.py:99-215) ----------------------------------------------------------
+// I(mu, v; alpha) = log int p(y | f)^alpha N(f | mu, v) df with g1 = dI/dmu and g2 = d2I/dmu2 at one point (v > 0).  Gaussian: closed
+// form.  The others: with v_i = alpha l(f_i) + log w_i (q.w holds the LOG weights), p_i = softmax_i v_i,
+//   I = logsumexp_i v_i,   g1 = sum p_i alpha l'_i,   g2 = sum p_i (alpha l''_i + alpha^2 l'_i^2) - g1^2
+// - the exact derivatives of the discretised sum.  ONE pass over the nodes: the three sums run under the running maximum m, and a
+// node costs ONE exponential, exp(-|v - m|), which is the rescale of the sums when the maximum moves and the node's own weight when
+// it does not (selects, no branch: the loop stays wavefront-uniform).  A node of weight exactly 0 (v = -inf: a Poisson rate that
+// overflowed, whose l' is infinite too) contributes nothing; a NaN lands in the sum of weights and makes all three results NaN.
+template <typename T, int LIK>
+__device__ __forceinline__ void log_expected_density(const Rule<T>& q, const Par<T>& p, T alpha, T mu, T s2, T y, T& led, T& g1,
+                                                     T& g2) {
+    if (LIK == 0) {
+        constexpr T LOG_2PI = T(1.8378770664093454835606594728112);
+        const T sa = p.p0 / alpha, iv = T(1) / (sa + s2), r = y - mu;
+        led = T(-0.5) * alpha * (LOG_2PI + m_log(p.p0)) + T(0.5) * (m_log(sa) + m_log(iv)) - T(0.5) * r * r * iv;
+        g1 = r * iv;
+        g2 = -iv;
+    } else {
+        const T sd = m_sqrt(T(2) * s2);
+        T m = -INFINITY, s0 = T(0), s1 = T(0), sq = T(0);
+        for (int i = 0; i < q.nq; ++i) {          // wavefront-uniform: q lives in the kernel arguments
+            T dl, d2l;
+            const T l = log_prob<T, LIK, true, true>(mu + sd * q.x[i], y, p, dl, d2l);
+            const T v = alpha * l + q.w[i], a = alpha * dl, b = alpha * d2l + a * a;
+            const bool up = v > m;
+            const T e = v == -INFINITY ? T(0) : m_exp(up ? m - v : v - m);
+            const T sc = up ? e : T(1), c = up ? T(1) : e;
+            const bool live = c > T(0);
+            s0 = s0 * sc + c;
+            s1 = s1 * sc + (live ? c * a : T(0));
+            sq = sq * sc + (live ? c * b : T(0));
+            m = up ? v : m;
+        }
+        const T inv = T(1) / s0;
+        // Poisson: the node-independent term of the log density, once.  It cancels against the log-sum-exp (y = 40: 107.8 - 110.3),
+        // so the three terms meet in double in both precisions: float32 pays one rounding, of the result.  The float32 Poisson
+        // instantiation therefore carries fp64 instructions ON PURPOSE - one double lgamma and two double adds per point, outside
+        // the loop over the nodes
+        led = LIK == 2 ? T(double(m) + double(m_log(s0)) - double(alpha) * lgamma(double(y) + 1.0)) : m + m_log(s0);
+        g1 = s1 * inv;
+        g2 = sq * inv - g1 * g1;
+    }
+}
+
+template <typename T, int LIK>
+__global__ void __launch_bounds__(256) lik_led_kernel(long N, Rule<T> q, Par<T> p, T alpha, const T* __restrict__ fmu,
+                                                      const T* __restrict__ fvar, const T* __restrict__ yobs, T* __restrict__ out_led,
+                                                      T* __restrict__ out_g1, T* __restrict__ out_g2) {
+    const long id = (long)blockIdx.x * 256 + threadIdx.x;
+    if (id >= N) return;
+    const T mu = fmu[id], s2 = fvar[id], y = yobs[id];
+    T led, g1, g2;
+    if (s2 > T(0)) {
+        log_expected_density<T, LIK>(q, p, alpha, mu, s2, y, led, g1, g2);
+    } else {                                       // outside the domain (non-positive or NaN variance): NaN for this point only
+        led = g1 = g2 = nan_of<T>();
+    }
+    if (out_led) out_led[id] = led;
+    if (out_g1) out_g1[id] = g1;
+    if (out_g2) out_g2[id] = g2;
+}
+
+// One power-EP step on the sites t(f) = exp(n1 f + n2 f^2 + ln), in place (pep.py:179-215), from the posterior marginal N(m, s) of f:
+//   cavity        1 / v_c = 1 / s + 2 alpha n2,   mu_c = v_c (m / s - alpha n1)      (the d x d route of pep.py:120-148 collapses to
+//                 this by Sherman-Morrison: the site touches the state through f = h . s only)
+//   correction    den = 1 + v_c g2,  L2 = g2 / (2 den),  L1 = (g1 - mu_c g2) / den   with I, g1, g2 at the cavity (pep.py:250-261)
+//   normaliser    I + G(mu_c, v_c) - G(m, s),   G(mu, v) = (log v + mu^2 / v) / 2
+//   step          pep = (1 - alpha) old + (L1, L2, normaliser),   new = (1 - lr) old + lr pep
+// A point is SKIPPED - nothing is stored to its site - when its update flag is off, when s, 1 / v_c or den is not > 0, or when one of
+// the new values is not finite.  The cavity goes out for every point (NaN where it does not exist).
+template <typename T, int LIK>
+__global__ void __launch_bounds__(256) lik_pep_kernel(long N, Rule<T> q, Par<T> p, T alpha, T lr, const T* __restrict__ fmu,
+                                                      const T* __restrict__ fvar, const T* __restrict__ yobs,
+                                                      const unsigned char* __restrict__ update, T* __restrict__ nat1,
+                                                      T* __restrict__ nat2, T* __restrict__ log_norm, T* __restrict__ cav_mu,
+                                                      T* __restrict__ cav_var) {
+    const long id = (long)blockIdx.x * 256 + threadIdx.x;
+    if (id >= N) return;
+    const T m = fmu[id], s = fvar[id], y = yobs[id];
+    const T n1 = nat1[id], n2 = nat2[id], ln = log_norm[id];
+    const T is = T(1) / s, pc = is + T(2) * alpha * n2;
+    const bool cavity = s > T(0) && pc > T(0);
+    const T vc = cavity ? T(1) / pc : nan_of<T>();
+    const T mc = cavity ? vc * (m * is - alpha * n1) : nan_of<T>();
+    if (cav_mu) cav_mu[id] = mc;
+    if (cav_var) cav_var[id] = vc;
+    if (!cavity || (update && !update[id])) return;       // (1 / v_c so small that v_c = inf: the finiteness check below)
+    T led, g1, g2;
+    log_expected_density<T, LIK>(q, p, alpha, mc, vc, y, led, g1, g2);
+    // (Gaussian: den in closed form, free of the cancellation in 1 + v_c g2 - with lr = alpha = 1 the step then returns -1 / (2 s2))
+    const T den = LIK == 0 ? (p.p0 / alpha) / (p.p0 / alpha + vc) : T(1) + vc * g2;
+    const T l2 = T(0.5) * g2 / den, l1 = (g1 - mc * g2) / den;
+    const T norm = led + T(0.5) * (m_log(vc) + mc * mc * pc) - T(0.5) * (m_log(s) + m * m * is);
+    const T keep = T(1) - lr, decay = T(1) - alpha;
+    const T new1 = keep * n1 + lr * (decay * n1 + l1);
+    const T new2 = keep * n2 + lr * (decay * n2 + l2);
+    const T newn = keep * ln + lr * (decay * ln + norm);
+    if (!(den > T(0)) || !__builtin_isfinite(new1) || !__builtin_isfinite(new2) || !__builtin_isfinite(newn)) return;
+    nat1[id] = new1;
+    nat2[id] = new2;
+    log_norm[id] = newn;
+}
+
+// argument checks shared by the five entry points: 0, or the (negative) position of the offending argument
 template <typename T>
 int prepare(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights, bool log_weights,
             Rule<T>& q, Par<T>& p) {
@@ -531,6 +650,68 @@ int run_pld(int64_t N, int lik, const double* params, int nq, const double* node
         case 1: return launch_pld<T, 1>(N, q, p, fmu, fvar, y, out, stream);
         case 2: return launch_pld<T, 2>(N, q, p, fmu, fvar, y, out, stream);
         default: return launch_pld<T, 3>(N, q, p, fmu, fvar, y, out, stream);
+    }
+}
+
+template <typename T, int LIK>
+int launch_led(int64_t N, const Rule<T>& q, const Par<T>& p, T alpha, const T* fmu, const T* fvar, const T* y, T* led, T* g1, T* g2,
+               void* stream) {
+    hipLaunchKernelGGL((lik_led_kernel<T, LIK>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       (long)N, q, p, alpha, fmu, fvar, y, led, g1, g2);
+    return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
+template <typename T>
+int run_led(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights, T alpha, const T* fmu,
+            const T* fvar, const T* y, T* led, T* g1, T* g2, void* stream) {
+    Rule<T> q;
+    Par<T> p;
+    const int bad = prepare<T>(N, lik, params, nq, nodes, weights, true, q, p);
+    if (bad) return bad;
+    if (!(alpha > T(0)) || !(alpha <= T(1))) return -7;
+    if (N == 0) return 0;
+    if (!fmu) return -8;
+    if (!fvar) return -9;
+    if (!y) return -10;
+    if (!led && !g1 && !g2) return 0;              // nothing asked for
+    switch (lik) {
+        case 0: return launch_led<T, 0>(N, q, p, alpha, fmu, fvar, y, led, g1, g2, stream);
+        case 1: return launch_led<T, 1>(N, q, p, alpha, fmu, fvar, y, led, g1, g2, stream);
+        case 2: return launch_led<T, 2>(N, q, p, alpha, fmu, fvar, y, led, g1, g2, stream);
+        default: return launch_led<T, 3>(N, q, p, alpha, fmu, fvar, y, led, g1, g2, stream);
+    }
+}
+
+template <typename T, int LIK>
+int launch_pep(int64_t N, const Rule<T>& q, const Par<T>& p, T alpha, T lr, const T* fmu, const T* fvar, const T* y,
+               const unsigned char* update, T* nat1, T* nat2, T* log_norm, T* cav_mu, T* cav_var, void* stream) {
+    hipLaunchKernelGGL((lik_pep_kernel<T, LIK>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       (long)N, q, p, alpha, lr, fmu, fvar, y, update, nat1, nat2, log_norm, cav_mu, cav_var);
+    return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
+template <typename T>
+int run_pep(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights, T alpha, T lr, const T* fmu,
+            const T* fvar, const T* y, const unsigned char* update, T* nat1, T* nat2, T* log_norm, T* cav_mu, T* cav_var,
+            void* stream) {
+    Rule<T> q;
+    Par<T> p;
+    const int bad = prepare<T>(N, lik, params, nq, nodes, weights, true, q, p);
+    if (bad) return bad;
+    if (!(alpha > T(0)) || !(alpha <= T(1))) return -7;
+    if (!(lr >= T(0)) || !(lr <= T(1))) return -8;
+    if (N == 0) return 0;
+    if (!fmu) return -9;
+    if (!fvar) return -10;
+    if (!y) return -11;
+    if (!nat1) return -13;
+    if (!nat2) return -14;
+    if (!log_norm) return -15;
+    switch (lik) {
+        case 0: return launch_pep<T, 0>(N, q, p, alpha, lr, fmu, fvar, y, update, nat1, nat2, log_norm, cav_mu, cav_var, stream);
+        case 1: return launch_pep<T, 1>(N, q, p, alpha, lr, fmu, fvar, y, update, nat1, nat2, log_norm, cav_mu, cav_var, stream);
+        case 2: return launch_pep<T, 2>(N, q, p, alpha, lr, fmu, fvar, y, update, nat1, nat2, log_norm, cav_mu, cav_var, stream);
+        default: return launch_pep<T, 3>(N, q, p, alpha, lr, fmu, fvar, y, update, nat1, nat2, log_norm, cav_mu, cav_var, stream);
     }
 }
 
@@ -714,6 +895,29 @@ int mf_lik_predict_log_density_f64(int64_t N, int lik, const double* params, int
 int mf_lik_predict_log_density_f32(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
                                    const float* fmu, const float* fvar, const float* y, float* out, void* stream) {
     return run_pld<float>(N, lik, params, nq, nodes, weights, fmu, fvar, y, out, stream);
+}
+int mf_lik_log_expected_density_f64(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                                    double alpha, const double* fmu, const double* fvar, const double* y, double* led, double* g1,
+                                    double* g2, void* stream) {
+    return run_led<double>(N, lik, params, nq, nodes, weights, alpha, fmu, fvar, y, led, g1, g2, stream);
+}
+int mf_lik_log_expected_density_f32(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                                    float alpha, const float* fmu, const float* fvar, const float* y, float* led, float* g1, float* g2,
+                                    void* stream) {
+    return run_led<float>(N, lik, params, nq, nodes, weights, alpha, fmu, fvar, y, led, g1, g2, stream);
+}
+int mf_lik_pep_site_update_f64(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                               double alpha, double lr, const double* fmu, const double* fvar, const double* y,
+                               const unsigned char* update, double* nat1, double* nat2, double* log_norm, double* cav_mu,
+                               double* cav_var, void* stream) {
+    return run_pep<double>(N, lik, params, nq, nodes, weights, alpha, lr, fmu, fvar, y, update, nat1, nat2, log_norm, cav_mu, cav_var,
+                           stream);
+}
+int mf_lik_pep_site_update_f32(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                               float alpha, float lr, const float* fmu, const float* fvar, const float* y, const unsigned char* update,
+                               float* nat1, float* nat2, float* log_norm, float* cav_mu, float* cav_var, void* stream) {
+    return run_pep<float>(N, lik, params, nq, nodes, weights, alpha, lr, fmu, fvar, y, update, nat1, nat2, log_norm, cav_mu, cav_var,
+                          stream);
 }
 int mf_lik_sparse_cvi_site_update_f64(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq,
                                       const double* nodes, const double* weights, const int64_t* seg_offsets, const double* w,

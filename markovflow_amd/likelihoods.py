@@ -20,11 +20,26 @@ Gaussian and Poisson expectations are closed forms; Bernoulli and Student-t use 
 - the exact derivatives of the discretised sum (what the reference's tape through ``ndiagquad`` computes).  The domain is
 ``var > 0``: a point with a non-positive or NaN variance gets NaN.
 
+Power expectation propagation (``PowerExpectationPropagation``) asks for the log of the expected ``alpha``-power density,
+
+    I(mu, var; alpha) = log int p(y | f)^alpha N(f | mu, var) df,    g1 = dI/dmu,    g2 = d2I/dmu2
+
+(``log_expected_density`` / ``grad_log_expected_density``) and for the site update built on it (``pep_site_update``).  Gaussian: closed
+form, ``I = -(alpha / 2) log(2 pi s2) + log(2 pi s2 / alpha) / 2 + log N(y; mu, s2 / alpha + var)``.  The others use the rule: with
+``v_i = alpha l(f_i) + log w_i`` and ``p_i = softmax_i v_i``,
+
+    I = logsumexp_i v_i,    g1 = sum p_i alpha l'(f_i),    g2 = sum p_i (alpha l''(f_i) + alpha^2 l'(f_i)^2) - g1^2
+
+- again the exact derivatives of the discretised sum (the reference's double tape); a node of weight exactly 0 contributes nothing.
+DEVIATION from the reference: its generic ``PEPScalarLikelihood.log_expected_density`` ignores ``alpha`` and its ``PEPGaussian`` returns
+``alpha log N(y; mu, s2 + var)``, which is not ``log int p^alpha q``; here the integral is computed.  At ``alpha = 1`` all three agree,
+and ``I`` is ``predict_log_density``.
+
 The parameters (``variance``, ``scale``, ``df``) are plain Python floats and are NOT trainable.
 """
 import ctypes
 import math
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -68,6 +83,10 @@ class Likelihood:
 
     def _log_prob_and_grad(self, f: torch.Tensor, y: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """``log p(y | f)`` and its derivative in ``f``, element-wise."""
+        raise NotImplementedError
+
+    def _log_prob_second_derivative(self, f: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """The second derivative of ``log p(y | f)`` in ``f``, element-wise."""
         raise NotImplementedError
 
     def _closed_expectations(self, mu, var, y):
@@ -155,6 +174,80 @@ class Likelihood:
             torch.autograd.graph.increment_version(nat1)
             torch.autograd.graph.increment_version(nat2)
 
+    # ---- power expectation propagation ---------------------------------------------------------------------------------------------
+    @staticmethod
+    def _check_alpha(what: str, alpha) -> float:
+        if not 0.0 < float(alpha) <= 1.0:
+            raise ValueError(f"{what}: alpha must lie in (0, 1], got {alpha}")
+        return float(alpha)
+
+    def _log_expected_density(self, fmu, fvar, y, alpha: float, want=(True, True, True)):
+        """``(I, g1, g2)``, each of ``fmu``'s shape or None where not wanted: ONE launch of ``mf_lik_log_expected_density_*`` on HIP
+        tensors, ``torch_log_expected_density`` on CPU tensors."""
+        if not fmu.is_cuda:
+            return tuple(o if w else None for o, w in zip(torch_log_expected_density(self, fmu, fvar, y, alpha), want))
+        mu, var, obs = fmu.contiguous(), fvar.contiguous(), y.contiguous()
+        outs = [torch.empty_like(mu) if w else None for w in want]
+        _lib.call("mf_lik_log_expected_density", mu.dtype, mu.numel(), self._id, self._c_params(), self.num_gauss_hermite_points,
+                  self._c_nodes, self._c_weights, alpha, _lib.ptr(mu), _lib.ptr(var), _lib.ptr(obs), *[_lib.ptr(o) for o in outs],
+                  _lib.stream_ptr(mu.device))
+        return tuple(outs)
+
+    def log_expected_density(self, fmu: torch.Tensor, fvar: torch.Tensor, y: torch.Tensor, alpha: float = 1.0) -> torch.Tensor:
+        """``log int p(y | f)^alpha N(f | fmu, fvar) df``, ``batch + [N]`` (not differentiable).  Unlike the reference's, it IS the
+        integral of the power (module docstring); at ``alpha = 1`` it is ``predict_log_density``."""
+        self._check("log_expected_density", fmu, fvar=fvar, y=y)
+        alpha = self._check_alpha("log_expected_density", alpha)
+        with torch.no_grad():
+            return self._log_expected_density(fmu, fvar, y, alpha, (True, False, False))[0][..., 0]
+
+    def grad_log_expected_density(self, fmu: torch.Tensor, fvar: torch.Tensor, y: torch.Tensor, alpha: float = 1.0):
+        """``(I, (g1, g2))``: the value, ``batch + [N]``, with its first and second derivative in the mean, ``batch + [N, 1]`` each
+        (the shapes of the reference's tape: the derivatives are taken with respect to ``fmu``).  Not differentiable further."""
+        self._check("grad_log_expected_density", fmu, fvar=fvar, y=y)
+        alpha = self._check_alpha("grad_log_expected_density", alpha)
+        with torch.no_grad():
+            led, g1, g2 = self._log_expected_density(fmu, fvar, y, alpha)
+        return led[..., 0], (g1, g2)
+
+    def pep_site_update(self, fmu: torch.Tensor, fvar: torch.Tensor, y: torch.Tensor, alpha: float, learning_rate: float,
+                        nat1: torch.Tensor, nat2: torch.Tensor, log_norm: torch.Tensor, update: Optional[torch.Tensor] = None) -> None:
+        """One power-EP step on the sites ``exp(nat1 f + nat2 f^2 + log_norm)``, IN PLACE, from the posterior marginals ``fmu``,
+        ``fvar`` of ``f`` (pep.py:179-215): cavity ``1 / v_c = 1 / fvar + 2 alpha nat2``, ``mu_c = v_c (fmu / fvar - alpha nat1)``;
+        ``I, g1, g2`` at the cavity; ``den = 1 + v_c g2``, ``L2 = g2 / (2 den)``, ``L1 = (g1 - mu_c g2) / den``; normaliser
+        ``I + G(mu_c, v_c) - G(fmu, fvar)``, ``G(mu, v) = (log v + mu^2 / v) / 2``; ``pep = (1 - alpha) old + (L1, L2, normaliser)``,
+        ``new = (1 - lr) old + lr pep``.  ``nat1``, ``nat2`` and ``log_norm`` hold one element per element of ``fmu`` (any shape) and
+        must be contiguous; ``update`` (bool or uint8, one element per point, None = every point) selects the points to update.
+        DEVIATION from the reference: a point whose ``fvar``, ``1 / v_c`` or ``den`` is not positive, or whose new values are not
+        finite, is SKIPPED - its three numbers stay as they were - where the reference would write NaN into the site.
+        HIP tensors: one launch of ``mf_lik_pep_site_update_*``.  Returns None on either device: the cavity, which the kernel can
+        write out and ``torch_pep_site_update`` returns, is ``PowerExpectationPropagation.compute_cavity``'s to report."""
+        what = f"{type(self).__name__}.pep_site_update"
+        self._check("pep_site_update", fmu, fvar=fvar, y=y)
+        _lib.same_dtype_device(fmu, what, nat1=nat1, nat2=nat2, log_norm=log_norm)
+        if any(t.numel() != fmu.numel() or not t.is_contiguous() for t in (nat1, nat2, log_norm)):
+            raise ValueError("pep_site_update: nat1, nat2 and log_norm must be contiguous and hold one element per data point")
+        alpha = self._check_alpha("pep_site_update", alpha)
+        if not 0.0 <= float(learning_rate) <= 1.0:
+            raise ValueError(f"pep_site_update: learning_rate must lie in [0, 1], got {learning_rate}")
+        lr = float(learning_rate)
+        if update is not None:
+            if update.dtype not in (torch.bool, torch.uint8) or update.numel() != fmu.numel() or update.device != fmu.device:
+                raise ValueError("pep_site_update: update must be a bool or uint8 tensor on the data's device with one element per "
+                                 "data point")
+            update = update.contiguous().view(torch.uint8)
+        with torch.no_grad():
+            if not fmu.is_cuda:
+                torch_pep_site_update(self, fmu, fvar, y, alpha, lr, nat1, nat2, log_norm, update)
+                return
+            mu, var, obs = fmu.contiguous(), fvar.contiguous(), y.contiguous()
+            _lib.call("mf_lik_pep_site_update", mu.dtype, mu.numel(), self._id, self._c_params(), self.num_gauss_hermite_points,
+                      self._c_nodes, self._c_weights, alpha, lr, _lib.ptr(mu), _lib.ptr(var), _lib.ptr(obs), _lib.ptr(update),
+                      _lib.ptr(nat1), _lib.ptr(nat2), _lib.ptr(log_norm), None, None, _lib.stream_ptr(mu.device))
+            # the kernel wrote through raw pointers: tell torch (as cvi_site_update does)
+            for t in (nat1, nat2, log_norm):
+                torch.autograd.graph.increment_version(t)
+
 
 class _VariationalExpectations(torch.autograd.Function):
     """Value ``batch + [N, 1]`` with the two derivatives computed in the same pass and saved for the backward."""
@@ -204,6 +297,64 @@ def torch_predict_log_density(lik: Likelihood, fmu: torch.Tensor, fvar: torch.Te
     return torch.where(ok, out, torch.full_like(fmu, float("nan")))
 
 
+def torch_log_expected_density(lik: Likelihood, fmu: torch.Tensor, fvar: torch.Tensor, y: torch.Tensor, alpha: float = 1.0):
+    """``(I, dI/dmu, d2I/dmu2)`` of ``I = log int p(y | f)^alpha N(f | fmu, fvar) df`` as element-wise torch operations over
+    ``[..., nq]`` temporaries, each of ``fmu``'s shape: the CPU route of ``Likelihood.log_expected_density``, and (inside
+    ``torch_pep_site_update``) the composition ``mf_lik_pep_site_update_*`` is measured against on the device."""
+    ok = fvar > 0
+    var = torch.where(ok, fvar, torch.ones_like(fvar))
+    if isinstance(lik, Gaussian):
+        sa = lik.variance / alpha
+        iv = 1.0 / (sa + var)
+        r = y - fmu
+        led = (-0.5 * alpha * math.log(2 * math.pi * lik.variance) + 0.5 * (math.log(sa) + torch.log(iv)) - 0.5 * r * r * iv)
+        outs = led, r * iv, -iv
+    else:
+        x, _, logw = lik._rule(fmu)
+        f, yy = fmu[..., None] + torch.sqrt(2.0 * var)[..., None] * x, y[..., None]
+        l, dl = lik._log_prob_and_grad(f, yy)
+        a = alpha * dl
+        b = alpha * lik._log_prob_second_derivative(f, yy) + a * a
+        v = alpha * l + logw
+        led = torch.logsumexp(v, dim=-1)
+        pr = torch.exp(v - led[..., None])
+        zero = torch.zeros_like(pr)
+        g1 = torch.sum(torch.where(pr > 0, pr * a, zero), dim=-1)       # (a node of weight exactly 0 may carry an infinite l')
+        outs = led, g1, torch.sum(torch.where(pr > 0, pr * b, zero), dim=-1) - g1 * g1
+    nan = torch.full_like(fmu, float("nan"))
+    return tuple(torch.where(ok, o, nan) for o in outs)
+
+
+def torch_pep_site_update(lik: Likelihood, fmu: torch.Tensor, fvar: torch.Tensor, y: torch.Tensor, alpha: float, learning_rate: float,
+                          nat1: torch.Tensor, nat2: torch.Tensor, log_norm: torch.Tensor, update: Optional[torch.Tensor] = None):
+    """``Likelihood.pep_site_update`` as a composition of element-wise torch operations, in place on ``nat1``, ``nat2``, ``log_norm``
+    (one element per element of ``fmu``): its CPU route, and what ``mf_lik_pep_site_update_*`` fuses and is timed against.  Unlike
+    the method, which returns None, it returns the cavity ``(mu_c, v_c)``, NaN where it does not exist - the counterpart of the
+    kernel's optional ``cav_mu`` / ``cav_var`` outputs, for the tests that compare the two."""
+    n1, n2, ln = (t.reshape(fmu.shape) for t in (nat1, nat2, log_norm))
+    prec = 1.0 / fvar + 2.0 * alpha * n2
+    cavity = (fvar > 0) & (prec > 0)
+    nan, one = torch.full_like(fmu, float("nan")), torch.ones_like(fmu)
+    vc = torch.where(cavity, 1.0 / prec, one)
+    mc = torch.where(cavity, vc * (fmu / fvar - alpha * n1), one)
+    led, g1, g2 = torch_log_expected_density(lik, mc, vc, y, alpha)
+    if isinstance(lik, Gaussian):                  # closed form, free of the cancellation in 1 + v_c g2 (as the kernel)
+        den = (lik.variance / alpha) / (lik.variance / alpha + vc)
+    else:
+        den = 1.0 + vc * g2
+    l2 = 0.5 * g2 / den
+    l1 = (g1 - mc * g2) / den
+    norm = led + 0.5 * (torch.log(vc) + mc * mc / vc) - 0.5 * (torch.log(fvar) + fmu * fmu / fvar)
+    lr = learning_rate
+    new = [(1.0 - lr) * old + lr * ((1.0 - alpha) * old + step) for old, step in ((n1, l1), (n2, l2), (ln, norm))]
+    ok = cavity & (den > 0) & torch.isfinite(new[0]) & torch.isfinite(new[1]) & torch.isfinite(new[2])
+    if update is not None:
+        ok = ok & (update.reshape(fmu.shape) != 0)
+    for t, old, fresh in zip((nat1, nat2, log_norm), (n1, n2, ln), new):
+        t.copy_(torch.where(ok, fresh, old).reshape(t.shape))
+    return torch.where(cavity, mc, nan), torch.where(cavity, vc, nan)
+
+
 class Gaussian(Likelihood):
     """``p(y | f) = N(y | f, variance)``; ``variance`` is a plain float, not trainable."""
 
@@ -221,6 +372,9 @@ class Gaussian(Likelihood):
     def _log_prob_and_grad(self, f, y):
         r = y - f
         return -0.5 * (math.log(2 * math.pi) + math.log(self.variance)) - 0.5 * r * r / self.variance, r / self.variance
+
+    def _log_prob_second_derivative(self, f, y):
+        return torch.full_like(f, -1.0 / self.variance)
 
     def _closed_expectations(self, mu, var, y):
         r = y - mu
@@ -241,6 +395,12 @@ class Bernoulli(Likelihood):
         dp = (1.0 - 2.0 * _JITTER) / math.sqrt(2 * math.pi) * torch.exp(-0.5 * f * f)
         return y * torch.log(p) + (1.0 - y) * torch.log1p(-p), dp * (y / p - (1.0 - y) / (1.0 - p))
 
+    def _log_prob_second_derivative(self, f, y):
+        # p'' = -f p':  l'' = -f l' - p'^2 (y / p^2 + (1 - y) / (1 - p)^2)
+        p = _inv_probit(f)
+        dp = (1.0 - 2.0 * _JITTER) / math.sqrt(2 * math.pi) * torch.exp(-0.5 * f * f)
+        return -f * dp * (y / p - (1.0 - y) / (1.0 - p)) - dp * dp * (y / (p * p) + (1.0 - y) / ((1.0 - p) * (1.0 - p)))
+
     def predict_mean_and_var(self, fmu, fvar):
         p = _inv_probit(fmu / torch.sqrt(1.0 + fvar))
         return p, p - p * p
@@ -254,6 +414,9 @@ class Poisson(Likelihood):
     def _log_prob_and_grad(self, f, y):
         e = torch.exp(f)
         return y * f - e - torch.lgamma(y + 1.0), y - e
+
+    def _log_prob_second_derivative(self, f, y):
+        return -torch.exp(f) + 0.0 * y
 
     def _closed_expectations(self, mu, var, y):
         e = torch.exp(mu + 0.5 * var)
@@ -286,6 +449,11 @@ class StudentT(Likelihood):
         r = y - f
         a = self.df * self.scale * self.scale
         return self._const - 0.5 * (self.df + 1.0) * torch.log1p(r * r / a), (self.df + 1.0) * r / (a + r * r)
+
+    def _log_prob_second_derivative(self, f, y):
+        r2 = (y - f) ** 2
+        a = self.df * self.scale * self.scale
+        return -(self.df + 1.0) * (a - r2) / ((a + r2) * (a + r2))
 
     def predict_mean_and_var(self, fmu, fvar):
         if not self.df > 2.0:

@@ -1,0 +1,234 @@
+"""
+numpy / scipy (fp64) reference of power expectation propagation - TEST INFRASTRUCTURE, NOT PRODUCT CODE.
+
+Independent of markovflow_amd/likelihoods.py, markovflow_amd/models.py and csrc/mf_lik.hip: the log densities and their first
+derivatives are those of tests/helpers/likelihood_closed_forms.py (scipy.stats / scipy.special), the second derivatives are written
+here and checked against central differences of the first (tests/test_pep_host.py), and the PEP loop is dense linear algebra on the
+kernel matrix with the SCALAR cavity - no state space form anywhere.
+
+Definitions.  Sites t(f) = exp(n1 f + n2 f^2 + ln).  I(mu, v; alpha) = log int p(y | f)^alpha N(f | mu, v) df, g1 = dI/dmu,
+g2 = d2I/dmu2: Gaussian in closed form, the others on the nq-point Gauss-Hermite rule as the exact derivatives of the discretised
+sum - with v_i = alpha l(f_i) + log w_i and p_i = softmax_i v_i:  I = logsumexp v,  g1 = sum p_i alpha l'_i,
+g2 = sum p_i (alpha l''_i + alpha^2 l'_i^2) - g1^2.  A node of weight exactly 0 contributes nothing (its l' may be infinite).
+
+Magnitudes (what scales a rounding-error bound K eps (magnitude + 1); always float64).
+  * I: the softmax-weighted mean of |v_i|, as ``predict_log_density_magnitude``.
+  * g1, g2: a softmax weight p_i = exp(v_i - I) carries the ABSOLUTE error of its exponent as a RELATIVE error, eps (|v_i| + mag_I),
+    so  mag_g1 = sum p_i |alpha l'_i| (1 + |v_i| + mag_I)  and
+    mag_g2 = sum p_i (alpha |l''_i|_terms + alpha^2 l'_i^2) (1 + |v_i| + mag_I) + 2 |g1| mag_g1 + g1^2,
+    with |l''|_terms the sum of the absolute terms of l'' (Bernoulli: |f l'| + p'^2 (y / p^2 + (1 - y) / (1 - p)^2)).
+  * the site update: a running error bound through its scalar algebra - every operation adds one rounding of its own result to the
+    propagated bounds of its operands (``_add`` ... ``_log`` below), the inputs are exact and (I, g1, g2) enter with their magnitudes
+    + 1.  The update may be evaluated at a GIVEN cavity (``cavity=``): the kernel's own, which is checked on its own, so that the
+    sensitivity of I, g1, g2 to the rounding of the cavity - third derivatives - does not have to be bounded.
+"""
+import numpy as np
+from scipy import special
+
+from helpers import likelihood_closed_forms as L
+from helpers import periodic_closed_forms as PC
+
+
+def _bernoulli_parts(f, y):
+    ty = f.dtype.type
+    p = L.inv_probit(f)
+    dp = ty(1 - 2 * L.JITTER) * np.exp(ty(-0.5) * f * f) / np.sqrt(ty(2 * np.pi))
+    return dp * dp * (y / (p * p) + (ty(1) - y) / ((ty(1) - p) * (ty(1) - p)))
+
+
+def d2log_prob(lik, f, y):
+    """d2 log p(y | f) / df2, element-wise, in the dtype of f."""
+    name, params = lik
+    f = np.asarray(f)
+    y = np.asarray(y, dtype=f.dtype)
+    ty = f.dtype.type
+    if name == L.GAUSSIAN:
+        return np.zeros_like(f + y) - ty(1) / ty(params[0])
+    if name == L.BERNOULLI:          # p'' = -f p'
+        return -f * L.dlog_prob(lik, f, y) - _bernoulli_parts(f, y)
+    if name == L.POISSON:
+        return -np.exp(f) + ty(0) * y
+    scale, df = params
+    r2 = (y - f) ** 2
+    a = ty(df * scale * scale)
+    return -ty(df + 1) * (a - r2) / ((a + r2) * (a + r2))
+
+
+def d2log_prob_terms(lik, f, y):
+    """The sum of the absolute terms of ``d2log_prob`` (float64)."""
+    if lik[0] == L.BERNOULLI:
+        return np.abs(f * L.dlog_prob(lik, f, y)) + _bernoulli_parts(np.asarray(f), np.asarray(y, dtype=np.asarray(f).dtype))
+    return np.abs(d2log_prob(lik, f, y))
+
+
+def log_expected_density(lik, mu, var, y, alpha=1.0, nq=20, dtype=np.float64):
+    """``((I, g1, g2), (mag_I, mag_g1, mag_g2))`` - values in ``dtype``, magnitudes in float64 (module docstring)."""
+    mu, var, y = (np.asarray(a, dtype=dtype) for a in (mu, var, y))
+    mu8, var8, y8 = (a.astype(np.float64) for a in (mu, var, y))
+    al = dtype(alpha)
+    if lik[0] == L.GAUSSIAN:
+        s2 = dtype(lik[1][0])
+        tot = s2 / al + var
+        r = y - mu
+        led = (dtype(-0.5) * al * np.log(dtype(2 * np.pi) * s2) + dtype(0.5) * np.log(dtype(2 * np.pi) * s2 / al)
+               - dtype(0.5) * np.log(dtype(2 * np.pi) * tot) - dtype(0.5) * r * r / tot)
+        tot8, r8 = lik[1][0] / alpha + var8, y8 - mu8
+        mags = (0.5 * alpha * abs(np.log(2 * np.pi * lik[1][0])) + 0.5 * abs(np.log(2 * np.pi * lik[1][0] / alpha))
+                + 0.5 * np.abs(np.log(2 * np.pi * tot8)) + 0.5 * r8 * r8 / tot8, np.abs(r8) / tot8, 1.0 / tot8)
+        return (led.astype(dtype), (r / tot).astype(dtype), (-dtype(1) / tot).astype(dtype)), mags
+    x, w = np.polynomial.hermite.hermgauss(nq)
+    logw = np.log(w / np.sqrt(np.pi))
+
+    def sums(m, v, obs, ty):
+        f = m[..., None] + np.sqrt(ty(2) * v)[..., None] * x.astype(ty)
+        yy = obs[..., None]
+        with np.errstate(all="ignore"):
+            l, dl, d2l = L.log_prob(lik, f, yy), L.dlog_prob(lik, f, yy), d2log_prob(lik, f, yy)
+            vals = ty(alpha) * l + logw.astype(ty)
+            led = special.logsumexp(vals, axis=-1).astype(ty)
+            p = np.exp(vals - led[..., None])
+            a = ty(alpha) * dl
+            b = ty(alpha) * d2l + a * a
+            g1 = np.sum(np.where(p > 0, p * a, ty(0)), -1)
+            g2 = np.sum(np.where(p > 0, p * b, ty(0)), -1) - g1 * g1
+        return f, yy, vals, p, a, led, g1, g2
+
+    _, _, _, _, _, led, g1, g2 = sums(mu, var, y, dtype)
+    f, yy, vals, p, a, _, g18, _ = sums(mu8, var8, y8, np.float64)
+    with np.errstate(all="ignore"):
+        mag_i = np.sum(np.where(p > 0, p * np.abs(vals), 0.0), -1)
+        rel = 1.0 + np.abs(vals) + mag_i[..., None]
+        mag_1 = np.sum(np.where(p > 0, p * np.abs(a) * rel, 0.0), -1)
+        terms = alpha * d2log_prob_terms(lik, f, yy) + a * a
+        mag_2 = np.sum(np.where(p > 0, p * terms * rel, 0.0), -1) + 2 * np.abs(g18) * mag_1 + g18 * g18
+    return (led.astype(dtype), g1.astype(dtype), g2.astype(dtype)), (mag_i, mag_1, mag_2)
+
+
+# ---- running error bounds: (value, bound in units of eps) -----------------------------------------------------------------------------
+def _exact(x):
+    x = np.asarray(x, dtype=np.float64)
+    return x, np.zeros_like(x)
+
+
+def _add(a, b, sign=1.0):
+    v = a[0] + sign * b[0]
+    return v, a[1] + b[1] + np.abs(v)
+
+
+def _mul(a, b):
+    v = a[0] * b[0]
+    return v, np.abs(a[0]) * b[1] + np.abs(b[0]) * a[1] + np.abs(v)
+
+
+def _div(a, b):
+    v = a[0] / b[0]
+    return v, a[1] / np.abs(b[0]) + np.abs(v) * b[1] / np.abs(b[0]) + np.abs(v)
+
+
+def _log(a):
+    v = np.log(a[0])
+    return v, a[1] / np.abs(a[0]) + np.abs(v)
+
+
+def cavity(m, s, nat1, nat2, alpha, dtype=np.float64):
+    """The scalar cavity ``1 / v_c = 1 / s + 2 alpha n2``, ``mu_c = v_c (m / s - alpha n1)``: ``(mu_c, v_c, exists)`` in ``dtype`` (NaN
+    where it does not exist) and the running error bounds ``(mag_mu, mag_v)`` in float64."""
+    m_, s_, n1_, n2_ = (np.asarray(a, dtype=dtype) for a in (m, s, nat1, nat2))
+    with np.errstate(all="ignore"):
+        prec = dtype(1) / s_ + dtype(2 * alpha) * n2_
+        exists = (s_ > 0) & (prec > 0)
+        vc = np.where(exists, dtype(1) / prec, dtype(np.nan)).astype(dtype)
+        mc = (vc * (m_ / s_ - dtype(alpha) * n1_)).astype(dtype)
+        m8, s8, n18, n28 = (_exact(a.astype(np.float64)) for a in (m_, s_, n1_, n2_))
+        one = _exact(np.ones_like(m8[0]))
+        pc = _add(_div(one, s8), _mul(_exact(2 * alpha), n28))
+        tv = _div(one, pc)
+        tm = _mul(tv, _add(_div(m8, s8), _mul(_exact(alpha), n18), -1.0))
+    return mc, vc, exists, (tm[1], tv[1])
+
+
+def pep_site_update(lik, m, s, y, alpha, lr, nat1, nat2, log_norm, nq=20, update=None, at_cavity=None, dtype=np.float64):
+    """One site update at every point (the issue's steps 1-6).  ``at_cavity`` = ``(mu_c, v_c)``: steps 2-5 at THAT cavity instead of
+    the one computed here (module docstring).  Returns a dict: ``nat1``, ``nat2``, ``log_norm`` (new values in ``dtype``; a skipped
+    point keeps its old ones), ``mags`` (their running error bounds, float64), ``cav_mu``, ``cav_var``, ``cav_mags``, ``den``,
+    ``lognorm`` (the fresh site normaliser), ``skipped`` (bool)."""
+    m_, s_, y_, n1, n2, ln = (np.asarray(a, dtype=dtype) for a in (m, s, y, nat1, nat2, log_norm))
+    mc, vc, exists, cav_mags = cavity(m_, s_, n1, n2, alpha, dtype)
+    cm, cv = (mc, vc) if at_cavity is None else (np.asarray(a, dtype=dtype) for a in at_cavity)
+    safe = exists & (cv > 0)
+    cm_s, cv_s = np.where(safe, cm, dtype(0)).astype(dtype), np.where(safe, cv, dtype(1)).astype(dtype)
+    (led, g1, g2), led_mags = log_expected_density(lik, cm_s, cv_s, y_, alpha, nq, dtype)
+    al, rate = dtype(alpha), dtype(lr)
+    with np.errstate(all="ignore"):
+        den = dtype(1) + cv_s * g2
+        l2 = dtype(0.5) * g2 / den
+        l1 = (g1 - cm_s * g2) / den
+        lognorm = led + dtype(0.5) * (np.log(cv_s) + cm_s * cm_s / cv_s) - dtype(0.5) * (np.log(s_) + m_ * m_ / s_)
+        new = [((dtype(1) - rate) * old + rate * ((dtype(1) - al) * old + step)).astype(dtype)
+               for old, step in ((n1, l1), (n2, l2), (ln, lognorm))]
+        ok = safe & (den > 0) & np.isfinite(new[0]) & np.isfinite(new[1]) & np.isfinite(new[2])
+        if update is not None:
+            ok = ok & (np.asarray(update) != 0)
+        # the running error bound of the same algebra in float64, from the (float64 view of the) same inputs
+        e = lambda a: _exact(np.asarray(a, dtype=np.float64))                                       # noqa: E731
+        (led8, g18, g28), _ = log_expected_density(lik, cm_s.astype(np.float64), cv_s.astype(np.float64),
+                                                   y_.astype(np.float64), alpha, nq) if dtype != np.float64 else ((led, g1, g2), None)
+        ti, t1, t2 = ((v, mag + 1.0) for v, mag in zip((led8, g18, g28), led_mags))
+        tm, tv, mm, ss = e(cm_s), e(cv_s), e(m_), e(s_)
+        one, half = e(np.ones_like(tm[0])), e(0.5)
+        tden = _add(one, _mul(tv, t2))
+        tl2 = _mul(half, _div(t2, tden))
+        tl1 = _div(_add(t1, _mul(tm, t2), -1.0), tden)
+        g_cav = _mul(half, _add(_log(tv), _div(_mul(tm, tm), tv)))
+        g_marg = _mul(half, _add(_log(ss), _div(_mul(mm, mm), ss)))
+        tnorm = _add(_add(ti, g_cav), g_marg, -1.0)
+        mags = []
+        for old, step in ((n1, tl1), (n2, tl2), (ln, tnorm)):
+            told = e(old)
+            pep = _add(_mul(e(1.0 - alpha), told), step)
+            mags.append(_add(_mul(e(1.0 - lr), told), _mul(e(lr), pep))[1])
+    out = [np.where(ok, fresh, old).astype(dtype) for fresh, old in zip(new, (n1, n2, ln))]
+    return dict(nat1=out[0], nat2=out[1], log_norm=out[2], mags=tuple(mags), cav_mu=mc, cav_var=vc, cav_mags=cav_mags,
+                den=np.where(safe, den, np.nan), lognorm=np.where(safe, lognorm, np.nan), skipped=~ok)
+
+
+# ---- the dense PEP iteration ------------------------------------------------------------------------------------------------------
+def dense_energy(lik, kmat, nat1, nat2, y, alpha, nq=20):
+    """The power-EP energy with dense matrices: A(q) - A(p) + (1 / alpha) sum_n lognorm_n, where the difference of the two chains'
+    normalisers is (log det Sigma - log det K + n1^T Sigma n1) / 2 (matrix determinant lemma; the prior mean is zero) and lognorm_n
+    is computed afresh at the cavity of the current q.  Also returns that cavity."""
+    mu, sigma = L.dense_posterior(kmat, nat1, nat2)
+    s = np.diag(sigma)
+    r = pep_site_update(lik, mu, s, y, alpha, 1.0, nat1, nat2, np.zeros_like(nat1), nq)
+    normalisers = 0.5 * (np.linalg.slogdet(sigma)[1] - np.linalg.slogdet(kmat)[1] + nat1 @ sigma @ nat1)
+    return normalisers + np.sum(r["lognorm"]) / alpha, (r["cav_mu"], r["cav_var"])
+
+
+def dense_pep(lik, comps, t, y, alpha, lr, iterations, record, nq=20):
+    """The PEP loop on one series on the kernel matrix: ``dense_posterior`` for the marginals of q and the scalar cavity, no state
+    space form.  Sites start at nat1 = 0, nat2 = -1e-10, log_norm = 0.  Returns ``{iteration: dict(nat1, nat2, log_norm, energy,
+    cav_mu, cav_var)}`` for the iterations in ``record`` (1-based, state AFTER that update; energy and cavity of the q after it).
+    Asserts that no site was skipped and that every site precision stayed positive."""
+    kmat = PC.dense_kernel(comps, t[:, None] - t[None, :])
+    nat1, nat2, log_norm = np.zeros(len(t)), np.full(len(t), -1e-10), np.zeros(len(t))
+    out = {}
+    for it in range(1, iterations + 1):
+        mu, sigma = L.dense_posterior(kmat, nat1, nat2)
+        r = pep_site_update(lik, mu, np.diag(sigma), y, alpha, lr, nat1, nat2, log_norm, nq)
+        assert not r["skipped"].any(), f"iteration {it}: the reference run skipped a site"
+        nat1, nat2, log_norm = r["nat1"], r["nat2"], r["log_norm"]
+        assert np.all(nat2 < 0.0), f"iteration {it}: a site precision of the reference run is not positive"
+        if it in record:
+            energy, (cav_mu, cav_var) = dense_energy(lik, kmat, nat1, nat2, y, alpha, nq)
+            out[it] = dict(nat1=nat1.copy(), nat2=nat2.copy(), log_norm=log_norm.copy(), energy=energy, cav_mu=cav_mu, cav_var=cav_var)
+    return out
+
+
+def cavity_dxd(mean, cov, h, nat1, nat2, alpha):
+    """The reference's route (pep.py:120-148) for ONE point in numpy: state marginal (mean [d], cov [d, d]) to natural form, minus
+    alpha times the site back-projected through h [d], back to moments, projected by h.  Returns (mu_c, v_c)."""
+    prec = np.linalg.inv(cov)
+    th2 = -0.5 * prec - alpha * nat2 * np.outer(h, h)
+    th1 = prec @ mean - alpha * nat1 * h
+    cav_cov = 0.5 * np.linalg.inv(-th2)
+    return h @ (cav_cov @ th1), h @ cav_cov @ h
