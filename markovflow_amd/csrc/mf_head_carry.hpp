@@ -1,10 +1,11 @@
-// Head carry of a streamed row-major tensor whose rows do not start on 128-B lines (mf_kf_lds.hpp, chol Q).
+// Head carry of a streamed row-major tensor whose rows do not start on 128-B lines (mf_kf_lds.hpp: chol Q, and A at one phase).
 //
 // A row of ROWB bytes is fetched as the UNIT-byte units that Keep flags.  When a row starts inside a line, that line was already
 // touched by the fetch of the previous row (whose last unit ends where this row starts).  If ALL kept units of the row that lie in
 // this first line belong to a small fixed set - the "tail units", at most MAXT of them - the previous row's fetch brings them
-// along (as extra units past its own end, out of a line it moves anyway), the consumer keeps their values in registers across
-// the step boundary, and the row's own fetch leaves the first line alone: one line less on the fabric for that row.
+// along (as extra units past its own end, out of a line it moves anyway), the consumer takes them from there - chol Q: copied to
+// registers and held across the step boundary; A: read from the tail slots themselves, which the next fetch masks out
+// (MaskedSchedule below) - and the row's own fetch leaves the first line alone: one line less on the fabric for that row.
 //
 // Everything here is integer arithmetic on BYTE ADDRESSES modulo 128 (base offsets, batch slices and chunk starts all shift the
 // phase, differently for every lane), shared by the two sides that have to agree:
@@ -96,7 +97,7 @@ template <int ROWB, int UNIT, typename Keep> struct HeadCarry {
 // (Rows are NOT padded to an odd stride: the per-lane row reads then take a 2..4-way LDS bank conflict, but
 // the kernel reads ~600 B per lane per step, nowhere near LDS bandwidth, while padding would push the
 // fp64 d=6 image over a quarter of the CU's 160 KB and cost a wave of occupancy.)
-// TAIL: the row's image ends with tail slots that hold the NEXT row's head units (mf_head_carry.hpp; chol Q only).
+// TAIL: the row's image ends with tail slots that hold the NEXT row's head units (chol Q; A where KfLdsCfg::ATAIL holds).
 template <int ROWB, typename Keep, bool TAIL = false> struct Stream {
     // 16-B granules whenever a row holds at least one; a row that is not a whole number of them (odd d) is fetched up
     // to the next 16-B boundary: the extra 4..12 bytes belong to the next row (or lie past the end of the tensor, where
@@ -132,6 +133,54 @@ template <int ROWB, typename Keep, bool TAIL = false> struct Stream {
         for (int u = 0; u < gu; ++u) n += Keep::keep(u, UNIT) ? 1 : 0;
         return n;
     }
+};
+
+// Packed per-lane schedule of a stream with tail slots whose left-out units are left out by the EXEC mask of their DMA instruction
+// (mf_kf_lds.hpp, A): a masked-out slot keeps what the previous fetch put there, so a tail slot filled with the rows of step j is
+// still intact after the fetch of step j + 1 (a row carries at most every second step) and the consumer reads it from LDS at the
+// top of step j + 1.  DMA instruction i, lane l moves image unit (64 i + l) % U: with G = gcd(64, U) a lane meets the units of ONE
+// residue mod G, each once in every PER = U / G consecutive instructions ("block"), and at most one unit per residue is a head or
+// a tail unit.  So one word describes the lane: bits 0..3 = index in its block of the instruction that holds that unit (15: none),
+// bits SH_F + b PB + p = fetch it with the rows of step jn, jn % PB == p, in block b (HeadCarry::producer_bits of the row it
+// belongs to), bits SH_C + t PB + p = HeadCarry::consumer_bits of the lane's OWN row.
+template <typename St> struct MaskedSchedule {
+    using HC = typename St::HC;
+    static constexpr int PB = HC::PERIOD > 0 ? HC::PERIOD : 1;
+    static constexpr int gcd(int a, int b) { return b == 0 ? a : gcd(b, a % b); }
+    static constexpr int G = gcd(64, St::U), PER = St::U / G, NB = (St::NI + PER - 1) / PER;
+    static constexpr int SH_F = 4, SH_C = SH_F + NB * PB;
+    static constexpr bool one_special_per_residue() {
+        for (int c = 0; c < G; ++c) {
+            int n = 0;
+            for (int u = c; u < St::U; u += G) n += St::unit_kind(u) != 0 ? 1 : 0;
+            if (n > 1) return false;
+        }
+        return true;
+    }
+    // the source offset of image unit c is c units from the row's start (every unit kept, the tail units are the row's first)
+    static constexpr bool linear() { for (int c = 0; c < St::U; ++c) if (St::global_offset(c) != c * St::UNIT) return false; return true; }
+    static constexpr bool no_back_to_back_carry() {
+        for (int r = 0; r < HC::LINE; r += 4) if (HC::carried_units(r) != 0u && HC::carried_units(r + HC::STEP) != 0u) return false;
+        return true;
+    }
+    static constexpr bool USABLE = St::NT > 0 && PER < 15 && SH_C + St::NT * PB <= 32 && one_special_per_residue() && linear() &&
+                                   no_back_to_back_carry();
+    static constexpr unsigned none() { return 0xFu | (((1u << (NB * PB)) - 1u) << SH_F); }     // every unit, every phase
+    // account for instruction i, in which the lane moves image unit cu of the row whose step-0 byte address is row_addr
+    static constexpr unsigned add(unsigned sch, int i, int cu, unsigned row_addr) {
+        int kind = 0;
+        for (int cc = 0; cc < St::U; ++cc) if (cu == cc && St::unit_kind(cc) != 0) kind = St::unit_kind(cc);
+        if (kind == 0) return sch;
+        const int sh = SH_F + (i / PER) * PB;
+        return (sch & ~(0xFu | (((1u << PB) - 1u) << sh))) | (unsigned)(i % PER) | (HC::producer_bits(row_addr, kind) << sh);
+    }
+    // is the lane's unit of instruction i fetched with the rows of a step of phase p (= jn % PB, jn >= 1)?
+    static constexpr bool fetch(unsigned sch, int i, unsigned p) {
+        return (sch & 0xFu) != (unsigned)(i % PER) || ((sch >> (SH_F + (i / PER) * PB + (int)p)) & 1u) != 0u;
+    }
+    static constexpr unsigned with_consumer(unsigned sch, unsigned own_addr) { return sch | (HC::consumer_bits(own_addr) << SH_C); }
+    // does the lane read tail unit t of its row of step j >= 1 (phase p = j % PB) from its tail slot?
+    static constexpr bool carried(unsigned sch, int t, unsigned p) { return ((sch >> (SH_C + t * PB + (int)p)) & 1u) != 0u; }
 };
 
 struct KeepAll { static constexpr bool keep(int, int) { return true; } };

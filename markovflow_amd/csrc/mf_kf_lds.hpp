@@ -5,7 +5,9 @@
 //
 //   * every lane's next transition (A_k, cholQ_k, b_k, H_k, y_k) is brought in by LDS-DMA
 //     (`buffer_load_dword[x4] ... lds`): no VGPR staging, and the load of step k+1 is in flight
-//     during almost all of step k, so one wavefront per SIMD is enough to cover HBM latency;
+//     during almost all of step k, so one wavefront per SIMD is enough to cover HBM latency
+//     (one exception: with KfLdsCfg::YREG - fp64, d = 6, m = 1 - y_k comes by plain buffer loads into
+//     registers, four steps per group, and its room in LDS holds tail slots of A);
 //   * one DMA wave-instruction moves 64 x 16 B as contiguous pieces of consecutive rows
 //     (lane -> (row, unit) = divmod(64 i + lane, units per row)), i.e. full 128-B lines of the
 //     row-major [B, T, d, d] tensors, instead of 64 lanes touching 64 different lines;
@@ -80,6 +82,33 @@ template <bool WIDE, int N> MF_DEV void dma_b128_group(mf_v4i srd, unsigned lds_
                      : "=&s"(keep) : "s"(srd), "s"(lds_addr), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]) : "memory", "scc");
     if (WIDE) { MF_DMA_B128_BODY(MF_POLICY_WIDE) } else { MF_DMA_B128_BODY(MF_POLICY_NARROW) }
 #undef MF_DMA_B128_BODY
+}
+// The same with an EXEC mask per instruction (em[k], wave-uniform): a lane outside the mask moves nothing and its LDS slot KEEPS
+// what it held (the out-of-range offset would put zeros there).  EXEC is saved and restored inside the statement.
+#define MF_DMA_HEAD_X "s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b64 %1, exec\n\ts_mov_b32 m0, %3\n\t"
+#define MF_DMA_TAIL_X "s_mov_b64 exec, %1\n\ts_mov_b32 m0, %0"
+#define MF_DMA_X4_X(v, e) "s_mov_b64 exec, " e "\n\ts_nop 0\n\tbuffer_load_dwordx4 " v ", %2, 0 offen" MF_POLICY_WIDE " lds\n\t"
+#define MF_DMA_STEP4_X "s_add_u32 m0, m0, 0x400\n\t"
+template <int N> MF_DEV void dma_b128_group_masked(mf_v4i srd, unsigned lds_addr, const unsigned* v, const unsigned long long* em) {
+    unsigned keep;
+    unsigned long long keepx;
+    static_assert(N >= 1 && N <= 4, "group size");
+    if constexpr (N == 1)
+        asm volatile(MF_DMA_HEAD_X MF_DMA_X4_X("%4", "%5") MF_DMA_TAIL_X
+                     : "=&s"(keep), "=&s"(keepx) : "s"(srd), "s"(lds_addr), "v"(v[0]), "s"(em[0]) : "memory", "scc");
+    else if constexpr (N == 2)
+        asm volatile(MF_DMA_HEAD_X MF_DMA_X4_X("%4", "%6") MF_DMA_STEP4_X MF_DMA_X4_X("%5", "%7") MF_DMA_TAIL_X
+                     : "=&s"(keep), "=&s"(keepx) : "s"(srd), "s"(lds_addr), "v"(v[0]), "v"(v[1]), "s"(em[0]), "s"(em[1]) : "memory", "scc");
+    else if constexpr (N == 3)
+        asm volatile(MF_DMA_HEAD_X MF_DMA_X4_X("%4", "%7") MF_DMA_STEP4_X MF_DMA_X4_X("%5", "%8") MF_DMA_STEP4_X MF_DMA_X4_X("%6", "%9") MF_DMA_TAIL_X
+                     : "=&s"(keep), "=&s"(keepx) : "s"(srd), "s"(lds_addr), "v"(v[0]), "v"(v[1]), "v"(v[2]), "s"(em[0]), "s"(em[1]), "s"(em[2])
+                     : "memory", "scc");
+    else
+        asm volatile(MF_DMA_HEAD_X MF_DMA_X4_X("%4", "%8") MF_DMA_STEP4_X MF_DMA_X4_X("%5", "%9") MF_DMA_STEP4_X MF_DMA_X4_X("%6", "%10")
+                     MF_DMA_STEP4_X MF_DMA_X4_X("%7", "%11") MF_DMA_TAIL_X
+                     : "=&s"(keep), "=&s"(keepx)
+                     : "s"(srd), "s"(lds_addr), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "s"(em[0]), "s"(em[1]), "s"(em[2]), "s"(em[3])
+                     : "memory", "scc");
 }
 template <int N> MF_DEV void dma_b32_group(mf_v4i srd, unsigned lds_addr, const unsigned* v) {
     unsigned keep;
@@ -192,6 +221,72 @@ template <typename St> struct DmaStream {
     }
 };
 
+// DmaStream for a stream with tail slots that keeps every unit (A with KfLdsCfg::ATAIL), a type of its own so that DmaStream
+// stays what it was for every other stream.  A unit the schedule leaves out is left out by the EXEC mask of its instruction, so
+// its slot keeps the previous fetch's data: a tail slot filled with the rows of step j survives the fetch of step j + 1 and the
+// consumer reads it at the top of step j + 1 straight from LDS - no carried values held in registers across the step.  The
+// schedule is one packed word per lane (MaskedSchedule, mf_head_carry.hpp), consumer bits included.
+template <typename St> struct DmaStreamMasked {
+    using MS = MaskedSchedule<St>;
+    static_assert(MS::USABLE && St::UNIT == 16 && St::UG >= 8, "masked schedule: see MaskedSchedule; a wide stream");
+    unsigned vo[St::NI];           // this lane's source byte offset for DMA instruction i
+    unsigned sch;                  // the lane's packed schedule
+    // base_lo: low 32 bits of the address the row offsets are relative to (the phase of a row); the lane-to-unit arithmetic is
+    // DmaStream::init's
+    MF_DEV void init(const char* smem, int lane, int rel_tab, int, unsigned base_lo) {
+        const int q0 = lane / St::U, c0 = lane - q0 * St::U;
+        sch = MS::none();
+        MF_UNROLL for (int i = 0; i < St::NI; ++i) {
+            const int a = (64 * i) / St::U, b = (64 * i) % St::U;
+            int cu = c0 + b;
+            const int carry = cu >= St::U ? 1 : 0;
+            cu -= carry * St::U;
+            const int row = q0 + a + carry;
+            const unsigned rel = *reinterpret_cast<const unsigned*>(smem + rel_tab + row * 4);
+            const unsigned off = (unsigned)cu * St::UNIT;          // (MaskedSchedule::linear)
+            vo[i] = rel + off;
+            sch = MS::add(sch, i, cu, base_lo + rel);
+#ifdef MF_EXPERIMENT
+            if (pack_base != 0xffffffffu && rel < MF_DMA_INVALID)
+                vo[i] |= ((((pack_base + rel) >> 5) & 3u) << 29) | ((unsigned)(off / St::UNIT) << 24);
+#endif
+        }
+    }
+#ifdef MF_EXPERIMENT
+    unsigned pack_base = 0xffffffffu;     // (as in DmaStream)
+    unsigned step_next = 0;
+    bool skip_carried = false;
+    MF_DEV unsigned exp_offset(unsigned v) const {
+        if (pack_base == 0xffffffffu || v >= MF_DMA_INVALID) return v;
+        const unsigned phase = ((v >> 29) + step_next) & 3u, gu = (v >> 24) & 31u, off = v & 0xffffffu;
+        const bool carried = skip_carried && phase != 0u && gu < 8u - 2u * phase;
+        return carried ? MF_DMA_INVALID : off;
+    }
+#endif
+    // issue DMA instructions [i0, i1), up to four per asm statement.  SCHED (every fetch but a chunk's first): phase = jn % period
+    // of the step jn being fetched; each instruction runs under the ballot of "this lane's unit is fetched".
+    template <int I0, int I1, bool SCHED = false> MF_DEV void issue(mf_v4i srd, unsigned lds_base, unsigned phase = 0u) const {
+        constexpr int HI = I1 < St::NI ? I1 : St::NI;
+        if constexpr (I0 < HI) {
+            constexpr int N = (HI - I0) < 4 ? (HI - I0) : 4;
+            unsigned voff[N];
+            MF_UNROLL for (int k = 0; k < N; ++k) {
+#ifdef MF_EXPERIMENT
+                voff[k] = exp_offset(vo[I0 + k]);
+#else
+                voff[k] = vo[I0 + k];
+#endif
+            }
+            if constexpr (SCHED) {
+                unsigned long long em[N];
+                MF_UNROLL for (int k = 0; k < N; ++k) em[k] = __builtin_amdgcn_ballot_w64(MS::fetch(sch, I0 + k, phase));
+                dma_b128_group_masked<N>(srd, lds_base + I0 * 1024, voff, em);
+            } else dma_b128_group<true, N>(srd, lds_base + I0 * 1024, voff);
+            issue<I0 + N, I1, SCHED>(srd, lds_base, phase);
+        }
+    }
+};
+
 // value of lane 0 as a wave-uniform (SGPR) 64-bit quantity
 MF_DEV unsigned long long uniform64(unsigned long long x) {
     const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)x);
@@ -211,6 +306,32 @@ MF_DEV mf_v4i make_srd(unsigned long long base, unsigned long long end, int debu
     srd.w = 0x00020000;
     return srd;
 }
+
+// YREG: the next group of this lane's y values, N doubles at byte offset voff of the range-checked descriptor [base, end) - plain
+// buffer loads, one dwordx4 per two values (the range check is per dword, as for the DMA: a value past the end reads as zero).
+// The compiler counts these loads itself and waits before it first touches their registers - with `vmcnt(n)` of ITS count, which
+// knows nothing of the DMA in flight.  So the kernel drains the counter itself at the END of the step that issued them (see
+// MF_KF_LDS_STEP): whatever the compiler then adds, for the copies on the loop's back edge, comes after and waits for nothing.
+template <typename T, int N> MF_DEV void yreg_load(unsigned long long base, unsigned long long end, int debug, unsigned voff, T (&q)[N]) {
+    static_assert(sizeof(T) == 8 && N % 2 == 0, "two values per dwordx4");
+    unsigned long long rem = end > base ? end - base : 0ull;
+    if (debug & 1) rem = 0;
+    if (rem > MF_DMA_MAXREC) rem = MF_DMA_MAXREC;
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)base);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(base >> 32));
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0,
+                                                                        __builtin_amdgcn_readfirstlane((int)(unsigned)rem), 0x00020000);
+    MF_UNROLL for (int k = 0; k < N; k += 2) {
+        struct Pair { T v[2]; };
+        const Pair pr = __builtin_bit_cast(Pair, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(voff + 8u * k), 0, 0));
+        q[k] = pr.v[0];
+        q[k + 1] = pr.v[1];
+    }
+}
+
+// the group's values and this lane's byte offset from the wave's descriptor base (nothing where y stays in LDS)
+template <typename T, int N, bool ON> struct YRegs { T q[N]; unsigned voff; };
+template <typename T, int N> struct YRegs<T, N, false> {};
 
 // read this lane's row from an LDS stream image
 template <typename T, typename St> struct RowReader {
@@ -240,7 +361,8 @@ template <typename T, typename St> struct RowReader {
 template <typename T, int D, int M, bool RSTEP = false, int BG = 1, bool CARRY = false> struct KfLdsCfg {
     static constexpr int S = sizeof(T);
     static constexpr int BGRP = BG;
-    using StA = Stream<D * D * S, KeepAll>;
+    using StA0 = Stream<D * D * S, KeepAll>;
+    using StAT = Stream<D * D * S, KeepAll, true>;
     using StC0 = Stream<D * D * S, KeepLower<D, S>>;
     using StCT = Stream<D * D * S, KeepLower<D, S>, true>;
     using Stb = Stream<BG * D * S, KeepAll>;
@@ -253,18 +375,32 @@ template <typename T, int D, int M, bool RSTEP = false, int BG = 1, bool CARRY =
     static constexpr bool RS = RSTEP;
     static constexpr int QUARTER_CU = (160 * 1024) / 4;
     static constexpr int TABLE_BYTES = 5 * 256 + ((StCT::U * 4 + 15) / 16) * 16;
-    static constexpr int IMAGE_T = StA::LDS_BYTES + StCT::LDS_BYTES + Stb::LDS_BYTES + StH::LDS_BYTES + ((Sty::LDS_BYTES + 15) / 16) * 16 +
+    static constexpr int IMAGE_T = StA0::LDS_BYTES + StCT::LDS_BYTES + Stb::LDS_BYTES + StH::LDS_BYTES + ((Sty::LDS_BYTES + 15) / 16) * 16 +
                                    (RSTEP ? ((StR::LDS_BYTES + 15) / 16) * 16 : 0);
     static constexpr bool TAIL = CARRY && StCT::NT > 0 && !StC0::ALL && StCT::NI * StCT::HC::PERIOD <= 64 &&
                                  StCT::NT * StCT::HC::PERIOD <= 32 && IMAGE_T <= QUARTER_CU && TABLE_BYTES <= IMAGE_T &&
-                                 (StA::NI + StCT::NI + Stb::NI + StH::NI + Sty::NI + (RSTEP ? StR::NI : 0)) < 64;
+                                 (StA0::NI + StCT::NI + Stb::NI + StH::NI + Sty::NI + (RSTEP ? StR::NI : 0)) < 64;
     using StC = Stream<D * D * S, KeepLower<D, S>, TAIL>;
+    // ATAIL (one output, shared precision, where chol Q carries): y leaves LDS - four doubles per group live in registers, loaded
+    // by plain buffer loads - and the room its image took becomes tail slots of A: HeadCarry<rows of A, KeepAll> carries the
+    // row's first units where the row starts 96 (units 0, 1) or 112 (unit 0) bytes into a line.  A's schedule goes through the
+    // EXEC mask (DmaStream MSK), chol Q's stays as it is.
+    static constexpr int Y_IMAGE = ((Sty::LDS_BYTES + 15) / 16) * 16;
+    static constexpr bool ATAIL = TAIL && M == 1 && !RSTEP && sizeof(T) == 8 && StAT::NT > 0 && StAT::HC::PERIOD == StCT::HC::PERIOD &&
+                                  StAT::LDS_BYTES + StCT::LDS_BYTES + Stb::LDS_BYTES + StH::LDS_BYTES <= QUARTER_CU &&
+                                  (StAT::NI + StCT::NI + Stb::NI + StH::NI) < 64;
+    static constexpr bool YREG = ATAIL;
+    // (groups of two - one dwordx4, a y line touched every second step - were measured and lost the whole gain)
+    static_assert(YG % 2 == 0 || !YREG, "whole dwordx4 loads");
+    using DA = std::conditional_t<ATAIL, DmaStreamMasked<StAT>, DmaStream<StA0>>;
+    using StA = Stream<D * D * S, KeepAll, ATAIL>;
+    static constexpr int NI_y = YREG ? 0 : Sty::NI;
     static constexpr int OFF_A = 0;
     static constexpr int OFF_C = OFF_A + StA::LDS_BYTES;
     static constexpr int OFF_b = OFF_C + StC::LDS_BYTES;
     static constexpr int OFF_H = OFF_b + Stb::LDS_BYTES;
     static constexpr int OFF_y = OFF_H + StH::LDS_BYTES;
-    static constexpr int OFF_R = OFF_y + ((Sty::LDS_BYTES + 15) / 16) * 16;
+    static constexpr int OFF_R = OFF_y + (YREG ? 0 : Y_IMAGE);
     static constexpr int IMAGE_END = OFF_R + (RSTEP ? ((StR::LDS_BYTES + 15) / 16) * 16 : 0);
     static constexpr int OFF_relA = TAIL ? 0 : IMAGE_END;                                       // row offsets of A and cholQ
     static constexpr int OFF_relb = OFF_relA + 256;
@@ -276,21 +412,25 @@ template <typename T, int D, int M, bool RSTEP = false, int BG = 1, bool CARRY =
     // the streaming kernel is instantiated only where matrix rows are whole 16-B units, the per-step DMA count
     // fits the 6-bit vm counter and the image fits 64 KB of LDS
     static constexpr bool SUPPORTED =
-                                      (StA::NI + StC::NI + Stb::NI + StH::NI + Sty::NI + (RSTEP ? StR::NI : 0)) < 64 &&
+                                      (StA::NI + StC::NI + Stb::NI + StH::NI + NI_y + (RSTEP ? StR::NI : 0)) < 64 &&
                                       LDS_TOTAL <= 64 * 1024;
 };
 
 template <typename T, int D, int M, bool RSTEP = false> using KfChunkCfg = KfLdsCfg<T, D, M, RSTEP, 1, true>;
 static_assert(KfChunkCfg<double, 6, 1>::TAIL && KfChunkCfg<double, 6, 1>::LDS_TOTAL <= 40960, "fp64 d = 6: four wavefronts per CU");
+static_assert(KfChunkCfg<double, 6, 1>::ATAIL && KfChunkCfg<double, 6, 1>::StA::U == 20 && KfChunkCfg<double, 6, 1>::LDS_TOTAL == 40960,
+              "fp64 d = 6, m = 1: A's two tail slots take the place of the y image");
+static_assert(!KfChunkCfg<double, 6, 2>::ATAIL && !KfChunkCfg<double, 6, 1, true>::ATAIL && !KfChunkCfg<float, 6, 1>::ATAIL &&
+              !KfLdsCfg<double, 6, 1>::ATAIL && !KfLdsCfg<double, 6, 1, false, 2>::ATAIL, "every other instantiation keeps its streams");
 
 // DMA batches of one step.  All of a step's data is pulled into registers at the top of the step behind ONE
 // `s_waitcnt vmcnt(0)`; the batches of the next step are then issued between the arithmetic phases.
 // (Counted waits - "all but the youngest n have landed" - were tried and are NOT safe here: with dword and
 // dwordx4 LDS-DMA mixed in one stream of requests the landing order did not follow the issue order.)
 template <typename Cfg> struct KfPump {
-    static constexpr int N_SMALL = Cfg::StC::NI + Cfg::Stb::NI + Cfg::StH::NI + Cfg::Sty::NI + (Cfg::RS ? Cfg::StR::NI : 0);
+    static constexpr int N_SMALL = Cfg::StC::NI + Cfg::Stb::NI + Cfg::StH::NI + Cfg::NI_y + (Cfg::RS ? Cfg::StR::NI : 0);
     static constexpr int N_BIG = Cfg::StA::NI;
-    const DmaStream<typename Cfg::StA>& dA; const DmaStream<typename Cfg::StC>& dC;
+    const typename Cfg::DA& dA; const DmaStream<typename Cfg::StC>& dC;
     const DmaStream<typename Cfg::Stb>& db; const DmaStream<typename Cfg::StH>& dH;
     const DmaStream<typename Cfg::Sty>& dy; const DmaStream<typename Cfg::StR>& dR;
     mf_v4i sA, sC, sb, sH, sy, sR;
@@ -310,7 +450,7 @@ template <typename Cfg> struct KfPump {
             dC.template issue<HC, 64, true>(sC, lds0 + Cfg::OFF_C, cphase);
             db.template issue<0, 64>(sb, lds0 + Cfg::OFF_b);
             dH.template issue<0, 64>(sH, lds0 + Cfg::OFF_H);
-            if (yfetch) dy.template issue<0, 64>(sy, lds0 + Cfg::OFF_y);
+            if constexpr (!Cfg::YREG) { if (yfetch) dy.template issue<0, 64>(sy, lds0 + Cfg::OFF_y); }
             if (Cfg::RS) dR.template issue<0, 64>(sR, lds0 + Cfg::OFF_R);
         }
     }
@@ -319,7 +459,7 @@ template <typename Cfg> struct KfPump {
         dC.template issue<0, 64>(sC, lds0 + Cfg::OFF_C);
         db.template issue<0, 64>(sb, lds0 + Cfg::OFF_b);
         dH.template issue<0, 64>(sH, lds0 + Cfg::OFF_H);
-        dy.template issue<0, 64>(sy, lds0 + Cfg::OFF_y);
+        if constexpr (!Cfg::YREG) dy.template issue<0, 64>(sy, lds0 + Cfg::OFF_y);
         if (Cfg::RS) dR.template issue<0, 64>(sR, lds0 + Cfg::OFF_R);
         dA.template issue<0, 64>(sA, lds0 + Cfg::OFF_A);
     }
@@ -339,7 +479,8 @@ template <typename Cfg> struct KfPump {
     template <int K> MF_DEV void big_do() const {
         if (!more) return;
         constexpr int Q = (Cfg::StA::NI + 3) / 4;
-        dA.template issue<K * Q, (K + 1) * Q>(sA, lds0 + Cfg::OFF_A);
+        if constexpr (Cfg::ATAIL) dA.template issue<K * Q, (K + 1) * Q, true>(sA, lds0 + Cfg::OFF_A, cphase);
+        else dA.template issue<K * Q, (K + 1) * Q>(sA, lds0 + Cfg::OFF_A);
     }
 };
 
@@ -448,7 +589,7 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
             tab[Cfg::OFF_gtabC / 4 + lane] = g;
         }
     }
-    DmaStream<typename Cfg::StA> dA;
+    typename Cfg::DA dA;
     DmaStream<typename Cfg::StC> dC;
     DmaStream<typename Cfg::Stb> db;
     DmaStream<typename Cfg::StH> dH;
@@ -503,11 +644,12 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
         dC.pack_base = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)pC);
     }
 #endif
-    dA.init(smem, lane, Cfg::OFF_relA, 0);
+    if constexpr (Cfg::ATAIL) dA.init(smem, lane, Cfg::OFF_relA, 0, (unsigned)pA);
+    else dA.init(smem, lane, Cfg::OFF_relA, 0);
     dC.init(smem, lane, Cfg::OFF_relA, Cfg::OFF_gtabC, (unsigned)pC);
     db.init(smem, lane, Cfg::OFF_relb, 0);
     dH.init(smem, lane, Cfg::OFF_relH, 0);
-    dy.init(smem, lane, Cfg::OFF_rely, 0);
+    if constexpr (!Cfg::YREG) dy.init(smem, lane, Cfg::OFF_rely, 0);
     if (RSTEP) dR.init(smem, lane, Cfg::OFF_relR, 0);
     // (with the head carry the tables lie over the image: the last table read is done before the first DMA writes there)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -517,6 +659,20 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
     const unsigned cbits = NTAIL > 0 ? HC::consumer_bits((unsigned)((unsigned long long)a.cholQ + offA)) : 0u;
     T cv[NTAIL > 0 ? NTAIL : 1][UEL];
     MF_UNROLL for (int t = 0; t < (NTAIL > 0 ? NTAIL : 1); ++t) MF_UNROLL for (int k = 0; k < UEL; ++k) cv[t][k] = T(0);
+
+    // A's head carry: the consumer schedule rides in dA's schedule word; the carried units are read from the tail slots themselves
+    using HCA = typename Cfg::StA::HC;
+    constexpr int NTA = Cfg::StA::NT;
+    if constexpr (NTA > 0) {
+        static_assert(HCA::PERIOD == CPER, "one phase for both schedules");
+        dA.sch = MaskedSchedule<typename Cfg::StA>::with_consumer(dA.sch, (unsigned)((unsigned long long)a.A + offA));
+    }
+    // YREG: this lane's group of y values (steps YG g ... YG g + YG - 1 of its chunk) and its offset from the wave's descriptor base
+    YRegs<T, Cfg::YG * M, Cfg::YREG> yr;
+    if constexpr (Cfg::YREG) {
+        MF_UNROLL for (int i = 0; i < Cfg::YG * M; ++i) yr.q[i] = T(0);
+        yr.voff = rowok ? (unsigned)(offy - offy0) : MF_DMA_INVALID;
+    }
 
     const RowReader<T, typename Cfg::StA> rA(smem, Cfg::OFF_A, lane);
     const RowReader<T, typename Cfg::StC> rC(smem, Cfg::OFF_C, lane);
@@ -532,6 +688,7 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
                 make_srd(pb, eb, a.debug | ((a.debug >> 1) & 1)), make_srd(pH, eH, a.debug | ((a.debug >> 1) & 1)),
                 make_srd(py, ey, a.debug | ((a.debug >> 1) & 1)), make_srd(pR, eR, a.debug | ((a.debug >> 1) & 1)), lds0, true};
         p0.template all<0>();
+        if constexpr (Cfg::YREG) yreg_load(py, ey, a.debug | ((a.debug >> 1) & 1), yr.voff, yr.q);
     }
 
     // One streamed step: wait for this step's cholQ/b/H/y (A may still be in flight), move them to registers,
@@ -565,9 +722,9 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                              \
         MF_STAMP_AT(ts1)                                                                                              \
         const bool more = (j + 1 < nsteps);                                                                           \
-        const bool yfetch = ((j + 1) % Cfg::YG) == 0;                                                                 \
+        const bool yfetch = ((j + 1) % Cfg::YG) == 0;                                                                \
         pA += D * D * S; pC += D * D * S; pb += D * S; pH += M * D * S; if (RSTEP) pR += M * M * S;                   \
-        if (yfetch) py += Cfg::YG * M * S;                                                                            \
+        if (yfetch) py += Cfg::YG * M * S;                                                                           \
         T C[D][D], mvec[D], hk[M * D], yk[M];                                                                         \
         MF_UNROLL for (int i = 0; i < D; ++i) MF_UNROLL for (int jj = 0; jj <= i; ++jj) C[i][jj] = rC.at(i * D + jj); \
         if constexpr (NTAIL > 0) {                                                                                    \
@@ -583,11 +740,32 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
         }                                                                                                             \
         MF_UNROLL for (int i = 0; i < D; ++i) mvec[i] = rb.at(i);                                                     \
         MF_UNROLL for (int i = 0; i < M * D; ++i) hk[i] = rH.at(i);                                                   \
-        MF_UNROLL for (int i = 0; i < M; ++i)                                                                         \
-            yk[i] = *reinterpret_cast<const T*>(ry.row + ((int)(j % Cfg::YG) * M + i) * (int)sizeof(T));              \
+        if constexpr (Cfg::YREG) {                                                                                    \
+            /* this step's y out of the group; in the group's last step the next group is loaded over it */           \
+            yk[0] = yr.q[0];                                                                                          \
+            MF_UNROLL for (int g = 1; g < Cfg::YG; ++g) yk[0] = ((int)(j % Cfg::YG) == g) ? yr.q[g] : yk[0];          \
+            /* (pins the compiler's own wait for the group's loads here, behind the drain above, not at y's first use) */ \
+            asm volatile("" : "+v"(yk[0]));                                                                           \
+            if (yfetch && more) yreg_load(py, ey, a.debug | ((a.debug >> 1) & 1), yr.voff, yr.q);                 \
+        } else {                                                                                                      \
+            MF_UNROLL for (int i = 0; i < M; ++i)                                                                     \
+                yk[i] = *reinterpret_cast<const T*>(ry.row + ((int)(j % Cfg::YG) * M + i) * (int)sizeof(T));          \
+        }                                                                                                             \
         if (RSTEP) { MF_UNROLL for (int i = 0; i < M * M; ++i) Rsh[i] = rR.at(i); }                                    \
         T Bm[D][D];                                                                                                   \
         MF_UNROLL for (int i = 0; i < D; ++i) MF_UNROLL for (int jj = 0; jj < D; ++jj) Bm[i][jj] = rA.at(i * D + jj); \
+        if constexpr (NTA > 0) {                                                                                      \
+            /* a head unit the previous fetch carried is read from the tail slot it left there: the fetch of this  */ \
+            /* step's rows masked that slot out (a row never carries on two steps running), so it still holds it    */ \
+            MF_UNROLL for (int t = 0; t < NTA; ++t) {                                                                 \
+                const bool got = !(FIRST) && MaskedSchedule<typename Cfg::StA>::carried(dA.sch, t, (unsigned)(j & (CPER - 1))); \
+                const int uoff = (got ? Cfg::StA::UB + t : HCA::tail_unit(t)) * Cfg::StA::UNIT;                       \
+                MF_UNROLL for (int k = 0; k < Cfg::StA::UNIT / S; ++k) {                                              \
+                    const int e = HCA::tail_unit(t) * (Cfg::StA::UNIT / S) + k;                                       \
+                    Bm[e / D][e % D] = *reinterpret_cast<const T*>(rA.row + uoff + k * S);                            \
+                }                                                                                                     \
+            }                                                                                                         \
+        }                                                                                                             \
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                            \
         MF_CHECKSUM_ACC                                                                                               \
         MF_STAMP_AT(ts2)                                                                                              \
@@ -603,6 +781,7 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
         const bool active = j < len;                                                                                  \
         kf_lds_step<T, D, M, SPIKE, FIRST>(E, laC, acc_yry, acc_ww, C, mvec, hk, yk, Rsh, Bm, pump, active, c > 0);    \
         if (E.bad && first_bad < 0) first_bad = tau0 + j;                                                             \
+        if constexpr (Cfg::YREG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   /* (yreg_load) */                 \
         MF_STAMP_ACC                                                                                                  \
     }
     long j = 0;
