@@ -15,6 +15,8 @@
 #include "../../include/markovflow_amd.h"
 
 #include <cmath>
+#include <initializer_list>
+#include <type_traits>
 #include <hip/hip_runtime.h>
 
 namespace {
@@ -142,17 +144,103 @@ __global__ void __launch_bounds__(256) lik_ve_kernel(long N, Rule<T> q, Par<T> p
     }
 }
 
+// ---- the front end of the two segmented kernels (sparse CVI's site update, SVGP's expected log-likelihood) -----------------------
+// One wavefront works on a tile of at most 64 consecutive points of one (series, segment):
+//   phase 1, a lane per point: the tile's rows of w travel through LDS, the segment's pair marginal (m_s, S_s) sits in LDS and is read
+//            as broadcasts: fmu = w . m_s, fvar = c + w^T S_s w, then the expectations, which leave ROWS rows of 64 values in LDS.
+//   phase 2, a lane per few entries of the accumulator - the lower triangle of a 2d x 2d matrix, a 2d vector and, with a third row,
+//            one scalar - looping over the tile's points with broadcast LDS reads: entry (i, j) += (row0_k w_kj) w_ki; a vector
+//            entry reads row1_k and the column of ones that pads every row of w, the scalar reads row2_k and the ones twice.
+// The helpers take the LDS buffers as references to arrays and a point's c as a reference to global memory, not as pointers and a
+// value: inlined, they then index and load exactly as the kernels would, and the register allocation stays what it was.
+
+// a range [lo, hi) of offsets that the caller built, clamped into 0 <= lo <= hi <= n and not trusted: a bad one reads nothing, gives
+// wrong numbers and no access outside the buffers
+__device__ __forceinline__ void clamp_range(long& lo, long& hi, long n) {
+    lo = lo < 0 ? 0 : (lo > n ? n : lo);
+    hi = hi < lo ? lo : (hi > n ? n : hi);
+}
+
+// entry e of a packed lower triangle is (i, j <= i)
+__device__ __forceinline__ void tri_decode(int e, int& i, int& j) {
+    i = 0;
+    while ((i + 1) * (i + 2) / 2 <= e) ++i;
+    j = e - i * (i + 1) / 2;
+}
+
+// the accumulator has the triangle, the vector and one scalar per row of LDS values beyond the first two
+constexpr int seg_entries(int d2, int rows) { return d2 * (d2 + 1) / 2 + d2 + rows - 2; }
+
+// accumulator entry e as (i, j, row of LDS values): e < TRI is (i, j <= i) of the matrix from row 0, then the vector's (j = D2: the
+// column of ones) from row 1, then - ROWS = 3 only - the scalar (i = j = D2) from row 2.  A lane's surplus entry decodes as entry 0.
+template <int D2, int ROWS>
+__device__ __forceinline__ void entry_decode(int e, int& ei, int& ej, int& es) {
+    constexpr int TRI = D2 * (D2 + 1) / 2, E = seg_entries(D2, ROWS);
+    if (e >= E) e = 0;
+    if (e < TRI) {
+        tri_decode(e, ei, ej);
+        es = 0;
+    } else if (ROWS == 2 || e < TRI + D2) {
+        ei = e - TRI;
+        ej = D2;
+        es = 64;
+    } else {
+        ei = D2;
+        ej = D2;
+        es = 128;
+    }
+}
+
+// segment bs' pair marginal into LDS, and the ones that pad every row of w
+template <typename T, int D2>
+__device__ __forceinline__ void stage_pair(int lane, long bs, const T* pair_mean, const T* pair_cov, T (&ls)[D2 * D2], T (&lm)[D2],
+                                           T (&lw)[64 * (D2 + 1)]) {
+    for (int idx = lane; idx < D2 * D2; idx += 64) ls[idx] = pair_cov[bs * (D2 * D2) + idx];
+    if (lane < D2) lm[lane] = pair_mean[bs * D2 + lane];
+    lw[lane * (D2 + 1) + D2] = T(1);
+}
+
+// npts rows of w into LDS: coalesced global loads, row stride 2d + 1 elements - odd, so the lanes' rows start on distinct banks
+template <typename T, int D2>
+__device__ __forceinline__ void stage_tile(int lane, int npts, const T* wt, T (&lw)[64 * (D2 + 1)]) {
+    for (int idx = lane; idx < npts * D2; idx += 64) lw[(idx / D2) * (D2 + 1) + idx % D2] = wt[idx];
+}
+
+// this lane's point: mu = w . m_s, s2 = c + w^T S_s w
+template <typename T, int D2>
+__device__ __forceinline__ void project_point(int lane, const T (&lw)[64 * (D2 + 1)], const T (&ls)[D2 * D2], const T (&lm)[D2],
+                                              const T& c, T& mu, T& s2) {
+    T wr[D2];
+#pragma unroll
+    for (int i = 0; i < D2; ++i) wr[i] = lw[lane * (D2 + 1) + i];
+    mu = T(0);
+    s2 = c;
+#pragma unroll
+    for (int i = 0; i < D2; ++i) {
+        T t = T(0);
+#pragma unroll
+        for (int j = 0; j < D2; ++j) t += ls[i * D2 + j] * wr[j];
+        s2 += wr[i] * t;
+        mu += wr[i] * lm[i];
+    }
+}
+
+// phase 2: point k of the tile onto this lane's entries.  The kernels call it for k = 0, 1, ... - the sums run over the points in
+// ascending order whatever the grid: the same bits on every launch, alone or inside a batch, and no floating-point atomics.  (The
+// loop over the points stays in the kernels: inside a helper the compiler derives its trip count a second time, and the site kernel
+// pays for that with five to eight scalar registers.)
+template <typename T, int D2, int R, int NG>
+__device__ __forceinline__ void accumulate_point(int k, const T (&lg)[NG], const T (&lw)[64 * (D2 + 1)], const int (&ei)[R],
+                                                 const int (&ej)[R], const int (&es)[R], T (&part)[R]) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) part[r] += (lg[es[r] + k] * lw[k * (D2 + 1) + ej[r]]) * lw[k * (D2 + 1) + ei[r]];
+}
+
 // ---- sparse CVI: the segmented site update (markovflow/models/sparse_variational_cvi.py:176-221) ------------------------------
-// One wavefront per (series, segment); the segment's points are walked in tiles of 64.
-//   phase 1, a lane per point: the tile's rows of w travel through LDS (coalesced global loads, row stride 2d + 1 elements - odd,
-//            so the lanes' rows start on distinct banks); the segment's pair marginal (m_s, S_s) sits in LDS and is read as
-//            broadcasts.  fmu = w . m_s, fvar = c + w^T S_s w, the expectations, then g2 = gv and g1 = gm - 2 gv fmu are left in LDS.
-//   phase 2, a lane per few entries of the accumulator - the lower triangle of nat2 and nat1, 2d (2d + 1) / 2 + 2d entries (90 at
-//            2d = 12: two per lane, 189 at 2d = 18: three) - looping over the tile's points in ascending order with broadcast LDS
-//            reads: entry (i, j) += (g2_k w_kj) w_ki; a nat1 entry reads g1_k and the column of ones that pads every row of w.
-//            A tile's sum is formed on its own and then added to the segment's running sum.
-// The sums run over the points in ascending order whatever the grid: the same bits on every launch, alone or inside a batch, and no
-// floating-point atomics.  A point outside the domain (fvar <= 0 or NaN) leaves NaN in its own outputs and in its segment's sites.
+// One wavefront per (series, segment); the segment's points are walked in tiles of 64.  Phase 1 leaves g2 = gv and g1 = gm - 2 gv fmu
+// in LDS; the accumulator is the lower triangle of nat2 and nat1, 2d (2d + 1) / 2 + 2d entries (90 at 2d = 12: two per lane, 189 at
+// 2d = 18: three).  A tile's sum is formed on its own and then added to the segment's running sum.
+// A point outside the domain (fvar <= 0 or NaN) leaves NaN in its own outputs and in its segment's sites.
 template <typename T, int LIK, int D2>
 __global__ void __launch_bounds__(64) sparse_site_kernel(long N, int S, Rule<T> q, Par<T> p, const long long* __restrict__ seg,
                                                          const T* __restrict__ w, const T* __restrict__ cvar,
@@ -160,7 +248,7 @@ __global__ void __launch_bounds__(64) sparse_site_kernel(long N, int S, Rule<T> 
                                                          const T* __restrict__ pair_cov, T lr, T* __restrict__ nat1,
                                                          T* __restrict__ nat2, T* __restrict__ out_fmu, T* __restrict__ out_fvar,
                                                          T* __restrict__ out_ve) {
-    constexpr int W = D2 + 1, TRI = D2 * (D2 + 1) / 2, E = TRI + D2, R = (E + 63) / 64;
+    constexpr int W = D2 + 1, TRI = D2 * (D2 + 1) / 2, E = seg_entries(D2, 2), R = (E + 63) / 64;
     __shared__ T lw[64 * W];
     __shared__ T ls[D2 * D2];
     __shared__ T lm[D2];
@@ -170,53 +258,24 @@ __global__ void __launch_bounds__(64) sparse_site_kernel(long N, int S, Rule<T> 
     const long b = bs / S;
     const long s = bs - b * S;
     long k_lo = (long)seg[b * (S + 1) + s], k_hi = (long)seg[b * (S + 1) + s + 1];
-    k_lo = k_lo < 0 ? 0 : (k_lo > N ? N : k_lo);                   // (the caller builds the offsets; a bad one reads nothing)
-    k_hi = k_hi < k_lo ? k_lo : (k_hi > N ? N : k_hi);
-    // this lane's entries: e < TRI is (i, j <= i) of nat2, the rest are nat1's (j = D2: the column of ones)
-    int ei[R], ej[R], es[R];
+    clamp_range(k_lo, k_hi, N);
+    int ei[R], ej[R], es[R];           // this lane's entries
     T acc[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        int e = lane + 64 * r;
         acc[r] = T(0);
-        if (e >= E) e = 0;
-        if (e < TRI) {
-            int i = 0;
-            while ((i + 1) * (i + 2) / 2 <= e) ++i;
-            ei[r] = i;
-            ej[r] = e - i * (i + 1) / 2;
-            es[r] = 0;
-        } else {
-            ei[r] = e - TRI;
-            ej[r] = D2;
-            es[r] = 64;
-        }
+        entry_decode<D2, 2>(lane + 64 * r, ei[r], ej[r], es[r]);
     }
-    if (k_hi > k_lo) {
-        for (int idx = lane; idx < D2 * D2; idx += 64) ls[idx] = pair_cov[bs * (D2 * D2) + idx];
-        if (lane < D2) lm[lane] = pair_mean[bs * D2 + lane];
-        lw[lane * W + D2] = T(1);
-    }
+    if (k_hi > k_lo) stage_pair<T, D2>(lane, bs, pair_mean, pair_cov, ls, lm, lw);
     for (long k0 = k_lo; k0 < k_hi; k0 += 64) {
         const int npts = k_hi - k0 < 64 ? int(k_hi - k0) : 64;
         __syncthreads();               // the previous tile's phase 2 has read lw and lg
-        const T* wt = w + (b * N + k0) * D2;
-        for (int idx = lane; idx < npts * D2; idx += 64) lw[(idx / D2) * W + idx % D2] = wt[idx];
+        stage_tile<T, D2>(lane, npts, w + (b * N + k0) * D2, lw);
         __syncthreads();
         if (lane < npts) {
             const long id = b * N + k0 + lane;
-            T wr[D2];
-#pragma unroll
-            for (int i = 0; i < D2; ++i) wr[i] = lw[lane * W + i];
-            T mu = T(0), s2 = cvar[id];
-#pragma unroll
-            for (int i = 0; i < D2; ++i) {
-                T t = T(0);
-#pragma unroll
-                for (int j = 0; j < D2; ++j) t += ls[i * D2 + j] * wr[j];
-                s2 += wr[i] * t;
-                mu += wr[i] * lm[i];
-            }
+            T mu, s2;
+            project_point<T, D2>(lane, lw, ls, lm, cvar[id], mu, s2);
             const T y = yobs[id];
             T ve, gm, gv;
             if (s2 > T(0)) {
@@ -237,10 +296,7 @@ __global__ void __launch_bounds__(64) sparse_site_kernel(long N, int S, Rule<T> 
             T part[R];                 // the tile's own sum first, then onto the running one: the rounding error grows with
 #pragma unroll                         // 64 + the number of tiles, not with the length of the segment
             for (int r = 0; r < R; ++r) part[r] = T(0);
-            for (int k = 0; k < npts; ++k) {
-#pragma unroll
-                for (int r = 0; r < R; ++r) part[r] += (lg[es[r] + k] * lw[k * W + ej[r]]) * lw[k * W + ei[r]];
-            }
+            for (int k = 0; k < npts; ++k) accumulate_point<T, D2, R>(k, lg, lw, ei, ej, es, part);
 #pragma unroll
             for (int r = 0; r < R; ++r) acc[r] += part[r];
         }
@@ -267,14 +323,10 @@ __global__ void __launch_bounds__(64) sparse_site_kernel(long N, int S, Rule<T> 
 // ---- SVGP: the segmented expected log-likelihood and its adjoint onto the pair marginals (markovflow/models/sparse_variational.py
 // :149-192, the data term of the ELBO) -----------------------------------------------------------------------------------------
 // Two passes, tile-parallel: the grid of pass 1 is the number of TILES, so one long segment spreads over the whole device.
-//   pass 1, one wavefront per tile: a tile is at most 64 consecutive points of one segment, tile j of a segment starting at the
-//            segment's first point + 64 j (the tiling of a segment depends on nothing but the segment).  Phase 1 is
-//            sparse_site_kernel's (w rows through LDS with the odd stride 2d + 1, the pair marginal in LDS read as broadcasts, a lane
-//            per point); it leaves gv, gm and ve of the tile's points in LDS.  Phase 2, a lane per few entries of the accumulator -
-//            the lower triangle of g_cov, g_mean and ONE more entry, sum ve: 2d (2d + 1) / 2 + 2d + 1 entries - loops over the
-//            tile's points in ascending order: entry (i, j) += (gv_k w_kj) w_ki, a g_mean entry reads gm_k and the column of ones
-//            that pads every row of w, the last entry reads ve_k and the ones twice.  The tile's sums go to the workspace as one
-//            contiguous row (coalesced stores).
+//   pass 1, one wavefront per tile: tile j of a segment starts at the segment's first point + 64 j (the tiling of a segment depends
+//            on nothing but the segment).  Phase 1 leaves gv, gm and ve of the tile's points in LDS; the accumulator is the lower
+//            triangle of g_cov, g_mean and ONE more entry, sum ve: 2d (2d + 1) / 2 + 2d + 1 entries.  The tile's sums go to the
+//            workspace as one contiguous row (coalesced stores).
 //   pass 2, one block per (series, segment), a lane per entry: the segment's rows are added in ascending tile order, the outputs
 //            are written and the triangle mirrored.  An empty segment writes zeros.
 // The tile table comes from the caller: tile_seg[t] = series * S + segment of tile t, seg_tile[series * S + segment] = the first
@@ -288,7 +340,7 @@ __global__ void __launch_bounds__(64) sparse_expect_tile_kernel(long N, int S, l
                                                                 const T* __restrict__ cvar, const T* __restrict__ yobs,
                                                                 const T* __restrict__ pair_mean, const T* __restrict__ pair_cov,
                                                                 int grads, T* __restrict__ ws) {
-    constexpr int W = D2 + 1, TRI = D2 * (D2 + 1) / 2, E = TRI + D2 + 1, R = (E + 63) / 64;
+    constexpr int W = D2 + 1, E = seg_entries(D2, 3), R = (E + 63) / 64;
     __shared__ T lw[64 * W];
     __shared__ T ls[D2 * D2];
     __shared__ T lm[D2];
@@ -300,56 +352,25 @@ __global__ void __launch_bounds__(64) sparse_expect_tile_kernel(long N, int S, l
     const long b = bs / S;
     const long s = bs - b * S;
     long k_lo = (long)seg[b * (S + 1) + s], k_hi = (long)seg[b * (S + 1) + s + 1];
-    k_lo = k_lo < 0 ? 0 : (k_lo > N ? N : k_lo);
-    k_hi = k_hi < k_lo ? k_lo : (k_hi > N ? N : k_hi);
+    clamp_range(k_lo, k_hi, N);
     const long j = t - (long)seg_tile[bs];                          // this tile's number within its segment
     const long k0 = (j >= 0 && j <= (k_hi - k_lo) / 64) ? k_lo + 64 * j : k_hi;
     const int npts = k_hi - k0 < 64 ? int(k_hi - k0) : 64;          // (0 only for a table that disagrees with the offsets)
-    // this lane's entries: e < TRI is (i, j <= i) of g_cov, then g_mean's (j = D2: the column of ones), then sum ve (i = j = D2)
-    int ei[R], ej[R], es[R];
+    int ei[R], ej[R], es[R];           // this lane's entries
     T part[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        int e = lane + 64 * r;
         part[r] = T(0);
-        if (e >= E) e = 0;
-        if (e < TRI) {
-            int i = 0;
-            while ((i + 1) * (i + 2) / 2 <= e) ++i;
-            ei[r] = i;
-            ej[r] = e - i * (i + 1) / 2;
-            es[r] = 0;
-        } else if (e < TRI + D2) {
-            ei[r] = e - TRI;
-            ej[r] = D2;
-            es[r] = 64;
-        } else {
-            ei[r] = D2;
-            ej[r] = D2;
-            es[r] = 128;
-        }
+        entry_decode<D2, 3>(lane + 64 * r, ei[r], ej[r], es[r]);
     }
     if (npts > 0) {
-        for (int idx = lane; idx < D2 * D2; idx += 64) ls[idx] = pair_cov[bs * (D2 * D2) + idx];
-        if (lane < D2) lm[lane] = pair_mean[bs * D2 + lane];
-        lw[lane * W + D2] = T(1);
-        const T* wt = w + (b * N + k0) * D2;
-        for (int idx = lane; idx < npts * D2; idx += 64) lw[(idx / D2) * W + idx % D2] = wt[idx];
+        stage_pair<T, D2>(lane, bs, pair_mean, pair_cov, ls, lm, lw);
+        stage_tile<T, D2>(lane, npts, w + (b * N + k0) * D2, lw);
         __syncthreads();
         if (lane < npts) {
             const long id = b * N + k0 + lane;
-            T wr[D2];
-#pragma unroll
-            for (int i = 0; i < D2; ++i) wr[i] = lw[lane * W + i];
-            T mu = T(0), s2 = cvar[id];
-#pragma unroll
-            for (int i = 0; i < D2; ++i) {
-                T u = T(0);
-#pragma unroll
-                for (int c = 0; c < D2; ++c) u += ls[i * D2 + c] * wr[c];
-                s2 += wr[i] * u;
-                mu += wr[i] * lm[i];
-            }
+            T mu, s2;
+            project_point<T, D2>(lane, lw, ls, lm, cvar[id], mu, s2);
             const T y = yobs[id];
             T ve, gm, gv;
             if (s2 > T(0)) {
@@ -363,10 +384,7 @@ __global__ void __launch_bounds__(64) sparse_expect_tile_kernel(long N, int S, l
         }
         __syncthreads();
         if (grads) {
-            for (int k = 0; k < npts; ++k) {
-#pragma unroll
-                for (int r = 0; r < R; ++r) part[r] += (lg[es[r] + k] * lw[k * W + ej[r]]) * lw[k * W + ei[r]];
-            }
+            for (int k = 0; k < npts; ++k) accumulate_point<T, D2, R>(k, lg, lw, ei, ej, es, part);
         } else if (lane == (E - 1) % 64) {         // value only: the one entry, with the bits it has beside the gradients
             for (int k = 0; k < npts; ++k) part[R - 1] += lg[128 + k];
         }
@@ -382,23 +400,21 @@ template <typename T, int D2>
 __global__ void __launch_bounds__(256) sparse_expect_reduce_kernel(long num_tiles, const long long* __restrict__ seg_tile,
                                                                    const T* __restrict__ ws, T* __restrict__ ve_sum,
                                                                    T* __restrict__ g_mean, T* __restrict__ g_cov) {
-    constexpr int TRI = D2 * (D2 + 1) / 2, E = TRI + D2 + 1;
+    constexpr int TRI = D2 * (D2 + 1) / 2, E = seg_entries(D2, 3);
     const long bs = blockIdx.x;
     long t_lo = 0, t_hi = 0;
     if (seg_tile) {                                // (NULL: no points at all)
         t_lo = (long)seg_tile[bs];
         t_hi = (long)seg_tile[bs + 1];
-        t_lo = t_lo < 0 ? 0 : (t_lo > num_tiles ? num_tiles : t_lo);
-        t_hi = t_hi < t_lo ? t_lo : (t_hi > num_tiles ? num_tiles : t_hi);
+        clamp_range(t_lo, t_hi, num_tiles);
     }
     for (int e = threadIdx.x; e < E; e += 256) {
         if (e < E - 1 ? !g_mean : !ve_sum) continue;
         T acc = T(0);
         for (long t = t_lo; t < t_hi; ++t) acc += ws[t * E + e];
         if (e < TRI) {
-            int i = 0;
-            while ((i + 1) * (i + 2) / 2 <= e) ++i;
-            const int c = e - i * (i + 1) / 2;
+            int i, c;
+            tri_decode(e, i, c);
             g_cov[bs * (D2 * D2) + i * D2 + c] = acc;
             g_cov[bs * (D2 * D2) + c * D2 + i] = acc;
         } else if (e < E - 1) {
@@ -545,7 +561,7 @@ __global__ void __launch_bounds__(256) lik_pep_kernel(long N, Rule<T> q, Par<T> 
     log_norm[id] = newn;
 }
 
-// argument checks shared by the five entry points: 0, or the (negative) position of the offending argument
+// argument checks shared by every entry point: 0, or the (negative) position of the offending argument
 template <typename T>
 int prepare(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights, bool log_weights,
             Rule<T>& q, Par<T>& p) {
@@ -575,23 +591,60 @@ int prepare(int64_t N, int lik, const double* params, int nq, const double* node
     return 0;
 }
 
-template <typename T, int LIK>
-int launch_ve(int64_t N, const Rule<T>& q, const Par<T>& p, const T* fmu, const T* fvar, const T* y, T lr, T* nat1, T* nat2, T* ve,
-              T* g_mu, T* g_var, void* stream) {
-    hipLaunchKernelGGL((lik_ve_kernel<T, LIK>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       (long)N, q, p, fmu, fvar, y, lr, nat1, nat2, ve, g_mu, g_var);
+// null-pointer checks of a run of arguments whose first has position `first`: 0, or the (negative) position of the first null one
+inline int first_null(int first, std::initializer_list<const void*> ptrs) {
+    for (const void* ptr : ptrs) {
+        if (!ptr) return -first;
+        ++first;
+    }
+    return 0;
+}
+
+// the runtime likelihood id (0 ... 3: prepare has checked it) as a compile-time constant: f(std::integral_constant<int, LIK>)
+template <typename F>
+int with_lik(int lik, F&& f) {
+    switch (lik) {
+        case 0: return f(std::integral_constant<int, 0>{});
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        default: return f(std::integral_constant<int, 3>{});
+    }
+}
+
+// the same for the pair dimension of the segmented kernels: 2, 4, ..., 18, -100 for any other
+template <typename F>
+int with_two_d(int two_d, F&& f) {
+    switch (two_d) {
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 10: return f(std::integral_constant<int, 10>{});
+        case 12: return f(std::integral_constant<int, 12>{});
+        case 14: return f(std::integral_constant<int, 14>{});
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 18: return f(std::integral_constant<int, 18>{});
+        default: return -100;
+    }
+}
+
+// one launch; the arguments are converted to the kernel's parameter types (NULL to a typed pointer, int64_t to long or int)
+template <typename... Params, typename... Args>
+int launch(void (*kernel)(Params...), int64_t grid, unsigned block, void* stream, const Args&... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(block), 0, static_cast<hipStream_t>(stream), static_cast<Params>(args)...);
     return hipGetLastError() == hipSuccess ? 0 : -1000;
 }
 
+inline const long long* ll(const int64_t* x) { return reinterpret_cast<const long long*>(x); }
+
+// variational expectations (nat1 == NULL) or the CVI site update: the one kernel behind both
 template <typename T>
-int dispatch_ve(int64_t N, int lik, const Rule<T>& q, const Par<T>& p, const T* fmu, const T* fvar, const T* y, T lr, T* nat1,
-                T* nat2, T* ve, T* g_mu, T* g_var, void* stream) {
-    switch (lik) {
-        case 0: return launch_ve<T, 0>(N, q, p, fmu, fvar, y, lr, nat1, nat2, ve, g_mu, g_var, stream);
-        case 1: return launch_ve<T, 1>(N, q, p, fmu, fvar, y, lr, nat1, nat2, ve, g_mu, g_var, stream);
-        case 2: return launch_ve<T, 2>(N, q, p, fmu, fvar, y, lr, nat1, nat2, ve, g_mu, g_var, stream);
-        default: return launch_ve<T, 3>(N, q, p, fmu, fvar, y, lr, nat1, nat2, ve, g_mu, g_var, stream);
-    }
+int launch_ve(int64_t N, int lik, const Rule<T>& q, const Par<T>& p, const T* fmu, const T* fvar, const T* y, T lr, T* nat1, T* nat2,
+              T* ve, T* g_mu, T* g_var, void* stream) {
+    return with_lik(lik, [&](auto L) {
+        return launch(lik_ve_kernel<T, decltype(L)::value>, (N + 255) / 256, 256, stream, N, q, p, fmu, fvar, y, lr, nat1, nat2, ve,
+                      g_mu, g_var);
+    });
 }
 
 template <typename T>
@@ -599,14 +652,12 @@ int run_ve(int64_t N, int lik, const double* params, int nq, const double* nodes
            const T* y, T* ve, T* g_mu, T* g_var, void* stream) {
     Rule<T> q;
     Par<T> p;
-    const int bad = prepare<T>(N, lik, params, nq, nodes, weights, false, q, p);
+    int bad = prepare<T>(N, lik, params, nq, nodes, weights, false, q, p);
     if (bad) return bad;
     if (N == 0) return 0;
-    if (!fmu) return -7;
-    if (!fvar) return -8;
-    if (!y) return -9;
+    if ((bad = first_null(7, {fmu, fvar, y}))) return bad;
     if (!ve && !g_mu && !g_var) return 0;          // nothing asked for
-    return dispatch_ve<T>(N, lik, q, p, fmu, fvar, y, T(0), nullptr, nullptr, ve, g_mu, g_var, stream);
+    return launch_ve<T>(N, lik, q, p, fmu, fvar, y, T(0), nullptr, nullptr, ve, g_mu, g_var, stream);
 }
 
 template <typename T>
@@ -614,23 +665,13 @@ int run_site(int64_t N, int lik, const double* params, int nq, const double* nod
              const T* y, T lr, T* nat1, T* nat2, T* ve, void* stream) {
     Rule<T> q;
     Par<T> p;
-    const int bad = prepare<T>(N, lik, params, nq, nodes, weights, false, q, p);
+    int bad = prepare<T>(N, lik, params, nq, nodes, weights, false, q, p);
     if (bad) return bad;
     if (!(lr >= T(0)) || !(lr <= T(1))) return -10;
     if (N == 0) return 0;
-    if (!fmu) return -7;
-    if (!fvar) return -8;
-    if (!y) return -9;
-    if (!nat1) return -11;
-    if (!nat2) return -12;
-    return dispatch_ve<T>(N, lik, q, p, fmu, fvar, y, lr, nat1, nat2, ve, nullptr, nullptr, stream);
-}
-
-template <typename T, int LIK>
-int launch_pld(int64_t N, const Rule<T>& q, const Par<T>& p, const T* fmu, const T* fvar, const T* y, T* out, void* stream) {
-    hipLaunchKernelGGL((lik_pld_kernel<T, LIK>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       (long)N, q, p, fmu, fvar, y, out);
-    return hipGetLastError() == hipSuccess ? 0 : -1000;
+    if ((bad = first_null(7, {fmu, fvar, y}))) return bad;
+    if ((bad = first_null(11, {nat1, nat2}))) return bad;
+    return launch_ve<T>(N, lik, q, p, fmu, fvar, y, lr, nat1, nat2, ve, nullptr, nullptr, stream);
 }
 
 template <typename T>
@@ -638,27 +679,13 @@ int run_pld(int64_t N, int lik, const double* params, int nq, const double* node
             const T* y, T* out, void* stream) {
     Rule<T> q;
     Par<T> p;
-    const int bad = prepare<T>(N, lik, params, nq, nodes, weights, true, q, p);
+    int bad = prepare<T>(N, lik, params, nq, nodes, weights, true, q, p);
     if (bad) return bad;
     if (N == 0) return 0;
-    if (!fmu) return -7;
-    if (!fvar) return -8;
-    if (!y) return -9;
-    if (!out) return -10;
-    switch (lik) {
-        case 0: return launch_pld<T, 0>(N, q, p, fmu, fvar, y, out, stream);
-        case 1: return launch_pld<T, 1>(N, q, p, fmu, fvar, y, out, stream);
-        case 2: return launch_pld<T, 2>(N, q, p, fmu, fvar, y, out, stream);
-        default: return launch_pld<T, 3>(N, q, p, fmu, fvar, y, out, stream);
-    }
-}
-
-template <typename T, int LIK>
-int launch_led(int64_t N, const Rule<T>& q, const Par<T>& p, T alpha, const T* fmu, const T* fvar, const T* y, T* led, T* g1, T* g2,
-               void* stream) {
-    hipLaunchKernelGGL((lik_led_kernel<T, LIK>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       (long)N, q, p, alpha, fmu, fvar, y, led, g1, g2);
-    return hipGetLastError() == hipSuccess ? 0 : -1000;
+    if ((bad = first_null(7, {fmu, fvar, y, out}))) return bad;
+    return with_lik(lik, [&](auto L) {
+        return launch(lik_pld_kernel<T, decltype(L)::value>, (N + 255) / 256, 256, stream, N, q, p, fmu, fvar, y, out);
+    });
 }
 
 template <typename T>
@@ -666,28 +693,15 @@ int run_led(int64_t N, int lik, const double* params, int nq, const double* node
             const T* fvar, const T* y, T* led, T* g1, T* g2, void* stream) {
     Rule<T> q;
     Par<T> p;
-    const int bad = prepare<T>(N, lik, params, nq, nodes, weights, true, q, p);
+    int bad = prepare<T>(N, lik, params, nq, nodes, weights, true, q, p);
     if (bad) return bad;
     if (!(alpha > T(0)) || !(alpha <= T(1))) return -7;
     if (N == 0) return 0;
-    if (!fmu) return -8;
-    if (!fvar) return -9;
-    if (!y) return -10;
+    if ((bad = first_null(8, {fmu, fvar, y}))) return bad;
     if (!led && !g1 && !g2) return 0;              // nothing asked for
-    switch (lik) {
-        case 0: return launch_led<T, 0>(N, q, p, alpha, fmu, fvar, y, led, g1, g2, stream);
-        case 1: return launch_led<T, 1>(N, q, p, alpha, fmu, fvar, y, led, g1, g2, stream);
-        case 2: return launch_led<T, 2>(N, q, p, alpha, fmu, fvar, y, led, g1, g2, stream);
-        default: return launch_led<T, 3>(N, q, p, alpha, fmu, fvar, y, led, g1, g2, stream);
-    }
-}
-
-template <typename T, int LIK>
-int launch_pep(int64_t N, const Rule<T>& q, const Par<T>& p, T alpha, T lr, const T* fmu, const T* fvar, const T* y,
-               const unsigned char* update, T* nat1, T* nat2, T* log_norm, T* cav_mu, T* cav_var, void* stream) {
-    hipLaunchKernelGGL((lik_pep_kernel<T, LIK>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       (long)N, q, p, alpha, lr, fmu, fvar, y, update, nat1, nat2, log_norm, cav_mu, cav_var);
-    return hipGetLastError() == hipSuccess ? 0 : -1000;
+    return with_lik(lik, [&](auto L) {
+        return launch(lik_led_kernel<T, decltype(L)::value>, (N + 255) / 256, 256, stream, N, q, p, alpha, fmu, fvar, y, led, g1, g2);
+    });
 }
 
 template <typename T>
@@ -696,151 +710,87 @@ int run_pep(int64_t N, int lik, const double* params, int nq, const double* node
             void* stream) {
     Rule<T> q;
     Par<T> p;
-    const int bad = prepare<T>(N, lik, params, nq, nodes, weights, true, q, p);
+    int bad = prepare<T>(N, lik, params, nq, nodes, weights, true, q, p);
     if (bad) return bad;
     if (!(alpha > T(0)) || !(alpha <= T(1))) return -7;
     if (!(lr >= T(0)) || !(lr <= T(1))) return -8;
     if (N == 0) return 0;
-    if (!fmu) return -9;
-    if (!fvar) return -10;
-    if (!y) return -11;
-    if (!nat1) return -13;
-    if (!nat2) return -14;
-    if (!log_norm) return -15;
-    switch (lik) {
-        case 0: return launch_pep<T, 0>(N, q, p, alpha, lr, fmu, fvar, y, update, nat1, nat2, log_norm, cav_mu, cav_var, stream);
-        case 1: return launch_pep<T, 1>(N, q, p, alpha, lr, fmu, fvar, y, update, nat1, nat2, log_norm, cav_mu, cav_var, stream);
-        case 2: return launch_pep<T, 2>(N, q, p, alpha, lr, fmu, fvar, y, update, nat1, nat2, log_norm, cav_mu, cav_var, stream);
-        default: return launch_pep<T, 3>(N, q, p, alpha, lr, fmu, fvar, y, update, nat1, nat2, log_norm, cav_mu, cav_var, stream);
-    }
+    if ((bad = first_null(9, {fmu, fvar, y}))) return bad;
+    if ((bad = first_null(13, {nat1, nat2, log_norm}))) return bad;       // (12 is update, which may be NULL)
+    return with_lik(lik, [&](auto L) {
+        return launch(lik_pep_kernel<T, decltype(L)::value>, (N + 255) / 256, 256, stream, N, q, p, alpha, lr, fmu, fvar, y, update,
+                      nat1, nat2, log_norm, cav_mu, cav_var);
+    });
 }
 
-template <typename T, int LIK, int D2>
-int launch_sparse(int64_t B, int64_t N, int64_t S, const Rule<T>& q, const Par<T>& p, const int64_t* seg, const T* w, const T* c,
-                  const T* y, const T* pm, const T* pc, T lr, T* nat1, T* nat2, T* fmu, T* fvar, T* ve, void* stream) {
-    hipLaunchKernelGGL((sparse_site_kernel<T, LIK, D2>), dim3((unsigned)(B * S)), dim3(64), 0, static_cast<hipStream_t>(stream),
-                       (long)N, (int)S, q, p, reinterpret_cast<const long long*>(seg), w, c, y, pm, pc, lr, nat1, nat2, fmu, fvar, ve);
-    return hipGetLastError() == hipSuccess ? 0 : -1000;
-}
-
-template <typename T, int D2>
-int dispatch_sparse(int lik, int64_t B, int64_t N, int64_t S, const Rule<T>& q, const Par<T>& p, const int64_t* seg, const T* w,
-                    const T* c, const T* y, const T* pm, const T* pc, T lr, T* nat1, T* nat2, T* fmu, T* fvar, T* ve, void* stream) {
-    switch (lik) {
-        case 0: return launch_sparse<T, 0, D2>(B, N, S, q, p, seg, w, c, y, pm, pc, lr, nat1, nat2, fmu, fvar, ve, stream);
-        case 1: return launch_sparse<T, 1, D2>(B, N, S, q, p, seg, w, c, y, pm, pc, lr, nat1, nat2, fmu, fvar, ve, stream);
-        case 2: return launch_sparse<T, 2, D2>(B, N, S, q, p, seg, w, c, y, pm, pc, lr, nat1, nat2, fmu, fvar, ve, stream);
-        default: return launch_sparse<T, 3, D2>(B, N, S, q, p, seg, w, c, y, pm, pc, lr, nat1, nat2, fmu, fvar, ve, stream);
-    }
-}
-
-// the sparse site update's argument checks: the (negative) position of the offending argument in ITS signature, -100 for a
-// two_d outside 2, 4, ..., 18
+// the leading argument checks of the two segmented entry points: the (negative) position of the offending argument in THEIR
+// signature, -100 for a two_d outside 2, 4, ..., 18
 template <typename T>
-int run_sparse(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq, const double* nodes,
-               const double* weights, const int64_t* seg, const T* w, const T* c, const T* y, const T* pm, const T* pc, T lr,
-               T* nat1, T* nat2, T* fmu, T* fvar, T* ve, void* stream) {
+int prepare_segmented(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq, const double* nodes,
+                      const double* weights, Rule<T>& q, Par<T>& p) {
     if (B < 0) return -1;
     if (N < 0) return -2;
     if (S < 1 || (B > 0 && S > int64_t(0x7fffffff) / B)) return -3;
     if (two_d < 2 || two_d > 18 || (two_d & 1)) return -100;
+    const int bad = prepare<T>(0, lik, params, nq, nodes, weights, false, q, p);      // -2 ... -6 there are arguments 5 ... 9 here
+    return bad ? bad - 3 : 0;
+}
+
+template <typename T>
+int run_sparse(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq, const double* nodes,
+               const double* weights, const int64_t* seg, const T* w, const T* c, const T* y, const T* pm, const T* pc, T lr,
+               T* nat1, T* nat2, T* fmu, T* fvar, T* ve, void* stream) {
     Rule<T> q;
     Par<T> p;
-    const int bad = prepare<T>(0, lik, params, nq, nodes, weights, false, q, p);      // -2 ... -6 there are arguments 5 ... 9 here
-    if (bad) return bad - 3;
+    int bad = prepare_segmented<T>(B, N, S, two_d, lik, params, nq, nodes, weights, q, p);
+    if (bad) return bad;
     if (!(lr >= T(0)) || !(lr <= T(1))) return -16;
     if (!nat1 && nat2) return -17;
     if (nat1 && !nat2) return -18;
     if (B == 0) return 0;
     if (!nat1 && (N == 0 || (!fmu && !fvar && !ve))) return 0;      // nothing asked for
     if (!seg) return -10;
-    if (N > 0) {
-        if (!w) return -11;
-        if (!c) return -12;
-        if (!y) return -13;
-        if (!pm) return -14;
-        if (!pc) return -15;
-    }
-#define MF_SPARSE_CASE(D2) \
-    case D2: return dispatch_sparse<T, D2>(lik, B, N, S, q, p, seg, w, c, y, pm, pc, lr, nat1, nat2, fmu, fvar, ve, stream);
-    switch (two_d) {
-        MF_SPARSE_CASE(2) MF_SPARSE_CASE(4) MF_SPARSE_CASE(6) MF_SPARSE_CASE(8) MF_SPARSE_CASE(10) MF_SPARSE_CASE(12)
-        MF_SPARSE_CASE(14) MF_SPARSE_CASE(16) MF_SPARSE_CASE(18)
-        default: return -100;
-    }
-#undef MF_SPARSE_CASE
+    if (N > 0 && (bad = first_null(11, {w, c, y, pm, pc}))) return bad;
+    return with_two_d(two_d, [&](auto D) {
+        return with_lik(lik, [&](auto L) {
+            return launch(sparse_site_kernel<T, decltype(L)::value, decltype(D)::value>, B * S, 64, stream, N, S, q, p, ll(seg), w, c,
+                          y, pm, pc, lr, nat1, nat2, fmu, fvar, ve);
+        });
+    });
 }
 
-constexpr size_t expect_row(int two_d) { return size_t(two_d) * (two_d + 1) / 2 + two_d + 1; }
+constexpr size_t expect_row(int two_d) { return size_t(seg_entries(two_d, 3)); }
 
-template <typename T, int LIK, int D2>
-int launch_expect(int64_t B, int64_t N, int64_t S, const Rule<T>& q, const Par<T>& p, const int64_t* seg, const T* w, const T* c,
-                  const T* y, const T* pm, const T* pc, int64_t tiles, const int64_t* tile_seg, const int64_t* seg_tile, T* ws,
-                  T* ve_sum, T* g_mean, T* g_cov, void* stream) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const long long* table = reinterpret_cast<const long long*>(seg_tile);
-    if (tiles > 0) {
-        hipLaunchKernelGGL((sparse_expect_tile_kernel<T, LIK, D2>), dim3((unsigned)tiles), dim3(64), 0, st, (long)N, (int)S,
-                           (long)(B * S), q, p, reinterpret_cast<const long long*>(seg),
-                           reinterpret_cast<const long long*>(tile_seg), table, w, c, y, pm, pc, g_mean ? 1 : 0, ws);
-        if (hipGetLastError() != hipSuccess) return -1000;
-    }
-    hipLaunchKernelGGL((sparse_expect_reduce_kernel<T, D2>), dim3((unsigned)(B * S)), dim3(256), 0, st, (long)tiles,
-                       tiles > 0 ? table : nullptr, ws, ve_sum, g_mean, g_cov);
-    return hipGetLastError() == hipSuccess ? 0 : -1000;
-}
-
-template <typename T, int D2>
-int dispatch_expect(int lik, int64_t B, int64_t N, int64_t S, const Rule<T>& q, const Par<T>& p, const int64_t* seg, const T* w,
-                    const T* c, const T* y, const T* pm, const T* pc, int64_t tiles, const int64_t* tile_seg,
-                    const int64_t* seg_tile, T* ws, T* ve_sum, T* g_mean, T* g_cov, void* stream) {
-    switch (lik) {
-        case 0: return launch_expect<T, 0, D2>(B, N, S, q, p, seg, w, c, y, pm, pc, tiles, tile_seg, seg_tile, ws, ve_sum, g_mean, g_cov, stream);
-        case 1: return launch_expect<T, 1, D2>(B, N, S, q, p, seg, w, c, y, pm, pc, tiles, tile_seg, seg_tile, ws, ve_sum, g_mean, g_cov, stream);
-        case 2: return launch_expect<T, 2, D2>(B, N, S, q, p, seg, w, c, y, pm, pc, tiles, tile_seg, seg_tile, ws, ve_sum, g_mean, g_cov, stream);
-        default: return launch_expect<T, 3, D2>(B, N, S, q, p, seg, w, c, y, pm, pc, tiles, tile_seg, seg_tile, ws, ve_sum, g_mean, g_cov, stream);
-    }
-}
-
-// the segmented expected log-likelihood's argument checks: the (negative) position of the offending argument in ITS signature
 template <typename T>
 int run_expect(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq, const double* nodes,
                const double* weights, const int64_t* seg, const T* w, const T* c, const T* y, const T* pm, const T* pc,
                int64_t tiles, const int64_t* tile_seg, const int64_t* seg_tile, void* ws, size_t ws_bytes, T* ve_sum, T* g_mean,
                T* g_cov, void* stream) {
-    if (B < 0) return -1;
-    if (N < 0) return -2;
-    if (S < 1 || (B > 0 && S > int64_t(0x7fffffff) / B)) return -3;
-    if (two_d < 2 || two_d > 18 || (two_d & 1)) return -100;
     Rule<T> q;
     Par<T> p;
-    const int bad = prepare<T>(0, lik, params, nq, nodes, weights, false, q, p);      // -2 ... -6 there are arguments 5 ... 9 here
-    if (bad) return bad - 3;
+    int bad = prepare_segmented<T>(B, N, S, two_d, lik, params, nq, nodes, weights, q, p);
+    if (bad) return bad;
     if (tiles < 0 || tiles > int64_t(0x7fffffff) || (N == 0 && tiles != 0)) return -16;
     if (!g_mean && g_cov) return -22;
     if (g_mean && !g_cov) return -23;
     if (B == 0 || (!ve_sum && !g_mean)) return 0;      // nothing asked for
     if (tiles > 0) {
-        if (!seg) return -10;
-        if (!w) return -11;
-        if (!c) return -12;
-        if (!y) return -13;
-        if (!pm) return -14;
-        if (!pc) return -15;
-        if (!tile_seg) return -17;
-        if (!seg_tile) return -18;
-        if (!ws) return -19;
+        if ((bad = first_null(10, {seg, w, c, y, pm, pc}))) return bad;
+        if ((bad = first_null(17, {tile_seg, seg_tile, ws}))) return bad;
         if (ws_bytes < size_t(tiles) * expect_row(two_d) * sizeof(T)) return -20;
     }
-#define MF_EXPECT_CASE(D2) \
-    case D2: return dispatch_expect<T, D2>(lik, B, N, S, q, p, seg, w, c, y, pm, pc, tiles, tile_seg, seg_tile, static_cast<T*>(ws), \
-                                           ve_sum, g_mean, g_cov, stream);
-    switch (two_d) {
-        MF_EXPECT_CASE(2) MF_EXPECT_CASE(4) MF_EXPECT_CASE(6) MF_EXPECT_CASE(8) MF_EXPECT_CASE(10) MF_EXPECT_CASE(12)
-        MF_EXPECT_CASE(14) MF_EXPECT_CASE(16) MF_EXPECT_CASE(18)
-        default: return -100;
-    }
-#undef MF_EXPECT_CASE
+    return with_two_d(two_d, [&](auto D) {
+        constexpr int D2 = decltype(D)::value;
+        if (tiles > 0) {
+            const int rc = with_lik(lik, [&](auto L) {
+                return launch(sparse_expect_tile_kernel<T, decltype(L)::value, D2>, tiles, 64, stream, N, S, B * S, q, p, ll(seg),
+                              ll(tile_seg), ll(seg_tile), w, c, y, pm, pc, g_mean ? 1 : 0, ws);
+            });
+            if (rc) return rc;
+        }
+        return launch(sparse_expect_reduce_kernel<T, D2>, B * S, 256, stream, tiles, tiles > 0 ? ll(seg_tile) : nullptr, ws, ve_sum,
+                      g_mean, g_cov);
+    });
 }
 
 }  // namespace

@@ -102,6 +102,10 @@ class Likelihood:
         p = self._params()
         return (ctypes.c_double * len(p))(*p) if p else None
 
+    def _kernel_args(self):
+        """What every ``mf_lik_*`` entry point takes behind its sizes: the id, the parameters and the Gauss-Hermite rule."""
+        return self._id, self._c_params(), self.num_gauss_hermite_points, self._c_nodes, self._c_weights
+
     def _check(self, what: str, fmu: torch.Tensor, **others: torch.Tensor):
         if fmu.dim() < 2 or fmu.shape[-1] != 1:
             raise ValueError(f"{type(self).__name__}.{what}: tensors must have shape batch + [N, 1], got {tuple(fmu.shape)}")
@@ -131,9 +135,8 @@ class Likelihood:
                 return torch_predict_log_density(self, fmu, fvar, y)[..., 0]
             mu, var, obs = fmu.contiguous(), fvar.contiguous(), y.contiguous()
             out = torch.empty_like(mu)
-            _lib.call("mf_lik_predict_log_density", mu.dtype, mu.numel(), self._id, self._c_params(), self.num_gauss_hermite_points,
-                      self._c_nodes, self._c_weights, _lib.ptr(mu), _lib.ptr(var), _lib.ptr(obs), _lib.ptr(out),
-                      _lib.stream_ptr(mu.device))
+            _lib.call("mf_lik_predict_log_density", mu.dtype, mu.numel(), *self._kernel_args(), _lib.ptr(mu), _lib.ptr(var),
+                      _lib.ptr(obs), _lib.ptr(out), _lib.stream_ptr(mu.device))
             return out[..., 0]
 
     def _expectations(self, fmu, fvar, y):
@@ -142,9 +145,8 @@ class Likelihood:
             return torch_variational_expectations(self, fmu, fvar, y)
         mu, var, obs = fmu.contiguous(), fvar.contiguous(), y.contiguous()
         ve, g_mu, g_var = torch.empty_like(mu), torch.empty_like(mu), torch.empty_like(mu)
-        _lib.call("mf_lik_variational_expectations", mu.dtype, mu.numel(), self._id, self._c_params(), self.num_gauss_hermite_points,
-                  self._c_nodes, self._c_weights, _lib.ptr(mu), _lib.ptr(var), _lib.ptr(obs), _lib.ptr(ve), _lib.ptr(g_mu),
-                  _lib.ptr(g_var), _lib.stream_ptr(mu.device))
+        _lib.call("mf_lik_variational_expectations", mu.dtype, mu.numel(), *self._kernel_args(), _lib.ptr(mu), _lib.ptr(var),
+                  _lib.ptr(obs), _lib.ptr(ve), _lib.ptr(g_mu), _lib.ptr(g_var), _lib.stream_ptr(mu.device))
         return ve, g_mu, g_var
 
     def cvi_site_update(self, fmu: torch.Tensor, fvar: torch.Tensor, y: torch.Tensor, learning_rate: float, nat1: torch.Tensor,
@@ -167,9 +169,8 @@ class Likelihood:
                 nat2.mul_(1.0 - lr).add_(lr * g_var.reshape(nat2.shape))
                 return
             mu, var, obs = fmu.contiguous(), fvar.contiguous(), y.contiguous()
-            _lib.call("mf_lik_cvi_site_update", mu.dtype, mu.numel(), self._id, self._c_params(), self.num_gauss_hermite_points,
-                      self._c_nodes, self._c_weights, _lib.ptr(mu), _lib.ptr(var), _lib.ptr(obs), lr, _lib.ptr(nat1), _lib.ptr(nat2),
-                      None, _lib.stream_ptr(mu.device))
+            _lib.call("mf_lik_cvi_site_update", mu.dtype, mu.numel(), *self._kernel_args(), _lib.ptr(mu), _lib.ptr(var),
+                      _lib.ptr(obs), lr, _lib.ptr(nat1), _lib.ptr(nat2), None, _lib.stream_ptr(mu.device))
             # the kernel wrote through raw pointers: tell torch, so that whatever keys a cache on (tensor, version) sees the write
             torch.autograd.graph.increment_version(nat1)
             torch.autograd.graph.increment_version(nat2)
@@ -188,9 +189,8 @@ class Likelihood:
             return tuple(o if w else None for o, w in zip(torch_log_expected_density(self, fmu, fvar, y, alpha), want))
         mu, var, obs = fmu.contiguous(), fvar.contiguous(), y.contiguous()
         outs = [torch.empty_like(mu) if w else None for w in want]
-        _lib.call("mf_lik_log_expected_density", mu.dtype, mu.numel(), self._id, self._c_params(), self.num_gauss_hermite_points,
-                  self._c_nodes, self._c_weights, alpha, _lib.ptr(mu), _lib.ptr(var), _lib.ptr(obs), *[_lib.ptr(o) for o in outs],
-                  _lib.stream_ptr(mu.device))
+        _lib.call("mf_lik_log_expected_density", mu.dtype, mu.numel(), *self._kernel_args(), alpha, _lib.ptr(mu), _lib.ptr(var),
+                  _lib.ptr(obs), *[_lib.ptr(o) for o in outs], _lib.stream_ptr(mu.device))
         return tuple(outs)
 
     def log_expected_density(self, fmu: torch.Tensor, fvar: torch.Tensor, y: torch.Tensor, alpha: float = 1.0) -> torch.Tensor:
@@ -241,9 +241,9 @@ class Likelihood:
                 torch_pep_site_update(self, fmu, fvar, y, alpha, lr, nat1, nat2, log_norm, update)
                 return
             mu, var, obs = fmu.contiguous(), fvar.contiguous(), y.contiguous()
-            _lib.call("mf_lik_pep_site_update", mu.dtype, mu.numel(), self._id, self._c_params(), self.num_gauss_hermite_points,
-                      self._c_nodes, self._c_weights, alpha, lr, _lib.ptr(mu), _lib.ptr(var), _lib.ptr(obs), _lib.ptr(update),
-                      _lib.ptr(nat1), _lib.ptr(nat2), _lib.ptr(log_norm), None, None, _lib.stream_ptr(mu.device))
+            _lib.call("mf_lik_pep_site_update", mu.dtype, mu.numel(), *self._kernel_args(), alpha, lr, _lib.ptr(mu), _lib.ptr(var),
+                      _lib.ptr(obs), _lib.ptr(update), _lib.ptr(nat1), _lib.ptr(nat2), _lib.ptr(log_norm), None, None,
+                      _lib.stream_ptr(mu.device))
             # the kernel wrote through raw pointers: tell torch (as cvi_site_update does)
             for t in (nat1, nat2, log_norm):
                 torch.autograd.graph.increment_version(t)

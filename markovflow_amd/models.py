@@ -714,6 +714,19 @@ def sparse_site_projections(kernel: SDEKernel, time_points: torch.Tensor, induci
     return w.contiguous(), c.contiguous(), indices, offsets.contiguous()
 
 
+def _sparse_point_marginals(w: torch.Tensor, c: torch.Tensor, indices: torch.Tensor, pair_mean: torch.Tensor, pair_cov: torch.Tensor,
+                            segs: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Per point ``fmu = w . m_s`` and ``fvar = c + w^T S_s w`` (``[.., N]`` each) with ``(m_s, S_s)`` the marginal of the pair the
+    point belongs to (``indices [.., N]``), and one flat segment index over the batch, ``series * segs + pair`` (``[B N]``)."""
+    two_d = w.shape[-1]
+    m = torch.gather(pair_mean, -2, indices[..., None].expand(tuple(indices.shape) + (two_d,)))
+    cov = torch.gather(pair_cov, -3, indices[..., None, None].expand(tuple(indices.shape) + (two_d, two_d)))
+    fmu = torch.sum(w * m, dim=-1)
+    fvar = c + torch.sum(w * torch.sum(cov * w[..., None, :], dim=-1), dim=-1)
+    series = torch.arange(math.prod(indices.shape[:-1]), device=indices.device).reshape(tuple(indices.shape[:-1]) + (1,))
+    return fmu, fvar, (indices + series * segs).reshape(-1)
+
+
 def sparse_cvi_site_update_torch(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor, indices: torch.Tensor,
                                  pair_mean: torch.Tensor, pair_cov: torch.Tensor, learning_rate: float, nat1: torch.Tensor,
                                  nat2: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -724,21 +737,15 @@ def sparse_cvi_site_update_torch(likelihood: Likelihood, w: torch.Tensor, c: tor
     runs on CPU tensors as a function (the model itself needs the HIP chain kernels, as every model here), it is the model's route
     for ``2d > 18``, and it is what the kernel is measured against.  ``w [.., N, 2d]``, ``c``, ``y``, ``indices``
     ``[.., N]``.  Returns ``(fmu, fvar, ve)``, ``[.., N]`` each."""
-    two_d, segs = w.shape[-1], nat1.shape[-2]
+    two_d = w.shape[-1]
     lr = float(learning_rate)
     with torch.no_grad():
-        m = torch.gather(pair_mean, -2, indices[..., None].expand(tuple(indices.shape) + (two_d,)))
-        cov = torch.gather(pair_cov, -3, indices[..., None, None].expand(tuple(indices.shape) + (two_d, two_d)))
-        fmu = torch.sum(w * m, dim=-1)
-        fvar = c + torch.sum(w * torch.sum(cov * w[..., None, :], dim=-1), dim=-1)
+        fmu, fvar, flat = _sparse_point_marginals(w, c, indices, pair_mean, pair_cov, nat1.shape[-2])
         ve, g_mu, g_var = likelihood._expectations(fmu[..., None], fvar[..., None], y[..., None])
         bad = ~(fvar > 0)
         fmu, fvar = (torch.where(bad, torch.full_like(v, float("nan")), v) for v in (fmu, fvar))
         g1, g2 = gradient_transformation_mean_var_to_expectation((fmu[..., None], fvar[..., None]), (g_mu, g_var))
         theta1, theta2 = back_project_nats(g1, g2, w[..., None, :])
-        # one flat segment index over the batch: series * (M + 1) + pair
-        series = torch.arange(math.prod(indices.shape[:-1]), device=indices.device).reshape(tuple(indices.shape[:-1]) + (1,))
-        flat = (indices + series * segs).reshape(-1)
         sum1 = torch.zeros_like(nat1).reshape(-1, two_d).index_add_(0, flat, theta1.reshape(-1, two_d))
         sum2 = torch.zeros_like(nat2).reshape(-1, two_d, two_d).index_add_(0, flat, theta2.reshape(-1, two_d, two_d))
         nat1.mul_(1.0 - lr).add_(lr * sum1.reshape(nat1.shape))
@@ -758,11 +765,10 @@ def sparse_cvi_site_update_hip(likelihood: Likelihood, w: torch.Tensor, c: torch
     if nat1 is not None and not (nat1.is_contiguous() and nat2.is_contiguous()):
         raise ValueError("sparse_cvi_site_update_hip: nat1 and nat2 must be contiguous")
     outs = tuple(torch.empty(tuple(w.shape[:-1]), dtype=dtype, device=dev) for _ in range(3)) if want_outputs else (None, None, None)
-    lik = likelihood
-    _lib.call("mf_lik_sparse_cvi_site_update", dtype, bsz, n, segs, two_d, lik._id, lik._c_params(), lik.num_gauss_hermite_points,
-              lik._c_nodes, lik._c_weights, _lib.ptr(offsets.contiguous()), _lib.ptr(w.contiguous()), _lib.ptr(c.contiguous()),
-              _lib.ptr(y.contiguous()), _lib.ptr(pair_mean.contiguous()), _lib.ptr(pair_cov.contiguous()), float(learning_rate),
-              _lib.ptr(nat1), _lib.ptr(nat2), *[_lib.ptr(o) for o in outs], _lib.stream_ptr(dev))
+    _lib.call("mf_lik_sparse_cvi_site_update", dtype, bsz, n, segs, two_d, *likelihood._kernel_args(), _lib.ptr(offsets.contiguous()),
+              _lib.ptr(w.contiguous()), _lib.ptr(c.contiguous()), _lib.ptr(y.contiguous()), _lib.ptr(pair_mean.contiguous()),
+              _lib.ptr(pair_cov.contiguous()), float(learning_rate), _lib.ptr(nat1), _lib.ptr(nat2), *[_lib.ptr(o) for o in outs],
+              _lib.stream_ptr(dev))
     if nat1 is not None:
         # the kernel wrote through raw pointers: tell torch, so that whatever keys a cache on (tensor, version) sees the write
         torch.autograd.graph.increment_version(nat1)
@@ -770,7 +776,89 @@ def sparse_cvi_site_update_hip(likelihood: Likelihood, w: torch.Tensor, c: torch
     return outs
 
 
-class SparseCVIGaussianProcess:
+class _SparseGaussianProcess:
+    """What the two inducing-point models share: the validated kernel, likelihood and inducing points, the checks on a data set,
+    the cache of the per-point projections, the stationary prior beyond the ends of the chain and ``predict_log_density``."""
+
+    def __init__(self, kernel: SDEKernel, likelihood: Likelihood, inducing_points: torch.Tensor, min_inducing: int) -> None:
+        if not isinstance(kernel, SDEKernel):
+            raise TypeError("kernel must be a markovflow_amd.kernels.SDEKernel")
+        if not isinstance(likelihood, Likelihood):
+            raise TypeError("likelihood must be a markovflow_amd.likelihoods.Likelihood")
+        if (not isinstance(inducing_points, torch.Tensor) or inducing_points.dim() < 1
+                or inducing_points.shape[-1] < min_inducing):
+            raise ValueError("inducing_points must be a tensor of shape batch + [num_inducing] with at least "
+                             + {1: "one point", 2: "two points"}[min_inducing])
+        if inducing_points.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"markovflow_amd supports float32 and float64 tensors, got {inducing_points.dtype}")
+        if bool((inducing_points[..., 1:] < inducing_points[..., :-1]).any()):
+            raise ValueError("inducing_points must be sorted")
+        self._kernel = kernel
+        self._likelihood = likelihood
+        self.inducing_inputs = inducing_points
+        self._projection_cache = None
+
+    @property
+    def kernel(self) -> SDEKernel:
+        return self._kernel
+
+    @property
+    def likelihood(self) -> Likelihood:
+        return self._likelihood
+
+    def _check_data(self, input_data: Tuple[torch.Tensor, torch.Tensor], what: str) -> Tuple[torch.Tensor, torch.Tensor]:
+        time_points, observations = input_data
+        if observations.dim() < 2 or observations.shape[-1] != 1:
+            raise ValueError(f"{what}: observations must have shape batch + [num_data, 1], got {tuple(observations.shape)}")
+        if tuple(time_points.shape) != tuple(observations.shape[:-1]):
+            raise ValueError(f"{what}: time_points must have shape observations.shape[:-1]")
+        if tuple(time_points.shape[:-1]) != tuple(self.inducing_inputs.shape[:-1]):
+            raise ValueError(f"{what}: the data must carry the batch shape of the inducing points, "
+                             f"{tuple(self.inducing_inputs.shape[:-1])}, got {tuple(time_points.shape[:-1])}")
+        _lib.same_dtype_device(self.inducing_inputs, f"{type(self).__name__}.{what}", time_points=time_points,
+                               observations=observations)
+        return time_points, observations
+
+    def _compute_projections(self, time_points: torch.Tensor):
+        """What ``_projections`` keeps for a data tensor (computed under ``no_grad``)."""
+        raise NotImplementedError
+
+    def _projections(self, time_points: torch.Tensor):
+        """``_compute_projections`` of the data, kept until the data, the inducing points or a hyper-parameter of the kernel is
+        replaced or written in place (tensor identity, data pointer and version counter, as the filter caches)."""
+        sources = [time_points, self.inducing_inputs] + [x for comp in self._kernel._components() for x in comp._leaves()]
+        key = tuple(_version_key(x) for x in sources)
+        cached = self._projection_cache
+        if (cached is not None and None not in key and cached[0] == key and len(cached[1]) == len(sources)
+                and all(a is b for a, b in zip(cached[1], sources))):          # (the cache holds the tensors: ids are not reused)
+            return cached[2]
+        with torch.no_grad():
+            out = self._compute_projections(time_points)
+        self._projection_cache = (key, sources, out)
+        return out
+
+    def _stationary_prior(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(m0, P0)`` of the kernel on the inducing points' batch, dtype and device: the outer neighbour of the first and the
+        last pair."""
+        z = self.inducing_inputs
+        m0 = self._kernel.initial_mean(tuple(z.shape[:-1])).to(dtype=z.dtype, device=z.device)
+        p0 = self._kernel.initial_covariance(z[..., :1]).to(dtype=z.dtype, device=z.device)
+        return m0, p0
+
+    def _predict_f(self, new_time_points: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        return self.posterior.predict_f(new_time_points)
+
+    def predict_log_density(self, input_data: Tuple[torch.Tensor, torch.Tensor], full_output_cov: bool = False) -> torch.Tensor:
+        """Log density of new data ``(time_points, observations)`` under the posterior, ``batch + [num_new]``
+        (sparse_variational.py:262-270)."""
+        if full_output_cov:
+            raise NotImplementedError("predict_log_density: the likelihoods are univariate (marginal variances only)")
+        new_times, new_obs = input_data
+        f_mean, f_var = self._predict_f(new_times)
+        return self._likelihood.predict_log_density(f_mean, f_var, new_obs)
+
+
+class SparseCVIGaussianProcess(_SparseGaussianProcess):
     """GP prior, general likelihood, Gaussian posterior on the states ``u = s(z)`` at ``M`` inducing points, parameterised by
     ``M + 1`` Gaussian sites in natural form on the pairs ``v_m = [u_{m-1}, u_m]`` of neighbouring inducing states,
     ``q(s) = p(s) prod_m t_m(v_m)``; pairs ``0`` and ``M`` have the stationary prior as their outer neighbour.  A data point with
@@ -783,37 +871,16 @@ class SparseCVIGaussianProcess:
         :param likelihood: a ``markovflow_amd.likelihoods.Likelihood``.
         :param learning_rate: the step ``rho`` of ``update_sites``, in [0, 1].
         """
-        if not isinstance(kernel, SDEKernel):
-            raise TypeError("kernel must be a markovflow_amd.kernels.SDEKernel")
-        if not isinstance(likelihood, Likelihood):
-            raise TypeError("likelihood must be a markovflow_amd.likelihoods.Likelihood")
+        super().__init__(kernel, likelihood, inducing_points, min_inducing=1)
         if not 0.0 <= float(learning_rate) <= 1.0:
             raise ValueError(f"learning_rate must lie in [0, 1], got {learning_rate}")
-        if not isinstance(inducing_points, torch.Tensor) or inducing_points.dim() < 1 or inducing_points.shape[-1] < 1:
-            raise ValueError("inducing_points must be a tensor of shape batch + [num_inducing] with at least one point")
-        if inducing_points.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"markovflow_amd supports float32 and float64 tensors, got {inducing_points.dtype}")
-        if bool((inducing_points[..., 1:] < inducing_points[..., :-1]).any()):
-            raise ValueError("inducing_points must be sorted")
-        self._kernel = kernel
-        self._likelihood = likelihood
         self.learning_rate = float(learning_rate)
-        self.inducing_inputs = inducing_points
         # sparse_variational_cvi.py:131-137
         batch, two_d = tuple(inducing_points.shape[:-1]), 2 * kernel.state_dim
         shape = batch + (inducing_points.shape[-1] + 1, two_d)
         self.nat1 = torch.zeros(shape, dtype=inducing_points.dtype, device=inducing_points.device)
         self.nat2 = torch.zeros(shape + (two_d,), dtype=inducing_points.dtype, device=inducing_points.device)
-        self._projection_cache = None
         self._sorted_data = None           # the data tensor last found sorted, and its (data pointer, version)
-
-    @property
-    def kernel(self) -> SDEKernel:
-        return self._kernel
-
-    @property
-    def likelihood(self) -> Likelihood:
-        return self._likelihood
 
     @property
     def _chain_points(self) -> torch.Tensor:
@@ -858,17 +925,8 @@ class SparseCVIGaussianProcess:
 
     # ---- data --------------------------------------------------------------------------------------------------------------------
     def _check_data(self, input_data: Tuple[torch.Tensor, torch.Tensor], what: str) -> Tuple[torch.Tensor, torch.Tensor]:
-        time_points, observations = input_data
-        if observations.dim() < 2 or observations.shape[-1] != 1:
-            raise ValueError(f"{what}: observations must have shape batch + [num_data, 1], got {tuple(observations.shape)}")
-        if tuple(time_points.shape) != tuple(observations.shape[:-1]):
-            raise ValueError(f"{what}: time_points must have shape observations.shape[:-1]")
-        if tuple(time_points.shape[:-1]) != tuple(self.inducing_inputs.shape[:-1]):
-            raise ValueError(f"{what}: the data must carry the batch shape of the inducing points, "
-                             f"{tuple(self.inducing_inputs.shape[:-1])}, got {tuple(time_points.shape[:-1])}")
-        _lib.same_dtype_device(self.inducing_inputs, f"SparseCVIGaussianProcess.{what}", time_points=time_points,
-                               observations=observations)
-        # (one pass over the data and one read-back: once per data tensor and version, not once per step)
+        time_points, observations = super()._check_data(input_data, what)
+        # the data must be sorted (one pass over the data and one read-back: once per data tensor and version, not once per step)
         key = _version_key(time_points)
         known = self._sorted_data
         if known is None or known[0] is not time_points or key is None or known[1] != key:
@@ -880,28 +938,14 @@ class SparseCVIGaussianProcess:
     def _fused(self, time_points: torch.Tensor) -> bool:
         return time_points.is_cuda and 2 * self._kernel.state_dim <= SPARSE_SITE_MAX_TWO_D
 
-    def _projections(self, time_points: torch.Tensor):
-        """``sparse_site_projections`` of the data, kept until the data, the inducing points or a hyper-parameter of the kernel is
-        replaced or written in place (tensor identity, data pointer and version counter, as the filter caches)."""
-        sources = [time_points, self.inducing_inputs] + [x for comp in self._kernel._components() for x in comp._leaves()]
-        key = tuple(_version_key(x) for x in sources)
-        cached = self._projection_cache
-        if (cached is not None and None not in key and cached[0] == key and len(cached[1]) == len(sources)
-                and all(a is b for a, b in zip(cached[1], sources))):          # (the cache holds the tensors: ids are not reused)
-            return cached[2]
-        with torch.no_grad():
-            out = sparse_site_projections(self._kernel, time_points, self.inducing_inputs)
-        self._projection_cache = (key, sources, out)
-        return out
+    def _compute_projections(self, time_points: torch.Tensor):
+        """``sparse_site_projections`` of the data."""
+        return sparse_site_projections(self._kernel, time_points, self.inducing_inputs)
 
     def _pair_marginals(self, dist_q: StateSpaceModel) -> Tuple[torch.Tensor, torch.Tensor]:
         """``(m_pair [.., M+1, 2d], S_pair [.., M+1, 2d, 2d])`` of ``dist_q``, the stationary prior beyond both ends."""
-        z = self.inducing_inputs
-        batch = tuple(z.shape[:-1])
-        m0 = self._kernel.initial_mean(batch).to(dtype=z.dtype, device=z.device)
-        p0 = self._kernel.initial_covariance(z[..., :1]).to(dtype=z.dtype, device=z.device)
-        pair_mean, pair_cov = conditionals.pairwise_marginals(dist_q, m0, p0)
-        segs = z.shape[-1] + 1                             # (``M = 1``: the pairs of the real state only, see ``_chain_points``)
+        pair_mean, pair_cov = conditionals.pairwise_marginals(dist_q, *self._stationary_prior())
+        segs = self.inducing_inputs.shape[-1] + 1                             # (``M = 1``: the pairs of the real state only, see ``_chain_points``)
         return pair_mean[..., :segs, :], pair_cov[..., :segs, :, :]
 
     def _site_kernel(self, time_points, observations, dist_q, update: bool):
@@ -966,14 +1010,6 @@ class SparseCVIGaussianProcess:
         """``-classic_elbo`` (sparse_variational_cvi.py:223-230)."""
         return -self.classic_elbo(input_data)
 
-    def predict_log_density(self, input_data: Tuple[torch.Tensor, torch.Tensor], full_output_cov: bool = False) -> torch.Tensor:
-        """Log density of new data ``(time_points, observations)`` under the posterior, ``batch + [num_new]``."""
-        if full_output_cov:
-            raise NotImplementedError("predict_log_density: the likelihoods are univariate (marginal variances only)")
-        new_times, new_obs = input_data
-        f_mean, f_var = self.posterior.predict_f(new_times)
-        return self._likelihood.predict_log_density(f_mean, f_var, new_obs)
-
 
 # ---- SVGP: the ELBO's data term ----------------------------------------------------------------------------------------------------
 SPARSE_EXPECT_TILE = 64         # mf_lik_sparse_expectations_*: points per tile of pass 1
@@ -1003,12 +1039,10 @@ def _sparse_expectations_launch(likelihood: Likelihood, w, c, y, offsets, tiles,
     g_cov = torch.empty(batch + (segs, two_d, two_d), dtype=dtype, device=dev) if want_grads else None
     ws_bytes = int(_lib.load().mf_lik_sparse_expectations_workspace_bytes(num_tiles, two_d, w.element_size()))
     ws = _lib.workspace(ws_bytes, dev)
-    lik = likelihood
-    _lib.call("mf_lik_sparse_expectations", dtype, bsz, n, segs, two_d, lik._id, lik._c_params(), lik.num_gauss_hermite_points,
-              lik._c_nodes, lik._c_weights, _lib.ptr(offsets.contiguous()), _lib.ptr(w.contiguous()), _lib.ptr(c.contiguous()),
-              _lib.ptr(y.contiguous()), _lib.ptr(pair_mean.contiguous()), _lib.ptr(pair_cov.contiguous()), num_tiles,
-              _lib.ptr(tile_seg), _lib.ptr(seg_tile), _lib.ptr(ws), ws_bytes, _lib.ptr(ve_sum), _lib.ptr(g_mean), _lib.ptr(g_cov),
-              _lib.stream_ptr(dev))
+    _lib.call("mf_lik_sparse_expectations", dtype, bsz, n, segs, two_d, *likelihood._kernel_args(), _lib.ptr(offsets.contiguous()),
+              _lib.ptr(w.contiguous()), _lib.ptr(c.contiguous()), _lib.ptr(y.contiguous()), _lib.ptr(pair_mean.contiguous()),
+              _lib.ptr(pair_cov.contiguous()), num_tiles, _lib.ptr(tile_seg), _lib.ptr(seg_tile), _lib.ptr(ws), ws_bytes,
+              _lib.ptr(ve_sum), _lib.ptr(g_mean), _lib.ptr(g_cov), _lib.stream_ptr(dev))
     return ve_sum, g_mean, g_cov
 
 
@@ -1071,14 +1105,8 @@ def sparse_expected_log_likelihood_torch(likelihood: Likelihood, w: torch.Tensor
     of the pair marginals by the per-point pair index (``indices [.., N]``), ``likelihood.variational_expectations`` and
     ``index_add_`` over the segments.  It runs on CPU tensors, it is the models' route for ``2d > 18`` and for a kernel
     hyper-parameter under the tape, and it is what ``mf_lik_sparse_expectations_*`` is measured against."""
-    two_d, segs = w.shape[-1], pair_mean.shape[-2]
-    m = torch.gather(pair_mean, -2, indices[..., None].expand(tuple(indices.shape) + (two_d,)))
-    cov = torch.gather(pair_cov, -3, indices[..., None, None].expand(tuple(indices.shape) + (two_d, two_d)))
-    fmu = torch.sum(w * m, dim=-1)
-    fvar = c + torch.sum(w * torch.sum(cov * w[..., None, :], dim=-1), dim=-1)
+    fmu, fvar, flat = _sparse_point_marginals(w, c, indices, pair_mean, pair_cov, pair_mean.shape[-2])
     ve = likelihood.variational_expectations(fmu[..., None], fvar[..., None], y[..., None])
-    series = torch.arange(math.prod(indices.shape[:-1]), device=indices.device).reshape(tuple(indices.shape[:-1]) + (1,))
-    flat = (indices + series * segs).reshape(-1)
     out = torch.zeros(math.prod(pair_mean.shape[:-1]), dtype=ve.dtype, device=ve.device).index_add(0, flat, ve.reshape(-1))
     return out.reshape(pair_mean.shape[:-1])
 
@@ -1091,7 +1119,7 @@ def _sorted_series(time_points: torch.Tensor) -> Tuple[Optional[torch.Tensor], t
     return order, torch.gather(time_points, -1, order)
 
 
-class SparseVariationalGaussianProcess:
+class SparseVariationalGaussianProcess(_SparseGaussianProcess):
     """GP prior, general likelihood, a free-form Gaussian posterior ``q(s(z))`` on the states at ``M`` inducing points held as a
     trainable ``StateSpaceModel`` (markovflow/models/sparse_variational.py:31-270; zero mean function, plain float likelihood
     parameters, a batch of series as leading dimensions).  The ELBO is ``scale sum_i E_q log p(y_i | f_i) - KL[q(s(z)) || p(s(z))]``;
@@ -1104,21 +1132,9 @@ class SparseVariationalGaussianProcess:
         :param num_data: the total number of observations per series when ``elbo`` is fed minibatches.
         :param initial_distribution: the initial ``q`` on the inducing points; the prior by default.
         """
-        if not isinstance(kernel, SDEKernel):
-            raise TypeError("kernel must be a markovflow_amd.kernels.SDEKernel")
-        if not isinstance(likelihood, Likelihood):
-            raise TypeError("likelihood must be a markovflow_amd.likelihoods.Likelihood")
-        if not isinstance(inducing_points, torch.Tensor) or inducing_points.dim() < 1 or inducing_points.shape[-1] < 2:
-            raise ValueError("inducing_points must be a tensor of shape batch + [num_inducing] with at least two points")
-        if inducing_points.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"markovflow_amd supports float32 and float64 tensors, got {inducing_points.dtype}")
-        if bool((inducing_points[..., 1:] < inducing_points[..., :-1]).any()):
-            raise ValueError("inducing_points must be sorted")
+        super().__init__(kernel, likelihood, inducing_points, min_inducing=2)
         if num_data is not None and not num_data > 0:
             raise ValueError(f"num_data must be positive, got {num_data}")
-        self._kernel = kernel
-        self._likelihood = likelihood
-        self.inducing_inputs = inducing_points
         self.num_data = num_data
         if initial_distribution is None:
             initial_distribution = kernel.state_space_model(inducing_points)
@@ -1131,20 +1147,11 @@ class SparseVariationalGaussianProcess:
                              f"{tuple(inducing_points.shape[:-1])}, {inducing_points.shape[-1]} states of dimension {kernel.state_dim}")
         self._dist_q = initial_distribution.create_trainable_copy()
         self._posterior = ConditionalProcess(posterior_dist=self._dist_q, kernel=kernel, conditioning_time_points=inducing_points)
-        self._projection_cache = None
 
     @property
     def time_points(self) -> torch.Tensor:
         """The inducing points (sparse_variational.py:194-202)."""
         return self.inducing_inputs
-
-    @property
-    def kernel(self) -> SDEKernel:
-        return self._kernel
-
-    @property
-    def likelihood(self) -> Likelihood:
-        return self._likelihood
 
     @property
     def dist_p(self) -> StateSpaceModel:
@@ -1166,48 +1173,21 @@ class SparseVariationalGaussianProcess:
         return self._dist_q.trainable_variables
 
     # ---- data --------------------------------------------------------------------------------------------------------------------
-    def _check_data(self, input_data: Tuple[torch.Tensor, torch.Tensor], what: str) -> Tuple[torch.Tensor, torch.Tensor]:
-        time_points, observations = input_data
-        if observations.dim() < 2 or observations.shape[-1] != 1:
-            raise ValueError(f"{what}: observations must have shape batch + [num_data, 1], got {tuple(observations.shape)}")
-        if tuple(time_points.shape) != tuple(observations.shape[:-1]):
-            raise ValueError(f"{what}: time_points must have shape observations.shape[:-1]")
-        if tuple(time_points.shape[:-1]) != tuple(self.inducing_inputs.shape[:-1]):
-            raise ValueError(f"{what}: the data must carry the batch shape of the inducing points, "
-                             f"{tuple(self.inducing_inputs.shape[:-1])}, got {tuple(time_points.shape[:-1])}")
-        _lib.same_dtype_device(self.inducing_inputs, f"SparseVariationalGaussianProcess.{what}", time_points=time_points,
-                               observations=observations)
-        return time_points, observations
-
     def _fused(self, time_points: torch.Tensor) -> bool:
         return (time_points.is_cuda and 2 * self._kernel.state_dim <= SPARSE_SITE_MAX_TWO_D and not self._kernel._needs_grad())
 
-    def _projections(self, time_points: torch.Tensor):
+    def _compute_projections(self, time_points: torch.Tensor):
         """``(order | None, w, c, indices, offsets, tiles)`` of the data: the permutation that sorts each series (None for sorted
-        data), ``sparse_site_projections`` of the sorted points and the tile table, kept until the data, the inducing points or a
-        hyper-parameter of the kernel is replaced or written in place (keyed as ``SparseCVIGaussianProcess._projections``)."""
-        sources = [time_points, self.inducing_inputs] + [x for comp in self._kernel._components() for x in comp._leaves()]
-        key = tuple(_version_key(x) for x in sources)
-        cached = self._projection_cache
-        if (cached is not None and None not in key and cached[0] == key and len(cached[1]) == len(sources)
-                and all(a is b for a, b in zip(cached[1], sources))):          # (the cache holds the tensors: ids are not reused)
-            return cached[2]
-        with torch.no_grad():
-            order, time_points = _sorted_series(time_points)
-            w, c, indices, offsets = sparse_site_projections(self._kernel, time_points, self.inducing_inputs)
-            tiles = sparse_expectation_tiles(offsets) if time_points.is_cuda else None
-        out = (order, w, c, indices, offsets, tiles)
-        self._projection_cache = (key, sources, out)
-        return out
+        data), ``sparse_site_projections`` of the sorted points and the tile table."""
+        order, time_points = _sorted_series(time_points)
+        w, c, indices, offsets = sparse_site_projections(self._kernel, time_points, self.inducing_inputs)
+        tiles = sparse_expectation_tiles(offsets) if time_points.is_cuda else None
+        return order, w, c, indices, offsets, tiles
 
     def _pair_marginals(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """``(m_pair [.., M+1, 2d], S_pair [.., M+1, 2d, 2d])`` of ``dist_q`` - under the tape when its leaves require a gradient -
         with the stationary prior beyond both ends."""
-        z = self.inducing_inputs
-        batch = tuple(z.shape[:-1])
-        m0 = self._kernel.initial_mean(batch).to(dtype=z.dtype, device=z.device)
-        p0 = self._kernel.initial_covariance(z[..., :1]).to(dtype=z.dtype, device=z.device)
-        return conditionals.pairwise_marginals(self._dist_q, m0, p0)
+        return conditionals.pairwise_marginals(self._dist_q, *self._stationary_prior())
 
     def _expected_log_likelihood(self, time_points: torch.Tensor, observations: torch.Tensor) -> torch.Tensor:
         """``sum_i E_q log p(y_i | f_i)`` per pair, ``batch + [M + 1]``."""
@@ -1255,11 +1235,4 @@ class SparseVariationalGaussianProcess:
         with torch.no_grad():
             return self._posterior.predict_f(new_time_points, full_output_cov)
 
-    def predict_log_density(self, input_data: Tuple[torch.Tensor, torch.Tensor], full_output_cov: bool = False) -> torch.Tensor:
-        """Log density of new data ``(time_points, observations)`` under the posterior, ``batch + [num_new]``
-        (sparse_variational.py:262-270)."""
-        if full_output_cov:
-            raise NotImplementedError("predict_log_density: the likelihoods are univariate (marginal variances only)")
-        new_times, new_obs = input_data
-        f_mean, f_var = self.predict_f(new_times)
-        return self._likelihood.predict_log_density(f_mean, f_var, new_obs)
+    _predict_f = predict_f          # (``predict_log_density`` predicts outside the tape here, as ``predict_f`` does)

@@ -156,7 +156,7 @@ def check_against_helper(tag, ref, dtype, nat1, nat2, outs, series=None):
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f64", "f32"])
-@pytest.mark.parametrize("two_d", [2, 4, 6, 12, 18])
+@pytest.mark.parametrize("two_d", [2, 4, 6, 8, 10, 12, 14, 16, 18])
 @pytest.mark.parametrize("name", NAMES)
 def test_batch_of_three_against_the_helper_and_each_series_alone_bit_for_bit(name, two_d, dtype):
     ref = reference(name, 20, two_d, dtype == torch.float32)
