@@ -825,6 +825,49 @@ int mf_lik_sparse_expectations_f32(int64_t B, int64_t N, int64_t S, int two_d, i
                                    int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile, void* workspace,
                                    size_t workspace_bytes, float* ve_sum, float* g_mean, float* g_cov, void* stream);
 
+/*
+ * The segmented site update of the sparse power-EP model (markovflow/models/sparse_pep.py:316-487; csrc/mf_lik.hip): B, N, S,
+ * two_d, the likelihood, the rule, seg_offsets, w, c, y, the tile table and the workspace as for mf_lik_sparse_expectations_*;
+ * alpha in (0, 1] is the power, lr in [0, 1] the damping.  The workspace row has the width of that entry point's, so its size is
+ * mf_lik_sparse_expectations_workspace_bytes(num_tiles, two_d, sizeof(T)): there is no second size function.
+ *   cav_mean [B, S, 2d], cav_cov [B, S, 2d, 2d]   the CAVITY of q on every pair (in place of pair_mean / pair_cov); NaN where it
+ *                                                 does not exist
+ *   seg_const [B, S]        added to the segment's summed log expected density before the blend; NULL: 0
+ *   nat1 [B, S, 2d], nat2 [B, S, 2d, 2d], log_norm [B, S]   the sites, updated IN PLACE; ALL THREE NULL: evaluation only
+ *   led_sum [B, S]          sum_k I_k of every segment (NaN for an undefined one); may be NULL
+ *   fmu, fvar, led [B, N]   per point, any of them may be NULL
+ * Pass 1, one wavefront per tile, per point k of segment s:  fmu = w_k . m_c,  fvar = c_k + w_k^T S_c w_k,  (I, g1, g2) as
+ * mf_lik_log_expected_density at (fmu, fvar),  den = 1 + fvar g2 (Gaussian: (var / alpha) / (var / alpha + fvar), the same number
+ * without the cancellation),  L2 = g2 / (2 den),  L1 = (g1 - fmu g2) / den.  A point is UNDEFINED when fvar or den is not > 0 or
+ * one of L2, L1, I is not finite; it contributes NaN.  fmu and fvar are NaN where fvar is not > 0; led is I wherever fvar > 0.
+ * The tile's sums  sum_k L2 w_k w_k^T (lower triangle),  sum_k L1 w_k,  sum_k I  are one row of the workspace.
+ * Pass 2, one block per (series, segment), adds the rows in ascending tile order and, if every entry - the scalar one with
+ * seg_const added - is finite, stores  pep = (1 - alpha) old + sum (+ seg_const),  new = (1 - lr) old + lr pep  into nat2 (both
+ * triangles), nat1 and log_norm.  Otherwise the three site tensors of THIS segment are left as they are, bit for bit; no other
+ * segment is touched.  An empty segment has sum 0: it decays by 1 - lr alpha.  led_sum gets the raw sum, without seg_const.
+ * No floating-point atomics, the same bits on every launch, for a series alone or inside a batch, and in evaluation-only mode
+ * beside the update; the tile table is clamped on the device, not validated.  No allocation, no synchronisation.
+ * Returns 0, -(position of the offending argument in THIS signature: 1 B, 2 N, 3 S, 5 lik, 6 params, 7 nq, 8 nodes, 9 weights,
+ * 10 alpha, 11 lr, 12 ... 17 a NULL input, 19 num_tiles negative, above 2^31 - 1 or non-zero for N = 0, 20 / 21 a NULL table, 22 a
+ * NULL workspace, 23 a workspace that is too small, 24 / 25 / 26 the first of nat1 / nat2 / log_norm that is NULL beside a given
+ * one), -100 for a two_d that is odd, < 2 or > 18, or -1000 (launch failed).  Nothing is launched on an error, for B = 0, or when
+ * every output is NULL.
+ */
+int mf_lik_sparse_pep_site_update_f64(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq,
+                                      const double* nodes, const double* weights, double alpha, double lr,
+                                      const int64_t* seg_offsets, const double* w, const double* c, const double* y,
+                                      const double* cav_mean, const double* cav_cov, const double* seg_const, int64_t num_tiles,
+                                      const int64_t* tile_seg, const int64_t* seg_tile, void* workspace, size_t workspace_bytes,
+                                      double* nat1, double* nat2, double* log_norm, double* led_sum, double* fmu, double* fvar,
+                                      double* led, void* stream);
+int mf_lik_sparse_pep_site_update_f32(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq,
+                                      const double* nodes, const double* weights, float alpha, float lr,
+                                      const int64_t* seg_offsets, const float* w, const float* c, const float* y,
+                                      const float* cav_mean, const float* cav_cov, const float* seg_const, int64_t num_tiles,
+                                      const int64_t* tile_seg, const int64_t* seg_tile, void* workspace, size_t workspace_bytes,
+                                      float* nat1, float* nat2, float* log_norm, float* led_sum, float* fmu, float* fvar,
+                                      float* led, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

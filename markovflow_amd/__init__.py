@@ -22,7 +22,7 @@ from .kernels import (Constant, HarmonicOscillator, IndependentMultiOutput, Mate
                       StationaryKernel, Sum)
 from .likelihoods import Bernoulli, Gaussian, Likelihood, Poisson, StudentT
 from .models import (CVIGaussianProcess, GaussianProcessRegression, PowerExpectationPropagation, SparseCVIGaussianProcess,
-                     SparseVariationalGaussianProcess)
+                     SparsePowerExpectationPropagation, SparseVariationalGaussianProcess)
 from .ssm_natgrad import SSMNaturalGradient
 from .posterior import AnalyticPosteriorProcess, ConditionalProcess
 from ._lib import MarkovflowAmdError, check_errors, errors_as_nan, set_synchronous_checks
@@ -36,4 +36,5 @@ __all__ = [
     "MarkovflowAmdError", "check_errors", "errors_as_nan", "set_synchronous_checks",
     "likelihoods", "Likelihood", "Gaussian", "Bernoulli", "Poisson", "StudentT", "CVIGaussianProcess", "PowerExpectationPropagation",
     "SparseCVIGaussianProcess", "SparseVariationalGaussianProcess", "SSMNaturalGradient", "ssm_natgrad",
+    "SparsePowerExpectationPropagation",
 ]

@@ -78,6 +78,8 @@ _SIGS = {
                                       "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_sparse_expectations": (_int, [_i64, _i64, _i64, _int, _int, _hd, _int, _hd, _hd, _vp, "Tp", "Tp", "Tp", "Tp", "Tp", _i64,
                                    _vp, _vp, _vp, _sz, "Tp", "Tp", "Tp", _vp]),
+    "mf_lik_sparse_pep_site_update": (_int, [_i64, _i64, _i64, _int, _int, _hd, _int, _hd, _hd, "T", "T", _vp, "Tp", "Tp", "Tp", "Tp",
+                                      "Tp", "Tp", _i64, _vp, _vp, _vp, _sz, "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
 }
 _PLAIN = {
     "mf_version": (_int, []),

@@ -561,6 +561,142 @@ __global__ void __launch_bounds__(256) lik_pep_kernel(long N, Rule<T> q, Par<T> 
     log_norm[id] = newn;
 }
 
+// ---- sparse power EP: the segmented site update (markovflow/models/sparse_pep.py:316-380, 473-487) ------------------------------
+// The two-pass, tile-parallel layout of the SVGP kernels above, with the same front end at ROWS = 3 and the same tile table.  The
+// caller supplies the CAVITY of every pair, N(m_c, S_c), where those kernels get the marginal.
+//   pass 1, one wavefront per tile: per point fmu = w . m_c, fvar = c + w^T S_c w, then I, g1, g2 of the log expected alpha-power
+//            density there and the gradient correction den = 1 + fvar g2, L2 = g2 / (2 den), L1 = (g1 - fmu g2) / den (Gaussian: den
+//            in closed form, as in lik_pep_kernel).  L2, L1 and I are the three rows of LDS values; a point where fvar or den is not
+//            > 0 or one of the three is not finite leaves NaN in all of them.  The tile's sums - sum L2 w w^T (lower triangle),
+//            sum L1 w, sum I - go to the workspace as one row, as wide as the SVGP kernels' row.
+//   pass 2, one block per (series, segment), a lane per entry (190 entries at 2d = 18): the segment's rows are added in ascending
+//            tile order; then, if EVERY entry of the segment is finite (the scalar one with seg_const added),
+//            pep = (1 - alpha) old + sum, new = (1 - lr) old + lr pep onto nat2 (both triangles), nat1 and log_norm; otherwise
+//            nothing is stored to the three site tensors of this segment.  The decision is the block's and precedes every store.
+// No floating-point atomics; every sum's order is fixed by the point order alone.  The tile table is clamped, not trusted.
+template <typename T, int LIK, int D2>
+__global__ void __launch_bounds__(64) sparse_pep_tile_kernel(long N, int S, long BS, Rule<T> q, Par<T> p, T alpha,
+                                                             const long long* __restrict__ seg,
+                                                             const long long* __restrict__ tile_seg,
+                                                             const long long* __restrict__ seg_tile, const T* __restrict__ w,
+                                                             const T* __restrict__ cvar, const T* __restrict__ yobs,
+                                                             const T* __restrict__ cav_mean, const T* __restrict__ cav_cov,
+                                                             int sites, T* __restrict__ ws, T* __restrict__ out_fmu,
+                                                             T* __restrict__ out_fvar, T* __restrict__ out_led) {
+    constexpr int W = D2 + 1, E = seg_entries(D2, 3), R = (E + 63) / 64;
+    __shared__ T lw[64 * W];
+    __shared__ T ls[D2 * D2];
+    __shared__ T lm[D2];
+    __shared__ T lg[3 * 64];           // L2 of the tile's points, then L1, then I
+    const int lane = threadIdx.x;
+    const long t = blockIdx.x;
+    long bs = (long)tile_seg[t];
+    bs = bs < 0 ? 0 : (bs >= BS ? BS - 1 : bs);
+    const long b = bs / S;
+    const long s = bs - b * S;
+    long k_lo = (long)seg[b * (S + 1) + s], k_hi = (long)seg[b * (S + 1) + s + 1];
+    clamp_range(k_lo, k_hi, N);
+    const long j = t - (long)seg_tile[bs];                          // this tile's number within its segment
+    const long k0 = (j >= 0 && j <= (k_hi - k_lo) / 64) ? k_lo + 64 * j : k_hi;
+    const int npts = k_hi - k0 < 64 ? int(k_hi - k0) : 64;          // (0 only for a table that disagrees with the offsets)
+    int ei[R], ej[R], es[R];           // this lane's entries
+    T part[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        part[r] = T(0);
+        entry_decode<D2, 3>(lane + 64 * r, ei[r], ej[r], es[r]);
+    }
+    if (npts > 0) {
+        stage_pair<T, D2>(lane, bs, cav_mean, cav_cov, ls, lm, lw);
+        stage_tile<T, D2>(lane, npts, w + (b * N + k0) * D2, lw);
+        __syncthreads();
+        if (lane < npts) {
+            const long id = b * N + k0 + lane;
+            T mu, s2;
+            project_point<T, D2>(lane, lw, ls, lm, cvar[id], mu, s2);
+            const T y = yobs[id];
+            T led, l1, l2;
+            if (s2 > T(0)) {
+                T g1, g2;
+                log_expected_density<T, LIK>(q, p, alpha, mu, s2, y, led, g1, g2);
+                const T den = LIK == 0 ? (p.p0 / alpha) / (p.p0 / alpha + s2) : T(1) + s2 * g2;
+                l2 = T(0.5) * g2 / den;
+                l1 = (g1 - mu * g2) / den;
+                if (out_led) out_led[id] = led;
+                if (!(den > T(0)) || !__builtin_isfinite(l2) || !__builtin_isfinite(l1) || !__builtin_isfinite(led))
+                    led = l1 = l2 = nan_of<T>();
+            } else {                               // outside the domain (a cavity that does not exist arrives as NaN)
+                led = l1 = l2 = mu = s2 = nan_of<T>();
+                if (out_led) out_led[id] = led;
+            }
+            if (out_fmu) out_fmu[id] = mu;
+            if (out_fvar) out_fvar[id] = s2;
+            lg[lane] = l2;
+            lg[64 + lane] = l1;
+            lg[128 + lane] = led;
+        }
+        __syncthreads();
+        if (sites) {
+            for (int k = 0; k < npts; ++k) accumulate_point<T, D2, R>(k, lg, lw, ei, ej, es, part);
+        } else if (lane == (E - 1) % 64) {         // evaluation only: the one entry, with the bits it has beside the update
+            for (int k = 0; k < npts; ++k) part[R - 1] += lg[128 + k];
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int e = lane + 64 * r;
+        if (e < E) ws[t * E + e] = part[r];
+    }
+}
+
+template <typename T, int D2>
+__global__ void __launch_bounds__(256) sparse_pep_reduce_kernel(long num_tiles, const long long* __restrict__ seg_tile,
+                                                                const T* __restrict__ ws, const T* __restrict__ seg_const, T alpha,
+                                                                T lr, T* __restrict__ nat1, T* __restrict__ nat2,
+                                                                T* __restrict__ log_norm, T* __restrict__ led_sum) {
+    constexpr int TRI = D2 * (D2 + 1) / 2, E = seg_entries(D2, 3);
+    static_assert(E <= 256, "one entry per lane");
+    __shared__ int undefined;
+    const long bs = blockIdx.x;
+    const int e = threadIdx.x;
+    long t_lo = 0, t_hi = 0;
+    if (seg_tile) {                                // (NULL: no points at all)
+        t_lo = (long)seg_tile[bs];
+        t_hi = (long)seg_tile[bs + 1];
+        clamp_range(t_lo, t_hi, num_tiles);
+    }
+    if (e == 0) undefined = 0;
+    __syncthreads();
+    T acc = T(0);
+    if (e < E && (nat1 || e == E - 1)) {           // (evaluation only: pass 1 has summed the scalar entry alone)
+        for (long t = t_lo; t < t_hi; ++t) acc += ws[t * E + e];
+        if (e == E - 1) {
+            if (led_sum) led_sum[bs] = acc;        // the raw sum, NaN included
+            if (seg_const) acc += seg_const[bs];
+        }
+        if (!__builtin_isfinite(acc)) undefined = 1;
+    }
+    __syncthreads();
+    if (!nat1 || undefined || e >= E) return;      // an undefined segment keeps its sites, bit for bit
+    const T keep = T(1) - lr, decay = T(1) - alpha;
+    if (e < TRI) {
+        int i, c;
+        tri_decode(e, i, c);
+        T* blk = nat2 + bs * (D2 * D2);
+        const int a = i * D2 + c, m = c * D2 + i;
+        const T lo = blk[a], up = blk[m];
+        blk[a] = keep * lo + lr * (decay * lo + acc);
+        if (a != m) blk[m] = keep * up + lr * (decay * up + acc);
+    } else if (e < E - 1) {
+        T* v = nat1 + bs * D2 + (e - TRI);
+        const T old = *v;
+        *v = keep * old + lr * (decay * old + acc);
+    } else {
+        const T old = log_norm[bs];
+        log_norm[bs] = keep * old + lr * (decay * old + acc);
+    }
+}
+
 // argument checks shared by every entry point: 0, or the (negative) position of the offending argument
 template <typename T>
 int prepare(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights, bool log_weights,
@@ -723,16 +859,16 @@ int run_pep(int64_t N, int lik, const double* params, int nq, const double* node
     });
 }
 
-// the leading argument checks of the two segmented entry points: the (negative) position of the offending argument in THEIR
+// the leading argument checks of the segmented entry points: the (negative) position of the offending argument in THEIR
 // signature, -100 for a two_d outside 2, 4, ..., 18
 template <typename T>
 int prepare_segmented(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq, const double* nodes,
-                      const double* weights, Rule<T>& q, Par<T>& p) {
+                      const double* weights, Rule<T>& q, Par<T>& p, bool log_weights = false) {
     if (B < 0) return -1;
     if (N < 0) return -2;
     if (S < 1 || (B > 0 && S > int64_t(0x7fffffff) / B)) return -3;
     if (two_d < 2 || two_d > 18 || (two_d & 1)) return -100;
-    const int bad = prepare<T>(0, lik, params, nq, nodes, weights, false, q, p);      // -2 ... -6 there are arguments 5 ... 9 here
+    const int bad = prepare<T>(0, lik, params, nq, nodes, weights, log_weights, q, p);      // -2 ... -6 there: arguments 5 ... 9 here
     return bad ? bad - 3 : 0;
 }
 
@@ -790,6 +926,43 @@ int run_expect(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double
         }
         return launch(sparse_expect_reduce_kernel<T, D2>, B * S, 256, stream, tiles, tiles > 0 ? ll(seg_tile) : nullptr, ws, ve_sum,
                       g_mean, g_cov);
+    });
+}
+
+// the sparse power-EP site update: the workspace row is the SVGP kernels' (expect_row), so is the workspace-size function
+template <typename T>
+int run_sparse_pep(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq, const double* nodes,
+                   const double* weights, T alpha, T lr, const int64_t* seg, const T* w, const T* c, const T* y, const T* cm,
+                   const T* cc, const T* seg_const, int64_t tiles, const int64_t* tile_seg, const int64_t* seg_tile, void* ws,
+                   size_t ws_bytes, T* nat1, T* nat2, T* log_norm, T* led_sum, T* fmu, T* fvar, T* led, void* stream) {
+    Rule<T> q;
+    Par<T> p;
+    int bad = prepare_segmented<T>(B, N, S, two_d, lik, params, nq, nodes, weights, q, p, true);
+    if (bad) return bad;
+    if (!(alpha > T(0)) || !(alpha <= T(1))) return -10;
+    if (!(lr >= T(0)) || !(lr <= T(1))) return -11;
+    if (tiles < 0 || tiles > int64_t(0x7fffffff) || (N == 0 && tiles != 0)) return -19;
+    if (nat1 || nat2 || log_norm) {                // all three, or none (evaluation only)
+        if ((bad = first_null(24, {nat1, nat2, log_norm}))) return bad;
+    }
+    if (B == 0 || (!nat1 && !led_sum && !fmu && !fvar && !led)) return 0;      // nothing asked for
+    if (tiles > 0) {
+        if ((bad = first_null(12, {seg, w, c, y, cm, cc}))) return bad;
+        if ((bad = first_null(20, {tile_seg, seg_tile, ws}))) return bad;
+        if (ws_bytes < size_t(tiles) * expect_row(two_d) * sizeof(T)) return -23;
+    }
+    return with_two_d(two_d, [&](auto D) {
+        constexpr int D2 = decltype(D)::value;
+        if (tiles > 0) {
+            const int rc = with_lik(lik, [&](auto L) {
+                return launch(sparse_pep_tile_kernel<T, decltype(L)::value, D2>, tiles, 64, stream, N, S, B * S, q, p, alpha, ll(seg),
+                              ll(tile_seg), ll(seg_tile), w, c, y, cm, cc, nat1 ? 1 : 0, ws, fmu, fvar, led);
+            });
+            if (rc) return rc;
+        }
+        if (!nat1 && !led_sum) return 0;           // per-point outputs only
+        return launch(sparse_pep_reduce_kernel<T, D2>, B * S, 256, stream, tiles, tiles > 0 ? ll(seg_tile) : nullptr, ws, seg_const,
+                      alpha, lr, nat1, nat2, log_norm, led_sum);
     });
 }
 
@@ -882,6 +1055,29 @@ int mf_lik_sparse_cvi_site_update_f32(int64_t B, int64_t N, int64_t S, int two_d
                                       float* nat1, float* nat2, float* fmu, float* fvar, float* ve, void* stream) {
     return run_sparse<float>(B, N, S, two_d, lik, params, nq, nodes, weights, seg_offsets, w, c, y, pair_mean, pair_cov, lr, nat1,
                              nat2, fmu, fvar, ve, stream);
+}
+
+int mf_lik_sparse_pep_site_update_f64(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq,
+                                      const double* nodes, const double* weights, double alpha, double lr,
+                                      const int64_t* seg_offsets, const double* w, const double* c, const double* y,
+                                      const double* cav_mean, const double* cav_cov, const double* seg_const, int64_t num_tiles,
+                                      const int64_t* tile_seg, const int64_t* seg_tile, void* workspace, size_t workspace_bytes,
+                                      double* nat1, double* nat2, double* log_norm, double* led_sum, double* fmu, double* fvar,
+                                      double* led, void* stream) {
+    return run_sparse_pep<double>(B, N, S, two_d, lik, params, nq, nodes, weights, alpha, lr, seg_offsets, w, c, y, cav_mean, cav_cov,
+                                  seg_const, num_tiles, tile_seg, seg_tile, workspace, workspace_bytes, nat1, nat2, log_norm, led_sum,
+                                  fmu, fvar, led, stream);
+}
+int mf_lik_sparse_pep_site_update_f32(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq,
+                                      const double* nodes, const double* weights, float alpha, float lr,
+                                      const int64_t* seg_offsets, const float* w, const float* c, const float* y,
+                                      const float* cav_mean, const float* cav_cov, const float* seg_const, int64_t num_tiles,
+                                      const int64_t* tile_seg, const int64_t* seg_tile, void* workspace, size_t workspace_bytes,
+                                      float* nat1, float* nat2, float* log_norm, float* led_sum, float* fmu, float* fvar,
+                                      float* led, void* stream) {
+    return run_sparse_pep<float>(B, N, S, two_d, lik, params, nq, nodes, weights, alpha, lr, seg_offsets, w, c, y, cav_mean, cav_cov,
+                                 seg_const, num_tiles, tile_seg, seg_tile, workspace, workspace_bytes, nat1, nat2, log_norm, led_sum,
+                                 fmu, fvar, led, stream);
 }
 
 }  // extern "C"

@@ -34,7 +34,7 @@ import torch
 from . import _lib, conditionals
 from .kalman_filter import KalmanFilter, KalmanFilterWithSites, UnivariateGaussianSitesNat
 from .kernels import IndependentMultiOutput, SDEKernel, _MaternBase, _version_key
-from .likelihoods import Likelihood
+from .likelihoods import Gaussian, Likelihood, torch_log_expected_density
 from .posterior import AnalyticPosteriorProcess, ConditionalProcess
 from .ssm_gaussian_transformations import naturals_to_ssm_params
 from .state_space_model import StateSpaceModel
@@ -777,7 +777,7 @@ def sparse_cvi_site_update_hip(likelihood: Likelihood, w: torch.Tensor, c: torch
 
 
 class _SparseGaussianProcess:
-    """What the two inducing-point models share: the validated kernel, likelihood and inducing points, the checks on a data set,
+    """What the inducing-point models share: the validated kernel, likelihood and inducing points, the checks on a data set,
     the cache of the per-point projections, the stationary prior beyond the ends of the chain and ``predict_log_density``."""
 
     def __init__(self, kernel: SDEKernel, likelihood: Likelihood, inducing_points: torch.Tensor, min_inducing: int) -> None:
@@ -858,19 +858,13 @@ class _SparseGaussianProcess:
         return self._likelihood.predict_log_density(f_mean, f_var, new_obs)
 
 
-class SparseCVIGaussianProcess(_SparseGaussianProcess):
-    """GP prior, general likelihood, Gaussian posterior on the states ``u = s(z)`` at ``M`` inducing points, parameterised by
-    ``M + 1`` Gaussian sites in natural form on the pairs ``v_m = [u_{m-1}, u_m]`` of neighbouring inducing states,
-    ``q(s) = p(s) prod_m t_m(v_m)``; pairs ``0`` and ``M`` have the stationary prior as their outer neighbour.  A data point with
-    ``z_{m-1} < x <= z_m`` contributes to site ``m`` through the conditional ``p(f(x) | v_m)`` (sparse_variational_cvi.py:38-313;
-    zero mean function, plain float likelihood parameters, a batch of series as leading dimensions)."""
+class _SparseSitesGaussianProcess(_SparseGaussianProcess):
+    """What the two site-based inducing-point models share: ``M + 1`` Gaussian sites in natural form on the pairs
+    ``v_m = [u_{m-1}, u_m]`` of neighbouring inducing states, ``q(s) = p(s) prod_m t_m(v_m)`` (pairs ``0`` and ``M`` have the stationary
+    prior as their outer neighbour) - the sites, the chains ``dist_p`` / ``dist_q`` on the inducing points, the posterior process, the
+    pair marginals, the sorted-data rule and the per-point projections."""
 
-    def __init__(self, kernel: SDEKernel, inducing_points: torch.Tensor, likelihood: Likelihood, learning_rate: float = 0.1) -> None:
-        """
-        :param inducing_points: ``batch + [num_inducing]``, sorted.
-        :param likelihood: a ``markovflow_amd.likelihoods.Likelihood``.
-        :param learning_rate: the step ``rho`` of ``update_sites``, in [0, 1].
-        """
+    def __init__(self, kernel: SDEKernel, inducing_points: torch.Tensor, likelihood: Likelihood, learning_rate: float) -> None:
         super().__init__(kernel, likelihood, inducing_points, min_inducing=1)
         if not 0.0 <= float(learning_rate) <= 1.0:
             raise ValueError(f"learning_rate must lie in [0, 1], got {learning_rate}")
@@ -948,6 +942,22 @@ class SparseCVIGaussianProcess(_SparseGaussianProcess):
         segs = self.inducing_inputs.shape[-1] + 1                             # (``M = 1``: the pairs of the real state only, see ``_chain_points``)
         return pair_mean[..., :segs, :], pair_cov[..., :segs, :, :]
 
+
+class SparseCVIGaussianProcess(_SparseSitesGaussianProcess):
+    """GP prior, general likelihood, Gaussian posterior on the states ``u = s(z)`` at ``M`` inducing points, parameterised by
+    ``M + 1`` Gaussian sites in natural form on the pairs ``v_m = [u_{m-1}, u_m]`` of neighbouring inducing states,
+    ``q(s) = p(s) prod_m t_m(v_m)``; pairs ``0`` and ``M`` have the stationary prior as their outer neighbour.  A data point with
+    ``z_{m-1} < x <= z_m`` contributes to site ``m`` through the conditional ``p(f(x) | v_m)`` (sparse_variational_cvi.py:38-313;
+    zero mean function, plain float likelihood parameters, a batch of series as leading dimensions)."""
+
+    def __init__(self, kernel: SDEKernel, inducing_points: torch.Tensor, likelihood: Likelihood, learning_rate: float = 0.1) -> None:
+        """
+        :param inducing_points: ``batch + [num_inducing]``, sorted.
+        :param likelihood: a ``markovflow_amd.likelihoods.Likelihood``.
+        :param learning_rate: the step ``rho`` of ``update_sites``, in [0, 1].
+        """
+        super().__init__(kernel, inducing_points, likelihood, learning_rate)
+
     def _site_kernel(self, time_points, observations, dist_q, update: bool):
         """ONE launch of ``mf_lik_sparse_cvi_site_update_*``: the in-place site update, or (``update`` False) its projection-only
         mode, which returns ``(fmu, fvar, ve)``, ``batch + [N]`` each."""
@@ -1008,6 +1018,268 @@ class SparseCVIGaussianProcess(_SparseGaussianProcess):
 
     def loss(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
         """``-classic_elbo`` (sparse_variational_cvi.py:223-230)."""
+        return -self.classic_elbo(input_data)
+
+
+# ---- sparse power EP ----------------------------------------------------------------------------------------------------------------
+def sparse_pep_site_update_torch(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor, indices: torch.Tensor,
+                                 cav_mean: torch.Tensor, cav_cov: torch.Tensor, alpha: float, learning_rate: float,
+                                 nat1: Optional[torch.Tensor], nat2: Optional[torch.Tensor], log_norm: Optional[torch.Tensor],
+                                 seg_const: Optional[torch.Tensor] = None
+                                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The sparse power-EP step as a torch composition (sparse_pep.py:316-380, 473-487), IN PLACE on ``nat1 [.., M+1, 2d]``,
+    ``nat2 [.., M+1, 2d, 2d]`` and ``log_norm [.., M+1]`` (all three ``None``: evaluation only).  Per point, with ``(m_c, S_c)`` the
+    CAVITY of the pair the point belongs to (``indices [.., N]``): ``fmu = w . m_c``, ``fvar = c + w^T S_c w``; ``I, g1, g2`` of
+    ``log int p(y | f)^alpha N(f | fmu, fvar) df``; ``den = 1 + fvar g2`` (Gaussian: in closed form, as ``torch_pep_site_update``),
+    ``L2 = g2 / (2 den)``, ``L1 = (g1 - fmu g2) / den``.  A point where ``fvar`` or ``den`` is not positive or a value is not finite
+    is undefined and contributes NaN.  Per segment, by ``index_add_`` over the segment index: ``sum L2 w w^T``, ``sum L1 w``,
+    ``sum I``; if all of them (the last with ``seg_const [.., M+1]`` added) are finite, ``pep = (1 - alpha) old + sum``,
+    ``new = (1 - lr) old + lr pep``; otherwise the segment's sites stay as they are.  What ``mf_lik_sparse_pep_site_update_*``
+    fuses: it runs on CPU tensors, it is the model's route for ``2d > 18``, and it is what the kernel pair is measured against.
+    Returns ``(led_sum [.., M+1], fmu, fvar, led [.., N])``: the raw ``sum I`` (NaN for an undefined segment), and per point the
+    cavity marginal (NaN where ``fvar`` is not positive) and ``I``."""
+    two_d, segs = w.shape[-1], cav_mean.shape[-2]
+    alpha, lr = Likelihood._check_alpha("sparse_pep_site_update_torch", alpha), float(learning_rate)
+    if not 0.0 <= lr <= 1.0:
+        raise ValueError(f"sparse_pep_site_update_torch: learning_rate must lie in [0, 1], got {learning_rate}")
+    sites = (nat1, nat2, log_norm)
+    if any(t is None for t in sites) and not all(t is None for t in sites):
+        raise ValueError("sparse_pep_site_update_torch: nat1, nat2 and log_norm are given together, or all None (evaluation only)")
+    with torch.no_grad():
+        fmu, fvar, flat = _sparse_point_marginals(w, c, indices, cav_mean, cav_cov, segs)
+        led, g1, g2 = (t[..., 0] for t in torch_log_expected_density(likelihood, fmu[..., None], fvar[..., None], y[..., None], alpha))
+        if isinstance(likelihood, Gaussian):
+            den = (likelihood.variance / alpha) / (likelihood.variance / alpha + fvar)
+        else:
+            den = 1.0 + fvar * g2
+        l2, l1 = 0.5 * g2 / den, (g1 - fmu * g2) / den
+        nan = torch.full_like(fmu, float("nan"))
+        inside = fvar > 0
+        defined = inside & (den > 0) & torch.isfinite(l2) & torch.isfinite(l1) & torch.isfinite(led)
+        l2, l1, row = (torch.where(defined, v, nan) for v in (l2, l1, led))
+        fmu, fvar = torch.where(inside, fmu, nan), torch.where(inside, fvar, nan)
+        batch = tuple(cav_mean.shape[:-2])
+        rows = math.prod(batch) * segs
+        sum2 = torch.zeros((rows, two_d, two_d), dtype=w.dtype, device=w.device).index_add_(
+            0, flat, (l2[..., None, None] * w[..., :, None] * w[..., None, :]).reshape(-1, two_d, two_d)).reshape(batch + (segs, two_d, two_d))
+        sum1 = torch.zeros((rows, two_d), dtype=w.dtype, device=w.device).index_add_(
+            0, flat, (l1[..., None] * w).reshape(-1, two_d)).reshape(batch + (segs, two_d))
+        led_sum = torch.zeros(rows, dtype=w.dtype, device=w.device).index_add_(0, flat, row.reshape(-1)).reshape(batch + (segs,))
+        if nat1 is not None:
+            total = led_sum if seg_const is None else led_sum + seg_const
+            ok = torch.isfinite(sum2).all(dim=-1).all(dim=-1) & torch.isfinite(sum1).all(dim=-1) & torch.isfinite(total)
+            for t, step, keep in ((nat2, sum2, ok[..., None, None]), (nat1, sum1, ok[..., None]), (log_norm, total, ok)):
+                t.copy_(torch.where(keep, (1.0 - lr) * t + lr * ((1.0 - alpha) * t + step), t))
+    return led_sum, fmu, fvar, led
+
+
+def sparse_pep_site_update_hip(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor, offsets: torch.Tensor,
+                               cav_mean: torch.Tensor, cav_cov: torch.Tensor, alpha: float, learning_rate: float,
+                               nat1: Optional[torch.Tensor], nat2: Optional[torch.Tensor], log_norm: Optional[torch.Tensor],
+                               seg_const: Optional[torch.Tensor] = None, tiles=None, want_led_sum: bool = False,
+                               want_outputs: bool = False):
+    """ONE call of ``mf_lik_sparse_pep_site_update_*`` on HIP tensors (``2d <= 18``): what ``sparse_pep_site_update_torch`` computes,
+    with the segment ``offsets [.., M + 2]`` in place of the per-point index and ``tiles = sparse_expectation_tiles(offsets)`` when the
+    caller keeps it.  ``nat1`` / ``nat2`` / ``log_norm`` (contiguous) are updated IN PLACE, or all ``None``: evaluation only.
+    Returns ``(led_sum | None, fmu | None, fvar | None, led | None)`` as ``want_led_sum`` / ``want_outputs`` ask."""
+    dtype, dev = w.dtype, w.device
+    n, two_d, segs = w.shape[-2], w.shape[-1], offsets.shape[-1] - 1
+    batch = tuple(offsets.shape[:-1])
+    bsz = offsets.numel() // (segs + 1)
+    alpha = Likelihood._check_alpha("sparse_pep_site_update_hip", alpha)
+    sites = (nat1, nat2, log_norm)
+    if any(t is None for t in sites) and not all(t is None for t in sites):
+        raise ValueError("sparse_pep_site_update_hip: nat1, nat2 and log_norm are given together, or all None (evaluation only)")
+    if nat1 is not None and not all(t.is_contiguous() for t in sites):
+        raise ValueError("sparse_pep_site_update_hip: nat1, nat2 and log_norm must be contiguous")
+    num_tiles, tile_seg, seg_tile = sparse_expectation_tiles(offsets) if tiles is None else tiles
+    led_sum = torch.empty(batch + (segs,), dtype=dtype, device=dev) if want_led_sum else None
+    outs = tuple(torch.empty(tuple(w.shape[:-1]), dtype=dtype, device=dev) for _ in range(3)) if want_outputs else (None, None, None)
+    # (the row of the workspace is the SVGP entry point's, and so is the size function: include/markovflow_amd.h)
+    ws_bytes = int(_lib.load().mf_lik_sparse_expectations_workspace_bytes(num_tiles, two_d, w.element_size()))
+    ws = _lib.workspace(ws_bytes, dev)
+    _lib.call("mf_lik_sparse_pep_site_update", dtype, bsz, n, segs, two_d, *likelihood._kernel_args(), alpha, float(learning_rate),
+              _lib.ptr(offsets.contiguous()), _lib.ptr(w.contiguous()), _lib.ptr(c.contiguous()), _lib.ptr(y.contiguous()),
+              _lib.ptr(cav_mean.contiguous()), _lib.ptr(cav_cov.contiguous()),
+              _lib.ptr(None if seg_const is None else seg_const.contiguous()), num_tiles, _lib.ptr(tile_seg), _lib.ptr(seg_tile),
+              _lib.ptr(ws), ws_bytes, _lib.ptr(nat1), _lib.ptr(nat2), _lib.ptr(log_norm), _lib.ptr(led_sum),
+              *[_lib.ptr(o) for o in outs], _lib.stream_ptr(dev))
+    if nat1 is not None:
+        # the kernels wrote through raw pointers: tell torch, so that whatever keys a cache on (tensor, version) sees the write
+        for t in sites:
+            torch.autograd.graph.increment_version(t)
+    return (led_sum,) + outs
+
+
+def pair_cavity(pair_mean: torch.Tensor, pair_cov: torch.Tensor, nat1: torch.Tensor, nat2: torch.Tensor, beta: torch.Tensor
+                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The cavity of every pair of neighbouring inducing states and the log of ``E_q[t^(-beta)]``: with the marginal ``N(m, S)`` of
+    ``q`` on a pair (``pair_mean [.., S, 2d]``, ``pair_cov [.., S, 2d, 2d]``), its site ``t(v) = exp(nat1 . v + v^T nat2 v + ...)`` and
+    the fraction ``beta [.., S]`` of the site to remove, the cavity ``N(m_c, S_c)`` has precision ``S^-1 + 2 beta nat2`` and linear
+    term ``S^-1 m - beta nat1`` (sparse_pep.py:251-293), and ``Gamma = G(m_c, S_c) - G(m, S)`` with
+    ``G(m, S) = (log det S + m^T S^-1 m) / 2``.  Batched torch: two Cholesky factorisations per pair, none of which raises - a pair
+    whose marginal or cavity precision is not positive definite gets NaN in all three results.
+    Returns ``(cav_mean, cav_cov, gamma [.., S])``."""
+    eye = torch.eye(pair_cov.shape[-1], dtype=pair_cov.dtype, device=pair_cov.device).expand(pair_cov.shape)
+    chol_s, info_s = torch.linalg.cholesky_ex(pair_cov, check_errors=False)
+    prec = _lib.chol_solve(chol_s, eye)
+    lin = _lib.chol_solve(chol_s, pair_mean[..., None])[..., 0]
+    cav_prec = prec + 2.0 * beta[..., None, None] * nat2
+    cav_prec = 0.5 * (cav_prec + cav_prec.transpose(-1, -2))
+    cav_lin = lin - beta[..., None] * nat1
+    chol_c, info_c = torch.linalg.cholesky_ex(cav_prec, check_errors=False)
+    cav_cov = _lib.chol_solve(chol_c, eye)
+    cav_mean = _lib.chol_solve(chol_c, cav_lin[..., None])[..., 0]
+    g_marg = torch.sum(torch.log(torch.diagonal(chol_s, dim1=-2, dim2=-1)), dim=-1) + 0.5 * torch.sum(pair_mean * lin, dim=-1)
+    g_cav = -torch.sum(torch.log(torch.diagonal(chol_c, dim1=-2, dim2=-1)), dim=-1) + 0.5 * torch.sum(cav_mean * cav_lin, dim=-1)
+    bad = (info_s != 0) | (info_c != 0)
+    nan = float("nan")
+    return (cav_mean.masked_fill(bad[..., None], nan), cav_cov.masked_fill(bad[..., None, None], nan),
+            (g_cav - g_marg).masked_fill(bad, nan))
+
+
+class SparsePowerExpectationPropagation(_SparseSitesGaussianProcess):
+    """GP prior, general likelihood, Gaussian posterior on the states at ``M`` inducing points with ``M + 1`` Gaussian sites
+    ``t_m(v) = exp(nat1_m . v + v^T nat2_m v + log_norm_m)`` on the pairs ``v_m = [u_{m-1}, u_m]`` of neighbouring inducing states,
+    updated by power expectation propagation (markovflow/models/sparse_pep.py:78-560; zero mean function, plain float likelihood
+    parameters, a batch of series as leading dimensions).  The ``n_m`` data points with ``z_{m-1} < x <= z_m`` share site ``m``: each
+    owns the fraction ``1 / n_m`` of it, so its cavity removes ``beta_m = alpha / n_m`` of the site from the pair marginal of ``q``,
+    and it sees the cavity through the conditional ``p(f(x) | v_m)``.  ``energy`` is the (power) EP approximation of the log marginal
+    likelihood.
+
+    The site normaliser.  The reference builds ``M + 1`` leave-one-out chains and takes ``log Z(q with t_m^(1 - beta_m)) - log Z(q)``
+    for every segment (sparse_pep.py:418-429).  That ratio is ``E_q[t_m(v_m)^(-beta_m)]``, an integral over the pair ``v_m`` alone:
+    with the marginal ``N(m, S)`` of ``q`` on the pair and its cavity ``N(m_c, S_c)`` it equals ``exp(Gamma_m)``,
+    ``Gamma_m = G(m_c, S_c) - G(m, S)``, ``G(m, S) = (log det S + m^T S^-1 m) / 2`` - the ``2d``-dimensional form of the dense model's
+    ``G(mu_c, v_c) - G(m, s)`` - so it comes from the two factorisations the cavity needs anyway, and segment ``m`` adds
+    ``n_m Gamma_m`` to its summed log expected density.
+
+    Deviations from the reference:
+      * the power is the integral's, as in ``PowerExpectationPropagation``: the local objective and its derivatives are those of
+        ``log int p^alpha q``; the reference calls the gradients with ``alpha = 1`` and multiplies the summed step by ``alpha``
+        (sparse_pep.py:338, 374).  The two agree at ``alpha = 1``;
+      * the sites start at zero (the reference starts ``nat2`` at ``-1e-10 I``);
+      * a segment with an undefined update - a cavity precision that is not positive definite, a point whose ``fvar`` or
+        ``1 + fvar g2`` is not positive, a non-finite sum - is SKIPPED: its three site tensors stay as they are;
+      * the site normaliser is the local integral above, not ``M + 1`` chains; ``log_norm`` is a blended site tensor updated in the
+        same call as ``nat1`` / ``nat2`` (from the ``q`` before the step, as the dense model's), and ``compute_log_norm`` returns the
+        per-segment sums WITHOUT the reference's division by ``alpha``, which ``energy`` applies."""
+
+    def __init__(self, kernel: SDEKernel, inducing_points: torch.Tensor, likelihood: Likelihood, learning_rate: float = 1.0,
+                 alpha: float = 1.0) -> None:
+        """
+        :param inducing_points: ``batch + [num_inducing]``, sorted.
+        :param likelihood: a ``markovflow_amd.likelihoods.Likelihood``.
+        :param learning_rate: the damping of ``update_sites``, in [0, 1].
+        :param alpha: the power, in (0, 1].
+        """
+        super().__init__(kernel, inducing_points, likelihood, learning_rate)
+        if not 0.0 < float(alpha) <= 1.0:
+            raise ValueError(f"alpha must lie in (0, 1], got {alpha}")
+        self.alpha = float(alpha)
+        self.log_norm = torch.zeros(self.nat1.shape[:-1], dtype=inducing_points.dtype, device=inducing_points.device)
+
+    def _compute_projections(self, time_points: torch.Tensor):
+        """``sparse_site_projections`` of the data and, on the device, the tile table of the kernel pair."""
+        w, c, indices, offsets = sparse_site_projections(self._kernel, time_points, self.inducing_inputs)
+        tiles = sparse_expectation_tiles(offsets) if time_points.is_cuda else None
+        return w, c, indices, offsets, tiles
+
+    def _data(self, input_data, what: str):
+        """The checked data, sorted in every series, with its cached projections."""
+        time_points, observations = self._check_data(input_data, what)
+        return time_points, observations, self._projections(time_points)
+
+    # ---- the cavity --------------------------------------------------------------------------------------------------------------
+    def compute_num_data_per_interval(self, time_points: torch.Tensor) -> torch.Tensor:
+        """The number ``n_m`` of data points in every segment, ``batch + [M + 1]`` (sparse_pep.py:450-462)."""
+        offsets = self._projections(time_points)[3]
+        return (offsets[..., 1:] - offsets[..., :-1]).to(self.inducing_inputs.dtype)
+
+    def fraction_sites(self, time_points: torch.Tensor) -> torch.Tensor:
+        """``1 / n_m`` per segment, 0 for an empty one, ``batch + [M + 1]`` (sparse_pep.py:176-195)."""
+        counts = self.compute_num_data_per_interval(time_points)
+        return torch.where(counts > 0, 1.0 / counts.clamp(min=1.0), torch.zeros_like(counts))
+
+    def _cavity(self, time_points: torch.Tensor, dist_q: StateSpaceModel):
+        """``(cav_mean, cav_cov, seg_const)``: the pair cavity of every segment with ``beta_m = alpha / n_m`` and ``n_m Gamma_m``."""
+        counts = self.compute_num_data_per_interval(time_points)
+        pair_mean, pair_cov = self._pair_marginals(dist_q)
+        cav_mean, cav_cov, gamma = pair_cavity(pair_mean, pair_cov, self.nat1, self.nat2, self.alpha * self.fraction_sites(time_points))
+        return cav_mean, cav_cov, torch.where(counts > 0, counts * gamma, torch.zeros_like(gamma))
+
+    def compute_cavity_state_pairs(self, time_points: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The cavity of every pair, ``(batch + [M + 1, 2d], batch + [M + 1, 2d, 2d])``: the marginal of
+        ``q(s) / t_m(v_m)^(alpha / n_m)`` on ``v_m`` (sparse_pep.py:251-285, before the projection to the data); NaN where the cavity
+        precision is not positive definite.  The segment counts are those of ``time_points``."""
+        with torch.no_grad():
+            return self._cavity(time_points, self.dist_q)[:2]
+
+    def compute_cavity(self, time_points: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The cavity marginals of ``f`` at the data, ``batch + [N, 1]`` each (sparse_pep.py:304-314)."""
+        with torch.no_grad():
+            w, c, indices = self._projections(time_points)[:3]
+            cav_mean, cav_cov, _ = self._cavity(time_points, self.dist_q)
+            fmu, fvar, _ = _sparse_point_marginals(w, c, indices, cav_mean, cav_cov, cav_mean.shape[-2])
+            return fmu[..., None], fvar[..., None]
+
+    # ---- inference ---------------------------------------------------------------------------------------------------------------
+    def local_objective(self, Fmu: torch.Tensor, Fvar: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
+        """``log E_{N(f | Fmu, Fvar)} p(y | f)^alpha``, ``[..., 1] -> [...]`` (sparse_pep.py:164-166)."""
+        return self._likelihood.log_expected_density(Fmu, Fvar, Y, alpha=self.alpha)
+
+    def local_objective_gradients(self, Fmu: torch.Tensor, Fvar: torch.Tensor, Y: torch.Tensor
+                                  ) -> Tuple[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
+        """The local objective, ``[...]``, and the corrected gradients ``(L1, L2)``, ``[..., 1]`` each (sparse_pep.py:168-174; the
+        power is the model's, class docstring)."""
+        obj, grads = self._likelihood.grad_log_expected_density(Fmu, Fvar, Y, alpha=self.alpha)
+        return obj, gradient_correction((Fmu, Fvar), grads)
+
+    def _site_step(self, input_data, what: str, update: bool) -> torch.Tensor:
+        """``dist_q``, its pair marginals, the batched cavity and ONE call of ``mf_lik_sparse_pep_site_update_*`` (``2d <= 18`` on the
+        device; otherwise ``sparse_pep_site_update_torch``): the in-place step, or (``update`` False) the evaluation-only mode.
+        Returns the per-segment ``sum I + n Gamma``, ``batch + [M + 1]`` (evaluation only)."""
+        time_points, observations, (w, c, indices, offsets, tiles) = self._data(input_data, what)
+        with torch.no_grad():
+            cav_mean, cav_cov, seg_const = self._cavity(time_points, self.dist_q)
+            sites = (self.nat1, self.nat2, self.log_norm) if update else (None, None, None)
+            if self._fused(time_points):
+                led_sum = sparse_pep_site_update_hip(self._likelihood, w, c, observations[..., 0], offsets, cav_mean, cav_cov, self.alpha,
+                                                     self.learning_rate, *sites, seg_const=seg_const, tiles=tiles,
+                                                     want_led_sum=not update)[0]
+            else:
+                led_sum = sparse_pep_site_update_torch(self._likelihood, w, c, observations[..., 0], indices, cav_mean, cav_cov,
+                                                       self.alpha, self.learning_rate, *sites, seg_const=seg_const)[0]
+            return None if update else led_sum + seg_const
+
+    def update_sites(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> None:
+        """One power-EP step on the sites, in place (sparse_pep.py:316-380, 473-487): ``dist_q``, its pair marginals, the batched
+        pair cavity and ONE call of ``mf_lik_sparse_pep_site_update_*`` on HIP tensors with ``2d <= 18``
+        (``sparse_pep_site_update_torch`` for ``2d > 18``)."""
+        self._site_step(input_data, "update_sites", update=True)
+
+    def compute_log_norm(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+        """The site normalisers from the current ``q``, per segment, ``batch + [M + 1]``: ``sum_k I_k + n_m Gamma_m`` with the
+        objective at the cavity (sparse_pep.py:382-448, class docstring); NaN for a segment whose update is undefined."""
+        return self._site_step(input_data, "compute_log_norm", update=False)
+
+    def energy(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+        """The power-EP energy per series, ``batch`` (sparse_pep.py:489-495): ``dist_q.normalizer() - dist_p.normalizer()
+        + (1 / alpha) sum_m log_norm_m`` with the normalisers computed afresh from the current ``q``.  Not differentiable."""
+        with torch.no_grad():
+            log_norm = torch.sum(self.compute_log_norm(input_data), dim=-1)
+            return self.dist_q.normalizer() - self.dist_p.normalizer() + log_norm / self.alpha
+
+    def classic_elbo(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+        """``sum_i E_q log p(y_i | f_i) - KL[q(u) || p(u)]`` (sparse_pep.py:520-542; for testing, not for optimisation)."""
+        time_points, observations = self._check_data(input_data, "classic_elbo")
+        dist_q = self.dist_q
+        fmu, fvar = self.posterior.predict_f(time_points)
+        ve = self._likelihood.variational_expectations(fmu, fvar, observations)
+        return torch.sum(ve) - torch.sum(dist_q.kl_divergence(self.dist_p))
+
+    def loss(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+        """``-classic_elbo`` (sparse_pep.py:497-504)."""
         return -self.classic_elbo(input_data)
 
 
