@@ -573,7 +573,8 @@ int mf_kf_loglik_plan(int64_t B, int64_t T, int d, int m, int rinv_per_step, int
  * (nullable).  adj_N [B,T,d,d], adj_n [B,T,d] (both or neither): the inputs of the recursion when the forward kept them
  * (mf_ssm_kl_divergence: out_N, out_n); NULL: they are formed here.
  * The gradient with respect to q2 is MINUS mf_kf_loglik_grad with H = NULL, q2's parameters and q1's moments.
- * State dimension 1..9.
+ * State dimension 1..9; 10..15 (row kernels) with adj_N / adj_n given only (-100 without them: the kernel that forms them is
+ * not compiled in row form).
  */
 int mf_ssm_kl_grad_f64(int64_t B, int64_t T, int d, const double* mu0_1, const double* cholP0_1, const double* A_1,
                        const double* b_1, const double* cholQ_1, const double* mu0_2, const double* cholP0_2, const double* A_2,
@@ -662,6 +663,9 @@ int mf_ssm_kl_divergence_f32(int64_t B, int64_t T, int d, const float* mu0_1, co
  * covs_1 [B,T,d,d], cross_1 [B,T-1,d,d] = Cov(x_{k+1}, x_k) and mean_diff [B,T,d] = mu_2 - mu_1; the two log-determinants ride along
  * (q1's factors are read on their diagonals only); a second small kernel sums the T terms of a series in a fixed order.  q2's
  * precision never exists in memory.  ws: mf_ssm_kl_from_moments_workspace_bytes (B T scalars).  -100 outside 16 <= d <= 32.
+ * The strict upper triangles of q2's factors are not read.  T = 1: cholQ_1, A_2, cholQ_2 and cross_1 may be NULL.
+ * (StateSpaceModel.kl_divergence takes the one-walk kernel above at these state dimensions; this entry point stays as a tested
+ * part of the C interface for callers that hold q1's moments already - tests/test_gpu_kl_from_moments.py.)
  */
 size_t mf_ssm_kl_from_moments_workspace_bytes(int64_t B, int64_t T, int d, int elem_size);
 int mf_ssm_kl_from_moments_f64(int64_t B, int64_t T, int d, const double* cholP0_1, const double* cholQ_1, const double* cholP0_2,

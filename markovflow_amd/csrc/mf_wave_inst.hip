@@ -115,9 +115,9 @@ int wave_kl(long B, long Tn, int d, const T* cp0_1, const T* cq_1, const T* cp0_
     T* terms = static_cast<T*>(ws);
     const wv::WvArgs<T> a{B, Tn, d, 1, nullptr, cp0_2, a_2, nullptr, cq_2, nullptr, nullptr, nullptr, 0, 1, 1, nullptr};
     const dim3 grid((unsigned)(B * Tn)), block(64);
-    if (d <= 16) {
-        if (d == 16) hipLaunchKernelGGL((wv::wave_ssm_kl_terms_kernel<T, 1, true>), grid, block, 0, st, a, cp0_1, cq_1, cov, cross, mdiff, terms);
-        else hipLaunchKernelGGL((wv::wave_ssm_kl_terms_kernel<T, 1, false>), grid, block, 0, st, a, cp0_1, cq_1, cov, cross, mdiff, terms);
+    // (wave_covers: 16 <= d, so one tile is always an exact one - there is no padded one-tile instantiation)
+    if (d == 16) {
+        hipLaunchKernelGGL((wv::wave_ssm_kl_terms_kernel<T, 1, true>), grid, block, 0, st, a, cp0_1, cq_1, cov, cross, mdiff, terms);
     } else {
         if (d == 32) hipLaunchKernelGGL((wv::wave_ssm_kl_terms_kernel<T, 2, true>), grid, block, 0, st, a, cp0_1, cq_1, cov, cross, mdiff, terms);
         else hipLaunchKernelGGL((wv::wave_ssm_kl_terms_kernel<T, 2, false>), grid, block, 0, st, a, cp0_1, cq_1, cov, cross, mdiff, terms);

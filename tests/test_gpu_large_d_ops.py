@@ -93,6 +93,8 @@ def test_large_d_posterior_marginals_and_kl(rng, dtype, d, m):
     np.testing.assert_allclose(nn(post.marginal_covariances), O.ssm_marginal_covariances(want[1], want[2], want[4]), **tol)
     prior = (kw["mu0"], kw["chol_p0"], kw["a_s"], kw["b_s"], kw["chol_q"])
     kl = O.ssm_kl_divergence(want, prior)
+    # (float32 at 2e-2: posterior against prior is the harder-conditioned quantity; the float32 KL kernels themselves are pinned on
+    # measured yardsticks by tests/test_gpu_kl_float32.py and tests/test_gpu_kl_from_moments.py)
     np.testing.assert_allclose(nn(post.kl_divergence(kf.prior_ssm)), kl, rtol=1e-6 if dtype == torch.float64 else 2e-2)
     # the log-likelihood of the same model agrees with the operator route: 0.5 |L^-1 eta|^2 - log|L| through cholesky/solve
     ref = O.kf_log_likelihood(**kw, r_inv=np.linalg.inv(cov))
@@ -196,6 +198,8 @@ def test_large_d_posterior_chain_partitioned_in_time(rng, dtype, d, m, t):
     np.testing.assert_allclose(nn(post.marginal_means), O.ssm_marginal_means(want[0], want[2], want[3]), **tol)
     np.testing.assert_allclose(nn(kf.prior_ssm.marginal_means), O.ssm_marginal_means(kw["mu0"], kw["a_s"], kw["b_s"]), **tol)
     kl = O.ssm_kl_divergence(want, (kw["mu0"], kw["chol_p0"], kw["a_s"], kw["b_s"], kw["chol_q"]))
+    # (float32 at 2e-2: posterior against prior is the harder-conditioned quantity; the float32 KL kernels themselves are pinned on
+    # measured yardsticks by tests/test_gpu_kl_float32.py and tests/test_gpu_kl_from_moments.py)
     np.testing.assert_allclose(nn(post.kl_divergence(kf.prior_ssm)), kl, rtol=1e-6 if dtype == torch.float64 else 2e-2)
 
 

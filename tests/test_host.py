@@ -493,3 +493,45 @@ def test_kernel_cache_follows_reseated_data_and_can_be_invalidated():
     ls.data.mul_(2.0)
     k.invalidate_cache()
     assert float(k._lambda) == pytest.approx(lam0 / 4)
+
+
+def test_kl_from_moments_argument_errors_and_workspace_need_no_gpu():
+    """mf_ssm_kl_from_moments_{f64,f32} (16 <= d <= 32; a tested C entry point, the Python route goes through the one-walk kernel):
+    every return code that needs no launch, in the order the header's argument groups are checked, and the workspace query."""
+    import ctypes
+    lib = _lib.load()
+    for suf, esz, ctype in (("_f64", 8, ctypes.c_double), ("_f32", 4, ctypes.c_float)):
+        fn = getattr(lib, "mf_ssm_kl_from_moments" + suf)
+        size = getattr(lib, "mf_ssm_kl_from_moments_workspace_bytes")
+        buf = (ctype * 8)(*([7.0] * 8))                       # never dereferenced on the host: the checks come before any launch
+        p = ctypes.cast(buf, ctypes.c_void_p)
+        names = ("cholP0_1", "cholQ_1", "cholP0_2", "A_2", "cholQ_2", "covs_1", "cross_1", "mean_diff", "out")
+
+        def call(b, t, d, ws=p, ws_bytes=1 << 30, **null):
+            assert set(null) <= set(names)
+            return fn(b, t, d, *[None if n in null else p for n in names], ws, ws_bytes, None)
+
+        assert call(-1, 4, 16) == -1
+        assert call(2, 0, 16) == -2 and call(2, -3, 16) == -2
+        assert call(2, 4, 15) == -100 and call(2, 4, 33) == -100 and call(2, 1, 9) == -100
+        assert call(0, 4, 16) == 0 and call(0, 1, 32, out=1) == 0 and list(buf) == [7.0] * 8     # an empty batch: nothing touched
+        for t in (1, 4):
+            assert call(2, t, 16, cholP0_1=1) == -4
+            assert call(2, t, 17, cholP0_2=1) == -6
+            assert call(2, t, 24, covs_1=1) == -9
+            assert call(2, t, 31, mean_diff=1) == -11
+            assert call(2, t, 32, out=1) == -12
+        assert call(2, 4, 16, cholQ_1=1) == -4
+        assert call(2, 4, 16, A_2=1) == -6 and call(2, 4, 16, cholQ_2=1) == -6
+        assert call(2, 4, 16, cross_1=1) == -9
+        # one block: the tensors over the transitions may be NULL - the call gets as far as the workspace check
+        assert call(2, 1, 16, ws=None, cholQ_1=1, A_2=1, cholQ_2=1, cross_1=1) == -15
+        assert call(2, 4, 20, ws=None) == -15 and call(2, 4, 20, ws_bytes=2 * 4 * esz - 1) == -15
+        assert call(3, 1, 32, ws_bytes=3 * esz - 1) == -15
+        assert list(buf) == [7.0] * 8
+        for d in (16, 17, 24, 31, 32):
+            for b, t in ((1, 1), (3, 2), (70, 5), (2, 130)):
+                assert size(b, t, d, esz) == b * t * esz
+        for b, t, d in ((2, 4, 15), (2, 4, 33), (2, 4, 9), (2, 4, 40), (0, 4, 16), (2, 0, 16), (-1, 4, 16)):
+            assert size(b, t, d, esz) == 0
+        assert size(2, 4, 16, 2) == 0
