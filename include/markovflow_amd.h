@@ -872,6 +872,50 @@ int mf_lik_sparse_pep_site_update_f32(int64_t B, int64_t N, int64_t S, int two_d
                                       float* nat1, float* nat2, float* log_norm, float* led_sum, float* fmu, float* fvar,
                                       float* led, void* stream);
 
+/*
+ * The data term of the log importance weights of importance-weighted VI and its adjoint onto the posterior draw at the inducing
+ * points (markovflow/models/iwvi.py:109-173, markovflow/posterior.py:522-580; csrc/mf_lik.hip): K Monte-Carlo evaluations of
+ * log p(y_n | f_n) at every data point.  B, N, S = M + 1, two_d = 2 d, the likelihood, seg_offsets, w = H [D E], y, the tile table
+ * as for mf_lik_sparse_expectations_*; no quadrature rule - the density is evaluated point-wise; h [d] is the emission row.
+ * u_post given ([K, B, M, d], the draw from q at the inducing points):
+ *   states [K, B, N + M, d] is ONE prior draw on the merged, sorted time points: data point n of segment s sits at row n + s,
+ *   inducing point m at row seg_offsets[b, m + 1] + m (points with x <= z_m precede z_m); per sample k, series b, point n of
+ *   segment s, in this order of evaluation
+ *     dL_i = s > 0 ? states[k, b, row(z_{s-1}), i] - u_post[k, b, s - 1, i] : 0
+ *     dR_i = s < M ? states[k, b, row(z_s), i]     - u_post[k, b, s, i]     : 0
+ *     f    = (sum_i h_i states[k, b, n + s, i] - sum_i w[b, n, i] dL_i) - sum_i w[b, n, d + i] dR_i
+ *     l, l' = log p(y_n | f) and its derivative in f   (Poisson: with - lgamma(y + 1), computed once per point)
+ *     log_lik [K, B, S]      sum over the points of segment s of l
+ *     g_u     [K, B, M, d]   sum_{n in segment m} l'_n w[b, n, d + i] + sum_{n in segment m + 1} l'_n w[b, n, i]: the adjoint of
+ *                            sum_s log_lik[k, b, s] with respect to u_post[k, b, m, i]
+ * u_post NULL: states [K, B, N, d] holds final samples, point n at row n, f = sum_i h_i states[k, b, n, i]; w is not read and may
+ * be NULL; g_u must be NULL.  Either output may be NULL; what is computed has the bits of the full call.
+ * Two passes.  Pass 1 runs one wavefront per (tile, chunk of 8 samples), a lane per point: w, y and the Poisson constant are read
+ * once and kept for the samples of the chunk, the prior draw is read exactly once, and the 2d + 1 partial sums of every
+ * (tile, sample) - over the tile's points in ascending order - go to the workspace,
+ * mf_lik_iw_log_weights_workspace_bytes(num_tiles, K, two_d, sizeof(T)) = num_tiles K (two_d + 1) sizeof(T) bytes (0 outside the
+ * supported two_d, for num_tiles = 0 or K = 0).  Pass 2 adds per (k, b, s) that segment's tiles in ascending order into log_lik, and
+ * per (k, b, m) the tiles of segment m, then those of segment m + 1, into g_u.  No atomics: the same bits on every launch, for a
+ * series alone or inside a batch, for a sample alone or among K.  A non-finite f makes log_lik of ITS (k, b, s) and the g_u rows
+ * that segment feeds non-finite; nothing else is touched.  An empty segment, and every segment for N = 0, gets zeros (N = 0
+ * needs no input, table or workspace).  The offsets and the tile table are clamped on the device, not validated.  No allocation,
+ * no synchronisation.
+ * Returns 0, -(position of the offending argument in THIS signature: 1 B, 2 N, 3 S, 5 K negative or above 2^31 - 1, 6 lik,
+ * 7 params, 8 seg_offsets NULL, 9 w NULL beside u_post, 10 / 11 / 12 y / h / states NULL, 14 num_tiles negative, above 2^31 - 1,
+ * non-zero for N = 0 or with more than 2^31 - 1 blocks, 15 / 16 a NULL table, 17 a NULL workspace, 18 a workspace that is too
+ * small, 20 g_u without u_post), -100 for a two_d that is odd, < 2 or > 18, or -1000 (launch failed).  Nothing is launched on an
+ * error, for B = 0 or K = 0, or when both outputs are NULL.
+ */
+size_t mf_lik_iw_log_weights_workspace_bytes(int64_t num_tiles, int64_t K, int two_d, int elem_size);
+int mf_lik_iw_log_weights_f64(int64_t B, int64_t N, int64_t S, int two_d, int64_t K, int lik, const double* params,
+                              const int64_t* seg_offsets, const double* w, const double* y, const double* h, const double* states,
+                              const double* u_post, int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile,
+                              void* workspace, size_t workspace_bytes, double* log_lik, double* g_u, void* stream);
+int mf_lik_iw_log_weights_f32(int64_t B, int64_t N, int64_t S, int two_d, int64_t K, int lik, const double* params,
+                              const int64_t* seg_offsets, const float* w, const float* y, const float* h, const float* states,
+                              const float* u_post, int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile,
+                              void* workspace, size_t workspace_bytes, float* log_lik, float* g_u, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

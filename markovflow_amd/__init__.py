@@ -21,10 +21,10 @@ from . import conditionals, distributed, kernels, likelihoods, models, ssm_gauss
 from .kernels import (Constant, HarmonicOscillator, IndependentMultiOutput, Matern12, Matern32, Matern52, Product, SDEKernel,
                       StationaryKernel, Sum)
 from .likelihoods import Bernoulli, Gaussian, Likelihood, Poisson, StudentT
-from .models import (CVIGaussianProcess, GaussianProcessRegression, PowerExpectationPropagation, SparseCVIGaussianProcess,
-                     SparsePowerExpectationPropagation, SparseVariationalGaussianProcess)
+from .models import (CVIGaussianProcess, GaussianProcessRegression, ImportanceWeightedVI, PowerExpectationPropagation,
+                     SparseCVIGaussianProcess, SparsePowerExpectationPropagation, SparseVariationalGaussianProcess)
 from .ssm_natgrad import SSMNaturalGradient
-from .posterior import AnalyticPosteriorProcess, ConditionalProcess
+from .posterior import AnalyticPosteriorProcess, ConditionalProcess, ImportanceWeightedPosteriorProcess
 from ._lib import MarkovflowAmdError, check_errors, errors_as_nan, set_synchronous_checks
 
 __all__ = [
@@ -36,5 +36,5 @@ __all__ = [
     "MarkovflowAmdError", "check_errors", "errors_as_nan", "set_synchronous_checks",
     "likelihoods", "Likelihood", "Gaussian", "Bernoulli", "Poisson", "StudentT", "CVIGaussianProcess", "PowerExpectationPropagation",
     "SparseCVIGaussianProcess", "SparseVariationalGaussianProcess", "SSMNaturalGradient", "ssm_natgrad",
-    "SparsePowerExpectationPropagation",
+    "SparsePowerExpectationPropagation", "ImportanceWeightedVI", "ImportanceWeightedPosteriorProcess",
 ]

@@ -10,6 +10,9 @@
 // - the exact derivatives of the discretised sum, which is what the reference's tape through ndiagquad yields.
 // Power expectation propagation (markovflow/models/pep.py) adds the log of the expected alpha-power density with its first two
 // derivatives in the mean, and the fused site update built on it (cavity, gradient correction, site normaliser, power / damping step).
+// Importance-weighted VI (markovflow/models/iwvi.py) adds the data term of the log importance weights: log p(y | f) itself, at K
+// Monte-Carlo samples per point that are assembled in the kernel from one prior draw (no quadrature), with the adjoint onto the draw
+// from q at the inducing points.
 // One lane per data point; the rule travels by value in the kernel arguments and the loop over its nodes is wavefront-uniform, so
 // nodes and weights are scalar loads; no LDS, no cross-lane traffic, no temporaries in memory.
 #include "../../include/markovflow_amd.h"
@@ -697,6 +700,175 @@ __global__ void __launch_bounds__(256) sparse_pep_reduce_kernel(long num_tiles, 
     }
 }
 
+// ---- importance-weighted VI: the log importance weights' data term (markovflow/models/iwvi.py:109-173, posterior.py:522-580) ---------
+// K Monte-Carlo evaluations of log p(y_n | f_n) at every data point, on samples assembled here from ONE prior draw on the merged,
+// sorted time points (states [K, B, N + M, d]: data point n of segment s at row n + s, inducing point m at row offsets[m + 1] + m)
+// and the posterior draw u_post [K, B, M, d] at the inducing points - Matheron's rule, whose correction only involves the two
+// inducing states around a point:
+//   dL = prior(z_{s-1}) - u_post_{s-1} (0 for s = 0),  dR = prior(z_s) - u_post_s (0 for s = M),
+//   f = (h . prior(x_n) - w[n, :d] . dL) - w[n, d:] . dR,   l = log p(y_n | f),  l' = dl/df
+// u_post == NULL: states [K, B, N, d] holds final samples, point n at row n, f = h . states(n) (w is not read and may be NULL).
+// The two-pass, tile-parallel layout of the SVGP kernels, with the same tile table.
+//   pass 1, one wavefront per (tile, chunk of IW_CHUNK samples), a lane per point: the tile's rows of w travel through LDS once and
+//            stay in the lane's registers with y and the Poisson constant for every sample of the chunk; the chunk's (dL, dR) sit in
+//            LDS and are read as broadcasts.  Per sample the tile's rows of the prior draw - npts d CONTIGUOUS values - come in
+//            with coalesced loads (the next sample's are in flight while this one's density is evaluated), pass through LDS at an
+//            odd row stride and leave l' and l there.  Then a lane per (sample, column) entry, 2d + 1 per sample: entry (k, c < 2d)
+//            = sum_n l'_n w[n, c], entry (k, 2d) = sum_n l_n (through the column of ones that pads every row of w), over the
+//            tile's points in ascending order.  The chunk's entries go to the workspace as one contiguous run, row (tile, sample).
+//   pass 2, one block per (series, segment), a lane per (sample, output): log_lik[k, b, s] adds the segment's tiles in ascending
+//            order; g_u[k, b, m, i] adds the tiles of segment m (column d + i), then those of segment m + 1 (column i).
+// No atomics; every sum's order is fixed by the point order alone, and a sum never mixes samples or series: the same bits on every
+// launch, for a series alone or in a batch, for a sample alone or among K.  The tile table and the offsets are clamped, not trusted.
+constexpr int IW_CHUNK = 8;            // samples per block of pass 1
+
+template <typename T, int LIK, int D2>
+__global__ void __launch_bounds__(64) iw_tile_kernel(long N, int S, long BS, long B, long K, int chunks, Par<T> p,
+                                                     const long long* __restrict__ seg, const long long* __restrict__ tile_seg,
+                                                     const long long* __restrict__ seg_tile, const T* __restrict__ w,
+                                                     const T* __restrict__ yobs, const T* __restrict__ h,
+                                                     const T* __restrict__ states, const T* __restrict__ u_post, int grads,
+                                                     T* __restrict__ ws) {
+    constexpr int D = D2 / 2, W = D2 + 1, E = D2 + 1, DP = D | 1, LG = 129, R = (IW_CHUNK * E + 63) / 64;
+    __shared__ T lw[64 * W];
+    __shared__ T lx[64 * DP];          // the tile's rows of one sample of the prior draw
+    __shared__ T ld[IW_CHUNK * D2];    // (dL, dR) of the chunk's samples
+    __shared__ T lg[IW_CHUNK * LG];    // per sample l' of the tile's points, then l (stride 129: the samples start on distinct banks)
+    const int lane = threadIdx.x;
+    const long t = blockIdx.x / chunks;
+    const long k_base = (blockIdx.x - t * chunks) * IW_CHUNK;
+    const int kc = K - k_base < IW_CHUNK ? int(K - k_base) : IW_CHUNK;
+    long bs = (long)tile_seg[t];
+    bs = bs < 0 ? 0 : (bs >= BS ? BS - 1 : bs);
+    const long b = bs / S;
+    const int s = int(bs - b * S);
+    long k_lo = (long)seg[b * (S + 1) + s], k_hi = (long)seg[b * (S + 1) + s + 1];
+    clamp_range(k_lo, k_hi, N);
+    const long j = t - (long)seg_tile[bs];                          // this tile's number within its segment
+    const long k0 = (j >= 0 && j <= (k_hi - k_lo) / 64) ? k_lo + 64 * j : k_hi;
+    const int npts = k_hi - k0 < 64 ? int(k_hi - k0) : 64;          // (0 only for a table that disagrees with the offsets)
+    const long rows = u_post ? N + (S - 1) : N;                     // rows of one (sample, series) of states
+    const long row0 = u_post ? k0 + s : k0;                         // the row of the tile's first point
+    T part[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) part[r] = T(0);
+    if (npts > 0) {
+        // (dL, dR) of every sample of the chunk; beyond both ends the correction vanishes
+        for (int idx = lane; idx < kc * D2; idx += 64) {
+            const int kk = idx / D2, c = idx - kk * D2, side = c / D, i = c - side * D;
+            const long m = s - 1 + side;                            // the inducing point left (side 0) or right of the segment
+            T delta = T(0);
+            if (u_post && m >= 0 && m < S - 1) {
+                const long kb = (k_base + kk) * B + b;
+                const long zrow = (side ? k_hi : k_lo) + m;         // offsets[m + 1] + m
+                delta = states[(kb * rows + zrow) * D + i] - u_post[(kb * (S - 1) + m) * D + i];
+            }
+            ld[idx] = delta;
+        }
+        lw[lane * W + D2] = T(1);
+        if (u_post) {
+            stage_tile<T, D2>(lane, npts, w + (b * N + k0) * D2, lw);
+        } else {
+            for (int idx = lane; idx < 64 * D2; idx += 64) lw[(idx / D2) * W + idx % D2] = T(0);
+        }
+        T xr[D];                       // this lane's share of the next sample's rows: elements lane, lane + 64, ...
+        const T* src = states + ((k_base * B + b) * rows + row0) * D;
+        const long k_stride = B * rows * D;
+#pragma unroll
+        for (int q = 0; q < D; ++q) xr[q] = lane + 64 * q < npts * D ? src[lane + 64 * q] : T(0);
+        __syncthreads();
+        T wr[D2], hr[D];
+        T y = T(0), lgam = T(0);
+#pragma unroll
+        for (int i = 0; i < D2; ++i) wr[i] = lw[lane * W + i];
+#pragma unroll
+        for (int i = 0; i < D; ++i) hr[i] = h[i];
+        if (lane < npts) {
+            y = yobs[b * N + k0 + lane];
+            if (LIK == 2) lgam = m_lgamma(y + T(1));                // once per point, not per sample
+        }
+        for (int kk = 0; kk < kc; ++kk) {
+#pragma unroll
+            for (int q = 0; q < D; ++q) {
+                const int idx = lane + 64 * q;
+                if (idx < npts * D) lx[(idx / D) * DP + idx % D] = xr[q];
+            }
+            __syncthreads();
+            if (kk + 1 < kc) {
+#pragma unroll
+                for (int q = 0; q < D; ++q) xr[q] = lane + 64 * q < npts * D ? src[(kk + 1) * k_stride + lane + 64 * q] : T(0);
+            }
+            if (lane < npts) {
+                T f = T(0);
+#pragma unroll
+                for (int i = 0; i < D; ++i) f += hr[i] * lx[lane * DP + i];
+                if (u_post) {
+                    T cl = T(0), cr = T(0);
+#pragma unroll
+                    for (int i = 0; i < D; ++i) cl += wr[i] * ld[kk * D2 + i];
+#pragma unroll
+                    for (int i = 0; i < D; ++i) cr += wr[D + i] * ld[kk * D2 + D + i];
+                    f = (f - cl) - cr;
+                }
+                T dl;
+                const T l = log_prob<T, LIK, true>(f, y, p, dl);
+                lg[kk * LG + lane] = dl;
+                lg[kk * LG + 64 + lane] = LIK == 2 ? l - lgam : l;
+            }
+            __syncthreads();           // lx is free for the next sample; after the last one l' and l are complete
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int e = lane + 64 * r, kk = e / E, c = e - kk * E;
+            if (kk >= kc || !(grads || c == D2)) continue;
+            const T* g = lg + kk * LG + (c == D2 ? 64 : 0);
+            T acc = T(0);
+            for (int n = 0; n < npts; ++n) acc += g[n] * lw[n * W + c];
+            part[r] = acc;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int e = lane + 64 * r, kk = e / E, c = e - kk * E;
+        if (kk < kc && (grads || c == D2)) ws[(t * K + k_base) * E + e] = part[r];
+    }
+}
+
+template <typename T, int D2>
+__global__ void __launch_bounds__(256) iw_reduce_kernel(long num_tiles, int S, long B, long K, const long long* __restrict__ seg_tile,
+                                                        const T* __restrict__ ws, T* __restrict__ log_lik, T* __restrict__ g_u) {
+    constexpr int D = D2 / 2, E = D2 + 1;
+    const long bs = blockIdx.x;
+    const long b = bs / S;
+    const int s = int(bs - b * S), M = S - 1;
+    long t_lo = 0, t_hi = 0, n_lo = 0, n_hi = 0;       // the tiles of this segment and of the next
+    if (seg_tile) {                                    // (NULL: no points at all)
+        t_lo = (long)seg_tile[bs];
+        t_hi = (long)seg_tile[bs + 1];
+        clamp_range(t_lo, t_hi, num_tiles);
+        if (s < M) {
+            n_lo = (long)seg_tile[bs + 1];
+            n_hi = (long)seg_tile[bs + 2];
+            clamp_range(n_lo, n_hi, num_tiles);
+        }
+    }
+    for (long idx = threadIdx.x; idx < K * (D + 1); idx += 256) {
+        const long k = idx / (D + 1);
+        const int i = int(idx - k * (D + 1));
+        T acc = T(0);
+        if (i == D) {
+            if (!log_lik) continue;
+            for (long t = t_lo; t < t_hi; ++t) acc += ws[(t * K + k) * E + D2];
+            log_lik[(k * B + b) * S + s] = acc;
+        } else {
+            if (!g_u || s >= M) continue;
+            for (long t = t_lo; t < t_hi; ++t) acc += ws[(t * K + k) * E + D + i];       // inducing point s is this segment's right
+            for (long t = n_lo; t < n_hi; ++t) acc += ws[(t * K + k) * E + i];           // neighbour and the next one's left
+            g_u[((k * B + b) * M + s) * D + i] = acc;
+        }
+    }
+}
+
 // argument checks shared by every entry point: 0, or the (negative) position of the offending argument
 template <typename T>
 int prepare(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights, bool log_weights,
@@ -966,9 +1138,71 @@ int run_sparse_pep(int64_t B, int64_t N, int64_t S, int two_d, int lik, const do
     });
 }
 
+// the log importance weights' data term: the workspace row of a (tile, sample) is the 2d column sums and the value sum
+constexpr size_t iw_row(int two_d) { return size_t(two_d) + 1; }
+
+template <typename T>
+int run_iw(int64_t B, int64_t N, int64_t S, int two_d, int64_t K, int lik, const double* params, const int64_t* seg, const T* w,
+           const T* y, const T* h, const T* states, const T* u_post, int64_t tiles, const int64_t* tile_seg, const int64_t* seg_tile,
+           void* ws, size_t ws_bytes, T* log_lik, T* g_u, void* stream) {
+    if (B < 0) return -1;
+    if (N < 0) return -2;
+    if (S < 1 || (B > 0 && S > int64_t(0x7fffffff) / B)) return -3;
+    if (two_d < 2 || two_d > 18 || (two_d & 1)) return -100;
+    if (K < 0 || K > int64_t(0x7fffffff)) return -5;
+    Rule<T> q;                         // no quadrature: the density is evaluated point-wise (a one-node rule satisfies prepare)
+    Par<T> p;
+    const double node = 0.0, weight = 1.0;
+    int bad = prepare<T>(0, lik, params, 1, &node, &weight, false, q, p);      // -2, -3 there: arguments 6, 7 here
+    if (bad) return bad - 4;
+    const int64_t chunks = (K + IW_CHUNK - 1) / IW_CHUNK;
+    if (tiles < 0 || tiles > int64_t(0x7fffffff) || (N == 0 && tiles != 0) || (chunks > 0 && tiles > int64_t(0x7fffffff) / chunks))
+        return -14;
+    if (g_u && !u_post) return -20;
+    if (B == 0 || K == 0 || (!log_lik && !g_u)) return 0;      // nothing asked for
+    if (tiles > 0) {
+        if (!seg) return -8;
+        if (u_post && !w) return -9;
+        if ((bad = first_null(10, {y, h, states}))) return bad;
+        if ((bad = first_null(15, {tile_seg, seg_tile, ws}))) return bad;
+        if (ws_bytes < size_t(tiles) * size_t(K) * iw_row(two_d) * sizeof(T)) return -18;
+    }
+    return with_two_d(two_d, [&](auto D) {
+        constexpr int D2 = decltype(D)::value;
+        if (tiles > 0) {
+            const int rc = with_lik(lik, [&](auto L) {
+                return launch(iw_tile_kernel<T, decltype(L)::value, D2>, tiles * chunks, 64, stream, N, S, B * S, B, K, chunks, p,
+                              ll(seg), ll(tile_seg), ll(seg_tile), w, y, h, states, u_post, g_u ? 1 : 0, ws);
+            });
+            if (rc) return rc;
+        }
+        return launch(iw_reduce_kernel<T, D2>, B * S, 256, stream, tiles, S, B, K, tiles > 0 ? ll(seg_tile) : nullptr, ws, log_lik,
+                      g_u);
+    });
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t mf_lik_iw_log_weights_workspace_bytes(int64_t num_tiles, int64_t K, int two_d, int elem_size) {
+    if (num_tiles <= 0 || K <= 0 || two_d < 2 || two_d > 18 || (two_d & 1) || elem_size < 1) return 0;
+    return size_t(num_tiles) * size_t(K) * iw_row(two_d) * size_t(elem_size);
+}
+int mf_lik_iw_log_weights_f64(int64_t B, int64_t N, int64_t S, int two_d, int64_t K, int lik, const double* params,
+                              const int64_t* seg_offsets, const double* w, const double* y, const double* h, const double* states,
+                              const double* u_post, int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile,
+                              void* workspace, size_t workspace_bytes, double* log_lik, double* g_u, void* stream) {
+    return run_iw<double>(B, N, S, two_d, K, lik, params, seg_offsets, w, y, h, states, u_post, num_tiles, tile_seg, seg_tile,
+                          workspace, workspace_bytes, log_lik, g_u, stream);
+}
+int mf_lik_iw_log_weights_f32(int64_t B, int64_t N, int64_t S, int two_d, int64_t K, int lik, const double* params,
+                              const int64_t* seg_offsets, const float* w, const float* y, const float* h, const float* states,
+                              const float* u_post, int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile,
+                              void* workspace, size_t workspace_bytes, float* log_lik, float* g_u, void* stream) {
+    return run_iw<float>(B, N, S, two_d, K, lik, params, seg_offsets, w, y, h, states, u_post, num_tiles, tile_seg, seg_tile,
+                         workspace, workspace_bytes, log_lik, g_u, stream);
+}
 
 size_t mf_lik_sparse_expectations_workspace_bytes(int64_t num_tiles, int two_d, int elem_size) {
     if (num_tiles <= 0 || two_d < 2 || two_d > 18 || (two_d & 1) || elem_size < 1) return 0;

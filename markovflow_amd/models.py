@@ -23,6 +23,10 @@ the bracketing pair, expectations, back-projection and the segmented sum).
 ``SparseVariationalGaussianProcess`` (mirror of ``markovflow/models/sparse_variational.py:31-270``, zero mean function) holds ``q`` on
 the inducing points as a trainable ``StateSpaceModel``; the data term of its ELBO and the adjoint onto the pair marginals of ``q`` are
 ONE call of ``mf_lik_sparse_expectations_*`` (two passes, tile-parallel), the KL term is ``StateSpaceModel.kl_divergence``.
+
+``ImportanceWeightedVI`` (mirror of ``markovflow/models/iwvi.py:29-173``, zero mean function) subclasses it: ``K`` proposals drawn by
+Matheron's rule, whose assembly from one prior draw, the ``K`` evaluations of ``log p(y_n | f_n)`` at every data point and the adjoint
+onto the draw from ``q`` are ONE call of ``mf_lik_iw_log_weights_*`` (two passes, tile-parallel, no atomics).
 """
 from typing import Optional, Tuple
 
@@ -35,7 +39,7 @@ from . import _lib, conditionals
 from .kalman_filter import KalmanFilter, KalmanFilterWithSites, UnivariateGaussianSitesNat
 from .kernels import IndependentMultiOutput, SDEKernel, _MaternBase, _version_key
 from .likelihoods import Gaussian, Likelihood, torch_log_expected_density
-from .posterior import AnalyticPosteriorProcess, ConditionalProcess
+from .posterior import AnalyticPosteriorProcess, ConditionalProcess, ImportanceWeightedPosteriorProcess
 from .ssm_gaussian_transformations import naturals_to_ssm_params
 from .state_space_model import StateSpaceModel
 
@@ -1508,3 +1512,205 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
             return self._posterior.predict_f(new_time_points, full_output_cov)
 
     _predict_f = predict_f          # (``predict_log_density`` predicts outside the tape here, as ``predict_f`` does)
+
+
+# ---- importance-weighted VI: the data term of the log weights ----------------------------------------------------------------------
+IW_SAMPLE_CHUNK = 8             # mf_lik_iw_log_weights_*: samples per block of pass 1
+
+
+def _segments_of(offsets: torch.Tensor, n: int) -> torch.Tensor:
+    """The segment of every point ``0 ... n - 1`` from the segment ``offsets [.., S + 1]``: the number of inner offsets ``<= n``."""
+    points = torch.arange(n, device=offsets.device).expand(tuple(offsets.shape[:-1]) + (n,)).contiguous()
+    return torch.searchsorted(offsets[..., 1:-1].contiguous(), points, right=True)
+
+
+def iw_merged_time_points(time_points_sorted: torch.Tensor, inducing_points: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+    """The merged, sorted time points ``[.., N + M]`` of the data (``[.., N]``, sorted) and the inducing points (``[.., M]``) in the
+    layout of ``mf_lik_iw_log_weights_*``: data point ``n`` of segment ``s`` at row ``n + s``, inducing point ``m`` at row
+    ``offsets[m + 1] + m`` (``offsets [.., M + 2]`` of ``sparse_site_projections``: points with ``x <= z_m`` precede ``z_m``).  Two
+    scatters, no argsort."""
+    n, m = time_points_sorted.shape[-1], inducing_points.shape[-1]
+    rows_x = torch.arange(n, device=offsets.device) + _segments_of(offsets, n)
+    rows_z = offsets[..., 1:-1] + torch.arange(m, device=offsets.device)
+    merged = torch.empty(tuple(offsets.shape[:-1]) + (n + m,), dtype=inducing_points.dtype, device=inducing_points.device)
+    merged.scatter_(-1, rows_x, time_points_sorted.to(inducing_points.dtype))
+    merged.scatter_(-1, rows_z, inducing_points)
+    return merged
+
+
+def _iw_log_weights_launch(likelihood: Likelihood, h, w, y, offsets, tiles, states, u_post, want_value: bool, want_grad: bool):
+    """ONE call of ``mf_lik_iw_log_weights_*``: ``(log_lik [K, .., S] | None, g_u [K, .., M, d] | None)``."""
+    dtype, dev = states.dtype, states.device
+    k, d, segs = states.shape[0], states.shape[-1], offsets.shape[-1] - 1
+    n = y.shape[-1]
+    batch = tuple(offsets.shape[:-1])
+    bsz = offsets.numel() // (segs + 1)
+    num_tiles, tile_seg, seg_tile = tiles
+    log_lik = torch.empty((k,) + batch + (segs,), dtype=dtype, device=dev) if want_value else None
+    g_u = torch.empty((k,) + batch + (segs - 1, d), dtype=dtype, device=dev) if want_grad else None
+    ws_bytes = int(_lib.load().mf_lik_iw_log_weights_workspace_bytes(num_tiles, k, 2 * d, states.element_size()))
+    ws = _lib.workspace(ws_bytes, dev)
+    _lib.call("mf_lik_iw_log_weights", dtype, bsz, n, segs, 2 * d, k, likelihood._id, likelihood._c_params(),
+              _lib.ptr(offsets.contiguous()), _lib.ptr(None if w is None else w.contiguous()), _lib.ptr(y.contiguous()),
+              _lib.ptr(h.contiguous()), _lib.ptr(states.contiguous()), _lib.ptr(None if u_post is None else u_post.contiguous()),
+              num_tiles, _lib.ptr(tile_seg), _lib.ptr(seg_tile), _lib.ptr(ws), ws_bytes, _lib.ptr(log_lik), _lib.ptr(g_u),
+              _lib.stream_ptr(dev))
+    return log_lik, g_u
+
+
+class _IWLogLikelihood(torch.autograd.Function):
+    """Value ``[K, batch...]``; the adjoint onto ``u_post`` comes out of the same launch and waits for the backward."""
+
+    @staticmethod
+    def forward(ctx, u_post, likelihood, h, w, y, offsets, tiles, states):
+        want = ctx.needs_input_grad[0]
+        with torch.no_grad():
+            log_lik, g_u = _iw_log_weights_launch(likelihood, h.detach(), w.detach(), y.detach(), offsets, tiles, states.detach(),
+                                                  u_post.detach(), True, want)
+        if want:
+            ctx.save_for_backward(g_u)
+        return torch.sum(log_lik, dim=-1)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if torch.is_grad_enabled():
+            raise RuntimeError("iw_log_likelihood is differentiable once: its backward uses the adjoint computed in the forward and "
+                               "has no second-order support (create_graph=True)")
+        (g_u,) = ctx.saved_tensors
+        return (grad_out[..., None, None] * g_u,) + (None,) * 7
+
+
+def iw_log_likelihood(likelihood: Likelihood, h: torch.Tensor, w: Optional[torch.Tensor], y: torch.Tensor, offsets: torch.Tensor,
+                      states: torch.Tensor, u_post: Optional[torch.Tensor], tiles=None) -> torch.Tensor:
+    """``sum_n log p(y_n | f_n)`` of ``K`` samples, ``[K, batch...]``: ONE call of ``mf_lik_iw_log_weights_*`` on HIP tensors, ``2d <= 18``.
+    With ``u_post [K, .., M, d]`` (a draw from ``q`` at the inducing points) ``states [K, .., N + M, d]`` is a prior draw on
+    ``iw_merged_time_points`` and the kernel applies Matheron's correction through ``w [.., N, 2d]`` (``sparse_site_projections``),
+    ``f_n = h . prior(x_n) - w[n, :d] . (prior(z_-) - u_-) - w[n, d:] . (prior(z_+) - u_+)``; ``u_post`` = None: ``states [K, .., N, d]`` holds
+    final samples (``w`` is not read).  ``h [d]`` is the emission row, ``y [.., N]``, ``offsets [.., M + 2]``.  Differentiable ONCE in
+    ``u_post`` - the backward multiplies the adjoint the forward computed beside the value, there is no second launch; not
+    differentiable in ``states``, ``w`` and ``h``.  ``tiles``: ``sparse_expectation_tiles(offsets)`` when the caller keeps it."""
+    if not isinstance(likelihood, Likelihood):
+        raise TypeError("likelihood must be a markovflow_amd.likelihoods.Likelihood")
+    d, segs = states.shape[-1], offsets.shape[-1] - 1
+    batch, k, n = tuple(offsets.shape[:-1]), states.shape[0], y.shape[-1]
+    if 2 * d > SPARSE_SITE_MAX_TWO_D:
+        raise NotImplementedError(f"iw_log_likelihood: 2d = {2 * d} is outside 2, 4, ..., {SPARSE_SITE_MAX_TWO_D}; use "
+                                  "iw_log_likelihood_torch")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (states, w, h)):
+        raise NotImplementedError("iw_log_likelihood has no adjoint onto states, w and h (a kernel hyper-parameter under the tape): "
+                                  "use iw_log_likelihood_torch")
+    rows = n if u_post is None else n + segs - 1
+    expect = dict(h=(h, (d,)), y=(y, batch + (n,)), states=(states, (k,) + batch + (rows, d)))
+    if u_post is not None:
+        expect.update(w=(w, batch + (n, 2 * d)), u_post=(u_post, (k,) + batch + (segs - 1, d)))
+    for name, (t, shape) in expect.items():
+        if t is None or tuple(t.shape) != shape:
+            raise ValueError(f"iw_log_likelihood: {name} has shape {None if t is None else tuple(t.shape)}, expected {shape}")
+    _lib.same_dtype_device(states, "iw_log_likelihood", h=h, w=w if u_post is not None else None, y=y, u_post=u_post)
+    if tiles is None:
+        tiles = sparse_expectation_tiles(offsets)
+    if u_post is None:
+        with torch.no_grad():
+            return torch.sum(_iw_log_weights_launch(likelihood, h, None, y, offsets, tiles, states, None, True, False)[0], dim=-1)
+    return _IWLogLikelihood.apply(u_post, likelihood, h, w, y, offsets, tiles, states)
+
+
+def iw_log_likelihood_torch(likelihood: Likelihood, h: torch.Tensor, w: Optional[torch.Tensor], y: torch.Tensor,
+                            indices: Optional[torch.Tensor], states: torch.Tensor, u_post: Optional[torch.Tensor]) -> torch.Tensor:
+    """The same quantity as a torch composition, differentiable by autograd in everything: gathers of the data rows and the inducing
+    rows of the prior draw (from ``indices [.., N]``, the pair every point belongs to), the two ``w . delta`` products, the emission
+    product and ``likelihood.log_prob``.  It runs on CPU tensors, it is the models' route for ``2d > 18`` and for a kernel
+    hyper-parameter under the tape, and it is what ``mf_lik_iw_log_weights_*`` is measured against."""
+    d, n = states.shape[-1], y.shape[-1]
+    lead = (states.shape[0],) + tuple(y.shape[:-1])
+    if u_post is None:
+        f = torch.sum(states * h, dim=-1)
+    else:
+        m = u_post.shape[-2]
+        z_index = torch.arange(m, device=indices.device).expand(tuple(indices.shape[:-1]) + (m,)).contiguous()
+        rows_z = torch.searchsorted(indices.contiguous(), z_index, right=True) + z_index          # offsets[m + 1] + m
+        rows_x = indices + torch.arange(n, device=indices.device)
+        pick = lambda src, idx: torch.gather(src, -2, idx.expand(lead + (idx.shape[-1],))[..., None].expand(lead + (idx.shape[-1], d)))  # noqa: E731
+        delta = pick(states, rows_z) - u_post
+        pad = torch.zeros_like(delta[..., :1, :])
+        delta = torch.cat([pad, delta, pad], dim=-2)          # beyond both ends the correction vanishes
+        f = (torch.sum(pick(states, rows_x) * h, dim=-1) - torch.sum(w[..., :d] * pick(delta, indices), dim=-1)
+             - torch.sum(w[..., d:] * pick(delta, indices + 1), dim=-1))
+    return torch.sum(likelihood.log_prob(f[..., None], y.expand(lead + (n,))[..., None]), dim=-1)
+
+
+class ImportanceWeightedVI(SparseVariationalGaussianProcess):
+    """Importance-weighted VI (markovflow/models/iwvi.py:29-173; Domke and Sheldon 2018; zero mean function): the SVGP model with the
+    bound ``L_K = log (1/K) sum_k w_k``, ``w_k = p(y | s_k) p(u_k) / q(u_k)``, ``(s_k, u_k) ~ q(u) p(s | u)``, which tightens with
+    ``K`` towards ``log p(y)``.  The proposals are drawn by Matheron's rule; on HIP tensors with ``2d <= 18`` and no kernel
+    hyper-parameter under the tape their assembly, the ``K`` evaluations of the likelihood at every data point and the adjoint onto
+    the draw from ``q`` are ONE call of ``mf_lik_iw_log_weights_*``."""
+
+    def __init__(self, kernel: SDEKernel, inducing_points: torch.Tensor, likelihood: Likelihood, num_importance_samples: int,
+                 initial_distribution: Optional[StateSpaceModel] = None) -> None:
+        super().__init__(kernel, likelihood, inducing_points, None, initial_distribution)
+        self._posterior = ImportanceWeightedPosteriorProcess(num_importance_samples, self._dist_q, kernel, inducing_points, likelihood)
+        self._merged_cache = None
+
+    @property
+    def posterior(self) -> ImportanceWeightedPosteriorProcess:
+        return self._posterior
+
+    def predict_f(self, new_time_points: torch.Tensor, full_output_cov: bool = False):
+        """Not available in closed form (posterior.py:772-786): use ``posterior.expected_value`` or ``posterior.sample_f``."""
+        return self._posterior.predict_f(new_time_points, full_output_cov)
+
+    _predict_f = predict_f
+
+    def _merged(self, projections, time_points: torch.Tensor) -> torch.Tensor:
+        """``iw_merged_time_points`` of the (sorted) data, kept as long as the cached projections are."""
+        cached = self._merged_cache
+        if cached is not None and cached[0] is projections:
+            return cached[1]
+        order, offsets = projections[0], projections[4]
+        with torch.no_grad():
+            x = time_points if order is None else torch.gather(time_points, -1, order)
+            merged = iw_merged_time_points(x, self.inducing_inputs, offsets)
+        self._merged_cache = (projections, merged)
+        return merged
+
+    def log_weights(self, input_data: Tuple[torch.Tensor, torch.Tensor], stop_gradient: bool = False, what: str = "log_weights"
+                    ) -> torch.Tensor:
+        """``log w_k``, ``[K]``, summed over the batch - the batch is one model, as in the SVGP ``elbo``: one prior draw on the merged
+        time points, one (reparameterised) draw from ``q``, the data term and ``log p(u) - log q(u)``.  Both routes make the same
+        two draws in the same order."""
+        time_points, observations = self._check_data(input_data, what)
+        k = self._posterior.num_importance_samples
+        projections = self._projections(time_points)
+        order, w, _, indices, offsets, tiles = projections
+        merged = self._merged(projections, time_points)
+        y = observations[..., 0]
+        if order is not None:
+            y = torch.gather(y, -1, order)
+        h = self._kernel.generate_emission_model(merged[..., :1]).emission_matrix.reshape(-1, self._kernel.state_dim)[0]
+        fused = self._fused(time_points)
+        if not fused and self._kernel._needs_grad():
+            # a hyper-parameter under the tape: w is part of the graph
+            x = time_points if order is None else torch.gather(time_points, -1, order)
+            proj, _, indices = conditionals._conditional_statistics(x, self.inducing_inputs, self._kernel)
+            w = (self._kernel.generate_emission_model(x).emission_matrix @ proj)[..., 0, :]
+        prior = self._kernel.state_space_model(merged).sample((k,))
+        u_post = self._dist_q.sample((k,))
+        if fused:
+            log_lik = iw_log_likelihood(self._likelihood, h, w, y, offsets, prior, u_post, tiles=tiles)
+        else:
+            log_lik = iw_log_likelihood_torch(self._likelihood, h, w, y, indices, prior, u_post)
+        log_w = log_lik + self._posterior._log_density_ratio(u_post, stop_gradient)
+        return torch.sum(log_w.reshape(k, -1), dim=-1)
+
+    def elbo(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+        """``logsumexp_k(log w_k) - log K`` (iwvi.py:109-141): a stochastic lower bound of ``log p(y)``, tighter than the SVGP ELBO for
+        ``K > 1``.  The data need not be sorted (a stable argsort on a copy, cached with the projections)."""
+        log_w = self.log_weights(input_data, False, "elbo")
+        return torch.logsumexp(log_w, dim=0) - math.log(log_w.shape[0])
+
+    def dregs_objective(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+        """A scalar whose gradient is the doubly-reparameterised (DReG) estimator (iwvi.py:143-173): ``sum_k stop_grad(softmax(log w))_k^2
+        log w_k`` with ``q`` stopped inside ``log q(u)`` only - for the variational parameters; ``elbo`` for the hyper-parameters."""
+        log_w = self.log_weights(input_data, True, "dregs_objective")
+        return torch.sum(torch.square(torch.softmax(log_w, dim=0).detach()) * log_w)

@@ -180,3 +180,107 @@ class AnalyticPosteriorProcess(ConditionalProcess):
             return f_mean, f_cov
         noise = self._chol_obs_covariance @ self._chol_obs_covariance.transpose(-1, -2)
         return f_mean, f_cov + (noise if full_output_cov else torch.diagonal(noise, dim1=-2, dim2=-1))
+
+
+class ImportanceWeightedPosteriorProcess:
+    """The approximate posterior process of importance-weighted VI (posterior.py:471-786; zero mean function): proposals
+    ``(s, u) ~ q(u) p(s | u)`` from a ``ConditionalProcess``, weighted by ``w = p(Y | s) p(u) / q(u)``.  The data term of the log
+    weights of samples that are already final is ONE call of ``mf_lik_iw_log_weights_*`` (its mode without ``u_post``) on HIP
+    tensors outside the tape, ``likelihood.log_prob`` in torch otherwise; ``log p(u)`` and ``log q(u)`` are ``StateSpaceModel.log_pdf``."""
+
+    def __init__(self, num_importance_samples: int, proposal_dist: GaussMarkovDistribution, kernel: SDEKernel,
+                 conditioning_time_points: torch.Tensor, likelihood) -> None:
+        from .likelihoods import Likelihood
+        if isinstance(num_importance_samples, bool) or int(num_importance_samples) != num_importance_samples or num_importance_samples < 1:
+            raise ValueError(f"num_importance_samples must be a positive integer, got {num_importance_samples}")
+        if not isinstance(likelihood, Likelihood):
+            raise TypeError("likelihood must be a markovflow_amd.likelihoods.Likelihood")
+        self.proposal_process = ConditionalProcess(proposal_dist, kernel, conditioning_time_points)
+        self.num_importance_samples = int(num_importance_samples)
+        self.likelihood = likelihood
+
+    def _log_density_ratio(self, samples_u: torch.Tensor, stop_gradient: bool = False) -> torch.Tensor:
+        """``log p(u) - log q(u)``, ``sample_shape + batch``; ``stop_gradient``: ``q`` is a non-trainable copy, so that no gradient
+        reaches its parameters through the density itself (posterior.py:504-520) - the samples keep theirs."""
+        proc = self.proposal_process
+        dist_q = proc.gauss_markov_model.create_non_trainable_copy() if stop_gradient else proc.gauss_markov_model
+        dist_p = proc.kernel.state_space_model(proc.conditioning_time_points)
+        return dist_p.log_pdf(samples_u) - dist_q.log_pdf(samples_u)
+
+    def log_importance_weights(self, samples_s: torch.Tensor, samples_u: torch.Tensor, input_data: Tuple[torch.Tensor, torch.Tensor],
+                               stop_gradient: bool = False) -> torch.Tensor:
+        """``log w = log p(Y | s) + log p(u) - log q(u)``, summed over the data and the batch: ``sample_shape`` (posterior.py:522-580).
+        ``samples_s``: ``sample_shape + batch + [num_data, d]`` at the time points of ``input_data`` (in their order), ``samples_u``:
+        ``sample_shape + batch + [num_inducing, d]``."""
+        from . import models
+        time_points, observations = input_data
+        batch = tuple(time_points.shape[:-1])
+        n, d = time_points.shape[-1], samples_s.shape[-1]
+        if tuple(samples_s.shape[-len(batch) - 2:]) != batch + (n, d) or tuple(observations.shape) != batch + (n, 1):
+            raise ValueError(f"log_importance_weights: samples_s has shape {tuple(samples_s.shape)} and the observations "
+                             f"{tuple(observations.shape)}, expected sample_shape + {batch + (n, d)} and {batch + (n, 1)}")
+        shape = tuple(samples_s.shape[:samples_s.dim() - len(batch) - 2])
+        h = self.proposal_process.kernel.generate_emission_model(time_points[..., :1]).emission_matrix.reshape(-1, d)[0]
+        y = observations[..., 0]
+        taped = torch.is_grad_enabled() and samples_s.requires_grad
+        flat = samples_s.reshape((-1,) + batch + (n, d))
+        if samples_s.is_cuda and not taped and 2 * d <= models.SPARSE_SITE_MAX_TWO_D:
+            offsets = torch.tensor([0, n], dtype=torch.int64, device=time_points.device).expand(batch + (2,)).contiguous()
+            log_lik = models.iw_log_likelihood(self.likelihood, h, None, y, offsets, flat.detach(), None)
+        else:
+            log_lik = models.iw_log_likelihood_torch(self.likelihood, h, None, y, None, flat, None)
+        log_w = log_lik.reshape(shape + batch) + self._log_density_ratio(samples_u, stop_gradient)
+        return torch.sum(log_w, dim=tuple(range(len(shape), len(shape) + len(batch)))) if batch else log_w
+
+    def _iwvi_samples_and_weights(self, new_time_points: torch.Tensor, input_data, sample_shape):
+        """Proposals at ``new_time_points`` with their log weights (posterior.py:582-621): ``(sample_shape + batch + [num_new, d],
+        sample_shape, sample_shape + batch + [num_inducing, d])``."""
+        if input_data is None:
+            raise ValueError("You need to provide `input_data` for doing inference with IW")
+        all_points = torch.cat([input_data[0], new_time_points.to(input_data[0].dtype)], dim=-1)
+        samples_s, samples_u = self.proposal_process.sample_state_trajectories(all_points, sample_shape)
+        num_new = new_time_points.shape[-1]
+        log_weights = self.log_importance_weights(samples_s[..., :all_points.shape[-1] - num_new, :], samples_u, input_data)
+        return samples_s[..., all_points.shape[-1] - num_new:, :], log_weights, samples_u
+
+    def sample_state_trajectories(self, new_time_points: torch.Tensor, sample_shape: Union[int, Sequence[int]],
+                                  *, input_data=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Samples of the importance-weighted posterior over states: per requested sample, ``num_importance_samples`` proposals and
+        one categorical draw among them by their weights (posterior.py:623-674).  Returns ``(sample_shape + batch + [num_new, d],
+        sample_shape + [num_importance_samples] + batch + [num_inducing, d])``."""
+        if input_data is None:
+            raise ValueError("You need to provide `input_data` for doing inference with IW")
+        shape = (sample_shape,) if isinstance(sample_shape, int) else tuple(sample_shape)
+        k = self.num_importance_samples
+        samples, log_weights, conditioning = self._iwvi_samples_and_weights(new_time_points, input_data, shape + (k,))
+        tail = tuple(samples.shape[len(shape) + 1:])
+        flat = samples.reshape((-1, k) + tail)
+        probs = torch.softmax(log_weights.reshape(-1, k), dim=-1)
+        pick = torch.multinomial(probs, 1)[:, 0]
+        chosen = flat[torch.arange(flat.shape[0], device=flat.device), pick]
+        return chosen.reshape(shape + tail), conditioning
+
+    def sample_state(self, new_time_points: torch.Tensor, sample_shape, *, input_data=None) -> torch.Tensor:
+        """State samples at ``new_time_points``, ``sample_shape + batch + [num_new, d]``."""
+        return self.sample_state_trajectories(new_time_points, sample_shape, input_data=input_data)[0]
+
+    def sample_f(self, new_time_points: torch.Tensor, sample_shape, *, input_data=None) -> torch.Tensor:
+        """Function samples, ``sample_shape + batch + [num_new, output_dim]`` (posterior.py:676-706)."""
+        if input_data is None:
+            raise ValueError("You need to provide `input_data` for doing inference with IW")
+        states = self.sample_state(new_time_points, sample_shape, input_data=input_data)
+        return self.proposal_process.kernel.generate_emission_model(new_time_points).project_state_to_f(states)
+
+    def expected_value(self, new_time_points: torch.Tensor, input_data, func=lambda f: f) -> torch.Tensor:
+        """``sum_k softmax(log w)_k func(f_k)`` at ``new_time_points`` from ``num_importance_samples`` proposals
+        (posterior.py:708-758); ``func`` acts on the last dimension."""
+        samples, log_weights, _ = self._iwvi_samples_and_weights(new_time_points, input_data, (self.num_importance_samples,))
+        weights = torch.softmax(log_weights, dim=0)
+        values = func(self.proposal_process.kernel.generate_emission_model(new_time_points).project_state_to_f(samples))
+        return torch.sum(weights.reshape((-1,) + (1,) * (values.dim() - 1)) * values, dim=0)
+
+    def predict_state(self, new_time_points: torch.Tensor):
+        raise NotImplementedError("The marginal state predictions are not available in closed form.")
+
+    def predict_f(self, new_time_points: torch.Tensor, full_output_cov: bool = False):
+        raise NotImplementedError("The marginal function predictions are not available in closed form.")

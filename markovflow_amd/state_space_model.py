@@ -348,11 +348,20 @@ class StateSpaceModel(GaussMarkovDistribution):
         d = self.state_dim
 
         def mvn_tril(loc, tril, x):
-            diff = (x - loc)[..., None]
-            tril_b = tril.expand(diff.shape[:-2] + tril.shape[-2:])
-            z = torch.linalg.solve_triangular(tril_b, diff, upper=False)[..., 0]
+            diff = x - loc
+            lead = diff.dim() - (tril.dim() - 1)               # leading sample dimensions that the factors do not have
             logdet = torch.sum(torch.log(torch.abs(torch.diagonal(tril, dim1=-2, dim2=-1))), dim=-1)
-            return -0.5 * torch.sum(z * z, dim=-1) - logdet - 0.5 * d * math.log(2 * math.pi)
+            if lead > 0 and tuple(diff.shape[lead:-1]) == tuple(tril.shape[:-2]):
+                # the samples are the right-hand-side columns of ONE triangular solve per factor, not one solve per (sample, factor):
+                # K = 16 samples of a [64, 100] chain are 6 400 solves with 16 columns instead of 102 400 with one
+                cols = diff.reshape((-1,) + tuple(diff.shape[lead:])).movedim(0, -1)
+                z = torch.linalg.solve_triangular(tril, cols, upper=False)
+                quad = torch.sum(z * z, dim=-2).movedim(-1, 0).reshape(diff.shape[:-1])
+            else:
+                tril_b = tril.expand(diff.shape[:-1] + tril.shape[-2:])
+                z = torch.linalg.solve_triangular(tril_b, diff[..., None], upper=False)[..., 0]
+                quad = torch.sum(z * z, dim=-1)
+            return -0.5 * quad - logdet - 0.5 * d * math.log(2 * math.pi)
 
         init = mvn_tril(self._mu_0, self._chol_P_0, states[..., 0, :])
         cond = torch.matmul(self._A_s, states[..., :-1, :, None])[..., 0] + self._b_s
