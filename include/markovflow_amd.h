@@ -916,6 +916,53 @@ int mf_lik_iw_log_weights_f32(int64_t B, int64_t N, int64_t S, int two_d, int64_
                               const float* u_post, int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile,
                               void* workspace, size_t workspace_bytes, float* log_lik, float* g_u, void* stream);
 
+/*
+ * The data term of the VGP ELBO (markovflow/models/variational.py:129-152; csrc/mf_lik.hip), dense: q lives on the states at the data
+ * points themselves, so point k of series b has its own emission row h [B, N, d], marginal mean means [B, N, d] and marginal
+ * covariance covs [B, N, d, d].  1 <= d <= 12; the likelihood and the rule as for mf_lik_variational_expectations; y [B, N].
+ * Per point:  fmu = h_k . m_k,  fvar = sum_i h_i (sum_j P_ij h_j) - the FULL matrix is read, both triangles, so the adjoint for an
+ * unconstrained P is g_var h h^T -,  (ve, gm, gv) as mf_lik_variational_expectations;
+ *   ve_sum [B]      sum_k ve_k
+ *   g_mu   [B, N]   gm_k = d ve_k / d fmu_k          the compact form of the adjoint: 2 values per point, not d^2 + d;
+ *   g_var  [B, N]   gv_k = d ve_k / d fvar_k         mf_lik_dense_expectations_adjoint_* expands them
+ * g_mu and g_var BOTH NULL: the value only (the same bits); ve_sum may be NULL beside the gradients (no workspace is needed then).
+ * THE ORDER OF THE SUMS, part of the contract: every sum starts from 0 and grows term by term, index ascending -
+ *   t_i = sum_j P_ij h_j in j,  fvar = sum_i h_i t_i and fmu = sum_i h_i m_i in i,
+ *   a TILE - points 64 t ... 64 t + 63 of a series - in its points (pass 1: one wavefront per tile, one partial per tile in the
+ *   workspace), a series in its tiles (pass 2).  These two sums run in a double accumulator in float32 as well and are rounded once
+ *   each, into the partial and into ve_sum.
+ * No floating-point atomics: the same bits on every launch and for a series alone or inside a batch.  The workspace holds
+ * mf_lik_dense_expectations_workspace_bytes(B, N, sizeof(T)) = B ceil(N / 64) sizeof(T) bytes (0 when B or N is 0).  A point with
+ * fvar <= 0 or NaN makes ITS series' ve_sum and its own g_mu, g_var NaN; no other series or point changes.  N = 0 gives zeros.
+ * No allocation, no synchronisation.
+ * Returns 0, -(position of the offending argument in THIS signature: 1 B, 2 N (negative, or more than 2^31 - 1 tiles), 4 lik,
+ * 5 params, 6 nq, 7 nodes, 8 weights, 9 ... 12 a NULL input, 13 a NULL workspace, 14 a workspace that is too small, 16 / 17 one of
+ * g_mu / g_var NULL without the other), -100 for a d outside 1 ... 12, or -1000 (launch failed).  Nothing is launched on an error,
+ * for B = 0, or when every output is NULL.
+ */
+size_t mf_lik_dense_expectations_workspace_bytes(int64_t B, int64_t N, int elem_size);
+int mf_lik_dense_expectations_f64(int64_t B, int64_t N, int d, int lik, const double* params, int nq, const double* nodes,
+                                  const double* weights, const double* h, const double* means, const double* covs, const double* y,
+                                  void* workspace, size_t workspace_bytes, double* ve_sum, double* g_mu, double* g_var,
+                                  void* stream);
+int mf_lik_dense_expectations_f32(int64_t B, int64_t N, int d, int lik, const double* params, int nq, const double* nodes,
+                                  const double* weights, const float* h, const float* means, const float* covs, const float* y,
+                                  void* workspace, size_t workspace_bytes, float* ve_sum, float* g_mu, float* g_var, void* stream);
+
+/*
+ * The expansion of that adjoint onto the marginals, what mf_ssm_marginals_grad_* takes as g_means / g_covs (csrc/mf_lik.hip):
+ *   g_means [B, N, d]      (weight_b g_mu[b, k]) h[b, k, i]
+ *   g_covs  [B, N, d, d]   (weight_b (g_var[b, k] h[b, k, i])) h[b, k, j]
+ * weight [B] is the incoming gradient of ve_sum; NULL means 1, with the bits a vector of ones gives.  One launch, store-bound:
+ * consecutive lanes write consecutive elements.  Either output may be NULL.  1 <= d <= 12.
+ * Returns 0, -(position: 1 B, 2 N, 4 h, 5 g_mu NULL beside g_means, 6 g_var NULL beside g_covs), -100 for a d outside 1 ... 12, or
+ * -1000 (launch failed).  Nothing is launched on an error, for B = 0 or N = 0, or when both outputs are NULL.
+ */
+int mf_lik_dense_expectations_adjoint_f64(int64_t B, int64_t N, int d, const double* h, const double* g_mu, const double* g_var,
+                                          const double* weight, double* g_means, double* g_covs, void* stream);
+int mf_lik_dense_expectations_adjoint_f32(int64_t B, int64_t N, int d, const float* h, const float* g_mu, const float* g_var,
+                                          const float* weight, float* g_means, float* g_covs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,8 @@ from .kernels import (Constant, HarmonicOscillator, IndependentMultiOutput, Mate
                       StationaryKernel, Sum)
 from .likelihoods import Bernoulli, Gaussian, Likelihood, Poisson, StudentT
 from .models import (CVIGaussianProcess, GaussianProcessRegression, ImportanceWeightedVI, PowerExpectationPropagation,
-                     SparseCVIGaussianProcess, SparsePowerExpectationPropagation, SparseVariationalGaussianProcess)
+                     SparseCVIGaussianProcess, SparsePowerExpectationPropagation, SparseVariationalGaussianProcess,
+                     VariationalGaussianProcess)
 from .ssm_natgrad import SSMNaturalGradient
 from .posterior import AnalyticPosteriorProcess, ConditionalProcess, ImportanceWeightedPosteriorProcess
 from ._lib import MarkovflowAmdError, check_errors, errors_as_nan, set_synchronous_checks
@@ -37,4 +38,5 @@ __all__ = [
     "likelihoods", "Likelihood", "Gaussian", "Bernoulli", "Poisson", "StudentT", "CVIGaussianProcess", "PowerExpectationPropagation",
     "SparseCVIGaussianProcess", "SparseVariationalGaussianProcess", "SSMNaturalGradient", "ssm_natgrad",
     "SparsePowerExpectationPropagation", "ImportanceWeightedVI", "ImportanceWeightedPosteriorProcess",
+    "VariationalGaussianProcess",
 ]

@@ -82,6 +82,9 @@ _SIGS = {
                                       "Tp", "Tp", _i64, _vp, _vp, _vp, _sz, "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_iw_log_weights": (_int, [_i64, _i64, _i64, _int, _i64, _int, _hd, _vp, "Tp", "Tp", "Tp", "Tp", "Tp", _i64, _vp, _vp, _vp,
                                      _sz, "Tp", "Tp", _vp]),
+    "mf_lik_dense_expectations": (_int, [_i64, _i64, _int, _int, _hd, _int, _hd, _hd, "Tp", "Tp", "Tp", "Tp", _vp, _sz, "Tp", "Tp", "Tp",
+                                         _vp]),
+    "mf_lik_dense_expectations_adjoint": (_int, [_i64, _i64, _int, "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
 }
 _PLAIN = {
     "mf_version": (_int, []),
@@ -112,6 +115,7 @@ _PLAIN = {
     "mf_btd_grad_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
     "mf_lik_sparse_expectations_workspace_bytes": (_sz, [_i64, _int, _int]),
     "mf_lik_iw_log_weights_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
+    "mf_lik_dense_expectations_workspace_bytes": (_sz, [_i64, _i64, _int]),
 }
 
 _lib = None

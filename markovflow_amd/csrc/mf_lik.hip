@@ -13,6 +13,8 @@
 // Importance-weighted VI (markovflow/models/iwvi.py) adds the data term of the log importance weights: log p(y | f) itself, at K
 // Monte-Carlo samples per point that are assembled in the kernel from one prior draw (no quadrature), with the adjoint onto the draw
 // from q at the inducing points.
+// The variational GP (markovflow/models/variational.py) adds the dense form of the ELBO's data term: every point has its own marginal
+// and emission row, two derivatives per point are kept, and a second kernel expands them onto the marginals.
 // One lane per data point; the rule travels by value in the kernel arguments and the loop over its nodes is wavefront-uniform, so
 // nodes and weights are scalar loads; no LDS, no cross-lane traffic, no temporaries in memory.
 #include "../../include/markovflow_amd.h"
@@ -869,6 +871,132 @@ __global__ void __launch_bounds__(256) iw_reduce_kernel(long num_tiles, int S, l
     }
 }
 
+// ---- VGP: the dense (unsegmented) expected log-likelihood and its adjoint onto the marginals of q (markovflow/models/variational.py
+// :129-152, the data term of the ELBO) --------------------------------------------------------------------------------------------
+// q lives on the states at the data points themselves: point k of series b has its own marginal (m_k [d], P_k [d, d]) and its own
+// emission row h_k [d].  Two passes, tile-parallel; tile t of a series is its points 64 t ... 64 t + 63, so no table is needed.
+//   pass 1, one wavefront per tile.  The tile's h, means and covs are CONTIGUOUS runs of 64 d, 64 d and 64 d^2 elements: they come in
+//            with consecutive lanes on consecutive elements and pass through LDS at the odd row stride d | 1 (a row = d elements:
+//            one point's h or m, one ROW of one point's P), so that lanes on consecutive rows start on distinct banks.  covs comes
+//            in slabs of DENSE_SLAB_BYTES at the most (whole points: 64, 32, 16 or 8 of them), which bounds the LDS of a block
+//            whatever d.  Per slab a lane per (point, row i): t_i = sum_j P_ij h_j into LDS.  Then a lane per point:
+//            fmu = sum_i h_i m_i, fvar = sum_i h_i t_i, the expectations, g_mu and g_var stored (coalesced), ve through LDS to
+//            lane 0, which adds the tile's points in ascending order and leaves ONE partial in the workspace.
+//   pass 2, one lane per series: the series' partials are added in ascending tile order.  N = 0 writes zeros.
+// THE ORDER OF THE SUMS IS PART OF THE CONTRACT (the float32 test helper repeats it): every sum starts from 0 and grows term by
+// term with its index ascending - t_i in j, fmu and fvar in i (the full matrix is read, both triangles), a tile in its points, a
+// series in its tiles; the last two run in a double accumulator in float32 too (one rounding into the workspace, one into ve_sum:
+// a series of 10^4 points adds 157 partials, which a float accumulator would round 157 times).  No atomics: the same bits on every
+// launch, for a series alone or inside a batch, with or without the gradients.  A point outside the domain (fvar <= 0 or NaN) leaves NaN in its g_mu, g_var and in its series' sum, nowhere else.
+constexpr int DENSE_MAX_D = 12;
+constexpr int DENSE_SLAB_BYTES = 16384;
+
+// points per slab of covs: the most of 64, 32, 16, 8 whose padded rows fit DENSE_SLAB_BYTES (d = 12 in float64: 8 points, 9984 B)
+template <typename T, int D>
+constexpr int dense_slab_points() {
+    int sp = 64;
+    while (sp > 8 && size_t(sp) * D * (D | 1) * sizeof(T) > size_t(DENSE_SLAB_BYTES)) sp /= 2;
+    return sp;
+}
+
+template <typename T, int LIK, int D>
+__global__ void __launch_bounds__(64) dense_expect_tile_kernel(long N, long tiles_per_series, Rule<T> q, Par<T> p,
+                                                               const T* __restrict__ h, const T* __restrict__ means,
+                                                               const T* __restrict__ covs, const T* __restrict__ yobs,
+                                                               T* __restrict__ ws, T* __restrict__ out_gm, T* __restrict__ out_gv) {
+    constexpr int DP = D | 1, SP = dense_slab_points<T, D>();
+    __shared__ T lh[64 * DP];          // the tile's rows of h
+    __shared__ T lm[64 * DP];          // the tile's means
+    __shared__ T lt[64 * DP];          // t_i = sum_j P_ij h_j of the tile's points
+    __shared__ T lp[SP * D * DP];      // one slab of covs: row (point, i) at stride DP
+    __shared__ T lv[64];               // ve of the tile's points
+    const int lane = threadIdx.x;
+    const long b = blockIdx.x / tiles_per_series;
+    const long k0 = (blockIdx.x - b * tiles_per_series) * 64;
+    const int npts = N - k0 < 64 ? int(N - k0) : 64;               // (>= 1: the grid has ceil(N / 64) tiles per series)
+    const long first = b * N + k0;                                 // the tile's first point
+    for (int idx = lane; idx < npts * D; idx += 64) {
+        const int at = (idx / D) * DP + idx % D;
+        lh[at] = h[first * D + idx];
+        lm[at] = means[first * D + idx];
+    }
+    for (int s0 = 0; s0 < npts; s0 += SP) {
+        const int sp = npts - s0 < SP ? npts - s0 : SP;
+        const T* src = covs + (first + s0) * (D * D);
+        __syncthreads();               // lh is staged; the previous slab's rows have been read
+        for (int idx = lane; idx < sp * D * D; idx += 64) lp[(idx / D) * DP + idx % D] = src[idx];
+        __syncthreads();
+        for (int r = lane; r < sp * D; r += 64) {                  // row r of the slab: point s0 + r / D, row r % D of its P
+            const int k = s0 + r / D;
+            T t = T(0);
+#pragma unroll
+            for (int j = 0; j < D; ++j) t += lp[r * DP + j] * lh[k * DP + j];
+            lt[k * DP + r % D] = t;
+        }
+    }
+    __syncthreads();
+    if (lane < npts) {
+        T mu = T(0), s2 = T(0);
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            mu += lh[lane * DP + i] * lm[lane * DP + i];
+            s2 += lh[lane * DP + i] * lt[lane * DP + i];
+        }
+        const T y = yobs[first + lane];
+        T ve, gm, gv;
+        if (s2 > T(0)) {
+            expectations<T, LIK>(q, p, mu, s2, y, ve, gm, gv);
+        } else {                                   // outside the domain: NaN for this point and its series' sum
+            ve = gm = gv = nan_of<T>();
+        }
+        if (out_gm) {
+            out_gm[first + lane] = gm;
+            out_gv[first + lane] = gv;
+        }
+        lv[lane] = ve;
+    }
+    if (!ws) return;                               // (the gradients alone)
+    __syncthreads();
+    if (lane == 0) {
+        double acc = 0.0;                          // (float32: the accumulator is a double, rounded once into the workspace)
+        for (int k = 0; k < npts; ++k) acc += double(lv[k]);
+        ws[blockIdx.x] = T(acc);
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(64) dense_expect_reduce_kernel(long B, long tiles_per_series, const T* __restrict__ ws,
+                                                                 T* __restrict__ ve_sum) {
+    const long b = (long)blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    double acc = 0.0;
+    for (long t = 0; t < tiles_per_series; ++t) acc += double(ws[b * tiles_per_series + t]);
+    ve_sum[b] = T(acc);
+}
+
+// The adjoint's expansion: g_means = (weight g_mu) h and g_covs = (weight (g_var h_i)) h_j, what mf_ssm_marginals_grad_* reads.  Pure
+// stores: a lane per output element, consecutive lanes on consecutive elements of g_covs [B N d^2], then of g_means [B N d] (one
+// index space, so one launch); the 2 + d values a point reads are shared by the d^2 + d lanes around it and come from the caches.
+template <typename T, int D>
+__global__ void __launch_bounds__(256) dense_adjoint_kernel(long BN, long N, const T* __restrict__ h, const T* __restrict__ g_mu,
+                                                            const T* __restrict__ g_var, const T* __restrict__ weight,
+                                                            T* __restrict__ g_means, T* __restrict__ g_covs) {
+    const long n_cov = g_covs ? BN * (D * D) : 0, n_all = n_cov + (g_means ? BN * D : 0);
+    const long stride = (long)gridDim.x * 256;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n_all; e += stride) {
+        if (e < n_cov) {
+            const long k = e / (D * D);
+            const int r = int(e - k * (D * D)), i = r / D, j = r - i * D;
+            const T w = weight ? weight[k / N] : T(1);
+            g_covs[e] = (w * (g_var[k] * h[k * D + i])) * h[k * D + j];
+        } else {
+            const long m = e - n_cov, k = m / D;
+            const T w = weight ? weight[k / N] : T(1);
+            g_means[m] = (w * g_mu[k]) * h[m];
+        }
+    }
+}
+
 // argument checks shared by every entry point: 0, or the (negative) position of the offending argument
 template <typename T>
 int prepare(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights, bool log_weights,
@@ -1181,9 +1309,114 @@ int run_iw(int64_t B, int64_t N, int64_t S, int two_d, int64_t K, int lik, const
     });
 }
 
+// the same for the state dimension of the dense kernels: 1 ... DENSE_MAX_D, -100 for any other
+template <typename F>
+int with_dense_d(int d, F&& f) {
+    switch (d) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 7: return f(std::integral_constant<int, 7>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 9: return f(std::integral_constant<int, 9>{});
+        case 10: return f(std::integral_constant<int, 10>{});
+        case 11: return f(std::integral_constant<int, 11>{});
+        case 12: return f(std::integral_constant<int, 12>{});
+        default: return -100;
+    }
+}
+
+// the leading argument checks of the two dense entry points; on success *tiles = ceil(N / 64)
+inline int prepare_dense(int64_t B, int64_t N, int d, int64_t* tiles) {
+    if (B < 0) return -1;
+    if (N < 0) return -2;
+    if (d < 1 || d > DENSE_MAX_D) return -100;
+    *tiles = (N + 63) / 64;
+    if (B > 0 && *tiles > int64_t(0x7fffffff) / B) return -2;      // one block per tile
+    return 0;
+}
+
+template <typename T>
+int run_dense_expect(int64_t B, int64_t N, int d, int lik, const double* params, int nq, const double* nodes, const double* weights,
+                     const T* h, const T* means, const T* covs, const T* y, void* ws, size_t ws_bytes, T* ve_sum, T* g_mu, T* g_var,
+                     void* stream) {
+    Rule<T> q;
+    Par<T> p;
+    int64_t tiles = 0;
+    int bad = prepare_dense(B, N, d, &tiles);
+    if (bad) return bad;
+    if ((bad = prepare<T>(0, lik, params, nq, nodes, weights, false, q, p))) return bad - 2;      // -2 ... -6 there: 4 ... 8 here
+    if (!g_mu && g_var) return -16;
+    if (g_mu && !g_var) return -17;
+    if (B == 0 || (!ve_sum && !g_mu)) return 0;        // nothing asked for
+    if (tiles > 0) {
+        if ((bad = first_null(9, {h, means, covs, y}))) return bad;
+        if (ve_sum && !ws) return -13;
+        if (ve_sum && ws_bytes < size_t(B) * size_t(tiles) * sizeof(T)) return -14;
+        const int rc = with_dense_d(d, [&](auto D) {
+            return with_lik(lik, [&](auto L) {
+                return launch(dense_expect_tile_kernel<T, decltype(L)::value, decltype(D)::value>, B * tiles, 64, stream, N, tiles, q,
+                              p, h, means, covs, y, ve_sum ? ws : nullptr, g_mu, g_var);
+            });
+        });
+        if (rc) return rc;
+    }
+    if (!ve_sum) return 0;
+    return launch(dense_expect_reduce_kernel<T>, (B + 63) / 64, 64, stream, B, tiles, ws, ve_sum);
+}
+
+template <typename T>
+int run_dense_adjoint(int64_t B, int64_t N, int d, const T* h, const T* g_mu, const T* g_var, const T* weight, T* g_means, T* g_covs,
+                      void* stream) {
+    int64_t tiles = 0;
+    int bad = prepare_dense(B, N, d, &tiles);
+    if (bad) return bad;
+    if (B == 0 || N == 0 || (!g_means && !g_covs)) return 0;       // nothing asked for
+    if (N > (int64_t(1) << 62) / (int64_t(d) * d + d) / B) return -2;
+    if (!h) return -4;
+    if (g_means && !g_mu) return -5;
+    if (g_covs && !g_var) return -6;
+    const int64_t n_all = B * N * ((g_covs ? int64_t(d) * d : 0) + (g_means ? d : 0));
+    const int64_t blocks = (n_all + 255) / 256;
+    constexpr int64_t MAX_BLOCKS = 256 * 64;           // beyond that a lane loops: 64 blocks on each of the 256 CUs
+    return with_dense_d(d, [&](auto D) {
+        return launch(dense_adjoint_kernel<T, decltype(D)::value>, blocks < MAX_BLOCKS ? blocks : MAX_BLOCKS, 256, stream, B * N, N, h,
+                      g_mu, g_var, weight, g_means, g_covs);
+    });
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t mf_lik_dense_expectations_workspace_bytes(int64_t B, int64_t N, int elem_size) {
+    if (B <= 0 || N <= 0 || elem_size < 1) return 0;
+    return size_t(B) * size_t((N + 63) / 64) * size_t(elem_size);
+}
+int mf_lik_dense_expectations_f64(int64_t B, int64_t N, int d, int lik, const double* params, int nq, const double* nodes,
+                                  const double* weights, const double* h, const double* means, const double* covs, const double* y,
+                                  void* workspace, size_t workspace_bytes, double* ve_sum, double* g_mu, double* g_var,
+                                  void* stream) {
+    return run_dense_expect<double>(B, N, d, lik, params, nq, nodes, weights, h, means, covs, y, workspace, workspace_bytes, ve_sum,
+                                    g_mu, g_var, stream);
+}
+int mf_lik_dense_expectations_f32(int64_t B, int64_t N, int d, int lik, const double* params, int nq, const double* nodes,
+                                  const double* weights, const float* h, const float* means, const float* covs, const float* y,
+                                  void* workspace, size_t workspace_bytes, float* ve_sum, float* g_mu, float* g_var, void* stream) {
+    return run_dense_expect<float>(B, N, d, lik, params, nq, nodes, weights, h, means, covs, y, workspace, workspace_bytes, ve_sum,
+                                   g_mu, g_var, stream);
+}
+int mf_lik_dense_expectations_adjoint_f64(int64_t B, int64_t N, int d, const double* h, const double* g_mu, const double* g_var,
+                                          const double* weight, double* g_means, double* g_covs, void* stream) {
+    return run_dense_adjoint<double>(B, N, d, h, g_mu, g_var, weight, g_means, g_covs, stream);
+}
+int mf_lik_dense_expectations_adjoint_f32(int64_t B, int64_t N, int d, const float* h, const float* g_mu, const float* g_var,
+                                          const float* weight, float* g_means, float* g_covs, void* stream) {
+    return run_dense_adjoint<float>(B, N, d, h, g_mu, g_var, weight, g_means, g_covs, stream);
+}
 
 size_t mf_lik_iw_log_weights_workspace_bytes(int64_t num_tiles, int64_t K, int two_d, int elem_size) {
     if (num_tiles <= 0 || K <= 0 || two_d < 2 || two_d > 18 || (two_d & 1) || elem_size < 1) return 0;
