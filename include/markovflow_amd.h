@@ -963,6 +963,61 @@ int mf_lik_dense_expectations_adjoint_f64(int64_t B, int64_t N, int d, const dou
 int mf_lik_dense_expectations_adjoint_f32(int64_t B, int64_t N, int d, const float* h, const float* g_mu, const float* g_var,
                                           const float* weight, float* g_means, float* g_covs, void* stream);
 
+/*
+ * The data term of the spatio-temporal sparse variational ELBO and its adjoints (markovflow/models/spatio_temporal_variational.py
+ * :149-236; csrc/mf_st.hip).  The chain state is Ms copies of a temporal state of dimension d_t = two_dt / 2 (copy s in columns
+ * s d_t ... (s + 1) d_t - 1), D = Ms d_t <= 64, and a pair of neighbouring inducing states has dimension n = 2 D <= 128.  B, N, S,
+ * the likelihood, the rule, seg_offsets, c, y, pair_mean [B, S, n] and pair_cov [B, S, n, n] as for mf_lik_sparse_expectations_*;
+ *   a  [B, N, Ms]      the spatial weights of every point, L^-1 K_s(Z_s, x_k)
+ *   wt [B, N, two_dt]  the temporal projection of the pair onto the point, h P_k
+ * The projection of the pair onto f_k is  W_k[half D + s d_t + i] = a_k[s] wt_k[half d_t + i]  (half in {0, 1}); it is never
+ * written to memory.  pair_cov is read in full and symmetrised, Sbar = (S + S^T) / 2.  Per point k of segment s, with V_k = Sbar W_k:
+ *   fmu = W_k . m_s,  fvar = c_k + W_k . V_k,  (ve, gm, gv) as mf_lik_variational_expectations
+ * Outputs, each group optional, every combination with the same bits:
+ *   ve_sum [B, S]                          sum_k ve_k
+ *   g_mean [B, S, n], g_cov [B, S, n, n]   sum_k gm_k W_k,  sum_k gv_k W_k W_k^T (symmetric, both triangles written); both or neither
+ *   g_a [B, N, Ms], g_wt [B, N, two_dt], g_c [B, N]     the adjoints of ve_k onto the point's own a, wt and c; all three or none:
+ *                                          g_a[k, s]              = gm_k Ma[s] + 2 gv_k Va[s]
+ *                                          g_wt[k, half d_t + i]  = gm_k Mwt[half d_t + i] + 2 gv_k Vwt[half d_t + i]
+ *                                          g_c[k]                 = gv_k
+ *                                          Xa[s] = sum_{half, i} X[half D + s d_t + i] wt_k[half d_t + i],
+ *                                          Xwt[half d_t + i] = sum_s X[half D + s d_t + i] a_k[s]   for X = m_s (M) and X = V_k (V)
+ *   fmu, fvar [B, N]                       the projection; with nothing else asked for y may be NULL
+ * Two passes.  Pass 1 runs one workgroup per ROW - at most 256 consecutive points of one segment, row j of a segment starting at
+ * the segment's first point + 256 j - and leaves the row's n (n + 1) / 2 + n + 1 partial sums in the workspace; pass 2 adds a
+ * segment's rows in ascending order.  The caller supplies the row table in the form of the siblings' tile table, with 256 points per
+ * tile: num_tiles = sum over the segments of ceil(length / 256), tile_seg [num_tiles], seg_tile [B S + 1]; and the workspace,
+ * mf_lik_st_expectations_workspace_bytes(num_tiles, Ms, two_dt, sizeof(T)) = num_tiles (n (n + 1) / 2 + n + 1) sizeof(T) bytes
+ * (0 outside the supported range or for num_tiles = 0; needed only beside ve_sum or g_mean).  The table is clamped on the device.
+ * THE ORDER OF THE SUMS, part of the contract: every sum starts from 0 and grows by ONE fused multiply-add per term (the sums of
+ * ve_k and of the rows: one addition), index ascending -
+ *   V_k[i] in j;  fmu, W_k . V_k (then c_k is added), Ma, Va, Mwt, Vwt in the pair index j of their terms;
+ *   g_a = fma(2 gv, Va, gm Ma), g_wt likewise;  a row's sums in its points, with (gv_k W_k[i]) W_k[j] for i >= j;  a segment's in
+ *   its rows.
+ * No floating-point atomics: the same bits on every launch and for a series alone or inside a batch.  A point with fvar <= 0 or
+ * NaN gets NaN in its own fmu, fvar, g_a, g_wt, g_c and makes the three segment outputs of ITS segment NaN; nothing else changes.
+ * An empty segment, and every segment for N = 0, gets zeros.  No allocation, no synchronisation.
+ * Returns 0, -(position of the offending argument in THIS signature: 1 B, 2 N, 3 S, 6 lik, 7 params, 8 nq, 9 nodes, 10 weights,
+ * 11 ... 14 a NULL input, 15 y NULL beside an output that needs the likelihood, 16 / 17 a NULL marginal, 18 num_tiles negative,
+ * above 2^31 - 1 or non-zero for N = 0, 19 / 20 a NULL table, 21 a NULL workspace, 22 a workspace that is too small, 24 / 25 one of
+ * g_mean / g_cov NULL without the other, 26 / 27 / 28 the first of g_a / g_wt / g_c that is NULL beside a given one), -100 for
+ * Ms < 1, a two_dt that is odd or < 2, or Ms two_dt / 2 > 64, or -1000 (launch failed).  Nothing is launched on an error, for
+ * B = 0, or when every output is NULL.
+ */
+size_t mf_lik_st_expectations_workspace_bytes(int64_t num_tiles, int Ms, int two_dt, int elem_size);
+int mf_lik_st_expectations_f64(int64_t B, int64_t N, int64_t S, int Ms, int two_dt, int lik, const double* params, int nq,
+                               const double* nodes, const double* weights, const int64_t* seg_offsets, const double* a,
+                               const double* wt, const double* c, const double* y, const double* pair_mean, const double* pair_cov,
+                               int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile, void* workspace,
+                               size_t workspace_bytes, double* ve_sum, double* g_mean, double* g_cov, double* g_a, double* g_wt,
+                               double* g_c, double* fmu, double* fvar, void* stream);
+int mf_lik_st_expectations_f32(int64_t B, int64_t N, int64_t S, int Ms, int two_dt, int lik, const double* params, int nq,
+                               const double* nodes, const double* weights, const int64_t* seg_offsets, const float* a,
+                               const float* wt, const float* c, const float* y, const float* pair_mean, const float* pair_cov,
+                               int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile, void* workspace,
+                               size_t workspace_bytes, float* ve_sum, float* g_mean, float* g_cov, float* g_a, float* g_wt,
+                               float* g_c, float* fmu, float* fvar, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,319 @@
+"""
+GPU tests of ``SpatioTemporalSparseVariational`` (markovflow_amd/models.py) on ``kernels.SparseSpatioTemporalKernel``: the
+reference's own model test against exact dense GP regression with the product kernel, the fused route
+(``mf_lik_st_expectations_*``) against the torch composition on the same model, and the model's bookkeeping.
+
+Fused against composed, float64: both routes evaluate the same formulas on the same pair marginals and differ in the order of
+their sums - N <= 130 points per series, pair dimension <= 128 - and the gradients then travel the same backward of the pair marginals.
+A sum of n terms carries at most n eps of its magnitude, and the backward of the marginals amplifies by the conditioning of the
+chain's covariances (variances between the jitter-free 1e-2 of the perturbed factors here and 1): rtol 1e-7 with an atol of 1e-9 of
+the largest entry of the gradient, 1e4 and more above both.
+
+State dimension 64 - the ``32x2`` cases - runs in float32: the chain operators both routes stand on (the marginals of ``dist_q``, their
+adjoint, the KL divergence) carry state dimensions up to 64 in float32 and up to 32 in float64 (``mf_max_state_dim_f64_tile_ops()``;
+the model says so with a ``NotImplementedError``, which ``test_routing_and_errors`` pins).  The float32 bound, from the formats and the
+recorded errors of the two data terms: the value is a sum of at most 260 expectations of one sign beside a KL term that is the same
+bits on both routes, gamma_260 = 260 eps32 = 3e-5 of its magnitude: rtol 3e-5.  The adjoints ``g_mean`` / ``g_cov`` of the two routes
+lie within 75 eps32 of their magnitude of the exact ones for the composition (the largest float32 yardstick at 20 nodes in
+tests/golden/st_yardsticks.json) and within 4 x that for the kernel (what tests/test_gpu_st_kernel.py holds it to), so they differ by
+at most 5 x 75 eps32 = 4.5e-5 of it; the backward of the pair marginals is the same linear map on both routes and carries that
+difference onto the leaves: 5e-5 of the largest entry of the gradient, with rtol 1e-4, and no further allowance.
+In float64 state dimension 64 is compared one level down, where no chain operator is involved:
+``test_the_data_term_at_state_dimension_64_in_float64`` holds ``st_expected_log_likelihood`` against
+``st_expected_log_likelihood_torch`` on random pair marginals, value and all five gradients, at the float64 bound above.
+"""
+import numpy as np
+import pytest
+import torch
+
+import markovflow_amd as mfa
+from markovflow_amd import _lib
+from markovflow_amd import likelihoods as ML
+from markovflow_amd import models as MM
+from markovflow_amd import spatial_kernels as SK
+from helpers import likelihood_closed_forms as L
+from helpers import sparse_cvi_closed_forms as SC
+from helpers import st_closed_forms as ST
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+NAMES = [L.GAUSSIAN, L.BERNOULLI, L.POISSON, L.STUDENTT]
+FN = "mf_lik_st_expectations"
+
+
+def tt(a, dtype=torch.float64):
+    return torch.tensor(np.asarray(a), dtype=dtype, device=DEV)
+
+
+def nn(t):
+    return t.detach().cpu().numpy()
+
+
+def build_likelihood(name):
+    params = L.LIKELIHOODS[name][1]
+    return {L.GAUSSIAN: lambda: mfa.Gaussian(params[0]), L.BERNOULLI: mfa.Bernoulli, L.POISSON: mfa.Poisson,
+            L.STUDENTT: lambda: mfa.StudentT(*params)}[name]()
+
+
+def matern32_space(x, x2, ls=1.0, var=1.0):
+    r = np.sqrt(3.0) * np.sqrt(np.sum((x[:, None, :] - x2[None, :, :]) ** 2, axis=-1)) / ls
+    return var * (1.0 + r) * np.exp(-r)
+
+
+# ---- the reference's model test -----------------------------------------------------------------------------------------------------
+def reference_data():
+    """markovflow's tests/integration/models/test_spatio_temporal_variational.py: x in {0, 1} crossed with t in {2, 3}, sorted by
+    time, Y from default_rng(42)."""
+    rng = np.random.default_rng(42)
+    inputs = np.array(np.meshgrid(np.array([0.0, 1.0]), np.array([2.0, 3.0]))).T.reshape(-1, 2)
+    inputs = inputs[np.argsort(inputs[:, 1]), :]
+    return inputs, rng.normal(size=(inputs.shape[0], 1))
+
+
+def reference_model(z_space, z_time, **kwargs):
+    return mfa.SpatioTemporalSparseVariational(tt(z_space), tt(z_time), SK.Matern32(1.0, 1.0, device=DEV),
+                                               mfa.Matern12(1.0, 1.0, device=DEV), mfa.Gaussian(1.0), **kwargs)
+
+
+def dense_product_gpr(inputs, obs, new=None):
+    kern = lambda p, q: matern32_space(p[:, :1], q[:, :1]) * np.exp(-np.abs(p[:, 1][:, None] - q[:, 1][None, :]))      # noqa: E731
+    return ST.dense_gpr(kern(inputs, inputs), obs[:, 0], 1.0, None if new is None else kern(new, inputs))
+
+
+def test_the_references_model_test_elbo_is_the_exact_log_marginal_likelihood():
+    inputs, obs = reference_data()
+    model = reference_model(np.unique(inputs[:, 0]).reshape(-1, 1), np.unique(inputs[:, 1]))
+    assert model.kernel.state_dim == 2 and model.kernel.output_dim == 2
+    xy = (tt(inputs), tt(obs))
+    opt = mfa.SSMNaturalGradient(gamma=1.0, momentum=False)          # a unit step reaches the optimum of a Gaussian likelihood
+    for _ in range(2):
+        opt.minimize(lambda: model.loss(xy), model.dist_q)
+    lml, mean = dense_product_gpr(inputs, obs, inputs)
+    elbo = float(model.elbo(xy).detach())
+    print(f"ELBO {elbo:.9f}  log marginal likelihood {lml:.9f}")
+    assert np.allclose(elbo, lml, atol=1e-4, rtol=1e-4)
+    st_mean, st_var = model.space_time_predict_f(xy[0])
+    assert tuple(st_mean.shape) == tuple(st_var.shape) == (4, 1)
+    assert np.allclose(mean, nn(st_mean)[:, 0], atol=1e-2, rtol=1e-2)
+
+
+def test_off_the_grid_the_elbo_is_a_lower_bound():
+    rng = np.random.default_rng(3)
+    inputs = np.stack([rng.uniform(-0.5, 1.5, 12), np.sort(rng.uniform(1.5, 3.5, 12))], axis=1)
+    obs = rng.normal(size=(12, 1))
+    model = reference_model(np.array([[0.0], [1.0]]), np.array([2.0, 3.0]))
+    xy = (tt(inputs), tt(obs))
+    opt = mfa.SSMNaturalGradient(gamma=1.0, momentum=False)
+    for _ in range(2):
+        opt.minimize(lambda: model.loss(xy), model.dist_q)
+    lml, _ = dense_product_gpr(inputs, obs)
+    elbo = float(model.elbo(xy).detach())
+    print(f"ELBO {elbo:.9f}  log marginal likelihood {lml:.9f}")
+    assert elbo <= lml and elbo > lml - 10.0, "a bound, and not a vacuous one"
+
+
+# ---- fused against composed --------------------------------------------------------------------------------------------------------
+def draw_model(name, ms, time_cls, n, batch=2, seed=0, num_data=None, space_grad=False, time_grad=False, dtype=torch.float64):
+    """A batch of series on ``Ms`` inducing locations in the plane and 4 inducing times, with a ``q`` that is not the prior."""
+    rng = np.random.default_rng(seed + 17 * ms + n)
+    z_space = rng.uniform(-1.0, 1.0, size=(ms, 2))
+    z_time = np.tile(np.array([0.5, 1.7, 2.6, 4.0]), (batch, 1)) + rng.uniform(0, 0.2, size=(batch, 4))
+    inputs = np.concatenate([rng.uniform(-1.0, 1.0, size=(batch, n, 2)), np.sort(rng.uniform(0.0, 4.5, size=(batch, n, 1)), axis=1)],
+                            axis=-1)
+    obs = np.resize(np.asarray(L.OBSERVED[name]), (batch, n, 1))
+    space = SK.Matern32(tt(1.3, dtype).requires_grad_(space_grad), tt([0.8, 1.4], dtype).requires_grad_(space_grad))
+    time = time_cls(tt(1.1, dtype).requires_grad_(time_grad), tt(1.0, dtype))
+    model = mfa.SpatioTemporalSparseVariational(tt(z_space, dtype), tt(z_time, dtype), space, time, build_likelihood(name),
+                                                num_data=num_data)
+    gen = torch.Generator(device="cpu").manual_seed(seed)
+    with torch.no_grad():
+        for i, leaf in enumerate(model.trainable_variables):          # (mu0, chol_P0, As, offsets, chol_Qs)
+            noise = (0.02 * torch.randn(leaf.shape, generator=gen, dtype=torch.float64)).to(device=DEV, dtype=dtype)
+            leaf.add_(torch.tril(noise) if i in (1, 4) else noise)
+    return model, (tt(inputs, dtype), tt(obs, dtype))
+
+
+def assert_close(got, want, what):
+    """The module docstring's bounds: float64, and float32 for the value (a scalar) and for a gradient."""
+    f32 = got.dtype == torch.float32
+    got, want = nn(got).astype(np.float64), nn(want).astype(np.float64)
+    if not f32:
+        rtol, atol = 1e-7, 1e-9 * max(1.0, float(np.abs(want).max()))
+    elif want.ndim == 0:
+        rtol, atol = 3e-5, 0.0
+    else:
+        rtol, atol = 1e-4, 5e-5 * float(np.abs(want).max())
+    print(f"DIFF {what}: {float(np.abs(got - want).max()):.3e} of {float(np.abs(want).max()):.3e}")
+    np.testing.assert_allclose(got, want, rtol=rtol, atol=atol, err_msg=what)
+
+
+SIZES = [(3, mfa.Matern12), (4, mfa.Matern32), (16, mfa.Matern32), (32, mfa.Matern32)]          # (Ms, d_t) = (3,1), (4,2), (16,2), (32,2)
+
+
+@pytest.mark.parametrize("ms,time_cls", SIZES, ids=["3x1", "4x2", "16x2", "32x2"])
+@pytest.mark.parametrize("name", NAMES)
+def test_fused_elbo_and_its_gradients_against_the_torch_composition(name, ms, time_cls, monkeypatch):
+    n = 33 if name in (L.GAUSSIAN, L.POISSON) else 130          # (every size meets both lengths, a batch of two each)
+    dtype = torch.float32 if ms * time_cls(1.0, 1.0).state_dim > 32 else torch.float64          # (state dimension 64: float32)
+    model, xy = draw_model(name, ms, time_cls, n, dtype=dtype)
+    leaves = model.trainable_variables
+    fused = model.elbo(xy)
+    g_fused = torch.autograd.grad(fused, leaves)
+    monkeypatch.setattr(model, "_fused", lambda inputs: False)
+    composed = model.elbo(xy)
+    g_composed = torch.autograd.grad(composed, leaves)
+    assert_close(fused, composed, "elbo")
+    for i, (a, b) in enumerate(zip(g_fused, g_composed)):
+        assert_close(a, b, f"gradient of leaf {i}")
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_the_data_term_at_state_dimension_64_in_float64(name):
+    """(Ms, d_t) = (32, 2) where the float64 chain operators end: the function against the composition on random pair marginals, a
+    batch of two with 130 points in 5 segments (one of them empty), a weighted sum so that ``grad_out`` is not all ones."""
+    ms, dt, n, segs, pair = 32, 2, 130, 5, 128
+    rng = np.random.default_rng(64)
+    indices = np.sort(rng.choice([0, 1, 3, 4], size=(2, n)), axis=1)
+    offsets = np.stack([np.searchsorted(row, np.arange(segs + 1)) for row in indices])
+    root = rng.normal(size=(2, segs, pair, pair))
+    values = dict(a=rng.uniform(-1, 1, size=(2, n, ms)) / np.sqrt(ms), wt=rng.uniform(-0.7, 0.7, size=(2, n, 2 * dt)) / np.sqrt(dt),
+                  c=rng.uniform(0.05, 0.5, size=(2, n)), pair_mean=rng.normal(size=(2, segs, pair)),
+                  pair_cov=root @ root.transpose(0, 1, 3, 2) / pair + 0.1 * np.eye(pair))
+    y, weight = tt(np.resize(np.asarray(L.OBSERVED[name]), (2, n))), tt(rng.uniform(0.5, 1.5, size=(2, segs)))
+    lik = build_likelihood(name)
+    results = []
+    for fused in (True, False):
+        a, wt, c, pm, pc = (tt(values[k]).requires_grad_(True) for k in ("a", "wt", "c", "pair_mean", "pair_cov"))
+        if fused:
+            ve = MM.st_expected_log_likelihood(lik, a, wt, c, y, tt(offsets, torch.int64), pm, pc)
+        else:
+            ve = MM.st_expected_log_likelihood_torch(lik, a, wt, c, y, tt(indices, torch.int64), pm, pc)
+        results.append((ve.detach(),) + torch.autograd.grad(torch.sum(weight * ve), (pm, pc, a, wt, c)))
+    for what, got, want in zip(("value", "pair_mean", "pair_cov", "a", "wt", "c"), *results):
+        assert_close(got, want, what)
+
+
+@pytest.mark.parametrize("name", [L.BERNOULLI, L.GAUSSIAN])
+def test_hyper_parameter_gradients_travel_the_per_point_adjoints(name, monkeypatch):
+    model, xy = draw_model(name, 4, mfa.Matern32, 130, space_grad=True, time_grad=True)
+    space, time = model.kernel.kernel_space, model.kernel.kernel_time
+    hyper = (space.variance, space.lengthscales, time._leaves()[0])
+    assert all(h.requires_grad for h in hyper)
+    seen = []
+    real_rc = _lib.call_rc
+    monkeypatch.setattr(_lib, "call_rc", lambda base, *a: (seen.append(base), real_rc(base, *a))[1])
+    fused = model.elbo(xy)
+    assert seen.count(FN) == 1, "a hyper-parameter under the tape stays on the fused route"
+    g_fused = torch.autograd.grad(fused, hyper)
+    monkeypatch.setattr(model, "_fused", lambda inputs: False)
+    composed = model.elbo(xy)
+    g_composed = torch.autograd.grad(composed, hyper)
+    assert_close(fused, composed, "elbo")
+    for what, a, b in zip(("spatial variance", "spatial lengthscales", "temporal lengthscale"), g_fused, g_composed):
+        assert float(b.abs().max()) > 0
+        assert_close(a, b, what)
+
+
+# ---- bookkeeping -------------------------------------------------------------------------------------------------------------------
+def test_shuffled_data_has_the_bits_of_sorted_data_and_num_data_scales_the_data_term():
+    model, (inputs, obs) = draw_model(L.BERNOULLI, 4, mfa.Matern32, 33)
+    sorted_elbo = model.elbo((inputs, obs))
+    perm = torch.stack([torch.randperm(33, generator=torch.Generator().manual_seed(b)) for b in range(2)]).to(DEV)
+    shuffled = (torch.gather(inputs, 1, perm[..., None].expand(inputs.shape)).contiguous(), torch.gather(obs, 1, perm[..., None]).contiguous())
+    assert torch.equal(model.elbo(shuffled), sorted_elbo)
+    fmu, fvar = model.space_time_predict_f(inputs)
+    fmu_s, fvar_s = model.space_time_predict_f(shuffled[0])
+    assert torch.equal(torch.gather(fmu, 1, perm[..., None]), fmu_s) and torch.equal(torch.gather(fvar, 1, perm[..., None]), fvar_s)
+    with torch.no_grad():
+        kl = torch.sum(model.dist_q.kl_divergence(model.dist_p))
+        ve = sorted_elbo.detach() + kl
+    scaled, _ = draw_model(L.BERNOULLI, 4, mfa.Matern32, 33, num_data=330)
+    np.testing.assert_allclose(float(scaled.elbo((inputs, obs)).detach()), float(10.0 * ve - kl), rtol=1e-12)
+
+
+def test_elbo_is_one_launch_and_the_backward_none(monkeypatch):
+    model, xy = draw_model(L.BERNOULLI, 4, mfa.Matern32, 33)
+    built = []
+    real = model._compute_projections
+    monkeypatch.setattr(model, "_compute_projections", lambda inputs: (built.append(1), real(inputs))[1])
+    model.elbo(xy)
+    seen = []
+    real_rc = _lib.call_rc
+    monkeypatch.setattr(_lib, "call_rc", lambda base, *a: (seen.append(base), real_rc(base, *a))[1])
+
+    def no_torch(*a, **k):
+        raise AssertionError("the torch route must not run on HIP tensors")
+
+    monkeypatch.setattr(ML, "torch_variational_expectations", no_torch)
+    monkeypatch.setattr(MM, "st_expected_log_likelihood_torch", no_torch)
+    elbo = model.elbo(xy)
+    assert len(built) == 1, "a, wt, c, the offsets and the row table are cached with the data"
+    assert seen.count(FN) == 1 and not any(s.startswith("mf_lik_") and s != FN for s in seen)
+    del seen[:]
+    elbo.backward()
+    assert not any(s.startswith("mf_lik_") for s in seen), "the backward reuses the forward's adjoints: no second launch"
+    assert all(leaf.grad is not None and bool(torch.isfinite(leaf.grad).all()) for leaf in model.trainable_variables)
+    model.elbo((xy[0][:, :20].contiguous(), xy[1][:, :20].contiguous()))
+    assert len(built) == 2, "other data: not the cached projections"
+    with torch.no_grad():
+        model.kernel.kernel_space.lengthscales.mul_(1.01)
+    model.elbo(xy)
+    assert len(built) == 3, "a spatial hyper-parameter written in place: not the cached projections"
+
+
+@pytest.mark.parametrize("name", [L.GAUSSIAN, L.BERNOULLI])
+def test_predictions_against_the_helper(name):
+    model, (inputs, obs) = draw_model(name, 4, mfa.Matern12, 33, batch=1)
+    with torch.no_grad():
+        pair_mean, pair_cov = (nn(x)[0] for x in model._pair_marginals())
+    x, t = nn(inputs)[0, :, :2], nn(inputs)[0, :, 2]
+    z_space, z_time = nn(model.inducing_space), nn(model.inducing_time)[0]
+    idx, wt, ct = SC.conditional_projections([dict(order=1, ls=1.1, var=1.0, period=None, osc=0)], t, z_time)
+    ls = np.array([0.8, 1.4])
+    kzz = matern32_space(z_space / ls, z_space / ls, var=1.3) + 1e-6 * np.eye(4)
+    a = np.linalg.solve(np.linalg.cholesky(kzz), matern32_space(z_space / ls, x / ls, var=1.3)).T
+    c = 1.3 - np.sum(a * a, axis=1) * (1.0 - ct)
+    want = ST.st_expectations(L.LIKELIHOODS[name], a, wt, c, nn(obs)[0, :, 0], SC.offsets_of(idx, 5), pair_mean, pair_cov)
+    fmu, fvar = model.space_time_predict_f(inputs)
+    np.testing.assert_allclose(nn(fmu)[0, :, 0], want["fmu"], rtol=1e-8, atol=1e-10)
+    np.testing.assert_allclose(nn(fvar)[0, :, 0], want["fvar"], rtol=1e-8, atol=1e-10)
+    density = model.predict_log_density((inputs, obs))
+    np.testing.assert_allclose(nn(density)[0].reshape(-1), L.predict_log_density(L.LIKELIHOODS[name], want["fmu"], want["fvar"],
+                                                                                 nn(obs)[0, :, 0]), rtol=1e-7, atol=1e-9)
+    with torch.no_grad():
+        model_mean, _ = model.posterior.predict_f(model.inducing_time)
+    assert tuple(model_mean.shape) == (1, 4, 4), "the posterior process predicts the Ms outputs at the inducing locations"
+
+
+def test_routing_and_errors():
+    model, (inputs, obs) = draw_model(L.GAUSSIAN, 3, mfa.Matern12, 33)
+    assert model.inducing_time is model.inducing_inputs and tuple(model.inducing_space.shape) == (3, 2)
+    assert isinstance(model.kernel, mfa.SparseSpatioTemporalKernel) and isinstance(model.posterior, mfa.ConditionalProcess)
+    assert len(model.trainable_variables) == 5 and model.trainable_variables == model.dist_q.trainable_variables
+    assert model.dist_p.state_dim == model.dist_q.state_dim == 3
+    np.testing.assert_allclose(float(model.loss((inputs, obs)).detach()), -float(model.elbo((inputs, obs)).detach()), rtol=0)
+    with pytest.raises(ValueError, match="time in the last column"):
+        model.elbo((inputs[..., :2], obs))
+    with pytest.raises(ValueError, match="batch shape"):
+        model.elbo((inputs[0], obs[0]))
+    with pytest.raises(ValueError, match="observations"):
+        model.elbo((inputs, obs[..., 0]))
+    with pytest.raises(ValueError):
+        model.elbo((inputs.float(), obs.float()))
+    with pytest.raises(NotImplementedError):
+        model.predict_log_density((inputs, obs), full_output_cov=True)
+    with pytest.raises(ValueError, match="num_data"):
+        draw_model(L.GAUSSIAN, 3, mfa.Matern12, 33, num_data=0)
+    wide, wide_xy = draw_model(L.GAUSSIAN, 32, mfa.Matern32, 33)
+    with pytest.raises(NotImplementedError, match="up to 32 in float64"):
+        wide.elbo(wide_xy)
+    with pytest.raises(NotImplementedError, match="exceeds 64"):
+        mfa.SpatioTemporalSparseVariational(tt(np.zeros((33, 2))), tt([0.0, 1.0]), SK.Matern32(device=DEV), mfa.Matern32(1.0, 1.0, device=DEV),
+                                            mfa.Gaussian())
+    with pytest.raises(TypeError):
+        mfa.SpatioTemporalSparseVariational(tt(np.zeros((3, 2))), tt([0.0, 1.0]), SK.Matern32(device=DEV), mfa.Matern32(1.0, 1.0, device=DEV),
+                                            mfa.Gaussian(), initial_distribution="prior")
+    leaves = model.trainable_variables
+    elbo = model.elbo((inputs, obs))
+    with pytest.raises(RuntimeError, match="differentiable once"):
+        torch.autograd.grad(elbo, leaves, create_graph=True)
