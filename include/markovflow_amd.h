@@ -1018,6 +1018,48 @@ int mf_lik_st_expectations_f32(int64_t B, int64_t N, int64_t S, int Ms, int two_
                                size_t workspace_bytes, float* ve_sum, float* g_mean, float* g_cov, float* g_a, float* g_wt,
                                float* g_c, float* fmu, float* fvar, void* stream);
 
+/*
+ * One conjugate-computation VI step on the sites of the spatio-temporal sparse model, in place (markovflow/models/
+ * spatio_temporal_variational.py:509-552; csrc/mf_st.hip).  Every input, the row table and the workspace as for
+ * mf_lik_st_expectations_* (mf_lik_st_cvi_site_update_workspace_bytes returns the same number); the range is the same,
+ * Ms >= 1, d_t >= 1, Ms d_t <= 64.  Per point k of segment s, with fmu, fvar and (ve, gm, gv) as there,
+ *   g1_k = fma(-2 gv_k, fmu_k, gm_k)        the gradient of ve_k in the first expectation parameter; gv_k is the one in the second
+ * and per segment
+ *   theta1 = sum_k g1_k W_k,   theta2 = sum_k gv_k W_k W_k^T
+ *   nat1 [B, S, n]     <-  fma(lr, theta1[j],      (1 - lr) nat1[j])
+ *   nat2 [B, S, n, n]  <-  fma(lr, theta2[i][j],   (1 - lr) nat2[i][j])
+ * with 1 - lr formed once in T.  theta2 is summed over its lower triangle only and both (i, j) and (j, i) take the entry
+ * (max(i, j), min(i, j)), each blended with its own old value: a symmetric nat2 stays symmetric bit for bit.  nat1 and nat2 are
+ * both required (mf_lik_st_expectations_* serves projection-only calls).  Optional outputs, every combination with the same bits in
+ * nat1 and nat2:  ve_sum [B, S] = sum_k ve_k,  fmu, fvar [B, N].
+ * Two passes: pass 1 is that of mf_lik_st_expectations_* with g1_k in place of gm_k in the vector sum, pass 2 adds a segment's rows
+ * and blends.  THE ORDER OF THE SUMS, part of the contract: that of mf_lik_st_expectations_* -
+ *   V_k[i] in j;  fmu and W_k . V_k (then c_k is added) in the pair index j;  a row's sums of ve_k, g1_k W_k[j] and
+ *   (gv_k W_k[i]) W_k[j], i >= j, in its points, one fused multiply-add per term from 0;  a segment's in its rows, ascending from
+ *   0, one addition per row;  then the blend above.
+ * From zero sites at lr = 1, nat2 has the bits of g_cov, and ve_sum, fmu and fvar the bits they have there.  No floating-point
+ * atomics.  A point with fvar <= 0 or NaN gets NaN in its own fmu and fvar and makes nat1, nat2 and ve_sum of ITS segment NaN; no
+ * other segment changes.  An empty segment, and every segment for N = 0, has sums of exactly 0: its sites become (1 - lr) nat.
+ * No allocation, no synchronisation.
+ * Returns 0, -(position of the offending argument in THIS signature: 1 B, 2 N, 3 S, 6 lik, 7 params, 8 nq, 9 nodes, 10 weights,
+ * 11 ... 17 a NULL input, 18 num_tiles negative, above 2^31 - 1 or non-zero for N = 0, 19 / 20 a NULL table, 21 a NULL workspace,
+ * 22 a workspace that is too small, 23 a learning_rate outside [0, 1] or NaN, 24 / 25 a NULL nat1 / nat2), -100 for Ms < 1, a
+ * two_dt that is odd or < 2, or Ms two_dt / 2 > 64, or -1000 (launch failed).  Nothing is launched on an error or for B = 0.
+ */
+size_t mf_lik_st_cvi_site_update_workspace_bytes(int64_t num_tiles, int Ms, int two_dt, int elem_size);
+int mf_lik_st_cvi_site_update_f64(int64_t B, int64_t N, int64_t S, int Ms, int two_dt, int lik, const double* params, int nq,
+                                  const double* nodes, const double* weights, const int64_t* seg_offsets, const double* a,
+                                  const double* wt, const double* c, const double* y, const double* pair_mean,
+                                  const double* pair_cov, int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile,
+                                  void* workspace, size_t workspace_bytes, double learning_rate, double* nat1, double* nat2,
+                                  double* ve_sum, double* fmu, double* fvar, void* stream);
+int mf_lik_st_cvi_site_update_f32(int64_t B, int64_t N, int64_t S, int Ms, int two_dt, int lik, const double* params, int nq,
+                                  const double* nodes, const double* weights, const int64_t* seg_offsets, const float* a,
+                                  const float* wt, const float* c, const float* y, const float* pair_mean, const float* pair_cov,
+                                  int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile, void* workspace,
+                                  size_t workspace_bytes, float learning_rate, float* nat1, float* nat2, float* ve_sum, float* fmu,
+                                  float* fvar, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,7 +23,7 @@ from .kernels import (Constant, HarmonicOscillator, IndependentMultiOutput, Mate
 from .likelihoods import Bernoulli, Gaussian, Likelihood, Poisson, StudentT
 from .models import (CVIGaussianProcess, GaussianProcessRegression, ImportanceWeightedVI, PowerExpectationPropagation,
                      SparseCVIGaussianProcess, SparsePowerExpectationPropagation, SparseVariationalGaussianProcess,
-                     SpatioTemporalSparseVariational, VariationalGaussianProcess)
+                     SpatioTemporalSparseCVI, SpatioTemporalSparseVariational, VariationalGaussianProcess)
 from .ssm_natgrad import SSMNaturalGradient
 from .posterior import AnalyticPosteriorProcess, ConditionalProcess, ImportanceWeightedPosteriorProcess
 from ._lib import MarkovflowAmdError, check_errors, errors_as_nan, set_synchronous_checks
@@ -38,5 +38,5 @@ __all__ = [
     "likelihoods", "Likelihood", "Gaussian", "Bernoulli", "Poisson", "StudentT", "CVIGaussianProcess", "PowerExpectationPropagation",
     "SparseCVIGaussianProcess", "SparseVariationalGaussianProcess", "SSMNaturalGradient", "ssm_natgrad",
     "SparsePowerExpectationPropagation", "ImportanceWeightedVI", "ImportanceWeightedPosteriorProcess",
-    "VariationalGaussianProcess", "spatial_kernels", "SparseSpatioTemporalKernel", "SpatioTemporalSparseVariational",
+    "VariationalGaussianProcess", "spatial_kernels", "SparseSpatioTemporalKernel", "SpatioTemporalSparseVariational", "SpatioTemporalSparseCVI",
 ]

@@ -87,6 +87,8 @@ _SIGS = {
     "mf_lik_dense_expectations_adjoint": (_int, [_i64, _i64, _int, "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_st_expectations": (_int, [_i64, _i64, _i64, _int, _int, _int, _hd, _int, _hd, _hd, _vp, "Tp", "Tp", "Tp", "Tp", "Tp", "Tp",
                                       _i64, _vp, _vp, _vp, _sz, "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
+    "mf_lik_st_cvi_site_update": (_int, [_i64, _i64, _i64, _int, _int, _int, _hd, _int, _hd, _hd, _vp, "Tp", "Tp", "Tp", "Tp", "Tp",
+                                         "Tp", _i64, _vp, _vp, _vp, _sz, "T", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
 }
 _PLAIN = {
     "mf_version": (_int, []),
@@ -119,6 +121,7 @@ _PLAIN = {
     "mf_lik_iw_log_weights_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
     "mf_lik_dense_expectations_workspace_bytes": (_sz, [_i64, _i64, _int]),
     "mf_lik_st_expectations_workspace_bytes": (_sz, [_i64, _int, _int, _int]),
+    "mf_lik_st_cvi_site_update_workspace_bytes": (_sz, [_i64, _int, _int, _int]),
 }
 
 _lib = None

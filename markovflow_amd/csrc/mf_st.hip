@@ -20,6 +20,9 @@
 //            registers across the groups (36 accumulators; the lower triangle is what leaves), thread j < n entry j of
 //            sum_k gm_k W_k, thread 0 sum_k ve_k: one workspace row of n (n + 1) / 2 + n + 1 values per workgroup.
 // Pass 2, one block per (series, segment), adds a segment's rows in ascending order and mirrors the triangle.
+// The CVI site update of the same model (spatio_temporal_variational.py:509-552, mf_lik_st_cvi_site_update_*) is pass 1 in the mode
+// ST_WANT_SITES - g1 = gm - 2 gv fmu rides into the vector sum in place of gm - and a pass 2 of its own, st_cvi_reduce_kernel, which
+// adds the rows in the same order and blends the sums into nat1 and nat2 in place.
 // Every sum starts from 0 and grows by one fused multiply-add per term, index ascending (include/markovflow_amd.h has the list); no
 // floating-point atomics.  The tile table is clamped here, not trusted.
 #include "../../include/markovflow_amd.h"
@@ -66,7 +69,9 @@ __host__ __device__ inline StLayout st_layout(int Ms, int dt, int R) {
     return L;
 }
 
-constexpr int ST_WANT_VE = 1, ST_WANT_GRADS = 2;
+// ST_WANT_SITES (with ST_WANT_GRADS): the value that rides with the point into the vector sum is g1 = gm - 2 gv fmu, the gradient in
+// the first expectation parameter, in place of gm - the sums are then the CVI site targets (st_cvi_reduce_kernel)
+constexpr int ST_WANT_VE = 1, ST_WANT_GRADS = 2, ST_WANT_SITES = 4;
 
 template <typename T, int LIK>
 __global__ void __launch_bounds__(ST_THREADS) st_expect_tile_kernel(
@@ -212,6 +217,7 @@ __global__ void __launch_bounds__(ST_THREADS) st_expect_tile_kernel(
                         ve = gm = gv = nan_of<T>();
                     }
                     if (g_c) g_c[id] = gv;
+                    if (want & ST_WANT_SITES) gm = m_fma(T(-2) * gv, mu, gm);
                 }
             }
             lsc[1 * ST_GROUP + lane] = ve;
@@ -323,6 +329,52 @@ __global__ void __launch_bounds__(256) st_expect_reduce_kernel(long num_tiles, i
     }
 }
 
+// Pass 2 of the CVI site update, one block per (series, segment): the segment's workspace rows are added in ascending row order
+// from 0 (the sums of st_expect_reduce_kernel, entry by entry) - the packed lower triangle into LDS, consecutive lanes on consecutive
+// entries of a row - and blended into the sites in place, nat <- fma(lr, sum, (1 - lr) nat).  nat2 is swept row by row, consecutive
+// lanes on consecutive columns, one read and one write per entry; both triangles take the one sum of the lower triangle, each entry
+// with its own old value.  n (n + 1) / 2 values of dynamic LDS.
+template <typename T>
+__global__ void __launch_bounds__(256) st_cvi_reduce_kernel(long num_tiles, int n, const long long* __restrict__ seg_tile,
+                                                            const T* __restrict__ ws, T lr, T* __restrict__ nat1,
+                                                            T* __restrict__ nat2, T* __restrict__ ve_sum) {
+    extern __shared__ double2 st_cvi_lds_raw[];
+    T* const lt = reinterpret_cast<T*>(st_cvi_lds_raw);
+    const long bs = blockIdx.x;
+    long t_lo = 0, t_hi = 0;
+    if (seg_tile) {                                // (NULL: no points at all)
+        t_lo = (long)seg_tile[bs];
+        t_hi = (long)seg_tile[bs + 1];
+        clamp_range(t_lo, t_hi, num_tiles);
+    }
+    const int tri = n * (n + 1) / 2;
+    const long rowlen = (long)tri + n + 1;
+    const T one_minus = T(1) - lr;
+    for (int idx = threadIdx.x; idx < tri; idx += 256) {
+        T acc = T(0);
+        for (long t = t_lo; t < t_hi; ++t) acc += ws[t * rowlen + idx];
+        lt[idx] = acc;
+    }
+    for (int idx = threadIdx.x; idx < n; idx += 256) {
+        T acc = T(0);
+        for (long t = t_lo; t < t_hi; ++t) acc += ws[t * rowlen + tri + idx];
+        T* const dst = nat1 + bs * n + idx;
+        *dst = m_fma(lr, acc, one_minus * *dst);
+    }
+    if (ve_sum && threadIdx.x == 0) {
+        T acc = T(0);
+        for (long t = t_lo; t < t_hi; ++t) acc += ws[t * rowlen + tri + n];
+        ve_sum[bs] = acc;
+    }
+    __syncthreads();
+    T* const dst2 = nat2 + bs * (long)n * n;
+    for (int idx = threadIdx.x; idx < n * n; idx += 256) {
+        const int i = idx / n, j = idx - i * n;
+        const int hi = i > j ? i : j, lo = i > j ? j : i;
+        dst2[idx] = m_fma(lr, lt[hi * (hi + 1) / 2 + lo], one_minus * dst2[idx]);
+    }
+}
+
 inline bool st_in_range(int Ms, int two_dt) {
     return Ms >= 1 && two_dt >= 2 && !(two_dt & 1) && Ms <= ST_MAX_D && two_dt <= 2 * ST_MAX_D && Ms * (two_dt / 2) <= ST_MAX_D;
 }
@@ -330,6 +382,72 @@ inline bool st_in_range(int Ms, int two_dt) {
 inline size_t st_row(int Ms, int two_dt) {
     const size_t n = size_t(Ms) * size_t(two_dt);
     return n * (n + 1) / 2 + n + 1;
+}
+
+// pass 1 on `tiles` > 0 rows: the slab height, the LDS limit and the launch
+template <typename T>
+int st_launch_tiles(int64_t B, int64_t N, int64_t S, int Ms, int two_dt, int lik, const Rule<T>& q, const Par<T>& p, const int64_t* seg,
+                    const T* a, const T* wt, const T* c, const T* y, const T* pm, const T* pc, int64_t tiles, const int64_t* tile_seg,
+                    const int64_t* seg_tile, int want, void* ws, T* g_a, T* g_wt, T* g_c, T* fmu, T* fvar, void* stream) {
+    const int dt = two_dt / 2;
+    int R = 32;
+    while (R > 8 && size_t(st_layout(Ms, dt, R).total) * sizeof(T) > ST_LDS_LIMIT) R >>= 1;
+    const size_t lds = size_t(st_layout(Ms, dt, R).total) * sizeof(T);
+    if (lds > ST_LDS_LIMIT) return -100;
+    return with_lik(lik, [&](auto L) {
+        auto kernel = st_expect_tile_kernel<T, decltype(L)::value>;
+        // past the 64 KB a kernel gets by default the limit is raised explicitly (gfx950: 160 KB per workgroup)
+        if (lds > size_t(64) * 1024 &&
+            hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+                hipSuccess)
+            return -1000;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(ST_THREADS), lds, static_cast<hipStream_t>(stream), (long)N, (int)S,
+                           (long)(B * S), Ms, dt, R, q, p, ll(seg), ll(tile_seg), ll(seg_tile), a, wt, c, y, pm, pc, want,
+                           static_cast<T*>(ws), g_a, g_wt, g_c, fmu, fvar);
+        return hipGetLastError() == hipSuccess ? 0 : -1000;
+    });
+}
+
+// The CVI site update: pass 1 in the ST_WANT_SITES mode, then st_cvi_reduce_kernel.  Argument positions are those of
+// mf_lik_st_cvi_site_update_*.
+template <typename T>
+int run_st_cvi(int64_t B, int64_t N, int64_t S, int Ms, int two_dt, int lik, const double* params, int nq, const double* nodes,
+               const double* weights, const int64_t* seg, const T* a, const T* wt, const T* c, const T* y, const T* pm, const T* pc,
+               int64_t tiles, const int64_t* tile_seg, const int64_t* seg_tile, void* ws, size_t ws_bytes, double learning_rate, T* nat1,
+               T* nat2, T* ve_sum, T* fmu, T* fvar, void* stream) {
+    Rule<T> q;
+    Par<T> p;
+    if (B < 0) return -1;
+    if (N < 0) return -2;
+    if (S < 1 || (B > 0 && S > int64_t(0x7fffffff) / B)) return -3;
+    if (!st_in_range(Ms, two_dt)) return -100;
+    int bad = prepare<T>(0, lik, params, nq, nodes, weights, false, q, p);      // -2 ... -6 there: arguments 6 ... 10 here
+    if (bad) return bad - 4;
+    if (tiles < 0 || tiles > int64_t(0x7fffffff) || (N == 0 && tiles != 0)) return -18;
+    if (!(learning_rate >= 0.0 && learning_rate <= 1.0)) return -23;           // (NaN fails both)
+    if ((bad = first_null(24, {nat1, nat2}))) return bad;
+    if (B == 0) return 0;
+    if (tiles > 0) {
+        if ((bad = first_null(11, {seg, a, wt, c, y, pm, pc}))) return bad;
+        if ((bad = first_null(19, {tile_seg, seg_tile}))) return bad;
+        if (!ws) return -21;
+        if (ws_bytes < size_t(tiles) * st_row(Ms, two_dt) * sizeof(T)) return -22;
+    }
+    const int n = Ms * two_dt;
+    const size_t lds2 = size_t(n) * (n + 1) / 2 * sizeof(T);
+    auto reduce = st_cvi_reduce_kernel<T>;
+    if (lds2 > size_t(64) * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(reduce), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess)
+        return -1000;
+    if (tiles > 0) {
+        const int want = (ve_sum ? ST_WANT_VE : 0) | ST_WANT_GRADS | ST_WANT_SITES;
+        const int rc = st_launch_tiles<T>(B, N, S, Ms, two_dt, lik, q, p, seg, a, wt, c, y, pm, pc, tiles, tile_seg, seg_tile, want, ws,
+                                          nullptr, nullptr, nullptr, fmu, fvar, stream);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(reduce, dim3((unsigned)(B * S)), dim3(256), lds2, static_cast<hipStream_t>(stream), (long)tiles, n,
+                       tiles > 0 ? ll(seg_tile) : nullptr, static_cast<const T*>(ws), T(learning_rate), nat1, nat2, ve_sum);
+    return hipGetLastError() == hipSuccess ? 0 : -1000;
 }
 
 template <typename T>
@@ -363,25 +481,11 @@ int run_st(int64_t B, int64_t N, int64_t S, int Ms, int two_dt, int lik, const d
             if (ws_bytes < size_t(tiles) * st_row(Ms, two_dt) * sizeof(T)) return -22;
         }
     }
-    const int dt = two_dt / 2, n = Ms * two_dt;
+    const int n = Ms * two_dt;
     if (tiles > 0) {
-        int R = 32;
-        while (R > 8 && size_t(st_layout(Ms, dt, R).total) * sizeof(T) > ST_LDS_LIMIT) R >>= 1;
-        const size_t lds = size_t(st_layout(Ms, dt, R).total) * sizeof(T);
-        if (lds > ST_LDS_LIMIT) return -100;
         const int want = (ve_sum ? ST_WANT_VE : 0) | (g_mean ? ST_WANT_GRADS : 0);
-        const int rc = with_lik(lik, [&](auto L) {
-            auto kernel = st_expect_tile_kernel<T, decltype(L)::value>;
-            // past the 64 KB a kernel gets by default the limit is raised explicitly (gfx950: 160 KB per workgroup)
-            if (lds > size_t(64) * 1024 &&
-                hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-                    hipSuccess)
-                return -1000;
-            hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(ST_THREADS), lds, static_cast<hipStream_t>(stream), (long)N, (int)S,
-                               (long)(B * S), Ms, dt, R, q, p, ll(seg), ll(tile_seg), ll(seg_tile), a, wt, c, y, pm, pc, want,
-                               static_cast<T*>(ws), g_a, g_wt, g_c, fmu, fvar);
-            return hipGetLastError() == hipSuccess ? 0 : -1000;
-        });
+        const int rc = st_launch_tiles<T>(B, N, S, Ms, two_dt, lik, q, p, seg, a, wt, c, y, pm, pc, tiles, tile_seg, seg_tile, want, ws,
+                                          g_a, g_wt, g_c, fmu, fvar, stream);
         if (rc) return rc;
     }
     if (!want_seg) return 0;                       // per-point outputs only
@@ -418,6 +522,31 @@ int mf_lik_st_expectations_f32(int64_t B, int64_t N, int64_t S, int Ms, int two_
     return run_st<float>(B, N, S, Ms, two_dt, lik, params, nq, nodes, weights, seg_offsets, a, wt, c, y, pair_mean, pair_cov,
                          num_tiles, tile_seg, seg_tile, workspace, workspace_bytes, ve_sum, g_mean, g_cov, g_a, g_wt, g_c, fmu, fvar,
                          stream);
+}
+
+size_t mf_lik_st_cvi_site_update_workspace_bytes(int64_t num_tiles, int Ms, int two_dt, int elem_size) {
+    return mf_lik_st_expectations_workspace_bytes(num_tiles, Ms, two_dt, elem_size);      // the same rows
+}
+
+int mf_lik_st_cvi_site_update_f64(int64_t B, int64_t N, int64_t S, int Ms, int two_dt, int lik, const double* params, int nq,
+                                  const double* nodes, const double* weights, const int64_t* seg_offsets, const double* a,
+                                  const double* wt, const double* c, const double* y, const double* pair_mean,
+                                  const double* pair_cov, int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile,
+                                  void* workspace, size_t workspace_bytes, double learning_rate, double* nat1, double* nat2,
+                                  double* ve_sum, double* fmu, double* fvar, void* stream) {
+    return run_st_cvi<double>(B, N, S, Ms, two_dt, lik, params, nq, nodes, weights, seg_offsets, a, wt, c, y, pair_mean, pair_cov,
+                              num_tiles, tile_seg, seg_tile, workspace, workspace_bytes, learning_rate, nat1, nat2, ve_sum, fmu, fvar,
+                              stream);
+}
+int mf_lik_st_cvi_site_update_f32(int64_t B, int64_t N, int64_t S, int Ms, int two_dt, int lik, const double* params, int nq,
+                                  const double* nodes, const double* weights, const int64_t* seg_offsets, const float* a,
+                                  const float* wt, const float* c, const float* y, const float* pair_mean, const float* pair_cov,
+                                  int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile, void* workspace,
+                                  size_t workspace_bytes, float learning_rate, float* nat1, float* nat2, float* ve_sum, float* fmu,
+                                  float* fvar, void* stream) {
+    return run_st_cvi<float>(B, N, S, Ms, two_dt, lik, params, nq, nodes, weights, seg_offsets, a, wt, c, y, pair_mean, pair_cov,
+                             num_tiles, tile_seg, seg_tile, workspace, workspace_bytes, learning_rate, nat1, nat2, ve_sum, fmu, fvar,
+                             stream);
 }
 
 }  // extern "C"

@@ -723,11 +723,16 @@ def sparse_site_projections(kernel: SDEKernel, time_points: torch.Tensor, induci
     h = kernel.generate_emission_model(time_points).emission_matrix                         # [.., N, 1, d]
     w = (h @ proj)[..., 0, :]
     c = (h @ cov @ h.transpose(-1, -2))[..., 0, 0]
+    return w.contiguous(), c.contiguous(), indices, _site_offsets(time_points, inducing_points)
+
+
+def _site_offsets(time_points: torch.Tensor, inducing_points: torch.Tensor) -> torch.Tensor:
+    """The segment offsets ``batch + [M + 2]`` of ``sparse_site_projections``."""
     x = time_points.to(inducing_points.dtype).contiguous()
     inner = torch.searchsorted(x, inducing_points.contiguous(), right=True)
     zero = torch.zeros_like(inner[..., :1])
     offsets = torch.cat([zero, inner, torch.full_like(zero, x.shape[-1])], dim=-1)
-    return w.contiguous(), c.contiguous(), indices, offsets.contiguous()
+    return offsets.contiguous()
 
 
 def _sparse_point_marginals(w: torch.Tensor, c: torch.Tensor, indices: torch.Tensor, pair_mean: torch.Tensor, pair_cov: torch.Tensor,
@@ -2042,14 +2047,19 @@ def st_expected_log_likelihood(likelihood: Likelihood, a: torch.Tensor, wt: torc
     return _STExpectedLogLikelihood.apply(pair_mean, pair_cov, a, wt, c, likelihood, y, offsets, tiles)
 
 
+def _st_kron_rows(a: torch.Tensor, wt: torch.Tensor) -> torch.Tensor:
+    """``W [B N, 2 Ms d_t]`` with ``W[k, half D + s d_t + i] = a[k, s] wt[k, half d_t + i]``, the batch flattened."""
+    ms, two_dt = a.shape[-1], wt.shape[-1]
+    return (wt.reshape(tuple(a.shape[:-1]) + (2, 1, two_dt // 2)) * a[..., None, :, None]).reshape(-1, ms * two_dt)
+
+
 def _st_torch_marginals(a, wt, c, indices, pair_mean, pair_cov) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Per point ``fmu`` and ``fvar`` (``[.., N]`` each) and the flat segment index ``[B N]`` in differentiable torch: ``W`` is
     ``O(N 2D)``, the symmetrised pair covariance is applied segment by segment (one matrix product per non-empty segment), never
     gathered per point."""
-    ms, two_dt = a.shape[-1], wt.shape[-1]
-    dt, pair, segs = two_dt // 2, ms * two_dt, pair_mean.shape[-2]
+    pair, segs = a.shape[-1] * wt.shape[-1], pair_mean.shape[-2]
     lead, n = tuple(a.shape[:-2]), a.shape[-2]
-    w = (wt.reshape(lead + (n, 2, 1, dt)) * a[..., None, :, None]).reshape(-1, pair)
+    w = _st_kron_rows(a, wt)
     series = torch.arange(math.prod(lead), device=indices.device).reshape(lead + (1,))
     flat = (indices + series * segs).reshape(-1)
     mean = pair_mean.reshape(-1, pair)
@@ -2097,52 +2107,100 @@ def st_point_marginals(a: torch.Tensor, wt: torch.Tensor, c: torch.Tensor, offse
         return fmu, fvar
 
 
-class SpatioTemporalSparseVariational(_SparseGaussianProcess):
-    """Sparse variational GP with the product kernel ``k((x, t), (x', t')) = k_s(x, x') k_t(t, t')``
-    (markovflow/models/spatio_temporal_variational.py:109-357): space is marginalised to ``Ms`` inducing locations, time to ``Mt``
-    inducing times, and ``q`` is a trainable ``StateSpaceModel`` of state dimension ``Ms d_t <= 64`` on the inducing times
-    (``kernels.SparseSpatioTemporalKernel``).  The ELBO is ``scale sum_i E_q log p(y_i | f_i) - KL[q || p]``; train ``q`` with any torch
-    optimiser on ``trainable_variables`` or with ``ssm_natgrad.SSMNaturalGradient`` on ``dist_q``, and the hyper-parameters of both
-    kernels by giving their tensors ``requires_grad_()``.
+# ---- the spatio-temporal sparse CVI model: the site update ---------------------------------------------------------------------------
+def _st_check_sites(what: str, a, lead, segs: int, pair: int, learning_rate, nat1, nat2) -> float:
+    for name, t, shape in (("nat1", nat1, lead + (segs, pair)), ("nat2", nat2, lead + (segs, pair, pair))):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+            raise ValueError(f"{what}: {name} must be a tensor of shape {shape}")
+    _lib.same_dtype_device(a, what, nat1=nat1, nat2=nat2)
+    lr = float(learning_rate)
+    if not 0.0 <= lr <= 1.0:
+        raise ValueError(f"{what}: learning_rate must lie in [0, 1], got {learning_rate}")
+    return lr
 
-    The data are ``(X [.., N, Dx + 1], Y [.., N, 1])`` with TIME IN THE LAST COLUMN of ``X``; leading batch dimensions go on
-    ``inducing_time`` and the data, ``inducing_space`` and both kernels are shared by the series.  The model has a zero mean function
-    and plain-float likelihood parameters, as every model here.  As in the reference the conditional of ``f(x, t)`` given the state
-    at ``t`` is that of a temporal kernel with unit variance: put the signal variance into ``kernel_space``.
 
-    ``mf_lik_st_expectations_*`` and the kernel class carry ``Ms d_t <= 64`` in both dtypes; the chain operators under ``elbo`` - the
-    marginals of ``dist_q``, their adjoint and the KL divergence - carry state dimensions up to 64 in float32 and up to 32 in float64
-    (``mf_max_state_dim_f64_tile_ops()``): a float64 model with ``Ms d_t > 32`` raises ``NotImplementedError`` in ``elbo`` until they
-    reach 64 there too (DESIGN §7 item 3)."""
+def st_cvi_site_update_torch(likelihood: Likelihood, a: torch.Tensor, wt: torch.Tensor, c: torch.Tensor, y: torch.Tensor,
+                             indices: torch.Tensor, pair_mean: torch.Tensor, pair_cov: torch.Tensor, learning_rate: float,
+                             nat1: torch.Tensor, nat2: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The spatio-temporal CVI step as a torch composition (spatio_temporal_variational.py:509-552), IN PLACE on
+    ``nat1 [.., Mt+1, 2D]`` and ``nat2 [.., Mt+1, 2D, 2D]``: the marginals of ``_st_torch_marginals``, the likelihood's
+    ``(ve, gm, gv)``, ``gradient_transformation_mean_var_to_expectation`` (``g1 = gm - 2 gv fmu``, ``g2 = gv``),
+    ``theta_1 = sum_k g1_k W_k`` over the per-point pair index (``indices [.., N]``) and ``theta_2 = sum_k gv_k W_k W_k^T`` formed
+    segment by segment as ``W_s^T diag(gv) W_s`` (memory ``O(N 2D)`` plus one ``2D x 2D`` product per non-empty segment, never
+    ``[N, 2D, 2D]``); ``nat <- (1 - lr) nat + lr sum``.  A point with ``fvar`` not positive has NaN in its marginals and makes the
+    sites of its segment NaN, as in ``sparse_cvi_site_update_torch``.  What ``mf_lik_st_cvi_site_update_*`` fuses: it runs on CPU
+    tensors, it is the model's route there and it is what the kernel is measured against.  Returns ``(ve_sum [.., Mt+1], fmu, fvar
+    [.., N])``."""
+    segs = pair_mean.shape[-2]
+    lead = tuple(indices.shape[:-1])
+    ms, two_dt = _st_check("st_cvi_site_update_torch", likelihood, a, wt, c, y, lead, segs, pair_mean, pair_cov)
+    pair = ms * two_dt
+    lr = _st_check_sites("st_cvi_site_update_torch", a, lead, segs, pair, learning_rate, nat1, nat2)
+    with torch.no_grad():
+        fmu, fvar, flat = _st_torch_marginals(a, wt, c, indices, pair_mean, pair_cov)
+        ve, g_mu, g_var = likelihood._expectations(fmu[..., None], fvar[..., None], y[..., None])
+        nan = torch.full_like(fvar, float("nan"))
+        bad = ~(fvar > 0)
+        fmu, fvar = torch.where(bad, nan, fmu), torch.where(bad, nan, fvar)
+        ve, g_mu, g_var = (torch.where(bad[..., None], nan[..., None], v) for v in (ve, g_mu, g_var))
+        g1, g2 = gradient_transformation_mean_var_to_expectation((fmu[..., None], fvar[..., None]), (g_mu, g_var))
+        w = _st_kron_rows(a, wt)
+        rows_total = math.prod(lead) * segs
+        sum1 = torch.zeros(rows_total, pair, dtype=w.dtype, device=w.device).index_add_(0, flat, g1.reshape(-1, 1) * w)
+        sum2 = torch.zeros(rows_total, pair, pair, dtype=w.dtype, device=w.device)
+        order = torch.argsort(flat, stable=True)
+        w_sorted, g2_sorted = w[order], g2.reshape(-1, 1)[order]
+        start = 0
+        for s, count in enumerate(torch.bincount(flat, minlength=rows_total).tolist()):
+            if count:
+                rows = w_sorted[start:start + count]
+                sum2[s] = rows.transpose(-1, -2) @ (g2_sorted[start:start + count] * rows)
+                start += count
+        ve_sum = torch.zeros(rows_total, dtype=w.dtype, device=w.device).index_add_(0, flat, ve.reshape(-1))
+        nat1.mul_(1.0 - lr).add_(lr * sum1.reshape(nat1.shape))
+        nat2.mul_(1.0 - lr).add_(lr * sum2.reshape(nat2.shape))
+    return ve_sum.reshape(lead + (segs,)), fmu, fvar
 
-    def __init__(self, inducing_space: torch.Tensor, inducing_time: torch.Tensor, kernel_space, kernel_time: SDEKernel,
-                 likelihood: Likelihood, num_data: Optional[int] = None,
-                 initial_distribution: Optional[StateSpaceModel] = None) -> None:
-        """
-        :param inducing_space: ``[Ms, Dx]``.
-        :param inducing_time: ``batch + [Mt]``, sorted, at least two.
-        :param kernel_space: a ``markovflow_amd.spatial_kernels.SpatialKernel``.
-        :param kernel_time: a stationary ``markovflow_amd.kernels.SDEKernel`` with one output; ``Ms d_t <= 64``.
-        :param num_data: the total number of observations per series when ``elbo`` is fed minibatches.
-        :param initial_distribution: the initial ``q`` on the inducing times; the prior by default.
-        """
-        kernel = SparseSpatioTemporalKernel(kernel_space, kernel_time, inducing_space)
-        super().__init__(kernel, likelihood, inducing_time, min_inducing=2)
-        _lib.same_dtype_device(inducing_time, "SpatioTemporalSparseVariational", inducing_space=inducing_space)
-        if num_data is not None and not num_data > 0:
-            raise ValueError(f"num_data must be positive, got {num_data}")
-        self.num_data = num_data
-        if initial_distribution is None:
-            initial_distribution = kernel.state_space_model(inducing_time)
-        elif not isinstance(initial_distribution, StateSpaceModel):
-            raise TypeError("initial_distribution must be a StateSpaceModel")
-        if (tuple(initial_distribution.batch_shape) != tuple(inducing_time.shape[:-1])
-                or initial_distribution.num_transitions + 1 != inducing_time.shape[-1]
-                or initial_distribution.state_dim != kernel.state_dim):
-            raise ValueError("initial_distribution must be a chain on the inducing times: batch shape "
-                             f"{tuple(inducing_time.shape[:-1])}, {inducing_time.shape[-1]} states of dimension {kernel.state_dim}")
-        self._dist_q = initial_distribution.create_trainable_copy()
-        self._posterior = ConditionalProcess(posterior_dist=self._dist_q, kernel=kernel, conditioning_time_points=inducing_time)
+
+def st_cvi_site_update_hip(likelihood: Likelihood, a: torch.Tensor, wt: torch.Tensor, c: torch.Tensor, y: torch.Tensor,
+                           offsets: torch.Tensor, pair_mean: torch.Tensor, pair_cov: torch.Tensor, learning_rate: float,
+                           nat1: torch.Tensor, nat2: torch.Tensor, tiles=None, want_outputs: bool = False):
+    """ONE call of ``mf_lik_st_cvi_site_update_*`` on HIP tensors (``Ms d_t <= 64``): what ``st_cvi_site_update_torch`` computes,
+    with the segment ``offsets [.., Mt + 2]`` in place of the per-point index; ``nat1`` / ``nat2`` (contiguous) are updated IN
+    PLACE.  ``want_outputs``: return ``(ve_sum [.., Mt+1], fmu, fvar [.., N])`` (else three Nones).  ``tiles``:
+    ``sparse_expectation_tiles(offsets, ST_EXPECT_TILE)`` when the caller keeps it."""
+    what = "st_cvi_site_update_hip"
+    segs = offsets.shape[-1] - 1
+    lead = tuple(offsets.shape[:-1])
+    ms, two_dt = _st_check(what, likelihood, a, wt, c, y, lead, segs, pair_mean, pair_cov)
+    lr = _st_check_sites(what, a, lead, segs, ms * two_dt, learning_rate, nat1, nat2)
+    if not (nat1.is_contiguous() and nat2.is_contiguous()):
+        raise ValueError(f"{what}: nat1 and nat2 must be contiguous")
+    dtype, dev, n = a.dtype, a.device, a.shape[-2]
+    bsz = offsets.numel() // (segs + 1)
+    if tiles is None:
+        tiles = sparse_expectation_tiles(offsets, ST_EXPECT_TILE)
+    num_tiles, tile_seg, seg_tile = tiles
+    new = lambda *shape: torch.empty(lead + shape, dtype=dtype, device=dev) if want_outputs else None      # noqa: E731
+    outs = (new(segs), new(n), new(n))
+    ws_bytes = int(_lib.load().mf_lik_st_cvi_site_update_workspace_bytes(num_tiles, ms, two_dt, a.element_size()))
+    ws = _lib.workspace(ws_bytes, dev)
+    # (contiguous copies are held in locals until the call has been issued: a pointer keeps no tensor alive)
+    offsets, a, wt, c, y, pair_mean, pair_cov = (t.contiguous() for t in (offsets, a, wt, c, y, pair_mean, pair_cov))
+    _lib.call("mf_lik_st_cvi_site_update", dtype, bsz, n, segs, ms, two_dt, *likelihood._kernel_args(), _lib.ptr(offsets),
+              _lib.ptr(a), _lib.ptr(wt), _lib.ptr(c), _lib.ptr(y), _lib.ptr(pair_mean), _lib.ptr(pair_cov), num_tiles,
+              _lib.ptr(tile_seg), _lib.ptr(seg_tile), _lib.ptr(ws), ws_bytes, lr, _lib.ptr(nat1), _lib.ptr(nat2),
+              *[_lib.ptr(o) for o in outs], _lib.stream_ptr(dev))
+    # the kernel wrote through raw pointers: tell torch, so that whatever keys a cache on (tensor, version) sees the write
+    torch.autograd.graph.increment_version(nat1)
+    torch.autograd.graph.increment_version(nat2)
+    return outs
+
+
+class _SpatioTemporalData:
+    """What the two spatio-temporal models share, mixed in ahead of their inducing-point base: the checks on ``(X, Y)`` with time in
+    the last column of ``X``, the sort-on-a-copy rule, the cache of the per-point projections ``(a, wt, c)``, the pair marginals of
+    ``dist_q`` with the float64 limit of the chain operators, the ELBO's data term and the predictions."""
 
     @property
     def inducing_time(self) -> torch.Tensor:
@@ -2151,26 +2209,6 @@ class SpatioTemporalSparseVariational(_SparseGaussianProcess):
     @property
     def inducing_space(self) -> torch.Tensor:
         return self._kernel.inducing_space
-
-    @property
-    def dist_p(self) -> StateSpaceModel:
-        """The prior chain on the inducing times, rebuilt on every access."""
-        return self._kernel.state_space_model(self.inducing_inputs)
-
-    @property
-    def dist_q(self) -> StateSpaceModel:
-        """The variational chain, a trainable copy of the prior chain: its leaves are ``trainable_variables``."""
-        return self._dist_q
-
-    @property
-    def posterior(self) -> ConditionalProcess:
-        """The posterior process of the ``Ms`` whitened outputs at the inducing locations."""
-        return self._posterior
-
-    @property
-    def trainable_variables(self) -> Tuple[torch.Tensor, ...]:
-        """The leaves of ``dist_q``: ``(mu0, chol_P0, As, offsets, chol_Qs)``."""
-        return self._dist_q.trainable_variables
 
     # ---- data --------------------------------------------------------------------------------------------------------------------
     def _check_data(self, input_data: Tuple[torch.Tensor, torch.Tensor], what: str) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -2230,7 +2268,7 @@ class SpatioTemporalSparseVariational(_SparseGaussianProcess):
             h = kernel.kernel_time.generate_emission_model(times).emission_matrix
             wt, ct = (h @ proj)[..., 0, :], (h @ cov @ h.transpose(-1, -2))[..., 0, 0]
             with torch.no_grad():
-                offsets = sparse_site_projections(kernel.kernel_time, times, self.inducing_inputs)[3]
+                offsets = _site_offsets(times, self.inducing_inputs)
         else:
             wt, ct, indices, offsets = sparse_site_projections(kernel.kernel_time, times, self.inducing_inputs)
         a = kernel.space_weights(space)
@@ -2238,18 +2276,23 @@ class SpatioTemporalSparseVariational(_SparseGaussianProcess):
         tiles = sparse_expectation_tiles(offsets, ST_EXPECT_TILE) if inputs.is_cuda else None
         return order, a.contiguous(), wt.contiguous(), c.contiguous(), indices, offsets, tiles
 
-    def _pair_marginals(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        """``(m_pair [.., Mt+1, 2D], S_pair [.., Mt+1, 2D, 2D])`` of ``dist_q`` with the stationary prior beyond both ends."""
+    def _pair_marginals(self, dist_q: Optional[StateSpaceModel] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(m_pair [.., Mt+1, 2D], S_pair [.., Mt+1, 2D, 2D])`` of ``dist_q`` (the model's own by default) with the stationary
+        prior beyond both ends."""
+        self._check_chain_limit()
+        return conditionals.pairwise_marginals(self.dist_q if dist_q is None else dist_q, *self._stationary_prior())
+
+    def _check_chain_limit(self) -> None:
         limit = _lib.load().mf_max_state_dim_f64_tile_ops()
         if self.inducing_inputs.dtype == torch.float64 and self._kernel.state_dim > limit:
             # mf_lik_st_expectations_* carries Ms d_t <= 64; the chain's marginals, their adjoint and the KL do not (DESIGN §7 item 3)
-            raise NotImplementedError(f"SpatioTemporalSparseVariational: the chain operators (marginals, KL divergence and their "
+            raise NotImplementedError(f"{type(self).__name__}: the chain operators (marginals, KL divergence and their "
                                       f"adjoints) carry state dimensions up to {limit} in float64, Ms d_t = {self._kernel.state_dim}")
-        return conditionals.pairwise_marginals(self._dist_q, *self._stationary_prior())
 
-    def _expected_log_likelihood(self, inputs: torch.Tensor, observations: torch.Tensor) -> torch.Tensor:
+    def _expected_log_likelihood(self, inputs: torch.Tensor, observations: torch.Tensor,
+                                 dist_q: Optional[StateSpaceModel] = None) -> torch.Tensor:
         """``sum_i E_q log p(y_i | f_i)`` per pair, ``batch + [Mt + 1]``."""
-        pair_mean, pair_cov = self._pair_marginals()
+        pair_mean, pair_cov = self._pair_marginals(dist_q)
         # a hyper-parameter under the tape: the projections are part of the graph, and the kernel's per-point adjoints carry it
         proj = self._compute_projections(inputs) if self._hyper_needs_grad() else self._projections(inputs)
         order, a, wt, c, indices, offsets, tiles = proj
@@ -2259,24 +2302,6 @@ class SpatioTemporalSparseVariational(_SparseGaussianProcess):
         if self._fused(inputs):
             return st_expected_log_likelihood(self._likelihood, a, wt, c, y, offsets, pair_mean, pair_cov, tiles=tiles)
         return st_expected_log_likelihood_torch(self._likelihood, a, wt, c, y, indices, pair_mean, pair_cov)
-
-    # ---- inference ---------------------------------------------------------------------------------------------------------------
-    def elbo(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
-        """``scale sum_i E_q log p(y_i | f_i) - KL[q || p]``, summed over the batch; ``scale = num_data / minibatch size`` when
-        ``num_data`` is set (spatio_temporal_variational.py:209-236).  The data need not be sorted by time: each series is sorted on
-        a copy (a stable argsort, cached with the projections), so the ELBO of shuffled data has the bits of the sorted data's.  On
-        HIP tensors: the pair marginals of ``dist_q`` under the tape and ONE call of ``mf_lik_st_expectations_*`` whose adjoints the
-        backward reuses - also with a hyper-parameter of either kernel under the tape, through the per-point adjoints."""
-        inputs, observations = self._check_data(input_data, "elbo")
-        ve = torch.sum(self._expected_log_likelihood(inputs, observations))
-        kl = torch.sum(self._dist_q.kl_divergence(self.dist_p))
-        if self.num_data is not None:
-            ve = ve * (float(self.num_data) / inputs.shape[-2])
-        return ve - kl
-
-    def loss(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
-        """``-elbo`` (spatio_temporal_variational.py:185-192)."""
-        return -self.elbo(input_data)
 
     def space_time_predict_f(self, inputs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """Posterior mean and variance of ``f`` at ``inputs [.., N, Dx + 1]`` (any order in time), ``batch + [N, 1]`` each
@@ -2298,3 +2323,181 @@ class SpatioTemporalSparseVariational(_SparseGaussianProcess):
         inputs, observations = self._check_data(input_data, "predict_log_density")
         f_mean, f_var = self.space_time_predict_f(inputs)
         return self._likelihood.predict_log_density(f_mean, f_var, observations)
+
+
+class SpatioTemporalSparseVariational(_SpatioTemporalData, _SparseGaussianProcess):
+    """Sparse variational GP with the product kernel ``k((x, t), (x', t')) = k_s(x, x') k_t(t, t')``
+    (markovflow/models/spatio_temporal_variational.py:109-357): space is marginalised to ``Ms`` inducing locations, time to ``Mt``
+    inducing times, and ``q`` is a trainable ``StateSpaceModel`` of state dimension ``Ms d_t <= 64`` on the inducing times
+    (``kernels.SparseSpatioTemporalKernel``).  The ELBO is ``scale sum_i E_q log p(y_i | f_i) - KL[q || p]``; train ``q`` with any torch
+    optimiser on ``trainable_variables`` or with ``ssm_natgrad.SSMNaturalGradient`` on ``dist_q``, and the hyper-parameters of both
+    kernels by giving their tensors ``requires_grad_()``.
+
+    The data are ``(X [.., N, Dx + 1], Y [.., N, 1])`` with TIME IN THE LAST COLUMN of ``X``; leading batch dimensions go on
+    ``inducing_time`` and the data, ``inducing_space`` and both kernels are shared by the series.  The model has a zero mean function
+    and plain-float likelihood parameters, as every model here.  As in the reference the conditional of ``f(x, t)`` given the state
+    at ``t`` is that of a temporal kernel with unit variance: put the signal variance into ``kernel_space``.
+
+    ``mf_lik_st_expectations_*`` and the kernel class carry ``Ms d_t <= 64`` in both dtypes; the chain operators under ``elbo`` - the
+    marginals of ``dist_q``, their adjoint and the KL divergence - carry state dimensions up to 64 in float32 and up to 32 in float64
+    (``mf_max_state_dim_f64_tile_ops()``): a float64 model with ``Ms d_t > 32`` raises ``NotImplementedError`` in ``elbo`` until they
+    reach 64 there too (DESIGN §7 item 3)."""
+
+    def __init__(self, inducing_space: torch.Tensor, inducing_time: torch.Tensor, kernel_space, kernel_time: SDEKernel,
+                 likelihood: Likelihood, num_data: Optional[int] = None,
+                 initial_distribution: Optional[StateSpaceModel] = None) -> None:
+        """
+        :param inducing_space: ``[Ms, Dx]``.
+        :param inducing_time: ``batch + [Mt]``, sorted, at least two.
+        :param kernel_space: a ``markovflow_amd.spatial_kernels.SpatialKernel``.
+        :param kernel_time: a stationary ``markovflow_amd.kernels.SDEKernel`` with one output; ``Ms d_t <= 64``.
+        :param num_data: the total number of observations per series when ``elbo`` is fed minibatches.
+        :param initial_distribution: the initial ``q`` on the inducing times; the prior by default.
+        """
+        kernel = SparseSpatioTemporalKernel(kernel_space, kernel_time, inducing_space)
+        super().__init__(kernel, likelihood, inducing_time, min_inducing=2)
+        _lib.same_dtype_device(inducing_time, "SpatioTemporalSparseVariational", inducing_space=inducing_space)
+        if num_data is not None and not num_data > 0:
+            raise ValueError(f"num_data must be positive, got {num_data}")
+        self.num_data = num_data
+        if initial_distribution is None:
+            initial_distribution = kernel.state_space_model(inducing_time)
+        elif not isinstance(initial_distribution, StateSpaceModel):
+            raise TypeError("initial_distribution must be a StateSpaceModel")
+        if (tuple(initial_distribution.batch_shape) != tuple(inducing_time.shape[:-1])
+                or initial_distribution.num_transitions + 1 != inducing_time.shape[-1]
+                or initial_distribution.state_dim != kernel.state_dim):
+            raise ValueError("initial_distribution must be a chain on the inducing times: batch shape "
+                             f"{tuple(inducing_time.shape[:-1])}, {inducing_time.shape[-1]} states of dimension {kernel.state_dim}")
+        self._dist_q = initial_distribution.create_trainable_copy()
+        self._posterior = ConditionalProcess(posterior_dist=self._dist_q, kernel=kernel, conditioning_time_points=inducing_time)
+
+    @property
+    def dist_p(self) -> StateSpaceModel:
+        """The prior chain on the inducing times, rebuilt on every access."""
+        return self._kernel.state_space_model(self.inducing_inputs)
+
+    @property
+    def dist_q(self) -> StateSpaceModel:
+        """The variational chain, a trainable copy of the prior chain: its leaves are ``trainable_variables``."""
+        return self._dist_q
+
+    @property
+    def posterior(self) -> ConditionalProcess:
+        """The posterior process of the ``Ms`` whitened outputs at the inducing locations."""
+        return self._posterior
+
+    @property
+    def trainable_variables(self) -> Tuple[torch.Tensor, ...]:
+        """The leaves of ``dist_q``: ``(mu0, chol_P0, As, offsets, chol_Qs)``."""
+        return self._dist_q.trainable_variables
+
+    # ---- inference ---------------------------------------------------------------------------------------------------------------
+    def elbo(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+        """``scale sum_i E_q log p(y_i | f_i) - KL[q || p]``, summed over the batch; ``scale = num_data / minibatch size`` when
+        ``num_data`` is set (spatio_temporal_variational.py:209-236).  The data need not be sorted by time: each series is sorted on
+        a copy (a stable argsort, cached with the projections), so the ELBO of shuffled data has the bits of the sorted data's.  On
+        HIP tensors: the pair marginals of ``dist_q`` under the tape and ONE call of ``mf_lik_st_expectations_*`` whose adjoints the
+        backward reuses - also with a hyper-parameter of either kernel under the tape, through the per-point adjoints."""
+        inputs, observations = self._check_data(input_data, "elbo")
+        ve = torch.sum(self._expected_log_likelihood(inputs, observations))
+        kl = torch.sum(self._dist_q.kl_divergence(self.dist_p))
+        if self.num_data is not None:
+            ve = ve * (float(self.num_data) / inputs.shape[-2])
+        return ve - kl
+
+    def loss(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+        """``-elbo`` (spatio_temporal_variational.py:185-192)."""
+        return -self.elbo(input_data)
+
+
+class SpatioTemporalSparseCVI(_SpatioTemporalData, _SparseSitesGaussianProcess):
+    """The site-based variant of ``SpatioTemporalSparseVariational`` (markovflow/models/spatio_temporal_variational.py:360-587): the
+    same product kernel, inducing locations and inducing times, with ``q(u) = p(u) prod_m t_m(v_m)`` - ``Mt + 1`` Gaussian sites in
+    natural form (``nat1 [.., Mt+1, 2D]``, ``nat2 [.., Mt+1, 2D, 2D]``, ``D = Ms d_t``) on the pairs ``v_m = [u_{m-1}, u_m]`` of
+    neighbouring inducing states, pairs ``0`` and ``Mt`` with the stationary prior as their outer neighbour.  ``update_sites`` is one
+    conjugate-computation VI step on all sites; ``elbo`` is ``scale sum_i E_q log p(y_i | f_i) - KL[q || p]`` and trains the
+    hyper-parameters of both kernels with the sites held fixed.  Data, batch dimensions, the zero mean function and the role of
+    ``kernel_space``'s variance are those of ``SpatioTemporalSparseVariational``.
+
+    ``mf_lik_st_cvi_site_update_*`` carries ``Ms d_t <= 64`` in both dtypes; ``dist_q`` - the block-tridiagonal Cholesky, the blocks
+    of the inverse and the solve under ``naturals_to_ssm_params`` - its marginals and the KL divergence carry state dimensions up
+    to 64 in float32 and up to 32 in float64 (``mf_max_state_dim_f64_tile_ops()``): a float64 model with ``Ms d_t > 32`` raises
+    ``NotImplementedError`` in ``update_sites``, ``elbo`` and the predictions."""
+
+    def __init__(self, inducing_space: torch.Tensor, inducing_time: torch.Tensor, kernel_space, kernel_time: SDEKernel,
+                 likelihood: Likelihood, num_data: Optional[int] = None, learning_rate: float = 0.1) -> None:
+        """
+        :param inducing_space: ``[Ms, Dx]``.
+        :param inducing_time: ``batch + [Mt]``, sorted, at least two.
+        :param kernel_space: a ``markovflow_amd.spatial_kernels.SpatialKernel``.
+        :param kernel_time: a stationary ``markovflow_amd.kernels.SDEKernel`` with one output; ``Ms d_t <= 64``.
+        :param num_data: the total number of observations per series when ``elbo`` is fed minibatches (it does not enter
+            ``update_sites``, as in the reference).
+        :param learning_rate: the step ``rho`` of ``update_sites``, in [0, 1].
+        """
+        kernel = SparseSpatioTemporalKernel(kernel_space, kernel_time, inducing_space)
+        super().__init__(kernel, inducing_time, likelihood, learning_rate)
+        if inducing_time.shape[-1] < 2:
+            raise ValueError("inducing_points must be a tensor of shape batch + [num_inducing] with at least two points")
+        _lib.same_dtype_device(inducing_time, "SpatioTemporalSparseCVI", inducing_space=inducing_space)
+        if num_data is not None and not num_data > 0:
+            raise ValueError(f"num_data must be positive, got {num_data}")
+        self.num_data = num_data
+
+    # ---- inference ---------------------------------------------------------------------------------------------------------------
+    local_objective = SparseCVIGaussianProcess.local_objective
+    local_objective_and_gradients = SparseCVIGaussianProcess.local_objective_and_gradients
+
+    def projection_inducing_states_to_observations(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+        """The projection of the pair of inducing states that brackets a point onto the conditional mean of ``f`` there, the dense
+        ``P A`` of the reference, ``batch + [N, 1, 2D]`` in the order of the data (spatio_temporal_variational.py:494-507):
+        ``W_k[half D + s d_t + i] = a_k[s] wt_k[half d_t + i]``.  Differentiable in the hyper-parameters of both kernels when one of
+        them is under the tape.  For users and tests; ``update_sites`` never forms it."""
+        inputs, _ = self._check_data(input_data, "projection_inducing_states_to_observations")
+        order, a, wt = (self._compute_projections(inputs) if self._hyper_needs_grad() else self._projections(inputs))[:3]
+        w = _st_kron_rows(a, wt).reshape(tuple(a.shape[:-1]) + (1, a.shape[-1] * wt.shape[-1]))
+        if order is not None:
+            inverse = torch.argsort(order, dim=-1)
+            w = torch.gather(w, -3, inverse[..., None, None].expand(w.shape))
+        return w
+
+    def update_sites(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> None:
+        """One joint CVI step on the sites, in place: ``theta_m <- (1 - rho) theta_m + rho g_m`` with ``g_m`` the gradients of the
+        variational expectations of the segment's points in the expectation parameters, projected back onto the pair through
+        ``p(f_k | v_m)`` (spatio_temporal_variational.py:509-552).  The data need not be sorted by time: each series is sorted on a
+        copy, cached with the projections, and the observations are permuted alike.  HIP tensors: the pair marginals of ``dist_q``,
+        the cached per-point projections and ONE call of ``mf_lik_st_cvi_site_update_*``; CPU tensors:
+        ``st_cvi_site_update_torch``."""
+        inputs, observations = self._check_data(input_data, "update_sites")
+        with torch.no_grad():
+            pair_mean, pair_cov = self._pair_marginals()
+            order, a, wt, c, indices, offsets, tiles = self._projections(inputs)
+            y = observations[..., 0]
+            if order is not None:
+                y = torch.gather(y, -1, order)
+            if self._fused(inputs):
+                st_cvi_site_update_hip(self._likelihood, a, wt, c, y, offsets, pair_mean, pair_cov, self.learning_rate, self.nat1,
+                                       self.nat2, tiles=tiles)
+            else:
+                st_cvi_site_update_torch(self._likelihood, a, wt, c, y, indices, pair_mean, pair_cov, self.learning_rate, self.nat1,
+                                         self.nat2)
+
+    def elbo(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+        """``scale sum_i E_q log p(y_i | f_i) - KL[q || p]``, summed over the batch; ``scale = num_data / minibatch size`` when
+        ``num_data`` is set (spatio_temporal_variational.py:209-236).  On HIP tensors the data term is ONE call of
+        ``mf_lik_st_expectations_*``, also with a hyper-parameter of either kernel under the tape: its per-point adjoints, the pair
+        marginals of ``dist_q`` under the tape and the KL adjoints give ``loss(...).backward()`` the hyper-parameter gradients with
+        the sites held fixed."""
+        inputs, observations = self._check_data(input_data, "elbo")
+        self._check_chain_limit()
+        dist_q = self.dist_q
+        ve = torch.sum(self._expected_log_likelihood(inputs, observations, dist_q))
+        kl = torch.sum(dist_q.kl_divergence(self.dist_p))
+        if self.num_data is not None:
+            ve = ve * (float(self.num_data) / inputs.shape[-2])
+        return ve - kl
+
+    def loss(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+        """``-elbo`` (spatio_temporal_variational.py:185-192)."""
+        return -self.elbo(input_data)
