@@ -325,6 +325,50 @@ int mf_sde_transitions_grad_f32(int64_t B, int64_t n, int ncomp, const int* orde
                                 const float* g_A, const float* g_cholQ, float* out, void* stream);
 
 /*
+ * The generator for a PIECEWISE-stationary kernel (markovflow/kernels/piecewise_stationary.py): as mf_sde_transitions_*, with the
+ * hyper-parameters of every step taken from the segment its start time lies in.
+ *   nseg >= 1 segments, change_points [nseg-1] (device, sorted ascending, finite; may be NULL when nseg = 1), shared by all series;
+ *   t_start [B,n]: the time every transition starts at (any order, -/+ 1e10 allowed); its segment is the number of change points
+ *     <= t_start, compared in the call's precision - searchsorted(.., "right") - 1 on the -/+ inf augmented array of the
+ *     reference: a start time exactly on a change point belongs to the segment AFTER it;
+ *   lam, var, omega: [nseg, ncomp], or [B, nseg, ncomp] with per_series; dt [B,n];
+ *   A, cholQ, Q [B,n,d,d] (the latter two optional), seg [B,n] int32 (optional): the segment of every step.
+ * Q_k = Pinf(seg) - A_k Pinf(seg) A_k^T + jitter I with A_k from the SAME segment: a transition that crosses a change point is
+ * generated entirely from the segment it starts in (the reference's behaviour; exact only when no transition crosses one).
+ * The lookup runs in the kernel (up to 256 change points staged in LDS next to the staging image, a binary search in global
+ * memory otherwise): nseg has no small cap.  With nseg = 1 the outputs are those of mf_sde_transitions_*.
+ * Errors: the negative position of the offending argument, checked before any launch; -100 as for mf_sde_transitions_*; B = 0 or
+ * n = 0 returns 0.
+ */
+int mf_sde_piecewise_transitions_f64(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, int nseg,
+                                     const double* change_points, const double* lam, const double* var, const double* omega,
+                                     int per_series, const double* t_start, const double* dt, double jitter, double* A, double* cholQ,
+                                     double* Q, int* seg, void* stream);
+int mf_sde_piecewise_transitions_f32(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, int nseg,
+                                     const float* change_points, const float* lam, const float* var, const float* omega,
+                                     int per_series, const float* t_start, const float* dt, float jitter, float* A, float* cholQ,
+                                     float* Q, int* seg, void* stream);
+/*
+ * Reverse mode of mf_sde_piecewise_transitions_*: out[b, s, c, 0 / 1 / 2] = d/d lam, d/d var, d/d omega of component c in segment s
+ * of  sum over the steps k of series b that start in segment s of  <g_A[b,k], A_k> + <g_cholQ[b,k], chol Q_k>  (g_A, g_cholQ
+ * [B,n,d,d], either may be NULL; out [B,nseg,ncomp,3]).  A caller with shared hyper-parameters sums out over B.  The per-step
+ * terms are those of mf_sde_transitions_grad_*; the sum over the steps of one (series, segment) runs on the device in a fixed
+ * order without floating-point atomics (two launches: per block of 64 steps one partial sum per segment present, then the blocks
+ * in order), so two calls agree bit for bit, for any order of t_start.  A segment without a step, d/d lam of an order-0
+ * component and d/d omega of a component without an oscillator are exact zeros.
+ * workspace: mf_sde_piecewise_transitions_grad_workspace_bytes(B, n, ncomp, sizeof(T)) bytes of device memory.
+ */
+size_t mf_sde_piecewise_transitions_grad_workspace_bytes(int64_t B, int64_t n, int ncomp, int elem_size);
+int mf_sde_piecewise_transitions_grad_f64(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, int nseg,
+                                          const double* change_points, const double* lam, const double* var, const double* omega,
+                                          int per_series, const double* t_start, const double* dt, double jitter, const double* g_A,
+                                          const double* g_cholQ, double* out, void* workspace, size_t workspace_bytes, void* stream);
+int mf_sde_piecewise_transitions_grad_f32(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, int nseg,
+                                          const float* change_points, const float* lam, const float* var, const float* omega,
+                                          int per_series, const float* t_start, const float* dt, float jitter, const float* g_A,
+                                          const float* g_cholQ, float* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * GaussianProcessRegression.log_likelihood (markovflow/models/gaussian_process_regression.py:150-160) for a Matern kernel or
  * a Sum of two, with the kernel -> state-space-model step FUSED into the Kalman sweep: A_k and chol(Q_k) are generated in
  * registers from dt_k = t_{k+1} - t_k, so a step reads 16 bytes (t, y) instead of the materialised tensors.  One output,

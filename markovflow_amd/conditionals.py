@@ -81,8 +81,9 @@ def _conditional_statistics(new_time_points: torch.Tensor, training_time_points:
     inf = torch.full(batch + (1,), APPROX_INF, dtype=dtype, device=dev)
     aug = torch.cat([-inf, training_time_points, inf], dim=-1)
     minus, plus = torch.gather(aug, -1, indices), torch.gather(aug, -1, indices + 1)
-    a_mt, q_mt = kernel.transition_statistics(minus, new - minus)
-    a_tp, q_tp = kernel.transition_statistics(new, plus - new)
+    from_minus, from_new = kernel._lookup_times(minus, training_time_points), kernel._lookup_times(new, training_time_points)
+    a_mt, q_mt = kernel.transition_statistics(from_minus, new - minus)
+    a_tp, q_tp = kernel.transition_statistics(from_new, plus - new)
     d_m, e_m, t_m = _conditional_statistics_from_transitions(a_mt, q_mt, a_tp, q_tp)
     return torch.cat([d_m, e_m], dim=-1), t_m, indices
 

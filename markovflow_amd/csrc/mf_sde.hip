@@ -691,6 +691,292 @@ int run_g_grad(int64_t B, int64_t n, int ncomp, const int* orders, const int* os
     return hipGetLastError() == hipSuccess ? 0 : -1000;
 }
 
+// ---- piecewise-stationary kernels: the hyper-parameters of a step are those of the segment its START TIME lies in -------------------
+// (markovflow/kernels/piecewise_stationary.py: searchsorted(change points augmented by -/+ inf, t, "right") - 1, dynamic_partition,
+// one generator call per segment, concat.)  Here every lane looks its own segment up - the number of change points <= t_start,
+// compared in T - and reads lam / var / omega of that segment ([nseg, ncomp] or [B, nseg, ncomp]); A_k, Pinf and hence Q_k all
+// come from that ONE segment, also when t_start + dt lies beyond the next change point (the reference's behaviour).  The block
+// arithmetic is the device code above (Comp::build, build_osc, emit, emit_g, comp_chol, contract3); sde_transitions_kernel and its
+// reverse mode are left as they are, so the dispatch over (order, osc) is repeated in the two helpers below.
+
+constexpr int PW_LDS_CHANGE_POINTS = 256;   // staged in LDS up to here (2 KB in fp64); not tuned: only K <= 15 has been timed
+
+// number of change points <= t (cp sorted ascending, LDS or global): in [0, ncp] for ANY t, NaN included
+template <typename T> __device__ __forceinline__ int segment_of(const T* __restrict__ cp, int ncp, T t) {
+    int lo = 0, hi = ncp;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (cp[mid] <= t) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// the blocks of ONE of A / chol Q / Q of every component into the lane's d x d image; l / v / w: the segment's hyper-parameters
+template <typename T>
+__device__ __forceinline__ void emit_components(const GSpec& sp, const T* __restrict__ l_, const T* __restrict__ v_,
+                                                const T* __restrict__ w_, T delta, T jitter, int which, T* __restrict__ mine) {
+    const int d = sp.d;
+    for (int c = 0; c < sp.ncomp; ++c) {
+        const int order = sp.order[c], osc = sp.osc[c], off = sp.off[c];
+        const T l = order == 0 ? T(0) : l_[c], v = v_[c];
+        if (osc == 0) {
+            if (order <= 1) { Comp<T, 1> k; k.build(l, v, delta); emit_g<T, 1>(k, order == 0, jitter, d, off, which, mine); }
+            else if (order == 3) { Comp<T, 2> k; k.build(l, v, delta); emit<T, 2>(k, jitter, d, off, which, mine); }
+            else { Comp<T, 3> k; k.build(l, v, delta); emit<T, 3>(k, jitter, d, off, which, mine); }
+            continue;
+        }
+        const T w = w_[c];
+        if (order <= 1) {
+            Comp<T, 2> k;
+            build_osc<T, 1, false>(l, v, w, delta, k);
+            emit_g<T, 2>(k, order == 0, jitter, d, off, which, mine);
+        } else if (order == 3) {
+            Comp<T, 4> k;
+            if (osc == 1) build_osc<T, 2, false>(l, v, w, delta, k); else build_osc<T, 2, true>(l, v, w, delta, k);
+            emit<T, 4>(k, jitter, d, off, which, mine);
+        } else {
+            Comp<T, 6> k;
+            if (osc == 1) build_osc<T, 3, false>(l, v, w, delta, k); else build_osc<T, 3, true>(l, v, w, delta, k);
+            emit<T, 6>(k, jitter, d, off, which, mine);
+        }
+    }
+}
+
+// sde_transitions_kernel with the segment lookup: the same staging and coalesced stores; the change points sit behind the
+// staging image in LDS when `cp_lds`, otherwise the binary search reads them from global memory (L2-resident: every lane
+// of the grid walks the same few lines)
+template <typename T>
+__global__ void __launch_bounds__(64) piecewise_transitions_kernel(long B, long n, GSpec sp, int nseg, const T* __restrict__ cp,
+                                                                   int cp_lds, const T* __restrict__ lam, const T* __restrict__ var,
+                                                                   const T* __restrict__ omega, long hstride,
+                                                                   const T* __restrict__ t_start, const T* __restrict__ dt, T jitter,
+                                                                   T* __restrict__ A, T* __restrict__ cholQ, T* __restrict__ Q,
+                                                                   int* __restrict__ seg_out) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    T* buf = reinterpret_cast<T*>(smem_raw);
+    const long base = (long)blockIdx.x * 64, total = B * n;
+    const long id = base + threadIdx.x;
+    const bool valid = id < total;
+    const int d = sp.d, dd = d * d, stride = dd | 1, ncp = nseg - 1;
+    const T* cps = cp;
+    if (cp_lds) {
+        T* stage = buf + 64 * stride;
+        for (int e = threadIdx.x; e < ncp; e += 64) stage[e] = cp[e];
+        __syncthreads();
+        cps = stage;
+    }
+    const long s = valid ? id / n : 0;
+    const T delta = valid ? dt[id] : T(1);
+    const int seg = valid ? segment_of<T>(cps, ncp, t_start[id]) : 0;
+    if (valid && seg_out) seg_out[id] = seg;
+    const long h = s * hstride + (long)seg * sp.ncomp;
+    T* mine = buf + threadIdx.x * stride;
+    T* outs[3] = {A, cholQ, Q};
+    for (int which = 0; which < 3; ++which) {
+        T* dst = outs[which];
+        if (!dst) continue;
+        for (int e = 0; e < dd; ++e) mine[e] = T(0);
+        emit_components<T>(sp, lam + h, var + h, omega ? omega + h : nullptr, delta, jitter, which, mine);
+        __syncthreads();
+        long nvalid = total - base;
+        if (nvalid > 64) nvalid = 64;
+        const long count = nvalid * dd;
+        T* gdst = dst + base * dd;
+        for (long e = threadIdx.x; e < count; e += 64) gdst[e] = buf[(e / dd) * stride + (e % dd)];
+        __syncthreads();
+    }
+}
+
+// argument checks shared by the two piecewise entry points (positions in THEIR signatures)
+inline int pw_spec(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, int nseg, const void* cp, const void* lam,
+                   const void* var, const void* omega, const void* t_start, const void* dt, GSpec& sp, bool& empty) {
+    if (B < 0) return -1;
+    if (n < 0) return -2;
+    bool any_osc;
+    const int bad = g_spec(ncomp, orders, osc, sp, any_osc);
+    if (bad) return bad;
+    if (nseg < 1) return -6;
+    empty = B == 0 || n == 0;
+    if (empty) return 0;
+    if (nseg > 1 && !cp) return -7;
+    if (!lam) return -8;
+    if (!var) return -9;
+    if (any_osc && !omega) return -10;
+    if (!t_start) return -12;
+    if (!dt) return -13;
+    return 0;
+}
+
+template <typename T>
+int run_pw(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, int nseg, const T* cp, const T* lam, const T* var,
+           const T* omega, int per_series, const T* t_start, const T* dt, T jitter, T* A, T* cholQ, T* Q, int* seg, void* stream) {
+    GSpec sp;
+    bool empty = false;
+    const int bad = pw_spec(B, n, ncomp, orders, osc, nseg, cp, lam, var, omega, t_start, dt, sp, empty);
+    if (bad) return bad;
+    if (empty) return 0;
+    if (!A) return -15;
+    const long total = B * n;
+    const size_t image = size_t(64) * size_t((sp.d * sp.d) | 1) * sizeof(T);
+    if (image > size_t(160) * 1024) return -100;            // (the limit of run_g())
+    // up to PW_LDS_CHANGE_POINTS change points ride behind the staging image (every block copies ALL of them, while a lane's search
+    // reads about log2(nseg): past a few hundred the copy costs more than it saves, and a large copy takes LDS from the occupancy),
+    // as long as the two stay inside what a kernel gets without asking (64 KB), or inside the raised limit once the image alone is
+    // past it; beyond that the lookup reads global memory
+    const size_t cpb = size_t(nseg - 1) * sizeof(T);
+    const size_t room = (image > size_t(64) * 1024 ? size_t(160) : size_t(64)) * 1024;
+    const int cp_lds = nseg > 1 && nseg - 1 <= PW_LDS_CHANGE_POINTS && image + cpb <= room;
+    const size_t lds = image + (cp_lds ? cpb : 0);
+    if (lds > size_t(64) * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&piecewise_transitions_kernel<T>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return -100;
+    hipLaunchKernelGGL((piecewise_transitions_kernel<T>), dim3((unsigned)((total + 63) / 64)), dim3(64), lds,
+                       static_cast<hipStream_t>(stream), (long)B, (long)n, sp, nseg, cp, cp_lds, lam, var, omega,
+                       per_series ? (long)nseg * ncomp : 0L, t_start, dt, jitter, A, cholQ, Q, seg);
+    return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
+// Reverse mode, launch 1 of 2.  One wavefront per 64 consecutive steps OF ONE SERIES (the grid is B x ceil(n / 64)): a lane forms
+// its step's contributions g[c][0..2] exactly as sde_transitions_grad_kernel does (contract3 on the Dual3 closed forms, with the
+// hyper-parameters of the step's segment), parks them in LDS, and the wave folds the lanes of equal segment together: the lowest
+// lane of every segment present ("slot" r, in order of first appearance) receives the sum over its lanes IN LANE ORDER, component
+// value `lane` summed by lane `lane`.  Record r of block (b, k) is (segment, nv = 3 ncomp sums); cnt[b, k] records are written.
+// No atomics: a segment appears in at most one record per block, and launch 2 walks the blocks in order.
+template <typename T>
+__device__ __forceinline__ void grad_components(const GSpec& sp, const T* __restrict__ l_, const T* __restrict__ v_,
+                                                const T* __restrict__ w_, T dt, T jitter, const T* __restrict__ gA,
+                                                const T* __restrict__ gC, T* __restrict__ o) {
+    using Du = Dual3<T>;
+    const int d = sp.d;
+    const Du delta(dt);
+    for (int c = 0; c < sp.ncomp; ++c) {
+        const int order = sp.order[c], osc = sp.osc[c], off = sp.off[c];
+        const Du l(order == 0 ? T(0) : l_[c], T(1), T(0), T(0)), v(v_[c], T(0), T(1), T(0));
+        const T* ga = gA ? gA + off * d + off : nullptr;
+        const T* gc = gC ? gC + off * d + off : nullptr;
+        T g[3];
+        if (osc == 0) {
+            if (order <= 1) { Comp<Du, 1> k; k.build(l, v, delta); contract3<T, 1>(k, order == 0, jitter, d, ga, gc, g); }
+            else if (order == 3) { Comp<Du, 2> k; k.build(l, v, delta); contract3<T, 2>(k, false, jitter, d, ga, gc, g); }
+            else { Comp<Du, 3> k; k.build(l, v, delta); contract3<T, 3>(k, false, jitter, d, ga, gc, g); }
+        } else {
+            const Du w(w_[c], T(0), T(0), T(1));
+            if (order <= 1) {
+                Comp<Du, 2> k;
+                build_osc<Du, 1, false>(l, v, w, delta, k);
+                contract3<T, 2>(k, order == 0, jitter, d, ga, gc, g);
+            } else if (order == 3) {
+                Comp<Du, 4> k;
+                if (osc == 1) build_osc<Du, 2, false>(l, v, w, delta, k); else build_osc<Du, 2, true>(l, v, w, delta, k);
+                contract3<T, 4>(k, false, jitter, d, ga, gc, g);
+            } else {
+                Comp<Du, 6> k;
+                if (osc == 1) build_osc<Du, 3, false>(l, v, w, delta, k); else build_osc<Du, 3, true>(l, v, w, delta, k);
+                contract3<T, 6>(k, false, jitter, d, ga, gc, g);
+            }
+        }
+        o[c * 3] = order == 0 ? T(0) : g[0];      // (order 0 has no lam)
+        o[c * 3 + 1] = g[1];
+        o[c * 3 + 2] = osc == 0 ? T(0) : g[2];
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(64) piecewise_grad_steps_kernel(long n, long nblk, GSpec sp, int nseg, const T* __restrict__ cp,
+                                                                  const T* __restrict__ lam, const T* __restrict__ var,
+                                                                  const T* __restrict__ omega, long hstride,
+                                                                  const T* __restrict__ t_start, const T* __restrict__ dt, T jitter,
+                                                                  const T* __restrict__ gA, const T* __restrict__ gC,
+                                                                  T* __restrict__ rec_val, int* __restrict__ rec_seg,
+                                                                  int* __restrict__ rec_cnt) {
+    __shared__ T park[64 * (3 * MAXC + 1)];
+    const int lane = threadIdx.x, nv = 3 * sp.ncomp, pstride = nv | 1;
+    const long blk = blockIdx.x, b = blk / nblk, k = blk % nblk;
+    const long step = k * 64 + lane;
+    const bool valid = step < n;
+    int seg = -1;
+    if (valid) {
+        const long id = b * n + step;
+        const long dd = (long)sp.d * sp.d;
+        seg = segment_of<T>(cp, nseg - 1, t_start[id]);
+        const long h = b * hstride + (long)seg * sp.ncomp;
+        grad_components<T>(sp, lam + h, var + h, omega ? omega + h : nullptr, dt[id], jitter, gA ? gA + id * dd : nullptr,
+                           gC ? gC + id * dd : nullptr, park + lane * pstride);
+    }
+    __syncthreads();
+    unsigned long long remaining = __ballot(valid);
+    int slot = 0;
+    while (remaining) {                                   // (wave-uniform: one round per segment present in this block)
+        const int leader = __ffsll(remaining) - 1;
+        const int sl = __shfl(seg, leader);
+        const unsigned long long members = __ballot(valid && seg == sl);
+        if (lane < nv) {
+            T acc = T(0);
+            for (unsigned long long m = members; m; m &= m - 1) acc += park[(__ffsll(m) - 1) * pstride + lane];
+            rec_val[(blk * 64 + slot) * nv + lane] = acc;
+        }
+        if (lane == 0) rec_seg[blk * 64 + slot] = sl;
+        remaining &= ~members;
+        ++slot;
+    }
+    if (lane == 0) rec_cnt[blk] = slot;
+}
+
+// Launch 2 of 2: one thread per (series, segment, value) adds the records of its segment over the series' blocks in block order -
+// a fixed order, so two runs agree bit for bit; a segment without a step keeps the exact zero it starts from.
+template <typename T>
+__global__ void __launch_bounds__(64) piecewise_grad_reduce_kernel(long B, long nblk, int nseg, int nv, const T* __restrict__ rec_val,
+                                                                   const int* __restrict__ rec_seg, const int* __restrict__ rec_cnt,
+                                                                   T* __restrict__ out) {
+    const long id = (long)blockIdx.x * 64 + threadIdx.x;
+    if (id >= B * nseg * nv) return;
+    const int v = (int)(id % nv), sg = (int)((id / nv) % nseg);
+    const long b = id / ((long)nv * nseg);
+    T acc = T(0);
+    for (long k = 0; k < nblk; ++k) {
+        const long blk = b * nblk + k;
+        const int cnt = rec_cnt[blk];
+        for (int r = 0; r < cnt; ++r)
+            if (rec_seg[blk * 64 + r] == sg) { acc += rec_val[(blk * 64 + r) * nv + v]; break; }
+    }
+    out[id] = acc;
+}
+
+// workspace of the reverse mode: per block of 64 steps up to 64 records of nv values | their segments | the record count
+inline size_t pw_grad_workspace(int64_t B, int64_t n, int ncomp, size_t elem) {
+    if (B <= 0 || n <= 0 || ncomp < 1 || ncomp > MAXC) return 0;
+    const size_t blocks = size_t(B) * size_t((n + 63) / 64);
+    return blocks * (size_t(64) * 3 * ncomp * elem + 64 * sizeof(int) + sizeof(int));
+}
+
+template <typename T>
+int run_pw_grad(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, int nseg, const T* cp, const T* lam,
+                const T* var, const T* omega, int per_series, const T* t_start, const T* dt, T jitter, const T* gA, const T* gC,
+                T* out, void* ws, size_t ws_bytes, void* stream) {
+    GSpec sp;
+    bool empty = false;
+    const int bad = pw_spec(B, n, ncomp, orders, osc, nseg, cp, lam, var, omega, t_start, dt, sp, empty);
+    if (bad) return bad;
+    if (empty) return 0;
+    if (!out) return -17;
+    if (!ws) return -18;
+    if (ws_bytes < pw_grad_workspace(B, n, ncomp, sizeof(T))) return -19;
+    const long nblk = (long)((n + 63) / 64), blocks = (long)B * nblk;
+    const int nv = 3 * ncomp;
+    T* rec_val = static_cast<T*>(ws);
+    int* rec_seg = reinterpret_cast<int*>(rec_val + (size_t)blocks * 64 * nv);
+    int* rec_cnt = rec_seg + (size_t)blocks * 64;
+    hipLaunchKernelGGL((piecewise_grad_steps_kernel<T>), dim3((unsigned)blocks), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       (long)n, nblk, sp, nseg, cp, lam, var, omega, per_series ? (long)nseg * ncomp : 0L, t_start, dt, jitter, gA, gC,
+                       rec_val, rec_seg, rec_cnt);
+    if (hipGetLastError() != hipSuccess) return -1000;
+    const long threads = (long)B * nseg * nv;
+    hipLaunchKernelGGL((piecewise_grad_reduce_kernel<T>), dim3((unsigned)((threads + 63) / 64)), dim3(64), 0,
+                       static_cast<hipStream_t>(stream), (long)B, nblk, nseg, nv, rec_val, rec_seg, rec_cnt, out);
+    return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
 // R^-1 = (L L^T)^-1 from the Cholesky factor of the observation covariance (KalmanFilter._r_inv, kalman_filter.py:341-348: a
 // tf.linalg.cholesky_solve against the identity).  m <= 32: one wavefront, thread j solves column j of L^-1 by forward
 // substitution, then the threads share the m^2 entries of L^-T L^-1.  ONE launch instead of the eleven small torch / rocBLAS
@@ -768,6 +1054,38 @@ int mf_sde_transitions_grad_f32(int64_t B, int64_t n, int ncomp, const int* orde
                                 const float* var, const float* omega, int per_series, const float* dt, float jitter,
                                 const float* g_A, const float* g_cholQ, float* out, void* stream) {
     return run_g_grad<float>(B, n, ncomp, orders, osc, lam, var, omega, per_series, dt, jitter, g_A, g_cholQ, out, stream);
+}
+
+int mf_sde_piecewise_transitions_f64(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, int nseg,
+                                     const double* change_points, const double* lam, const double* var, const double* omega,
+                                     int per_series, const double* t_start, const double* dt, double jitter, double* A, double* cholQ,
+                                     double* Q, int* seg, void* stream) {
+    return run_pw<double>(B, n, ncomp, orders, osc, nseg, change_points, lam, var, omega, per_series, t_start, dt, jitter, A, cholQ, Q,
+                          seg, stream);
+}
+int mf_sde_piecewise_transitions_f32(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, int nseg,
+                                     const float* change_points, const float* lam, const float* var, const float* omega,
+                                     int per_series, const float* t_start, const float* dt, float jitter, float* A, float* cholQ,
+                                     float* Q, int* seg, void* stream) {
+    return run_pw<float>(B, n, ncomp, orders, osc, nseg, change_points, lam, var, omega, per_series, t_start, dt, jitter, A, cholQ, Q,
+                         seg, stream);
+}
+size_t mf_sde_piecewise_transitions_grad_workspace_bytes(int64_t B, int64_t n, int ncomp, int elem_size) {
+    return (elem_size == 4 || elem_size == 8) ? pw_grad_workspace(B, n, ncomp, (size_t)elem_size) : 0;
+}
+int mf_sde_piecewise_transitions_grad_f64(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, int nseg,
+                                          const double* change_points, const double* lam, const double* var, const double* omega,
+                                          int per_series, const double* t_start, const double* dt, double jitter, const double* g_A,
+                                          const double* g_cholQ, double* out, void* workspace, size_t workspace_bytes, void* stream) {
+    return run_pw_grad<double>(B, n, ncomp, orders, osc, nseg, change_points, lam, var, omega, per_series, t_start, dt, jitter, g_A,
+                               g_cholQ, out, workspace, workspace_bytes, stream);
+}
+int mf_sde_piecewise_transitions_grad_f32(int64_t B, int64_t n, int ncomp, const int* orders, const int* osc, int nseg,
+                                          const float* change_points, const float* lam, const float* var, const float* omega,
+                                          int per_series, const float* t_start, const float* dt, float jitter, const float* g_A,
+                                          const float* g_cholQ, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    return run_pw_grad<float>(B, n, ncomp, orders, osc, nseg, change_points, lam, var, omega, per_series, t_start, dt, jitter, g_A,
+                              g_cholQ, out, workspace, workspace_bytes, stream);
 }
 
 int mf_sde_matern_transitions_grad_f64(int64_t B, int64_t n, int ncomp, const int* orders, const double* lam, const double* var,

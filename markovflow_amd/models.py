@@ -48,12 +48,20 @@ import torch
 from . import _lib, conditionals
 from .emission_model import EmissionModel
 from .kalman_filter import KalmanFilter, KalmanFilterWithSites, UnivariateGaussianSitesNat
-from .kernels import (ST_MAX_STATE_DIM, IndependentMultiOutput, SDEKernel, SparseSpatioTemporalKernel, _MaternBase,
-                      _version_key)
+from .kernels import (ST_MAX_STATE_DIM, IndependentMultiOutput, NonStationaryKernel, SDEKernel, SparseSpatioTemporalKernel,
+                      _MaternBase, _version_key)
 from .likelihoods import Gaussian, Likelihood, torch_log_expected_density
 from .posterior import AnalyticPosteriorProcess, ConditionalProcess, ImportanceWeightedPosteriorProcess
 from .ssm_gaussian_transformations import naturals_to_ssm_params
 from .state_space_model import StateSpaceModel
+
+
+def _refuse_non_stationary(kernel, who: str) -> None:
+    """Every model but ``GaussianProcessRegression`` takes stationary kernels only: the sparse and site-based models put the
+    stationary prior (``_stationary_prior``) at both ends of their chains, which is only right for a stationary kernel."""
+    if isinstance(kernel, NonStationaryKernel):
+        raise NotImplementedError(f"{who} supports stationary kernels only: a non-stationary kernel ({type(kernel).__name__}) is "
+                                  "supported by GaussianProcessRegression alone")
 
 
 def _all_matern(comps) -> bool:
@@ -455,6 +463,7 @@ class _GaussianProcessWithSites:
             raise TypeError("likelihood must be a markovflow_amd.likelihoods.Likelihood")
         if not 0.0 <= float(learning_rate) <= 1.0:
             raise ValueError(f"learning_rate must lie in [0, 1], got {learning_rate}")
+        _refuse_non_stationary(kernel, type(self).__name__)
         _lib.same_dtype_device(observations, type(self).__name__, time_points=time_points)
         self._kernel = kernel
         self._likelihood = likelihood
@@ -804,6 +813,7 @@ class _SparseGaussianProcess:
     def __init__(self, kernel: SDEKernel, likelihood: Likelihood, inducing_points: torch.Tensor, min_inducing: int) -> None:
         if not isinstance(kernel, SDEKernel):
             raise TypeError("kernel must be a markovflow_amd.kernels.SDEKernel")
+        _refuse_non_stationary(kernel, type(self).__name__)
         if not isinstance(likelihood, Likelihood):
             raise TypeError("likelihood must be a markovflow_amd.likelihoods.Likelihood")
         if (not isinstance(inducing_points, torch.Tensor) or inducing_points.dim() < 1
@@ -1836,6 +1846,7 @@ class VariationalGaussianProcess:
         time_points, observations = input_data
         if not isinstance(kernel, SDEKernel):
             raise TypeError("kernel must be a markovflow_amd.kernels.SDEKernel")
+        _refuse_non_stationary(kernel, "VariationalGaussianProcess")
         if not isinstance(likelihood, Likelihood):
             raise TypeError("likelihood must be a markovflow_amd.likelihoods.Likelihood")
         if observations.dim() < 2 or observations.shape[-1] != 1:

@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from .gauss_markov import GaussMarkovDistribution
-from .kernels import SDEKernel
+from .kernels import NonStationaryKernel, SDEKernel
 
 APPROX_INF = 1e10   # markovflow/base.py:46: the "time" of the stationary prior beyond both ends of the data
 
@@ -49,8 +49,11 @@ class ConditionalProcess:
         aug = torch.cat([-inf, train, inf], dim=-1)
         minus, plus = torch.gather(aug, -1, idx), torch.gather(aug, -1, idx + 1)
         m0 = kern.initial_mean(batch).to(dtype=dtype, device=dev).expand(batch + (d,)).contiguous()
-        p0 = kern.initial_covariance(new[..., :1]).to(dtype=dtype, device=dev)
+        # (the prior beyond the ends: a stationary kernel has ONE P-infinity whatever the time; a non-stationary one is stationary
+        # before the first conditioning point under the kernel active AT that point - DESIGN.md "Piecewise-stationary kernels")
+        p0 = kern.initial_covariance((train if isinstance(kern, NonStationaryKernel) else new)[..., :1]).to(dtype=dtype, device=dev)
         p0 = p0.expand(batch + (d, d)).contiguous()
+        from_minus, from_new = kern._lookup_times(minus, train), kern._lookup_times(new, train)
         if d > _lib.load().mf_max_state_dim():
             # beyond the lane-per-point kernel (d <= 9): the reference's own composition (posterior.py:217-221) of the functions of
             # conditionals.py - pairwise_marginals -> conditional_predict - as batched products (the posterior chain and its moments
@@ -59,8 +62,8 @@ class ConditionalProcess:
             from . import conditionals
             pair_mean, pair_cov = conditionals.pairwise_marginals(dist, m0, p0)
             return conditionals.conditional_predict(new, train, kern, pair_mean, pair_cov)
-        a_mt, q_mt = kern.transition_statistics(minus, new - minus)
-        a_tp, q_tp = kern.transition_statistics(new, plus - new)
+        a_mt, q_mt = kern.transition_statistics(from_minus, new - minus)
+        a_tp, q_tp = kern.transition_statistics(from_new, plus - new)
         means, covs, sub = dist._moments(want_sub=n > 1)
         flat = lambda t, k: t.reshape((-1,) + tuple(t.shape[-k:])).contiguous()  # noqa: E731
         bsz = max(1, int(torch.tensor(batch).prod())) if batch else 1
@@ -87,7 +90,9 @@ class ConditionalProcess:
         n, n_new = train.shape[-1], new.shape[-1]
         joint = torch.cat([train, new], dim=-1)
         sort_ind = torch.argsort(joint, dim=-1)
-        sorted_samples = kern.state_space_model(torch.gather(joint, -1, sort_ind).contiguous()).sample(shape)
+        # (the joint prior follows the rule of predict_state: before the first conditioning point, the dynamics active AT it)
+        joint_sorted = torch.gather(joint, -1, sort_ind).contiguous()
+        sorted_samples = kern.state_space_model(joint_sorted, lookup_times=kern._lookup_times(joint_sorted, train)).sample(shape)
         unsort = torch.argsort(sort_ind, dim=-1)
         unsort = unsort.expand(shape + tuple(unsort.shape))[..., None].expand(shape + batch + (n + n_new, sorted_samples.shape[-1]))
         joint_samples = torch.gather(sorted_samples, -2, unsort)
@@ -112,8 +117,9 @@ class ConditionalProcess:
         inf = torch.full(batch + (1,), APPROX_INF, dtype=train.dtype, device=train.device)
         aug = torch.cat([-inf, train, inf], dim=-1)
         minus, plus = torch.gather(aug, -1, idx), torch.gather(aug, -1, idx + 1)
-        a_mt, q_mt = kern.transition_statistics(minus, new - minus)
-        a_tp, q_tp = kern.transition_statistics(new, plus - new)
+        from_minus, from_new = kern._lookup_times(minus, train), kern._lookup_times(new, train)
+        a_mt, q_mt = kern.transition_statistics(from_minus, new - minus)
+        a_tp, q_tp = kern.transition_statistics(from_new, plus - new)
         g = a_tp @ q_mt
         e_m = torch.linalg.solve(q_tp + g @ a_tp.transpose(-1, -2), g).transpose(-1, -2)
         return a_mt - e_m @ a_tp @ a_mt, e_m
