@@ -1,0 +1,270 @@
+"""
+The models with one univariate Gaussian site per data point.
+
+``CVIGaussianProcess`` (mirror of ``markovflow/models/variational_cvi.py:32-460``: ``GaussianProcessWithSitesBase`` +
+``CVIGaussianProcess`` with a zero mean function) is the site-based model for non-Gaussian likelihoods
+(``markovflow_amd/likelihoods.py``): its ``update_sites`` is the filter route's posterior chain followed by ONE launch of
+``mf_lik_cvi_site_update_*``.
+
+``PowerExpectationPropagation`` (mirror of ``markovflow/models/pep.py:28-261``, zero mean function) shares the sites, ``dist_q`` and
+the sites filter with it; its ``update_sites`` is the same posterior chain followed by ONE launch of ``mf_lik_pep_site_update_*``
+(cavity, log expected density with two derivatives, gradient correction, site normaliser, power / damping step), and ``energy()`` is
+the EP approximation of the log marginal likelihood.
+"""
+from typing import Optional, Tuple
+
+import torch
+
+from .. import _lib
+from ..kalman_filter import KalmanFilterWithSites, UnivariateGaussianSitesNat
+from ..kernels import SDEKernel
+from ..likelihoods import Likelihood
+from ..posterior import ConditionalProcess
+from ..ssm_gaussian_transformations import naturals_to_ssm_params
+from ..state_space_model import StateSpaceModel
+from ._common import (_PredictLogDensity, _check_dense_data, _refuse_non_stationary, _require_likelihood, back_project_nats,
+                      gradient_correction, gradient_transformation_mean_var_to_expectation)
+
+
+class _GaussianProcessWithSites(_PredictLogDensity):
+    """What the site-based models share (variational_cvi.py:32-216, ``GaussianProcessWithSitesBase``; zero mean function): a GP
+    prior, a general likelihood and a Gaussian posterior ``q(s) = p(s) prod_k t_k(f_k)`` parameterised by univariate Gaussian sites
+    in natural form - the data, the sites, ``dist_p`` / ``dist_q``, the sites filter and its log-likelihood, prediction."""
+
+    def __init__(self, input_data: Tuple[torch.Tensor, torch.Tensor], kernel: SDEKernel, likelihood: Likelihood,
+                 learning_rate: float) -> None:
+        time_points, observations = input_data
+        _check_dense_data(time_points, observations)
+        _require_likelihood(likelihood)
+        if not 0.0 <= float(learning_rate) <= 1.0:
+            raise ValueError(f"learning_rate must lie in [0, 1], got {learning_rate}")
+        _refuse_non_stationary(kernel, type(self).__name__)
+        _lib.same_dtype_device(observations, type(self).__name__, time_points=time_points)
+        self._kernel = kernel
+        self._likelihood = likelihood
+        self._time_points = time_points
+        self._observations = observations
+        self.learning_rate = float(learning_rate)
+        # variational_cvi.py:98-103
+        self.sites = UnivariateGaussianSitesNat(nat1=torch.zeros_like(observations),
+                                                nat2=torch.full_like(observations, -1e-10)[..., None],
+                                                log_norm=torch.zeros_like(observations))
+
+    @property
+    def time_points(self) -> torch.Tensor:
+        return self._time_points
+
+    @property
+    def conditioning_points(self) -> torch.Tensor:
+        return self._time_points
+
+    @property
+    def observations(self) -> torch.Tensor:
+        return self._observations
+
+    @property
+    def dist_p(self) -> StateSpaceModel:
+        """The prior chain on the training time points (variational_cvi.py:211-216)."""
+        return self._kernel.state_space_model(self._time_points)
+
+    @property
+    def dist_q(self) -> StateSpaceModel:
+        """The posterior chain on the training time points by the conjugate update of the natural parameters, prior + back-projected
+        sites, then ``naturals_to_ssm_params`` (variational_cvi.py:105-135)."""
+        prec = self.dist_p.precision
+        h = self._kernel.generate_emission_model(self._time_points).emission_matrix
+        bp_nat1, bp_nat2 = back_project_nats(self.sites.nat1, self.sites.nat2[..., 0], h)
+        theta_diag = -0.5 * prec.block_diagonal + bp_nat2
+        a_s, offsets, chol_p0, chol_q, mu0 = naturals_to_ssm_params(bp_nat1, theta_diag, -prec.block_sub_diagonal)
+        return StateSpaceModel(initial_mean=mu0, chol_initial_covariance=chol_p0, state_transitions=a_s, state_offsets=offsets,
+                               chol_process_covariances=chol_q)
+
+    @property
+    def posterior_kalman(self) -> KalmanFilterWithSites:
+        """The filter over the prior chain and the sites (variational_cvi.py:137-144)."""
+        return KalmanFilterWithSites(state_space_model=self.dist_p,
+                                     emission_model=self._kernel.generate_emission_model(self._time_points), sites=self.sites)
+
+    @property
+    def posterior(self) -> ConditionalProcess:
+        """Posterior process for prediction away from the training time points (variational_cvi.py:146-153)."""
+        return ConditionalProcess(posterior_dist=self.dist_q, kernel=self._kernel, conditioning_time_points=self._time_points)
+
+    def log_likelihood(self) -> torch.Tensor:
+        """Log marginal likelihood of the model whose likelihood terms are the Gaussian sites (variational_cvi.py:155-161);
+        differentiable with respect to the kernel's hyper-parameters through the filter's backward (the sites carry no graph)."""
+        return self.posterior_kalman.log_likelihood()
+
+    def elbo(self) -> torch.Tensor:
+        """variational_cvi.py:370-379."""
+        return self.log_likelihood()
+
+    def loss(self) -> torch.Tensor:
+        return -self.log_likelihood()
+
+    def _project(self, dist: StateSpaceModel) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Marginals of ``f`` at the training time points, ``batch + [N, 1]`` each."""
+        means, covs = dist.marginals
+        return self._kernel.generate_emission_model(self._time_points).project_state_marginals_to_f(means, covs)
+
+    def _predict_f(self, new_time_points: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        return self.posterior.predict_f(new_time_points)
+
+
+class CVIGaussianProcess(_GaussianProcessWithSites):
+    """GP prior, general likelihood, Gaussian posterior parameterised by univariate Gaussian sites in natural form,
+    ``q(s) = p(s) prod_k t_k(f_k)``, updated by conjugate-computation variational inference (Khan & Lin 2017):
+    ``theta <- (1 - rho) theta + rho g`` with ``g`` the gradient of the variational expectations in the expectation parameters
+    (variational_cvi.py:32-420; zero mean function)."""
+
+    def __init__(self, input_data: Tuple[torch.Tensor, torch.Tensor], kernel: SDEKernel, likelihood: Likelihood,
+                 learning_rate: float = 0.1) -> None:
+        """
+        :param input_data: ``(time_points [batch + [num_data]], observations [batch + [num_data, 1]])``.
+        :param likelihood: a ``markovflow_amd.likelihoods.Likelihood``.
+        :param learning_rate: the step ``rho`` of ``update_sites``, in [0, 1].
+        """
+        super().__init__(input_data, kernel, likelihood, learning_rate)
+
+    def local_objective(self, Fmu: torch.Tensor, Fvar: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
+        """The variational expectations, ``[..., 1] -> [...]`` (variational_cvi.py:321-330)."""
+        return self._likelihood.variational_expectations(Fmu, Fvar, Y)
+
+    def local_objective_and_gradients(self, Fmu: torch.Tensor, Fvar: torch.Tensor) -> Tuple[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
+        """The summed local objective and its gradients with respect to ``[mu, var + mu^2]`` (variational_cvi.py:332-349; the
+        reference's tape is the derivative pair the likelihood computes with the value)."""
+        fmu, fvar = Fmu.detach(), Fvar.detach()
+        with torch.no_grad():
+            ve, g_mu, g_var = self._likelihood._expectations(fmu, fvar, self._observations)
+        return torch.sum(ve), gradient_transformation_mean_var_to_expectation((fmu, fvar), (g_mu, g_var))
+
+    def update_sites(self) -> None:
+        """One joint CVI step on the sites, in place (variational_cvi.py:351-368).  The marginals of ``f`` at the training points
+        come from the filter route's posterior chain - the distribution ``posterior.predict_f(time_points)`` describes, without
+        the interpolation to "new" points - and the step itself is one launch of ``mf_lik_cvi_site_update_*``."""
+        with torch.no_grad():
+            fmu, fvar = self._project(self.posterior_kalman.posterior_state_space_model())
+            self._likelihood.cvi_site_update(fmu, fvar, self._observations, self.learning_rate, self.sites.nat1, self.sites.nat2)
+
+    def classic_elbo(self) -> torch.Tensor:
+        """``sum_i E_q log p(y_i | f_i) - KL[q(s) || p(s)]`` (variational_cvi.py:381-404; for testing, not for optimisation)."""
+        dist_q = self.dist_q
+        fmu, fvar = self._project(dist_q)
+        ve = torch.sum(self._likelihood.variational_expectations(fmu, fvar, self._observations))
+        return ve - torch.sum(dist_q.kl_divergence(self.dist_p))
+
+
+class PowerExpectationPropagation(_GaussianProcessWithSites):
+    """GP prior, general likelihood, Gaussian posterior ``q(s) = p(s) prod_k t_k(f_k)`` with univariate Gaussian sites
+    ``t_k(f) = exp(nat1 f + nat2 f^2 + log_norm)`` updated by power expectation propagation (pep.py:28-261, zero mean function;
+    Seeger 2005, Minka 2004): remove the fraction ``alpha`` of a site from the posterior marginal (the cavity), match the moments
+    of cavity x ``p(y | f)^alpha`` through the derivatives of the log expected density, and step with damping ``learning_rate``.
+    ``energy()`` is the (power) EP approximation of the log marginal likelihood.
+
+    Deviations from the reference:
+      * the power: ``Likelihood.log_expected_density`` IS ``log int p^alpha q`` (the reference's ignores ``alpha``, or returns
+        ``alpha log int p q`` for its Gaussian); at ``alpha = 1`` this model is the reference's;
+      * ``update_sites(site_indices=None)`` updates EVERY site (in the reference the mask is then all zeros and nothing moves);
+      * ``compute_log_norm`` evaluates the objective at the CAVITY, as ``update_sites`` does and as the energy assumes (the
+        reference's evaluates it at the posterior marginals, pep.py:171);
+      * a site whose cavity or correction is undefined (``fvar``, ``1 / v_c`` or ``1 + v_c g2`` not positive, a non-finite result) is
+        SKIPPED; the reference would write NaN into it."""
+
+    def __init__(self, input_data: Tuple[torch.Tensor, torch.Tensor], kernel: SDEKernel, likelihood: Likelihood,
+                 learning_rate: float = 1.0, alpha: float = 1.0) -> None:
+        """
+        :param input_data: ``(time_points [batch + [num_data]], observations [batch + [num_data, 1]])``.
+        :param likelihood: a ``markovflow_amd.likelihoods.Likelihood``.
+        :param learning_rate: the damping of ``update_sites``, in [0, 1].
+        :param alpha: the power, in (0, 1].
+        """
+        super().__init__(input_data, kernel, likelihood, learning_rate)
+        if not 0.0 < float(alpha) <= 1.0:
+            raise ValueError(f"alpha must lie in (0, 1], got {alpha}")
+        self.alpha = float(alpha)
+
+    def local_objective(self, Fmu: torch.Tensor, Fvar: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
+        """``log E_{N(f | Fmu, Fvar)} p(y | f)^alpha``, ``[..., 1] -> [...]`` (pep.py:99-101)."""
+        return self._likelihood.log_expected_density(Fmu, Fvar, Y, alpha=self.alpha)
+
+    def local_objective_gradients(self, Fmu: torch.Tensor, Fvar: torch.Tensor) -> Tuple[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
+        """The local objective at the training observations, ``batch + [N]``, and the corrected gradients ``(L1, L2)``,
+        ``batch + [N, 1]`` (pep.py:103-109)."""
+        obj, grads = self._likelihood.grad_log_expected_density(Fmu, Fvar, self._observations, alpha=self.alpha)
+        return obj, gradient_correction((Fmu, Fvar), grads)
+
+    def compute_cavity_from_marginals(self, marginals: Tuple[torch.Tensor, torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The cavity marginals of ``f`` at the training points, ``batch + [N, 1]`` each, from the STATE marginals
+        ``(means [.., N, d], covs [.., N, d, d])`` of ``q``.  The reference (pep.py:120-148) goes through ``d x d`` natural
+        parameters - marginal to natural form, minus ``alpha`` times the back-projected site, back to moments, projected by ``H``;
+        the site touches the state through ``f = h . s`` only, so by Sherman-Morrison that is the scalar statement on the marginal
+        ``N(m, s)`` of ``f``:  ``1 / v_c = 1 / s + 2 alpha nat2``,  ``mu_c = v_c (m / s - alpha nat1)``.  NaN where ``1 / v_c`` is
+        not positive."""
+        with torch.no_grad():
+            return self._scalar_cavity(*self._f_marginals(marginals))
+
+    def _f_marginals(self, marginals: Tuple[torch.Tensor, torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The state marginals projected to ``f`` at the training points, ``batch + [N, 1]`` each."""
+        return self._kernel.generate_emission_model(self._time_points).project_state_marginals_to_f(marginals[0], marginals[1])
+
+    def _scalar_cavity(self, fmu: torch.Tensor, fvar: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        prec = 1.0 / fvar + 2.0 * self.alpha * self.sites.nat2[..., 0]
+        ok = (fvar > 0) & (prec > 0)
+        cav_var = torch.where(ok, 1.0 / prec, torch.full_like(fmu, float("nan")))
+        return cav_var * (fmu / fvar - self.alpha * self.sites.nat1), cav_var
+
+    def compute_cavity(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The marginals of ``q(f) / t_n(f_n)^alpha`` at ``f_n`` for every data point (pep.py:150-157)."""
+        return self.compute_cavity_from_marginals(self.dist_q.marginals)
+
+    def compute_log_norm(self) -> torch.Tensor:
+        """The site normalisers from the current ``q``, ``batch + [N]``: ``I(mu_c, v_c) + G(mu_c, v_c) - G(m, s)`` with
+        ``G(mu, v) = (log v + mu^2 / v) / 2`` - the objective at the CAVITY (class docstring), one ``mf_lik_*`` launch.  A point
+        whose cavity does not exist (``1 / v_c`` not positive) has no normaliser: NaN at that point, as in ``compute_cavity``.
+        (``update_sites`` skips such a point; here nothing is skipped, because a sum without it would not be the energy.)"""
+        return self._log_norm(self.dist_q)
+
+    def _log_norm(self, dist_q: StateSpaceModel) -> torch.Tensor:
+        with torch.no_grad():
+            fmu, fvar = self._f_marginals(dist_q.marginals)
+            cav_mu, cav_var = self._scalar_cavity(fmu, fvar)
+            obj = self.local_objective(cav_mu, cav_var, self._observations)
+            log_norm_cav = 0.5 * (torch.log(cav_var) + cav_mu * cav_mu / cav_var)
+            log_norm_marg = 0.5 * (torch.log(fvar) + fmu * fmu / fvar)
+            return obj + log_norm_cav[..., 0] - log_norm_marg[..., 0]
+
+    def _update_flags(self, site_indices: torch.Tensor) -> torch.Tensor:
+        """The byte mask ``batch + [N]`` of ``update_sites``: 1 at the chosen points of every series.  Built by comparison, not by an
+        indexed store, so that no index can write outside the mask."""
+        if site_indices.dim() != 1 or site_indices.dtype.is_floating_point or site_indices.dtype == torch.bool:
+            raise ValueError("update_sites: site_indices must be a 1-D integer tensor")
+        n = self._observations.shape[-2]
+        if site_indices.numel() and not (-n <= int(site_indices.min()) and int(site_indices.max()) < n):
+            raise IndexError(f"update_sites: site_indices must lie in [-{n}, {n}) for {n} data points")
+        idx = site_indices.to(device=self._observations.device, dtype=torch.long)
+        idx = torch.where(idx < 0, idx + n, idx)
+        flags = (torch.arange(n, device=idx.device)[:, None] == idx[None, :]).any(dim=-1).to(torch.uint8)
+        return flags.expand(self._observations.shape[:-1]).contiguous()
+
+    def update_sites(self, site_indices: Optional[torch.Tensor] = None) -> None:
+        """One power-EP step on the sites, in place (pep.py:179-215).  The marginals of ``f`` come from the filter route's posterior
+        chain, as in ``CVIGaussianProcess.update_sites``; cavity, log expected density with its derivatives, gradient correction,
+        normaliser and the power / damping step are ONE launch of ``mf_lik_pep_site_update_*``.
+
+        :param site_indices: a 1-D integer tensor of point indices, applied to every series; None: all points.  Indices follow
+            torch's convention - ``-N <= i < N``, a negative one counts from the end, repeats are allowed - and anything outside
+            that range raises IndexError on either device (for indices held on the device the check is one host read)."""
+        with torch.no_grad():
+            update = None if site_indices is None else self._update_flags(site_indices)
+            fmu, fvar = self._project(self.posterior_kalman.posterior_state_space_model())
+            self._likelihood.pep_site_update(fmu, fvar, self._observations, self.alpha, self.learning_rate, self.sites.nat1,
+                                             self.sites.nat2, self.sites.log_norm, update)
+
+    def energy(self) -> torch.Tensor:
+        """The power-EP energy per series, ``batch`` (pep.py:223-230): ``dist_q.normalizer() - dist_p.normalizer()
+        + (1 / alpha) sum_n log_norm_n`` with the normalisers computed afresh from the current ``q``.  Not differentiable.  A series
+        with a point whose cavity does not exist has no energy: NaN for that series (``compute_log_norm``), the others are unaffected."""
+        with torch.no_grad():
+            dist_q = self.dist_q
+            log_norm = torch.sum(self._log_norm(dist_q), dim=-1)
+            return dist_q.normalizer() - self.dist_p.normalizer() + log_norm / self.alpha

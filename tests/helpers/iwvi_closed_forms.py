@@ -2,7 +2,7 @@
 Reference of the data term of the importance weights - TEST INFRASTRUCTURE, NOT PRODUCT CODE.
 
 ``iw_log_weights``: the formulas of ``mf_lik_iw_log_weights_*`` for ONE series in numpy, on ``likelihood_closed_forms.log_prob`` /
-``dlog_prob`` and the second derivatives stated here, independent of markovflow_amd/models.py and csrc/mf_lik.hip.  The sums run in
+``dlog_prob`` and the second derivatives stated here, independent of markovflow_amd/models/sparse.py and csrc/mf_lik.hip.  The sums run in
 the kernel's order - the points of a tile of 64 ascending, then the tiles ascending, then the two segments of ``g_u`` in the stated
 order - so that ``dtype`` = numpy.float32 carries the kernel's rounding.  ``dense_gaussian_logpdf`` evaluates a chain's density from
 its dense moments.

@@ -1,7 +1,7 @@
 """
 numpy / scipy (fp64) reference of power expectation propagation - TEST INFRASTRUCTURE, NOT PRODUCT CODE.
 
-Independent of markovflow_amd/likelihoods.py, markovflow_amd/models.py and csrc/mf_lik.hip: the log densities and their first
+Independent of markovflow_amd/likelihoods.py, markovflow_amd/models/sites.py and csrc/mf_lik.hip: the log densities and their first
 derivatives are those of tests/helpers/likelihood_closed_forms.py (scipy.stats / scipy.special), the second derivatives are written
 here and checked against central differences of the first (tests/test_pep_host.py), and the PEP loop is dense linear algebra on the
 kernel matrix with the SCALAR cavity - no state space form anywhere.

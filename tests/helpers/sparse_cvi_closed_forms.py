@@ -1,7 +1,7 @@
 """
 numpy (fp64) reference of the sparse CVI model - TEST INFRASTRUCTURE, NOT PRODUCT CODE.
 
-Two things, both independent of markovflow_amd/models.py and csrc/mf_lik.hip:
+Two things, both independent of markovflow_amd/models/ (sparse.py, segmented_ops.py) and csrc/mf_lik.hip:
 
   * ``segment_update``: the per-segment formulas of ``mf_lik_sparse_cvi_site_update_*`` for one series, on
     ``likelihood_closed_forms.expectations``, with the magnitudes that scale a rounding-error bound;

@@ -1,7 +1,7 @@
 """
 numpy (fp64) reference of the sparse power-EP model - TEST INFRASTRUCTURE, NOT PRODUCT CODE.
 
-Two things, both independent of markovflow_amd/models.py and csrc/mf_lik.hip:
+Two things, both independent of markovflow_amd/models/ (sparse.py, segmented_ops.py) and csrc/mf_lik.hip:
 
   * ``segment_pep_update``: both passes of ``mf_lik_sparse_pep_site_update_*`` for one series in numpy, in any dtype, on
     ``pep_closed_forms.log_expected_density``, summed in the kernel's order (tiles of 64 points in ascending order, then the tiles),

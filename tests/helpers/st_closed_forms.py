@@ -1,7 +1,7 @@
 """
 Reference of the spatio-temporal sparse variational model - TEST INFRASTRUCTURE, NOT PRODUCT CODE.
 
-Independent of markovflow_amd/models.py, markovflow_amd/kernels.py and csrc/mf_st.hip:
+Independent of markovflow_amd/models/spatio_temporal.py, markovflow_amd/kernels.py and csrc/mf_st.hip:
 
   * ``st_expectations``: the formulas of ``mf_lik_st_expectations_*`` for one series in numpy, in the kernel's summation order
     (include/markovflow_amd.h), in any numpy float type, with the magnitude ``sum |terms|`` of every output.  The likelihood's own

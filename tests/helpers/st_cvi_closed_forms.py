@@ -1,7 +1,7 @@
 """
 Reference of the spatio-temporal sparse CVI site update - TEST INFRASTRUCTURE, NOT PRODUCT CODE.
 
-Independent of markovflow_amd/models.py and csrc/mf_st.hip.  ``st_cvi_site_update`` states one step of
+Independent of markovflow_amd/models/spatio_temporal.py and csrc/mf_st.hip.  ``st_cvi_site_update`` states one step of
 markovflow/models/spatio_temporal_variational.py:509-552 literally, for one series in numpy, in any numpy float type: the marginals
 of every point (``st_closed_forms.st_expectations``), the gradients of its variational expectation in ``[mu, var + mu^2]``, the DENSE
 projection ``P [N, 1, n]``, ``back_project_nats``, the partition of the points by their ``searchsorted`` index, the sum over each

@@ -1,7 +1,7 @@
 """
 Reference of the SVGP model and of the natural-gradient optimiser - TEST INFRASTRUCTURE, NOT PRODUCT CODE.
 
-Two things, both independent of markovflow_amd/models.py, markovflow_amd/ssm_natgrad.py and csrc/mf_lik.hip:
+Two things, both independent of markovflow_amd/models/ (sparse.py, segmented_ops.py), markovflow_amd/ssm_natgrad.py and csrc/mf_lik.hip:
 
   * ``segment_expectations``: the per-segment formulas of ``mf_lik_sparse_expectations_*`` for one series in numpy, on
     ``likelihood_closed_forms.expectations``, with the magnitudes that scale a rounding-error bound; ``segment_value_torch`` restates

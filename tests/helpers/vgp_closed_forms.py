@@ -2,7 +2,7 @@
 Numpy statement of the VGP data-term kernels - TEST INFRASTRUCTURE, NOT PRODUCT CODE.
 
 ``dense_expectations`` states ``mf_lik_dense_expectations_*`` and ``dense_adjoint`` states ``mf_lik_dense_expectations_adjoint_*`` for
-ONE series, on ``likelihood_closed_forms.expectations``, independent of markovflow_amd/models.py and csrc/mf_lik.hip.
+ONE series, on ``likelihood_closed_forms.expectations``, independent of markovflow_amd/models/variational.py and csrc/mf_lik.hip.
 ``dense_value_torch`` restates the VALUE in torch (float64, CPU) so that autograd can be asked for the adjoints.
 
 With ``dtype = numpy.float32`` everything is evaluated in float32 in the kernel's summation order (include/markovflow_amd.h): every

@@ -190,7 +190,7 @@ def test_update_sites_is_one_launch_of_the_sparse_site_kernel_and_no_torch_route
 
     monkeypatch.setattr(ML, "torch_variational_expectations", no_torch)
     monkeypatch.setattr(ML, "torch_predict_log_density", no_torch)
-    monkeypatch.setattr(MM, "sparse_cvi_site_update_torch", no_torch)
+    monkeypatch.setattr(MM.sparse, "sparse_cvi_site_update_torch", no_torch)
     versions = (model.nat1._version, model.nat2._version)
     model.update_sites(data(x, y))
     assert seen.count("mf_lik_sparse_cvi_site_update") == 1

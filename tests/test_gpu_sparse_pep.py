@@ -219,8 +219,8 @@ def test_update_sites_is_one_call_of_the_kernel_pair_and_no_torch_route(monkeypa
 
     for route in ("torch_variational_expectations", "torch_predict_log_density", "torch_log_expected_density", "torch_pep_site_update"):
         monkeypatch.setattr(ML, route, no_torch)
-    monkeypatch.setattr(MM, "torch_log_expected_density", no_torch)
-    monkeypatch.setattr(MM, "sparse_pep_site_update_torch", no_torch)
+    monkeypatch.setattr(MM.segmented_ops, "torch_log_expected_density", no_torch)
+    monkeypatch.setattr(MM.sparse, "sparse_pep_site_update_torch", no_torch)
     sites = (model.nat1, model.nat2, model.log_norm)
     versions = [s._version for s in sites]
     model.update_sites(xy)
@@ -245,7 +245,7 @@ def test_pairs_of_dimension_twenty_take_the_torch_route(monkeypatch):
     seen, calls = [], []
     real_rc, real_torch = _lib.call_rc, MM.sparse_pep_site_update_torch
     monkeypatch.setattr(_lib, "call_rc", lambda base, *a: (seen.append(base), real_rc(base, *a))[1])
-    monkeypatch.setattr(MM, "sparse_pep_site_update_torch", lambda *a, **k: (calls.append(1), real_torch(*a, **k))[1])
+    monkeypatch.setattr(MM.sparse, "sparse_pep_site_update_torch", lambda *a, **k: (calls.append(1), real_torch(*a, **k))[1])
     model.update_sites(data(x, y))
     assert len(calls) == 1 and FN not in seen
     assert all(bool(torch.isfinite(s).all()) and float(s.abs().max()) > 0.0 for s in (model.nat1, model.nat2, model.log_norm))

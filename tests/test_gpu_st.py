@@ -245,7 +245,7 @@ def test_elbo_is_one_launch_and_the_backward_none(monkeypatch):
         raise AssertionError("the torch route must not run on HIP tensors")
 
     monkeypatch.setattr(ML, "torch_variational_expectations", no_torch)
-    monkeypatch.setattr(MM, "st_expected_log_likelihood_torch", no_torch)
+    monkeypatch.setattr(MM.spatio_temporal, "st_expected_log_likelihood_torch", no_torch)
     elbo = model.elbo(xy)
     assert len(built) == 1, "a, wt, c, the offsets and the row table are cached with the data"
     assert seen.count(FN) == 1 and not any(s.startswith("mf_lik_") and s != FN for s in seen)

@@ -136,7 +136,7 @@ def test_update_sites_is_one_call_and_the_version_counters_advance(monkeypatch):
     def no_torch(*a, **k):
         raise AssertionError("the torch route must not run on HIP tensors")
 
-    monkeypatch.setattr(MM, "st_cvi_site_update_torch", no_torch)
+    monkeypatch.setattr(MM.spatio_temporal, "st_cvi_site_update_torch", no_torch)
     versions = model.nat1._version, model.nat2._version
     model.update_sites(xy)
     assert [s for s in seen if s.startswith("mf_lik_")] == [FN], "ONE call of the new entry point, none of mf_lik_st_expectations_*"

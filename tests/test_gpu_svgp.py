@@ -146,7 +146,7 @@ def test_elbo_is_one_launch_of_the_expectations_kernel_and_no_torch_route(monkey
         raise AssertionError("the torch route must not run on HIP tensors")
 
     monkeypatch.setattr(ML, "torch_variational_expectations", no_torch)
-    monkeypatch.setattr(MM, "sparse_expected_log_likelihood_torch", no_torch)
+    monkeypatch.setattr(MM.sparse, "sparse_expected_log_likelihood_torch", no_torch)
     elbo = model.elbo(xy)
     assert len(projections) == 1, "w, c, the offsets and the tile table are cached with the data"
     assert seen.count("mf_lik_sparse_expectations") == 1

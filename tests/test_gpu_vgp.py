@@ -142,7 +142,7 @@ def test_elbo_is_one_launch_of_the_expectations_kernel_and_backward_one_of_the_a
         raise AssertionError("the torch route must not run on HIP tensors")
 
     monkeypatch.setattr(ML, "torch_variational_expectations", no_torch)
-    monkeypatch.setattr(MM, "dense_expected_log_likelihood_torch", no_torch)
+    monkeypatch.setattr(MM.variational, "dense_expected_log_likelihood_torch", no_torch)
     elbo = model.elbo()
     assert seen.count(FWD) == 1 and seen.count(ADJ) == 0
     assert "mf_lik_variational_expectations" not in seen
