@@ -369,6 +369,36 @@ int mf_sde_piecewise_transitions_grad_f32(int64_t B, int64_t n, int ncomp, const
                                           const float* g_cholQ, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The generator of the LatentExponentiallyGenerated kernel (markovflow/kernels/latent_exp_generated.py): a dense feedback matrix
+ * F [d,d] (per_series: [B,d,d]) with steady-state covariance I, 1 <= d <= 16; dt [B,n]; outputs [B,n,d,d], A required, cholQ and Q
+ * optional:
+ *   A_k = expm(dt_k F),  Q_k = I - A_k A_k^T + jitter I (symmetric),  cholQ_k its lower factor (upper triangle exactly zero).
+ * Scaling and squaring with expm - I carried through the squarings, from which Q is formed without the cancellation of
+ * I - A A^T at short gaps.  An all-zero Q passes through as a zero factor; a non-positive pivot gives NaN through the square root
+ * (no info word); a step whose dt F is not finite gives NaN outputs for that step.  Any finite dt is covered (dt = 1e10: A -> 0).
+ * Errors: the negative position of the offending argument, checked before any launch; -100 for d > 16; B = 0 or n = 0 returns 0
+ * without a launch.
+ */
+int mf_sde_leg_transitions_f64(int64_t B, int64_t n, int d, const double* F, int per_series, const double* dt, double jitter,
+                               double* A, double* cholQ, double* Q, void* stream);
+int mf_sde_leg_transitions_f32(int64_t B, int64_t n, int d, const float* F, int per_series, const float* dt, float jitter, float* A,
+                               float* cholQ, float* Q, void* stream);
+/*
+ * Reverse mode of mf_sde_leg_transitions_*: out[b] [d,d] = d/dF of  sum over the steps k of series b of
+ * <g_A[b,k], A_k> + <g_cholQ[b,k], chol Q_k>  (g_A, g_cholQ [B,n,d,d], either may be NULL; only the lower triangle of g_cholQ is
+ * read; out [B,d,d]).  A caller with a shared F sums out over B.  A step with an all-zero Q contributes through g_A only.  The sum
+ * over the steps runs on the device in a fixed order without floating-point atomics (two launches), so two calls agree bit for bit.
+ * workspace: mf_sde_leg_transitions_grad_workspace_bytes(B, n, d, sizeof(T)) bytes of device memory.
+ */
+size_t mf_sde_leg_transitions_grad_workspace_bytes(int64_t B, int64_t n, int d, int elem_size);
+int mf_sde_leg_transitions_grad_f64(int64_t B, int64_t n, int d, const double* F, int per_series, const double* dt, double jitter,
+                                    const double* g_A, const double* g_cholQ, double* out, void* workspace, size_t workspace_bytes,
+                                    void* stream);
+int mf_sde_leg_transitions_grad_f32(int64_t B, int64_t n, int d, const float* F, int per_series, const float* dt, float jitter,
+                                    const float* g_A, const float* g_cholQ, float* out, void* workspace, size_t workspace_bytes,
+                                    void* stream);
+
+/*
  * GaussianProcessRegression.log_likelihood (markovflow/models/gaussian_process_regression.py:150-160) for a Matern kernel or
  * a Sum of two, with the kernel -> state-space-model step FUSED into the Kalman sweep: A_k and chol(Q_k) are generated in
  * registers from dt_k = t_{k+1} - t_k, so a step reads 16 bytes (t, y) instead of the materialised tensors.  One output,

@@ -18,7 +18,7 @@ from .kalman_filter import (
 )
 from .state_space_model import StateSpaceModel, state_space_model_from_covariances
 from . import conditionals, distributed, kernels, likelihoods, models, spatial_kernels, ssm_gaussian_transformations, ssm_natgrad
-from .kernels import (Constant, HarmonicOscillator, IndependentMultiOutput, Matern12, Matern32, Matern52, NonStationaryKernel,
+from .kernels import (Constant, HarmonicOscillator, IndependentMultiOutput, LatentExponentiallyGenerated, Matern12, Matern32, Matern52, NonStationaryKernel,
                       PiecewiseKernel, Product, SDEKernel, SparseSpatioTemporalKernel, StationaryKernel, Sum)
 from .likelihoods import Bernoulli, Gaussian, Likelihood, Poisson, StudentT
 from .models import (CVIGaussianProcess, GaussianProcessRegression, ImportanceWeightedVI, PowerExpectationPropagation,
@@ -39,5 +39,5 @@ __all__ = [
     "SparseCVIGaussianProcess", "SparseVariationalGaussianProcess", "SSMNaturalGradient", "ssm_natgrad",
     "SparsePowerExpectationPropagation", "ImportanceWeightedVI", "ImportanceWeightedPosteriorProcess",
     "VariationalGaussianProcess", "spatial_kernels", "SparseSpatioTemporalKernel", "SpatioTemporalSparseVariational", "SpatioTemporalSparseCVI",
-    "NonStationaryKernel", "PiecewiseKernel",
+    "NonStationaryKernel", "PiecewiseKernel", "LatentExponentiallyGenerated",
 ]

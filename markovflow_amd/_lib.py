@@ -73,6 +73,8 @@ _SIGS = {
                                             _int, "Tp", "Tp", "T", "Tp", "Tp", "Tp", _vp, _vp]),
     "mf_sde_piecewise_transitions_grad": (_int, [_i64, _i64, _int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _int, "Tp", "Tp", "Tp",
                                                  "Tp", _int, "Tp", "Tp", "T", "Tp", "Tp", "Tp", _vp, _sz, _vp]),
+    "mf_sde_leg_transitions": (_int, [_i64, _i64, _int, "Tp", _int, "Tp", "T", "Tp", "Tp", "Tp", _vp]),
+    "mf_sde_leg_transitions_grad": (_int, [_i64, _i64, _int, "Tp", _int, "Tp", "T", "Tp", "Tp", "Tp", _vp, _sz, _vp]),
     "mf_lik_variational_expectations": (_int, [_i64, _int, _hd, _int, _hd, _hd, "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_cvi_site_update": (_int, [_i64, _int, _hd, _int, _hd, _hd, "Tp", "Tp", "Tp", "T", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_predict_log_density": (_int, [_i64, _int, _hd, _int, _hd, _hd, "Tp", "Tp", "Tp", "Tp", _vp]),
@@ -122,6 +124,7 @@ _PLAIN = {
     "mf_btd_udl_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
     "mf_btd_grad_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
     "mf_sde_piecewise_transitions_grad_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
+    "mf_sde_leg_transitions_grad_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
     "mf_lik_sparse_expectations_workspace_bytes": (_sz, [_i64, _int, _int]),
     "mf_lik_iw_log_weights_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
     "mf_lik_dense_expectations_workspace_bytes": (_sz, [_i64, _i64, _int]),

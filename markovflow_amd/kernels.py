@@ -22,7 +22,11 @@ of a transition taken from the segment it STARTS in.  ``mf_sde_piecewise_transit
 (series, segment) on the device in a fixed order.  Supported by ``GaussianProcessRegression`` only; see ``PiecewiseKernel`` for the
 crossing rule and the other limitations.
 
-Nothing else of the reference's kernels package (Stack, FactorAnalysis, latent-exp kernels, products of two Matérns) is mirrored.
+The latent exponentially generated kernel: ``LatentExponentiallyGenerated`` (``kernels/latent_exp_generated.py``) - a dense,
+trainable feedback matrix ``F = −½(N Nᵀ + R − Rᵀ)`` with ``P∞ = I``.  ``mf_sde_leg_transitions_*`` computes ``A_k = expm(Δt_k F)`` and
+``chol Q_k`` by scaling and squaring on a group of lanes per step; ``mf_sde_leg_transitions_grad_*`` is its reverse mode.
+
+Nothing else of the reference's kernels package (Stack, FactorAnalysis, products of two Matérns) is mirrored.
 
 Hyper-parameters are plain tensors / floats (the reference wraps them in ``gpflow.Parameter``); a hyper-parameter may also
 carry ``batch_shape`` (one value per series), which the reference expresses with ``StackKernel``.
@@ -523,6 +527,9 @@ def _refuse_non_stationary_children(who: str, kernels) -> None:
     if any(isinstance(k, NonStationaryKernel) for k in kernels):
         raise NotImplementedError(f"{who} does not take a non-stationary child kernel (a sum of piecewise kernels is written as a "
                                   "PiecewiseKernel of Sums, with shared change points)")
+    if any(isinstance(k, LatentExponentiallyGenerated) for k in kernels):
+        raise NotImplementedError(f"{who} does not take a LatentExponentiallyGenerated child kernel: its dense feedback matrix is "
+                                  "not a component of the closed-form generators")
 
 
 # (tensor, version) pairs whose positivity has been read back from the device: the check of matern.py:52-56 is a host
@@ -1153,6 +1160,7 @@ class PiecewiseKernel(NonStationaryKernel):
         if any(isinstance(k, (IndependentMultiOutput, NonStationaryKernel)) for k in self._kernels):
             raise NotImplementedError("PiecewiseKernel segments are single-output stationary kernels: IndependentMultiOutput, "
                                       "SparseSpatioTemporalKernel and PiecewiseKernel children are not supported")
+        _refuse_non_stationary_children("PiecewiseKernel", [k for k in self._kernels if isinstance(k, LatentExponentiallyGenerated)])
         if not all(isinstance(k, StationaryKernel) for k in self._kernels):
             raise TypeError("can only combine Kernel instances")
         assert len({k.output_dim for k in self._kernels}) == 1, "All kernels must have the same output dimension"
@@ -1315,4 +1323,183 @@ class PiecewiseKernel(NonStationaryKernel):
                   (ctypes.c_int * len(comps))(*oscs), self.num_change_points + 1, _lib.ptr(cp if self.num_change_points else None),
                   _lib.ptr(lam_t), _lib.ptr(var_t), _lib.ptr(om_t), int(per_series), _lib.ptr(t_start), _lib.ptr(dt), self._jitter,
                   _lib.ptr(a_s), _lib.ptr(chol), _lib.ptr(cov), None, _lib.stream_ptr(dt.device))
+        return (a_s.reshape(shape), None if chol is None else chol.reshape(shape), None if cov is None else cov.reshape(shape))
+
+
+class _LegTransitions(torch.autograd.Function):
+    """``(A [B,n,d,d], chol Q [B,n,d,d])`` of a ``LatentExponentiallyGenerated`` kernel as a differentiable function of its feedback
+    matrix ``F`` (``[d,d]`` or ``[B,d,d]``) - forward ``mf_sde_leg_transitions_*``, backward ``mf_sde_leg_transitions_grad_*`` (the
+    Cholesky adjoint and the Fréchet adjoint of the exponential per step, summed over the steps of a series on the device in a fixed
+    order); only the sum over the series of a shared ``F`` is left to torch.  ``F`` is assembled from ``N`` and ``R`` by differentiable
+    torch ops, which carry the gradient on."""
+
+    @staticmethod
+    def forward(ctx, dt, f_t, per_series, jitter, want_chol):
+        bsz, n = dt.shape
+        d = f_t.shape[-1]
+        a_s = torch.empty((bsz, n, d, d), dtype=dt.dtype, device=dt.device)
+        chol = torch.empty_like(a_s) if want_chol else None
+        f_c = f_t.detach().contiguous()
+        _lib.call("mf_sde_leg_transitions", dt.dtype, bsz, n, d, _lib.ptr(f_c), int(per_series), _lib.ptr(dt), jitter, _lib.ptr(a_s),
+                  _lib.ptr(chol), None, _lib.stream_ptr(dt.device))
+        ctx.save_for_backward(dt, f_c)
+        ctx.meta = (per_series, jitter)
+        if not want_chol:
+            chol = a_s.new_zeros(())
+            ctx.mark_non_differentiable(chol)
+        return a_s, chol
+
+    @staticmethod
+    def backward(ctx, g_a, g_chol):
+        dt, f_c = ctx.saved_tensors
+        per_series, jitter = ctx.meta
+        bsz, n = dt.shape
+        d = f_c.shape[-1]
+        out = torch.empty((bsz, d, d), dtype=dt.dtype, device=dt.device)
+        with torch.no_grad():
+            ga = None if g_a is None else g_a.contiguous()
+            gc = None if (g_chol is None or g_chol.dim() == 0) else g_chol.contiguous()
+            ws_bytes = int(_lib.load().mf_sde_leg_transitions_grad_workspace_bytes(bsz, n, d, dt.element_size()))
+            ws = _lib.workspace(ws_bytes, dt.device)
+            _lib.call("mf_sde_leg_transitions_grad", dt.dtype, bsz, n, d, _lib.ptr(f_c), int(per_series), _lib.ptr(dt), jitter,
+                      _lib.ptr(ga), _lib.ptr(gc), _lib.ptr(out), _lib.ptr(ws), ws_bytes, _lib.stream_ptr(dt.device))
+            g = out if per_series else torch.sum(out, dim=0)              # a shared F: [d, d]
+        return None, g, None, None, None
+
+
+LEG_MAX_DEVICE_STATE_DIM = 16
+
+
+class LatentExponentiallyGenerated(StationaryKernel):
+    """The latent exponentially generated kernel of Loper et al. 2020 (markovflow/kernels/latent_exp_generated.py): a state of
+    dimension ``d`` with a DENSE feedback matrix ``F = −½(N Nᵀ + R − Rᵀ)`` and steady-state covariance ``I``,
+
+        ``A_k = expm(Δt_k F)``,  ``Q_k = I − A_k A_kᵀ + jitter·I``,
+
+    ``N`` and ``R`` being ``[d, d]`` tensors (or ``batch_shape + [d, d]``: dynamics per series) that may require gradients.
+
+    On a HIP device and for ``d <= 16`` the transitions come from ``mf_sde_leg_transitions_*`` (csrc/mf_leg.hip: scaling and squaring
+    with ``expm − I`` carried through the squarings, so that ``Q_k`` keeps its relative accuracy at short gaps, where ``I − A Aᵀ``
+    cancels), and under a gradient from ``_LegTransitions``, whose backward is ``mf_sde_leg_transitions_grad_*``.  CPU tensors, ``Q``
+    under a gradient, gradients with respect to the times, ``d > 16`` and empty inputs take a torch restatement
+    (``torch.linalg.matrix_exp``), which forms ``I − A Aᵀ`` as the reference does.
+
+    ``output_dim=None`` reproduces the reference: ``output_dim = state_dim`` and every row of the emission matrix is ``[1, 0, …]``.
+    ``output_dim=1`` is this project's extension: the scalar process that the one-output likelihood models need.
+
+    Models: ``GaussianProcessRegression`` (the materialised route generator → ``KalmanFilter``) and, with ``output_dim=1``,
+    ``SparseVariationalGaussianProcess`` are covered by tests; other models reach the kernel through the same public methods but
+    are not.  As a child of ``Sum``, ``Product``, ``IndependentMultiOutput``, ``SparseSpatioTemporalKernel`` or ``PiecewiseKernel`` it
+    is refused."""
+
+    def __init__(self, N: torch.Tensor, R: torch.Tensor, jitter: float = 0.0, output_dim: Optional[int] = None) -> None:
+        if not (isinstance(N, torch.Tensor) and isinstance(R, torch.Tensor)):
+            raise TypeError("N and R must be tensors")
+        if N.dim() < 2 or N.shape[-1] != N.shape[-2] or tuple(N.shape) != tuple(R.shape):
+            raise ValueError("N and R must be square matrices of one shape, batch_shape + [state_dim, state_dim]")
+        if N.dtype != R.dtype or N.device != R.device:
+            raise ValueError("N and R must share dtype and device")
+        self._state_dim = int(N.shape[-1])
+        super().__init__(self._state_dim if output_dim is None else int(output_dim), jitter)
+        self._N, self._R = N, R
+
+    @property
+    def state_dim(self) -> int:
+        return self._state_dim
+
+    @property
+    def N(self) -> torch.Tensor:
+        return self._N
+
+    @property
+    def R(self) -> torch.Tensor:
+        return self._R
+
+    @property
+    def feedback_matrix(self) -> torch.Tensor:
+        """``F = −½(N Nᵀ + R − Rᵀ)`` (latent_exp_generated.py ``feedback_matrix``), differentiable in ``N`` and ``R``."""
+        n, r = self._N, self._R
+        return -0.5 * (n @ n.transpose(-1, -2) + r - r.transpose(-1, -2))
+
+    @property
+    def steady_state_covariance(self) -> torch.Tensor:
+        eye = torch.eye(self._state_dim, dtype=self._N.dtype, device=self._N.device)
+        return eye.expand(tuple(self._N.shape)).clone()
+
+    # -- what the rest of the package asks of a kernel ------------------------------------------------------------------------------
+    def _components(self):
+        return [self]
+
+    def _leaves(self):
+        return (self._N, self._R)
+
+    def invalidate_cache(self) -> None:
+        """Nothing is cached: ``F`` is assembled from ``N`` and ``R`` at every call."""
+
+    @property
+    def jitter_matrix(self) -> torch.Tensor:
+        return self._jitter * torch.eye(self._state_dim, dtype=self._N.dtype, device=self._N.device)
+
+    def initial_mean(self, batch_shape) -> torch.Tensor:
+        return torch.zeros(tuple(batch_shape) + (self._state_dim,), dtype=self._N.dtype, device=self._N.device)
+
+    def initial_covariance(self, initial_time_point: torch.Tensor) -> torch.Tensor:
+        """``(1 + jitter)·I``."""
+        assert initial_time_point.shape[-1] == 1
+        batch = tuple(initial_time_point.shape[:-1])
+        eye = torch.eye(self._state_dim, dtype=self._N.dtype, device=self._N.device)
+        return ((1.0 + self._jitter) * eye).expand(batch + (self._state_dim, self._state_dim)).clone()
+
+    def _needs_grad(self) -> bool:
+        return torch.is_grad_enabled() and (self._N.requires_grad or self._R.requires_grad)
+
+    def _initial_cholesky(self, batch, dtype, device):
+        eye = torch.eye(self._state_dim, dtype=dtype, device=device)
+        return (math.sqrt(1.0 + self._jitter) * eye).expand(tuple(batch) + (self._state_dim, self._state_dim)).contiguous()
+
+    # -- transitions -----------------------------------------------------------------------------------------------------------------
+    def _torch_transitions(self, time_deltas: torch.Tensor, want_chol: bool, want_cov: bool):
+        """The reference's formulas in differentiable torch ops: ``A = matrix_exp(Δt F)``, ``Q = I − A Aᵀ + jitter·I`` (symmetrised),
+        its Cholesky factor with an all-zero ``Q`` passed through as a zero factor."""
+        f = self.feedback_matrix.to(dtype=time_deltas.dtype, device=time_deltas.device)
+        f_b = f[..., None, :, :] if f.dim() > 2 else f
+        a_s = torch.linalg.matrix_exp(f_b * time_deltas[..., None, None])
+        if not (want_chol or want_cov):
+            return a_s, None, None
+        eye = torch.eye(self._state_dim, dtype=time_deltas.dtype, device=time_deltas.device)
+        q = eye - a_s @ a_s.transpose(-1, -2)
+        # (a skew F - N = 0 - has no process noise at all: exact zeros, as the device kernel gives, not the rounding of I − A Aᵀ)
+        noisy = ~(f_b + f_b.transpose(-1, -2) == 0).all(dim=-1).all(dim=-1)[..., None, None]
+        q_s = 0.5 * (q + q.transpose(-1, -2)) * noisy.to(q.dtype) + self._jitter * eye
+        chol = None
+        if want_chol:
+            zero = (q_s == 0).all(dim=-1).all(dim=-1)[..., None, None]
+            chol = torch.linalg.cholesky(torch.where(zero, eye, q_s)) * (~zero).to(q_s.dtype)
+        return a_s, chol, (q_s if want_cov else None)
+
+    def _device_transitions(self, time_deltas: torch.Tensor, want_chol: bool, want_cov: bool, transition_times=None):
+        """``(A, chol Q, Q)`` for ``time_deltas`` of shape ``batch_shape + [n]``: ``mf_sde_leg_transitions_*``, under a gradient
+        ``_LegTransitions``; the torch restatement where the class docstring says so."""
+        batch = tuple(time_deltas.shape[:-1])
+        n, d = time_deltas.shape[-1], self._state_dim
+        needs_grad = self._needs_grad()
+        times_grad = torch.is_grad_enabled() and time_deltas.requires_grad
+        if (not time_deltas.is_cuda or time_deltas.numel() == 0 or d > LEG_MAX_DEVICE_STATE_DIM or times_grad
+                or (needs_grad and want_cov)):
+            return self._torch_transitions(time_deltas, want_chol, want_cov)
+        dt = time_deltas.detach().reshape(-1, n).contiguous()
+        bsz = dt.shape[0]
+        f = self.feedback_matrix.to(dtype=dt.dtype, device=dt.device)
+        per_series = f.dim() > 2
+        f_t = f.expand(batch + (d, d)).reshape(-1, d, d) if per_series else f
+        shape = batch + (n, d, d)
+        if needs_grad:
+            a_s, chol = _LegTransitions.apply(dt, f_t, bool(per_series), float(self._jitter), bool(want_chol))
+            return a_s.reshape(shape), (chol.reshape(shape) if want_chol else None), None
+        f_c = f_t.detach().contiguous()
+        a_s = torch.empty((bsz, n, d, d), dtype=dt.dtype, device=dt.device)
+        chol = torch.empty_like(a_s) if want_chol else None
+        cov = torch.empty_like(a_s) if want_cov else None
+        _lib.call("mf_sde_leg_transitions", dt.dtype, bsz, n, d, _lib.ptr(f_c), int(per_series), _lib.ptr(dt), self._jitter,
+                  _lib.ptr(a_s), _lib.ptr(chol), _lib.ptr(cov), _lib.stream_ptr(dt.device))
         return (a_s.reshape(shape), None if chol is None else chol.reshape(shape), None if cov is None else cov.reshape(shape))
