@@ -207,13 +207,12 @@ int run_m(int m, long B, long Tn, const T* mu0, const T* cholP0, const T* A, con
         default: return -2;
     }
 }
-}  // namespace
 
-extern "C" int mf_post_host_sim_f64(int64_t B, int64_t Tn, int d, int m, const double* mu0, const double* cholP0, const double* A,
-                                    const double* b, const double* cholQ, const double* H, const double* y, const double* Rinv,
-                                    int per_step, int64_t L, double* a_post, double* mu0_post, double* b_post, double* cp0_post,
-                                    double* cq_post) {
-#define MF_CASE(DD) case DD: return run_m<double, DD>(m, B, Tn, mu0, cholP0, A, b, cholQ, H, y, Rinv, per_step, L, a_post, mu0_post, b_post, cp0_post, cq_post);
+template <typename T>
+int post_entry(int64_t B, int64_t Tn, int d, int m, const T* mu0, const T* cholP0, const T* A, const T* b, const T* cholQ,
+               const T* H, const T* y, const T* Rinv, int per_step, int64_t L, T* a_post, T* mu0_post, T* b_post, T* cp0_post,
+               T* cq_post, const GradOut<T>* go = nullptr) {
+#define MF_CASE(DD) case DD: return run_m<T, DD>(m, B, Tn, mu0, cholP0, A, b, cholQ, H, y, Rinv, per_step, L, a_post, mu0_post, b_post, cp0_post, cq_post, go);
     switch (d) {
         MF_CASE(1) MF_CASE(2) MF_CASE(3) MF_CASE(4) MF_CASE(5) MF_CASE(6)
         default: return -3;
@@ -222,17 +221,33 @@ extern "C" int mf_post_host_sim_f64(int64_t B, int64_t Tn, int d, int m, const d
 }
 
 // the same three passes, then the streamed backward of log_likelihood on the chain they produced (only cholQ' and b' are read)
-extern "C" int mf_grad_host_sim_f64(int64_t B, int64_t Tn, int d, int m, const double* mu0, const double* cholP0, const double* A,
-                                    const double* b, const double* cholQ, const double* H, const double* y, const double* Rinv,
-                                    int per_step, int64_t L, const double* weights, double* gmu0, double* gC0, double* gA,
-                                    double* gb, double* gC, double* gH, double* gy, double* gOm) {
+template <typename T>
+int grad_entry(int64_t B, int64_t Tn, int d, int m, const T* mu0, const T* cholP0, const T* A, const T* b, const T* cholQ,
+               const T* H, const T* y, const T* Rinv, int per_step, int64_t L, const T* weights, T* gmu0, T* gC0, T* gA, T* gb,
+               T* gC, T* gH, T* gy, T* gOm) {
     const long nt = Tn - 1;
-    std::vector<double> a_post(B * nt * d * d), b_post(B * nt * d), cq_post(B * nt * d * d), mu0_post(B * d), cp0_post(B * d * d);
-    const GradOut<double> go{weights, gmu0, gC0, gA, gb, gC, gH, gy, gOm};
-#define MF_CASE(DD) case DD: return run_m<double, DD>(m, B, Tn, mu0, cholP0, A, b, cholQ, H, y, Rinv, per_step, L, a_post.data(), mu0_post.data(), b_post.data(), cp0_post.data(), cq_post.data(), &go);
-    switch (d) {
-        MF_CASE(1) MF_CASE(2) MF_CASE(3) MF_CASE(4) MF_CASE(5) MF_CASE(6)
-        default: return -3;
-    }
-#undef MF_CASE
+    std::vector<T> a_post(B * nt * d * d), b_post(B * nt * d), cq_post(B * nt * d * d), mu0_post(B * d), cp0_post(B * d * d);
+    const GradOut<T> go{weights, gmu0, gC0, gA, gb, gC, gH, gy, gOm};
+    return post_entry<T>(B, Tn, d, m, mu0, cholP0, A, b, cholQ, H, y, Rinv, per_step, L, a_post.data(), mu0_post.data(),
+                         b_post.data(), cp0_post.data(), cq_post.data(), &go);
 }
+}  // namespace
+
+// _f64 and _f32: the kernels are templates on the real type, and so is everything above
+#define MF_HOST_SIM(SUF, T)                                                                                                   \
+    extern "C" int mf_post_host_sim_##SUF(int64_t B, int64_t Tn, int d, int m, const T* mu0, const T* cholP0, const T* A,    \
+                                          const T* b, const T* cholQ, const T* H, const T* y, const T* Rinv, int per_step,   \
+                                          int64_t L, T* a_post, T* mu0_post, T* b_post, T* cp0_post, T* cq_post) {           \
+        return post_entry<T>(B, Tn, d, m, mu0, cholP0, A, b, cholQ, H, y, Rinv, per_step, L, a_post, mu0_post, b_post,       \
+                             cp0_post, cq_post);                                                                             \
+    }                                                                                                                         \
+    extern "C" int mf_grad_host_sim_##SUF(int64_t B, int64_t Tn, int d, int m, const T* mu0, const T* cholP0, const T* A,    \
+                                          const T* b, const T* cholQ, const T* H, const T* y, const T* Rinv, int per_step,   \
+                                          int64_t L, const T* weights, T* gmu0, T* gC0, T* gA, T* gb, T* gC, T* gH, T* gy,   \
+                                          T* gOm) {                                                                          \
+        return grad_entry<T>(B, Tn, d, m, mu0, cholP0, A, b, cholQ, H, y, Rinv, per_step, L, weights, gmu0, gC0, gA, gb, gC, \
+                             gH, gy, gOm);                                                                                   \
+    }
+MF_HOST_SIM(f64, double)
+MF_HOST_SIM(f32, float)
+#undef MF_HOST_SIM

@@ -4,7 +4,9 @@ GPU parity tests of the streamed backward of KalmanFilter.log_likelihood (csrc/m
 tests/integration/models/test_gaussian_process_regression.py:117-130, test_variational.py:123-132).  Through the C ABI, every
 gradient tensor, against torch autograd of the DENSE log-likelihood on the CPU (rtol 1e-6) and, at sizes beyond it, against
 the route the kernels replace (posterior chain -> marginal scans -> one lane per time point).  The same arithmetic runs on the
-CPU, lane by lane, in tests/test_post_host_sim.py.
+CPU, lane by lane, in tests/test_post_host_sim.py.  float32: against the same dense autograd in float64 on float32-representable
+draws, within FP32_FACTOR x the error of that CPU run in float32 (tests/helpers/loglik_fp32_cases.py, loglik_fp32_table.py:
+STREAMED) - no tolerance typed here; what a dropped chunk-boundary term costs is recorded in tests/test_gpu_loglik_grad_float32.py.
 """
 import numpy as np
 import pytest
@@ -12,6 +14,9 @@ import torch
 
 import markovflow_amd as mfa
 from markovflow_amd import _lib, kalman_filter as kfm
+from helpers import loglik_fp32_cases as C
+from helpers import loglik_fp32_table as TABLE
+from helpers.kl_fp32_cases import abi_calls  # noqa: F401  (fixture)
 from test_gpu_kalman import DEV, build_kf, nn, random_ssm, tt
 from test_post_host_sim import _dense_log_likelihood
 
@@ -176,26 +181,74 @@ def test_streamed_backward_is_the_route_of_few_long_series_and_agrees_with_the_r
         np.testing.assert_allclose(streamed[k], other[k], rtol=1e-7, atol=1e-9 * (1 + scale), err_msg=k)
 
 
-@pytest.mark.parametrize("d,m", [(1, 1), (2, 2), (3, 1), (4, 3), (5, 1)])
-def test_streamed_backward_fp32_other_state_dimensions(rng, d, m):
-    kw = random_ssm(rng, (3,), 90, d, m, well=True)
-    kw = {k: v.astype(np.float32).astype(np.float64) for k, v in kw.items()}
-    r_inv = np.eye(m) * 2.0
-    w = np.ones(3)
-    want, _ = dense_autograd(kw, r_inv, w, False)
+# ---- float32: judged by the kernels' own arithmetic in float32 on the CPU (tests/helpers/loglik_fp32_cases.py: STREAMED) -------------
+def judge_fp32(what, key, fwd_chunks):
+    """One float32 call on the case's draw (non-unit weights; a shared or per-step precision), all eight tensors - Omega through the
+    precision's gradient - against dense autograd in float64, within FP32_FACTOR x the yardstick of ``key``."""
+    d, m, t, bsz, chunks, per_step = key
+    kw, r_inv, w, want = C.streamed_reference(d, m, t, bsz, per_step)
+    got = grad_streamed_abi(kw, r_inv, w, chunks, dtype=torch.float32, per_step=per_step, fwd_chunks=fwd_chunks)
+    for name, g in zip(NAMES, got):
+        assert np.all(np.isfinite(g)), name
+    for i in (1, 4):
+        assert np.abs(np.triu(got[i], 1)).max() == 0.0, NAMES[i]
+    return C.report(f"{what} d={d} m={m} T={t} B={bsz} chunks={chunks} per_step={per_step} fwd_chunks={fwd_chunks}",
+                    C.streamed_errors(got, r_inv, w, t, per_step, want), TABLE.STREAMED[key])
+
+
+@pytest.mark.parametrize("d,m", C.STREAMED_OTHER_DIMS)
+def test_streamed_backward_fp32_other_state_dimensions(d, m):
     for fwd_chunks in (None, 5):
-        got = grad_streamed_abi(kw, r_inv, w, 4, dtype=torch.float32, fwd_chunks=fwd_chunks)
-        for name, g, ref in zip(NAMES[:7], got[:7], want):
-            np.testing.assert_allclose(g, ref, rtol=5e-3, atol=5e-3 * (1 + np.abs(ref).max()), err_msg=name)
+        judge_fp32("streamed backward", (d, m, 90, 3, 4, False), fwd_chunks)
 
 
 @pytest.mark.parametrize("fwd_chunks", [None, 0, 9])
-def test_streamed_backward_fp32(rng, fwd_chunks):
-    kw = random_ssm(rng, (3,), 120, 6, 1, well=True)
-    kw = {k: v.astype(np.float32).astype(np.float64) for k, v in kw.items()}
-    r_inv = np.eye(1) * 2.0
-    w = np.ones(3)
-    got = grad_streamed_abi(kw, r_inv, w, 0, dtype=torch.float32, fwd_chunks=fwd_chunks)
-    want, _ = dense_autograd(kw, r_inv, w, False)
-    for name, g, ref in zip(NAMES[:7], got[:7], want):
-        np.testing.assert_allclose(g, ref, rtol=5e-3, atol=5e-3 * (1 + np.abs(ref).max()), err_msg=name)
+def test_streamed_backward_fp32(fwd_chunks):
+    judge_fp32("streamed backward", (6, 1, 120, 3, 0, False), fwd_chunks)
+
+
+@pytest.mark.parametrize("fwd_chunks", C.STREAMED_FWD_CHUNKS)
+@pytest.mark.parametrize("d,m,t,bsz,chunks,per_step", C.STREAMED_CASES)
+def test_streamed_backward_fp32_weights_precisions_and_omega(d, m, t, bsz, chunks, per_step, fwd_chunks):
+    """What the float64 tests above cover, in float32: series weighted differently, Omega, per-step precisions, one to three
+    outputs, ragged last chunks, from the backward's own passes and from the forward's chunk summaries."""
+    judge_fp32("streamed backward", (d, m, t, bsz, chunks, per_step), fwd_chunks)
+
+
+def test_gradients_nobody_asked_for_are_not_stored_fp32():
+    """g_b, g_H, g_y, g_omega = NULL in float32: their buffers stay NaN and the others are bit-equal to the full call."""
+    d, m, t, bsz, chunks, per_step = C.STREAMED_NULL_CASE
+    kw, r_inv, w, _ = C.streamed_reference(d, m, t, bsz, per_step)
+    full = grad_streamed_abi(kw, r_inv, w, chunks, dtype=torch.float32, fwd_chunks=0)
+    part = grad_streamed_abi(kw, r_inv, w, chunks, dtype=torch.float32, fwd_chunks=0, skip=(3, 5, 6, 7))
+    for i, name in enumerate(NAMES):
+        if i in (3, 5, 6, 7):
+            assert np.all(np.isnan(part[i])), name
+        else:
+            assert np.all(np.isfinite(full[i])), name
+            np.testing.assert_array_equal(part[i], full[i], err_msg=name)
+
+
+def test_log_likelihood_backward_fp32_takes_the_streamed_route(abi_calls):
+    """KalmanFilter.log_likelihood().backward() on float32 leaves, few long series at d <= 6: mf_kf_loglik_grad_streamed_f32 ran, and
+    the gradient of every tensor of the chain and the emission is within the same allowance - against dense autograd in float64
+    with the float32 precision the class formed from the factor of R and handed to the kernels."""
+    key = C.STREAMED_API_CASE
+    d, m, t, bsz, _, per_step = key
+    kw, r_inv, w, _ = C.streamed_reference(d, m, t, bsz, per_step)
+    leaves = [tt(kw[k], torch.float32).requires_grad_(True) for k in C.KEYS]
+    chol_r = tt(np.linalg.cholesky(np.linalg.inv(r_inv)), torch.float32)
+    kf = mfa.KalmanFilter(mfa.StateSpaceModel(*leaves[:5]), mfa.EmissionModel(leaves[5]), leaves[6], chol_r)
+    per_series = kf._per_series()[0]                    # what log_likelihood() sums (plus constants that carry no gradient here)
+    del abi_calls[:]
+    torch.sum(per_series * tt(w, torch.float32)).backward()
+    assert ("mf_kf_loglik_grad_streamed", torch.float32, 0) in abi_calls
+    assert not any(name == "mf_kf_loglik_grad" for name, _, _ in abi_calls)
+    got = [nn(x.grad) for x in leaves]
+    for i in (1, 4):
+        assert np.abs(np.triu(got[i], 1)).max() == 0.0, NAMES[i]
+    with torch.no_grad():
+        seen = nn(kf._r_inv)
+    want = C.dense_autograd(kw, seen, w, per_step)
+    C.report(f"log_likelihood().backward(), streamed route d={d} m={m} T={t} B={bsz}", C.errors(NAMES[:7], got, want[:7]),
+             TABLE.STREAMED[key])

@@ -31,9 +31,10 @@ def _lib():
     if stale:
         subprocess.check_call([hipcc, "-O1", "-std=c++17", "-shared", "-fPIC", "--offload-arch=gfx950", "-o", LIB, SRC])
     lib = ctypes.CDLL(LIB)
-    lib.mf_post_host_sim_f64.restype = ctypes.c_int
-    lib.mf_post_host_sim_f64.argtypes = ([ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 8 +
-                                         [ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 5)
+    for fn in (lib.mf_post_host_sim_f64, lib.mf_post_host_sim_f32):
+        fn.restype = ctypes.c_int
+        fn.argtypes = ([ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 8 +
+                       [ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 5)
     return lib
 
 
@@ -41,14 +42,9 @@ def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
-@pytest.mark.parametrize("bsz,t,d,m,length,per_step", [
-    (2, 30, 3, 1, 7, False), (2, 30, 6, 1, 5, False), (3, 101, 6, 2, 8, True), (1, 200, 4, 3, 3, False), (2, 2, 6, 1, 1, False),
-    (2, 50, 1, 1, 49, False), (2, 50, 2, 1, 60, False), (1, 600, 6, 1, 4, False), (2, 65, 5, 1, 1, False),
-])
-def test_three_passes_on_the_host_agree_with_the_oracle(bsz, t, d, m, length, per_step):
-    lib = _lib()
-    rng = np.random.default_rng(7)
-    a = 0.9 * np.eye(d) + 0.05 * rng.normal(size=(bsz, t - 1, d, d))
+def _draw(rng, bsz, t, d, m, per_step, diag, noise):
+    """``(mu0, cholP0, A, b, cholQ, H, y, R^-1)`` of the host tests: transitions ``diag I + noise N``."""
+    a = diag * np.eye(d) + noise * rng.normal(size=(bsz, t - 1, d, d))
     cq = np.tril(0.1 * rng.normal(size=(bsz, t - 1, d, d))) + 0.5 * np.eye(d)
     cp0 = np.tril(0.1 * rng.normal(size=(bsz, d, d))) + np.eye(d)
     mu0 = rng.normal(size=(bsz, d))
@@ -61,11 +57,59 @@ def test_three_passes_on_the_host_agree_with_the_oracle(bsz, t, d, m, length, pe
     else:
         r = rng.normal(size=(m, m))
         r_inv = r @ r.T + np.eye(m)
-    r_inv = np.ascontiguousarray(r_inv)
+    return mu0, cp0, a, b, cq, h, y, np.ascontiguousarray(r_inv)
+
+
+def _entry(lib, base, dtype):
+    return getattr(lib, base + ("_f32" if dtype == np.float32 else "_f64"))
+
+
+def post_host_sim(mu0, cp0, a, b, cq, h, y, r_inv, per_step, length, dtype=np.float64):
+    """The three passes in ``dtype`` (numpy float64 or float32) on chunks of ``length`` transitions: ``(return code, (mu0', cholP0',
+    A', b', cholQ'))``, the outputs as float64 arrays (NaN where nothing was written)."""
+    bsz, t, m, d = h.shape
+    ins = [np.ascontiguousarray(x, dtype=dtype) for x in (mu0, cp0, a, b, cq, h, y, r_inv)]
+    ap, bp, cqp, mp, cpp = (np.full_like(ins[i], np.nan) for i in (2, 3, 4, 0, 1))
+    rc = _entry(_lib(), "mf_post_host_sim", dtype)(bsz, t, d, m, *[_p(x) for x in ins], int(per_step), length, _p(ap), _p(mp), _p(bp),
+                                                   _p(cpp), _p(cqp))
+    return rc, tuple(x.astype(np.float64) for x in (mp, cpp, ap, bp, cqp))
+
+
+def grad_host_sim(mu0, cp0, a, b, cq, h, y, r_inv, per_step, length, w, dtype=np.float64):
+    """The streamed backward in ``dtype``: ``(return code, (g_mu0, g_cholP0, g_A, g_b, g_cholQ, g_H, g_y, Omega))`` as float64."""
+    bsz, t, m, d = h.shape
+    ins = [np.ascontiguousarray(x, dtype=dtype) for x in (mu0, cp0, a, b, cq, h, y, r_inv)]
+    outs = [np.full_like(x, np.nan) for x in ins[:7]] + [np.full((bsz, t, m, m), np.nan, dtype=dtype)]
+    wv = np.ascontiguousarray(w, dtype=dtype)
+    rc = _entry(_grad_lib(), "mf_grad_host_sim", dtype)(bsz, t, d, m, *[_p(x) for x in ins], int(per_step), length, _p(wv),
+                                                        *[_p(x) for x in outs])
+    return rc, tuple(x.astype(np.float64) for x in outs)
+
+
+POST_SHAPES = [
+    (2, 30, 3, 1, 7, False), (2, 30, 6, 1, 5, False), (3, 101, 6, 2, 8, True), (1, 200, 4, 3, 3, False), (2, 2, 6, 1, 1, False),
+    (2, 50, 1, 1, 49, False), (2, 50, 2, 1, 60, False), (1, 600, 6, 1, 4, False), (2, 65, 5, 1, 1, False),
+]
+FLOAT_SANITY = 1e-4     # of a tensor's maximum: a cap that catches a broken float instantiation, not a yardstick (measured: <= 6e-6)
+
+
+def _to_float32(arrays):
+    return [np.asarray(x).astype(np.float32).astype(np.float64) for x in arrays]
+
+
+def _assert_float_close(names, got, want):
+    for name, g, w in zip(names, got, want):
+        assert np.all(np.isfinite(g)), name
+        err = np.abs(g - w).max() / np.abs(w).max()
+        print(f"  float host simulation {name}: {err:.3g} of the tensor's maximum")
+        assert err <= FLOAT_SANITY, (name, err)
+
+
+@pytest.mark.parametrize("bsz,t,d,m,length,per_step", POST_SHAPES)
+def test_three_passes_on_the_host_agree_with_the_oracle(bsz, t, d, m, length, per_step):
+    mu0, cp0, a, b, cq, h, y, r_inv = _draw(np.random.default_rng(7), bsz, t, d, m, per_step, 0.9, 0.05)
     want = O.kf_posterior_ssm(mu0, cp0, a, b, cq, h, y, r_inv)
-    ap, bp, cqp, mp, cpp = (np.full_like(x, np.nan) for x in (a, b, cq, mu0, cp0))
-    rc = lib.mf_post_host_sim_f64(bsz, t, d, m, _p(mu0), _p(cp0), _p(a), _p(b), _p(cq), _p(h), _p(y), _p(r_inv), int(per_step),
-                                  length, _p(ap), _p(mp), _p(bp), _p(cpp), _p(cqp))
+    rc, (mp, cpp, ap, bp, cqp) = post_host_sim(mu0, cp0, a, b, cq, h, y, r_inv, per_step, length)
     assert rc == 0
     for name, g, w in zip(("mu0", "cholP0", "A", "b", "cholQ"), (mp, cpp, ap, bp, cqp), want):
         np.testing.assert_allclose(g, w, rtol=1e-9, atol=1e-12, err_msg=name)
@@ -85,12 +129,23 @@ def test_host_simulation_flags_a_singular_process_covariance():
     assert rc == 1
 
 
+@pytest.mark.parametrize("bsz,t,d,m,length,per_step", POST_SHAPES)
+def test_three_passes_on_the_host_in_float_follow_the_double_run(bsz, t, d, m, length, per_step):
+    """mf_post_host_sim_f32: the same run_m<T, D> with float buffers, on float32-representable inputs, against the double run."""
+    ins = _to_float32(_draw(np.random.default_rng(7), bsz, t, d, m, per_step, 0.9, 0.05))
+    rc64, want = post_host_sim(*ins, per_step, length)
+    rc32, got = post_host_sim(*ins, per_step, length, dtype=np.float32)
+    assert rc64 == 0 and rc32 == 0
+    _assert_float_close(("mu0", "cholP0", "A", "b", "cholQ"), got, want)
+
+
 # ---- the streamed backward of log_likelihood (csrc/mf_grad_math.hpp) ------------------------------------------------------------
 def _grad_lib():
     lib = _lib()
-    lib.mf_grad_host_sim_f64.restype = ctypes.c_int
-    lib.mf_grad_host_sim_f64.argtypes = ([ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 8 +
-                                         [ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 9)
+    for fn in (lib.mf_grad_host_sim_f64, lib.mf_grad_host_sim_f32):
+        fn.restype = ctypes.c_int
+        fn.argtypes = ([ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 8 +
+                       [ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 9)
     return lib
 
 
@@ -119,37 +174,23 @@ def _dense_log_likelihood(mu0, cp0, a_s, b_s, cq, h, y, r_inv):
     return -0.5 * (res @ torch.linalg.solve(cov_y, res) + torch.linalg.slogdet(cov_y)[1] + n * m * np.log(2 * np.pi))
 
 
-@pytest.mark.parametrize("bsz,t,d,m,length,per_step", [
+GRAD_SHAPES = [
     (2, 12, 3, 1, 4, False), (2, 17, 6, 1, 5, False), (2, 21, 6, 2, 8, True), (1, 30, 4, 3, 3, False), (2, 2, 6, 1, 1, False),
     (2, 9, 1, 1, 50, False), (1, 40, 6, 1, 1, False), (2, 26, 5, 2, 7, False), (2, 14, 2, 1, 2, True),
-])
+]
+
+
+@pytest.mark.parametrize("bsz,t,d,m,length,per_step", GRAD_SHAPES)
 def test_streamed_backward_on_the_host_agrees_with_dense_autograd(bsz, t, d, m, length, per_step):
     """Three passes of the posterior chain, start moments per chunk from the two sides of every chunk boundary, then the forward
     pass with the pairwise marginals in registers: every gradient of sum_s w_s log p(y_s) against torch autograd of the dense
     log-likelihood (the precision's gradient through the quadratic form only: its log-determinant is the caller's)."""
     import torch
-    lib = _grad_lib()
     rng = np.random.default_rng(11)
-    a = 0.8 * np.eye(d) + 0.1 * rng.normal(size=(bsz, t - 1, d, d))
-    cq = np.tril(0.1 * rng.normal(size=(bsz, t - 1, d, d))) + 0.5 * np.eye(d)
-    cp0 = np.tril(0.1 * rng.normal(size=(bsz, d, d))) + np.eye(d)
-    mu0 = rng.normal(size=(bsz, d))
-    b = 0.1 * rng.normal(size=(bsz, t - 1, d))
-    h = rng.normal(size=(bsz, t, m, d))
-    y = rng.normal(size=(bsz, t, m))
-    if per_step:
-        r = rng.normal(size=(bsz, t, m, m))
-        r_inv = r @ np.swapaxes(r, -1, -2) + np.eye(m)
-    else:
-        r = rng.normal(size=(m, m))
-        r_inv = r @ r.T + np.eye(m)
-    r_inv = np.ascontiguousarray(r_inv)
+    mu0, cp0, a, b, cq, h, y, r_inv = _draw(rng, bsz, t, d, m, per_step, 0.8, 0.1)
     w = rng.uniform(0.5, 1.5, size=bsz)
-    outs = dict(gmu0=np.full_like(mu0, np.nan), gC0=np.full_like(cp0, np.nan), gA=np.full_like(a, np.nan), gb=np.full_like(b, np.nan),
-                gC=np.full_like(cq, np.nan), gH=np.full_like(h, np.nan), gy=np.full_like(y, np.nan),
-                gOm=np.full((bsz, t, m, m), np.nan))
-    rc = lib.mf_grad_host_sim_f64(bsz, t, d, m, _p(mu0), _p(cp0), _p(a), _p(b), _p(cq), _p(h), _p(y), _p(r_inv), int(per_step),
-                                  length, _p(w), *[_p(v) for v in outs.values()])
+    rc, got = grad_host_sim(mu0, cp0, a, b, cq, h, y, r_inv, per_step, length, w)
+    outs = dict(zip(("gmu0", "gC0", "gA", "gb", "gC", "gH", "gy", "gOm"), got))
     assert rc == 0
     leaves = [torch.tensor(x, requires_grad=True) for x in (mu0, cp0, a, b, cq, h, y, r_inv)]
     total = 0.0
@@ -169,3 +210,15 @@ def test_streamed_backward_on_the_host_agrees_with_dense_autograd(bsz, t, d, m, 
     else:
         got = -0.5 * om.sum(axis=(0, 1)) + 0.5 * w.sum() * t * np.linalg.inv(r_inv)
     np.testing.assert_allclose(got, 0.5 * (want[7] + np.swapaxes(want[7], -1, -2)), rtol=1e-7, atol=1e-9, err_msg="R^-1")
+
+
+@pytest.mark.parametrize("bsz,t,d,m,length,per_step", GRAD_SHAPES)
+def test_streamed_backward_on_the_host_in_float_follows_the_double_run(bsz, t, d, m, length, per_step):
+    """mf_grad_host_sim_f32 on float32-representable inputs against the double run, all eight gradient tensors."""
+    rng = np.random.default_rng(11)
+    ins = _to_float32(_draw(rng, bsz, t, d, m, per_step, 0.8, 0.1))
+    w = _to_float32([rng.uniform(0.5, 1.5, size=bsz)])[0]
+    rc64, want = grad_host_sim(*ins, per_step, length, w)
+    rc32, got = grad_host_sim(*ins, per_step, length, w, dtype=np.float32)
+    assert rc64 == 0 and rc32 == 0
+    _assert_float_close(("mu0", "cholP0", "A", "b", "cholQ", "H", "y", "Omega"), got, want)
