@@ -6,8 +6,8 @@
 //   * every lane's next transition (A_k, cholQ_k, b_k, H_k, y_k) is brought in by LDS-DMA
 //     (`buffer_load_dword[x4] ... lds`): no VGPR staging, and the load of step k+1 is in flight
 //     during almost all of step k, so one wavefront per SIMD is enough to cover HBM latency
-//     (one exception: with KfLdsCfg::YREG - fp64, d = 6, m = 1 - y_k comes by plain buffer loads into
-//     registers, four steps per group, and its room in LDS holds tail slots of A);
+//     (one exception: with KfLdsCfg::YREG / HREG - fp64, d = 6, m = 1 - y_k and H_k come by plain buffer loads
+//     into registers, y four steps per group, H for the step itself, and their room in LDS holds tail slots of A);
 //   * one DMA wave-instruction moves 64 x 16 B as contiguous pieces of consecutive rows
 //     (lane -> (row, unit) = divmod(64 i + lane, units per row)), i.e. full 128-B lines of the
 //     row-major [B, T, d, d] tensors, instead of 64 lanes touching 64 different lines;
@@ -223,19 +223,20 @@ template <typename St> struct DmaStream {
 
 // DmaStream for a stream with tail slots that keeps every unit (A with KfLdsCfg::ATAIL), a type of its own so that DmaStream
 // stays what it was for every other stream.  A unit the schedule leaves out is left out by the EXEC mask of its instruction, so
-// its slot keeps the previous fetch's data: a tail slot filled with the rows of step j survives the fetch of step j + 1 and the
-// consumer reads it at the top of step j + 1 straight from LDS - no carried values held in registers across the step.  The
-// schedule is one packed word per lane (MaskedSchedule, mf_head_carry.hpp), consumer bits included.
-template <typename St> struct DmaStreamMasked {
-    using MS = MaskedSchedule<St>;
-    static_assert(MS::USABLE && St::UNIT == 16 && St::UG >= 8, "masked schedule: see MaskedSchedule; a wide stream");
+// its slot keeps what it held: a head slot keeps the carried unit that the consumer moved there from the tail slot (see
+// MovedSchedule, mf_head_carry.hpp, and the top of MF_KF_LDS_STEP) - no carried values held in registers across the step.  The
+// schedule is two packed words per lane, consumer bits included.
+template <typename St> struct DmaStreamMoved {
+    using MS = MovedSchedule<St>;
+    static_assert(MS::USABLE && St::UNIT == 16 && St::UG >= 8, "moved schedule: see MovedSchedule; a wide stream");
     unsigned vo[St::NI];           // this lane's source byte offset for DMA instruction i
-    unsigned sch;                  // the lane's packed schedule
+    unsigned sch0, sch1;           // the lane's packed schedule
     // base_lo: low 32 bits of the address the row offsets are relative to (the phase of a row); the lane-to-unit arithmetic is
     // DmaStream::init's
     MF_DEV void init(const char* smem, int lane, int rel_tab, int, unsigned base_lo) {
         const int q0 = lane / St::U, c0 = lane - q0 * St::U;
-        sch = MS::none();
+        MS::build(sch0, sch1, lane,
+                  [&](int row) { return base_lo + *reinterpret_cast<const unsigned*>(smem + rel_tab + row * 4); });
         MF_UNROLL for (int i = 0; i < St::NI; ++i) {
             const int a = (64 * i) / St::U, b = (64 * i) % St::U;
             int cu = c0 + b;
@@ -243,9 +244,8 @@ template <typename St> struct DmaStreamMasked {
             cu -= carry * St::U;
             const int row = q0 + a + carry;
             const unsigned rel = *reinterpret_cast<const unsigned*>(smem + rel_tab + row * 4);
-            const unsigned off = (unsigned)cu * St::UNIT;          // (MaskedSchedule::linear)
+            const unsigned off = (unsigned)cu * St::UNIT;          // (MovedSchedule::linear)
             vo[i] = rel + off;
-            sch = MS::add(sch, i, cu, base_lo + rel);
 #ifdef MF_EXPERIMENT
             if (pack_base != 0xffffffffu && rel < MF_DMA_INVALID)
                 vo[i] |= ((((pack_base + rel) >> 5) & 3u) << 29) | ((unsigned)(off / St::UNIT) << 24);
@@ -278,8 +278,9 @@ template <typename St> struct DmaStreamMasked {
 #endif
             }
             if constexpr (SCHED) {
+                const unsigned mask = MS::fetch_mask(sch0, sch1, phase);
                 unsigned long long em[N];
-                MF_UNROLL for (int k = 0; k < N; ++k) em[k] = __builtin_amdgcn_ballot_w64(MS::fetch(sch, I0 + k, phase));
+                MF_UNROLL for (int k = 0; k < N; ++k) em[k] = __builtin_amdgcn_ballot_w64(MS::fetch(mask, I0 + k));
                 dma_b128_group_masked<N>(srd, lds_base + I0 * 1024, voff, em);
             } else dma_b128_group<true, N>(srd, lds_base + I0 * 1024, voff);
             issue<I0 + N, I1, SCHED>(srd, lds_base, phase);
@@ -362,7 +363,7 @@ template <typename T, int D, int M, bool RSTEP = false, int BG = 1, bool CARRY =
     static constexpr int S = sizeof(T);
     static constexpr int BGRP = BG;
     using StA0 = Stream<D * D * S, KeepAll>;
-    using StAT = Stream<D * D * S, KeepAll, true>;
+    using StAT = Stream<D * D * S, KeepAll, true, 4>;
     using StC0 = Stream<D * D * S, KeepLower<D, S>>;
     using StCT = Stream<D * D * S, KeepLower<D, S>, true>;
     using Stb = Stream<BG * D * S, KeepAll>;
@@ -381,25 +382,30 @@ template <typename T, int D, int M, bool RSTEP = false, int BG = 1, bool CARRY =
                                  StCT::NT * StCT::HC::PERIOD <= 32 && IMAGE_T <= QUARTER_CU && TABLE_BYTES <= IMAGE_T &&
                                  (StA0::NI + StCT::NI + Stb::NI + StH::NI + Sty::NI + (RSTEP ? StR::NI : 0)) < 64;
     using StC = Stream<D * D * S, KeepLower<D, S>, TAIL>;
-    // ATAIL (one output, shared precision, where chol Q carries): y leaves LDS - four doubles per group live in registers, loaded
-    // by plain buffer loads - and the room its image took becomes tail slots of A: HeadCarry<rows of A, KeepAll> carries the
-    // row's first units where the row starts 96 (units 0, 1) or 112 (unit 0) bytes into a line.  A's schedule goes through the
-    // EXEC mask (DmaStream MSK), chol Q's stays as it is.
+    // ATAIL (one output, shared precision, where chol Q carries): y and H leave LDS and the room their images took becomes tail
+    // slots of A.  HeadCarry<rows of A, KeepAll> with four tail units carries the whole of a row's part of its first line where
+    // that part is at most 64 bytes: units 0 ... 3, 0 ... 2, 0 ... 1, 0 of a row that starts 64, 80, 96, 112 bytes into a line.
+    // A's schedule goes through the EXEC mask (DmaStreamMoved) and the consumer moves the carried units from the tail slots to the
+    // head slots inside LDS; chol Q's stays as it is.
+    // YREG: four values of y per group live in registers, loaded by plain buffer loads.  HREG: the step's own row of H is loaded
+    // at the top of the step by plain buffer loads into the registers that hold it anyway; the step drains the counter in front
+    // of the row's first use (Obs::apply) instead of at its end.
     static constexpr int Y_IMAGE = ((Sty::LDS_BYTES + 15) / 16) * 16;
     static constexpr bool ATAIL = TAIL && M == 1 && !RSTEP && sizeof(T) == 8 && StAT::NT > 0 && StAT::HC::PERIOD == StCT::HC::PERIOD &&
-                                  StAT::LDS_BYTES + StCT::LDS_BYTES + Stb::LDS_BYTES + StH::LDS_BYTES <= QUARTER_CU &&
-                                  (StAT::NI + StCT::NI + Stb::NI + StH::NI) < 64;
-    static constexpr bool YREG = ATAIL;
+                                  (M * D * S) % 16 == 0 && StAT::LDS_BYTES + StCT::LDS_BYTES + Stb::LDS_BYTES <= QUARTER_CU &&
+                                  (StAT::NI + StCT::NI + Stb::NI + (M * D * S) / 16 + (YG * M * S) / 16) < 64;
+    static constexpr bool YREG = ATAIL, HREG = ATAIL;
     // (groups of two - one dwordx4, a y line touched every second step - were measured and lost the whole gain)
     static_assert(YG % 2 == 0 || !YREG, "whole dwordx4 loads");
-    using DA = std::conditional_t<ATAIL, DmaStreamMasked<StAT>, DmaStream<StA0>>;
-    using StA = Stream<D * D * S, KeepAll, ATAIL>;
+    using DA = std::conditional_t<ATAIL, DmaStreamMoved<StAT>, DmaStream<StA0>>;
+    using StA = std::conditional_t<ATAIL, StAT, StA0>;
     static constexpr int NI_y = YREG ? 0 : Sty::NI;
+    static constexpr int NI_H = HREG ? 0 : StH::NI;
     static constexpr int OFF_A = 0;
     static constexpr int OFF_C = OFF_A + StA::LDS_BYTES;
     static constexpr int OFF_b = OFF_C + StC::LDS_BYTES;
     static constexpr int OFF_H = OFF_b + Stb::LDS_BYTES;
-    static constexpr int OFF_y = OFF_H + StH::LDS_BYTES;
+    static constexpr int OFF_y = OFF_H + (HREG ? 0 : StH::LDS_BYTES);
     static constexpr int OFF_R = OFF_y + (YREG ? 0 : Y_IMAGE);
     static constexpr int IMAGE_END = OFF_R + (RSTEP ? ((StR::LDS_BYTES + 15) / 16) * 16 : 0);
     static constexpr int OFF_relA = TAIL ? 0 : IMAGE_END;                                       // row offsets of A and cholQ
@@ -412,14 +418,16 @@ template <typename T, int D, int M, bool RSTEP = false, int BG = 1, bool CARRY =
     // the streaming kernel is instantiated only where matrix rows are whole 16-B units, the per-step DMA count
     // fits the 6-bit vm counter and the image fits 64 KB of LDS
     static constexpr bool SUPPORTED =
-                                      (StA::NI + StC::NI + Stb::NI + StH::NI + NI_y + (RSTEP ? StR::NI : 0)) < 64 &&
+                                      (StA::NI + StC::NI + Stb::NI + NI_H + NI_y + (RSTEP ? StR::NI : 0)) < 64 &&
                                       LDS_TOTAL <= 64 * 1024;
 };
 
 template <typename T, int D, int M, bool RSTEP = false> using KfChunkCfg = KfLdsCfg<T, D, M, RSTEP, 1, true>;
 static_assert(KfChunkCfg<double, 6, 1>::TAIL && KfChunkCfg<double, 6, 1>::LDS_TOTAL <= 40960, "fp64 d = 6: four wavefronts per CU");
-static_assert(KfChunkCfg<double, 6, 1>::ATAIL && KfChunkCfg<double, 6, 1>::StA::U == 20 && KfChunkCfg<double, 6, 1>::LDS_TOTAL == 40960,
-              "fp64 d = 6, m = 1: A's two tail slots take the place of the y image");
+static_assert(KfChunkCfg<double, 6, 1>::ATAIL && KfChunkCfg<double, 6, 1>::StA::U == 22 && KfChunkCfg<double, 6, 1>::LDS_TOTAL == 39936,
+              "fp64 d = 6, m = 1: A's four tail slots take the place of the y and H images, one unit per lane to spare");
+static_assert(KfChunkCfg<double, 6, 1>::StA::NI + KfChunkCfg<double, 6, 1>::StC::NI + KfChunkCfg<double, 6, 1>::Stb::NI == 39,
+              "39 LDS-DMA instructions, 3 loads of H and 2 of y per step: 44 in flight, below the 6-bit counter's 63");
 static_assert(!KfChunkCfg<double, 6, 2>::ATAIL && !KfChunkCfg<double, 6, 1, true>::ATAIL && !KfChunkCfg<float, 6, 1>::ATAIL &&
               !KfLdsCfg<double, 6, 1>::ATAIL && !KfLdsCfg<double, 6, 1, false, 2>::ATAIL, "every other instantiation keeps its streams");
 
@@ -428,7 +436,8 @@ static_assert(!KfChunkCfg<double, 6, 2>::ATAIL && !KfChunkCfg<double, 6, 1, true
 // (Counted waits - "all but the youngest n have landed" - were tried and are NOT safe here: with dword and
 // dwordx4 LDS-DMA mixed in one stream of requests the landing order did not follow the issue order.)
 template <typename Cfg> struct KfPump {
-    static constexpr int N_SMALL = Cfg::StC::NI + Cfg::Stb::NI + Cfg::StH::NI + Cfg::NI_y + (Cfg::RS ? Cfg::StR::NI : 0);
+    static constexpr int N_SMALL = Cfg::StC::NI + Cfg::Stb::NI + Cfg::NI_H + Cfg::NI_y + (Cfg::RS ? Cfg::StR::NI : 0);
+    static constexpr bool HREG = Cfg::HREG;   // kf_lds_step drains the vector-memory counter in front of the first use of H
     static constexpr int N_BIG = Cfg::StA::NI;
     const typename Cfg::DA& dA; const DmaStream<typename Cfg::StC>& dC;
     const DmaStream<typename Cfg::Stb>& db; const DmaStream<typename Cfg::StH>& dH;
@@ -449,7 +458,7 @@ template <typename Cfg> struct KfPump {
         else {
             dC.template issue<HC, 64, true>(sC, lds0 + Cfg::OFF_C, cphase);
             db.template issue<0, 64>(sb, lds0 + Cfg::OFF_b);
-            dH.template issue<0, 64>(sH, lds0 + Cfg::OFF_H);
+            if constexpr (!Cfg::HREG) dH.template issue<0, 64>(sH, lds0 + Cfg::OFF_H);
             if constexpr (!Cfg::YREG) { if (yfetch) dy.template issue<0, 64>(sy, lds0 + Cfg::OFF_y); }
             if (Cfg::RS) dR.template issue<0, 64>(sR, lds0 + Cfg::OFF_R);
         }
@@ -458,7 +467,7 @@ template <typename Cfg> struct KfPump {
     template <int K> MF_DEV void all() const {
         dC.template issue<0, 64>(sC, lds0 + Cfg::OFF_C);
         db.template issue<0, 64>(sb, lds0 + Cfg::OFF_b);
-        dH.template issue<0, 64>(sH, lds0 + Cfg::OFF_H);
+        if constexpr (!Cfg::HREG) dH.template issue<0, 64>(sH, lds0 + Cfg::OFF_H);
         if constexpr (!Cfg::YREG) dy.template issue<0, 64>(sy, lds0 + Cfg::OFF_y);
         if (Cfg::RS) dR.template issue<0, 64>(sR, lds0 + Cfg::OFF_R);
         dA.template issue<0, 64>(sA, lds0 + Cfg::OFF_A);
@@ -491,6 +500,21 @@ template <typename Cfg> struct KfPump {
 // `pump` issues the LDS-DMA of the NEXT step in small batches between the arithmetic phases: a burst of
 // ~40 wave-instructions back to back fills the CU's address queue and stalls the (only) wave of the SIMD
 // at issue, while one batch every few hundred VALU instructions is absorbed for free.
+// HREG pumps (KfPump of a KfLdsCfg::HREG configuration): the step's row of H was loaded into hk by plain buffer loads at the top of
+// the step.  The step then drains the vector-memory counter itself, in full, right in front of the first use of hk - a compiler
+// wait there would carry the compiler's count, which knows nothing of the DMA in flight - and pins the compiler's own wait behind it.
+template <typename Pump, typename = void> struct PumpHreg { static constexpr bool value = false; };
+template <typename Pump> struct PumpHreg<Pump, std::enable_if_t<Pump::HREG>> { static constexpr bool value = true; };
+template <typename T, int N> MF_DEV void hreg_arrive(T (&h)[N], const T (&hk)[N]) {
+    // (the asm statements are ordered among themselves only: without the barrier the scheduler draws the drain and the
+    // observation update far up into the arithmetic that is meant to cover the last batch of A)
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    MF_UNROLL for (int i = 0; i < N; ++i) h[i] = hk[i];
+    MF_UNROLL for (int i = 0; i < N; ++i) asm volatile("" : "+v"(h[i]));
+}
+
 template <typename T, int D, int M, bool SPIKE, bool FIRST, typename Pump>
 MF_DEV void kf_lds_step(Elim<T, D, SPIKE>& E, LogAcc<T>& laC, T& acc_yry, T& acc_ww, const T (&C)[D][D],
                         const T (&mvec)[D], const T (&hk)[M * D], const T (&yk)[M], const T (&Rsh)[M * M],
@@ -532,10 +556,18 @@ MF_DEV void kf_lds_step(Elim<T, D, SPIKE>& E, LogAcc<T>& laC, T& acc_yry, T& acc
     }
     if (ord) E.eliminate_main();
     pump.template big<3>();
+    // HREG: H arrives in h.  A chunk's first step takes it ONCE, in front of its two forms: the compiler then shares the products
+    // of H, R and y between them as it does where H comes from LDS - with H arriving inside each form it paired the fused
+    // multiply-adds of Obs::apply differently and the results moved in the last bits.  Every later step takes it inside the one
+    // form it has, behind the arithmetic that covers the last batch of A.
+    constexpr bool HR = PumpHreg<Pump>::value;
+    T h[HR ? M * D : 1];
+    if constexpr (HR && FIRST) hreg_arrive(h, hk);
     if (FIRST && active && sep) {
         trimulT_self_lower<T, D>(Ci, E.Phi);
         trimulT_lower_vec<T, D>(Ci, w, E.t);
-        acc_yry += Obs<T, D, M>::apply(hk, yk, Rsh, M, E.Phi, E.t);
+        if constexpr (HR) acc_yry += Obs<T, D, M>::apply(h, yk, Rsh, M, E.Phi, E.t);
+        else acc_yry += Obs<T, D, M>::apply(hk, yk, Rsh, M, E.Phi, E.t);
     }
     if (ord) {
         E.eliminate_spike();
@@ -544,7 +576,10 @@ MF_DEV void kf_lds_step(Elim<T, D, SPIKE>& E, LogAcc<T>& laC, T& acc_yry, T& acc
         T Dn[D][D], rn[D];
         trimulT_self_lower<T, D>(Ci, Dn);
         trimulT_lower_vec<T, D>(Ci, w, rn);
-        acc_yry += Obs<T, D, M>::apply(hk, yk, Rsh, M, Dn, rn);
+        if constexpr (HR) {
+            if constexpr (!FIRST) hreg_arrive(h, hk);
+            acc_yry += Obs<T, D, M>::apply(h, yk, Rsh, M, Dn, rn);
+        } else acc_yry += Obs<T, D, M>::apply(hk, yk, Rsh, M, Dn, rn);
         E.advance(Bm, Dn, rn);
     }
 }
@@ -648,7 +683,7 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
     else dA.init(smem, lane, Cfg::OFF_relA, 0);
     dC.init(smem, lane, Cfg::OFF_relA, Cfg::OFF_gtabC, (unsigned)pC);
     db.init(smem, lane, Cfg::OFF_relb, 0);
-    dH.init(smem, lane, Cfg::OFF_relH, 0);
+    if constexpr (!Cfg::HREG) dH.init(smem, lane, Cfg::OFF_relH, 0);
     if constexpr (!Cfg::YREG) dy.init(smem, lane, Cfg::OFF_rely, 0);
     if (RSTEP) dR.init(smem, lane, Cfg::OFF_relR, 0);
     // (with the head carry the tables lie over the image: the last table read is done before the first DMA writes there)
@@ -660,12 +695,13 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
     T cv[NTAIL > 0 ? NTAIL : 1][UEL];
     MF_UNROLL for (int t = 0; t < (NTAIL > 0 ? NTAIL : 1); ++t) MF_UNROLL for (int k = 0; k < UEL; ++k) cv[t][k] = T(0);
 
-    // A's head carry: the consumer schedule rides in dA's schedule word; the carried units are read from the tail slots themselves
+    // A's head carry: the consumer schedule rides in dA's second schedule word; the lane moves the carried units of its next row
+    // from the tail slots to the head slots (MF_KF_LDS_STEP) and reads every row from the row's own slots
     using HCA = typename Cfg::StA::HC;
     constexpr int NTA = Cfg::StA::NT;
     if constexpr (NTA > 0) {
         static_assert(HCA::PERIOD == CPER, "one phase for both schedules");
-        dA.sch = MaskedSchedule<typename Cfg::StA>::with_consumer(dA.sch, (unsigned)((unsigned long long)a.A + offA));
+        dA.sch1 = MovedSchedule<typename Cfg::StA>::with_consumer(dA.sch1, (unsigned)((unsigned long long)a.A + offA));
     }
     // YREG: this lane's group of y values (steps YG g ... YG g + YG - 1 of its chunk) and its offset from the wave's descriptor base
     YRegs<T, Cfg::YG * M, Cfg::YREG> yr;
@@ -673,6 +709,9 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
         MF_UNROLL for (int i = 0; i < Cfg::YG * M; ++i) yr.q[i] = T(0);
         yr.voff = rowok ? (unsigned)(offy - offy0) : MF_DMA_INVALID;
     }
+    // HREG: this lane's offset of its row of H from the wave's descriptor base (the descriptor advances by a row per step)
+    unsigned hvoff = 0u;
+    if constexpr (Cfg::HREG) hvoff = rowok ? (unsigned)(offH - offH0) : MF_DMA_INVALID;
 
     const RowReader<T, typename Cfg::StA> rA(smem, Cfg::OFF_A, lane);
     const RowReader<T, typename Cfg::StC> rC(smem, Cfg::OFF_C, lane);
@@ -739,7 +778,10 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
             }                                                                                                         \
         }                                                                                                             \
         MF_UNROLL for (int i = 0; i < D; ++i) mvec[i] = rb.at(i);                                                     \
-        MF_UNROLL for (int i = 0; i < M * D; ++i) hk[i] = rH.at(i);                                                   \
+        /* HREG: this step's row of H (pH is a row ahead by now), straight into hk; first used, behind a full drain, */ \
+        /* in front of Obs::apply                                                                                    */ \
+        if constexpr (Cfg::HREG) yreg_load(pH - M * D * S, eH, a.debug | ((a.debug >> 1) & 1), hvoff, hk);            \
+        else { MF_UNROLL for (int i = 0; i < M * D; ++i) hk[i] = rH.at(i); }                                          \
         if constexpr (Cfg::YREG) {                                                                                    \
             /* this step's y out of the group; in the group's last step the next group is loaded over it */           \
             yk[0] = yr.q[0];                                                                                          \
@@ -755,15 +797,17 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
         T Bm[D][D];                                                                                                   \
         MF_UNROLL for (int i = 0; i < D; ++i) MF_UNROLL for (int jj = 0; jj < D; ++jj) Bm[i][jj] = rA.at(i * D + jj); \
         if constexpr (NTA > 0) {                                                                                      \
-            /* a head unit the previous fetch carried is read from the tail slot it left there: the fetch of this  */ \
-            /* step's rows masked that slot out (a row never carries on two steps running), so it still holds it    */ \
+            /* the head units that the NEXT row carries go from the tail slots, where this step's fetch left them, to  */ \
+            /* the row's head slots, which are dead now: the fetch of the next row masks exactly those out and may    */ \
+            /* refill the tail slots.  A unit that is not carried is written back to its own tail slot: no branch.    */ \
+            /* (copied as values of T, the type the row was read with: the stores stay behind those reads)            */ \
+            char* arow = smem + Cfg::OFF_A + lane * (Cfg::StA::U * Cfg::StA::UNIT);                                   \
             MF_UNROLL for (int t = 0; t < NTA; ++t) {                                                                 \
-                const bool got = !(FIRST) && MaskedSchedule<typename Cfg::StA>::carried(dA.sch, t, (unsigned)(j & (CPER - 1))); \
-                const int uoff = (got ? Cfg::StA::UB + t : HCA::tail_unit(t)) * Cfg::StA::UNIT;                       \
-                MF_UNROLL for (int k = 0; k < Cfg::StA::UNIT / S; ++k) {                                              \
-                    const int e = HCA::tail_unit(t) * (Cfg::StA::UNIT / S) + k;                                       \
-                    Bm[e / D][e % D] = *reinterpret_cast<const T*>(rA.row + uoff + k * S);                            \
-                }                                                                                                     \
+                const bool mv = MovedSchedule<typename Cfg::StA>::carried(dA.sch1, t, (unsigned)((j + 1) & (CPER - 1))); \
+                const int src = (Cfg::StA::UB + t) * Cfg::StA::UNIT, dst = mv ? HCA::tail_unit(t) * Cfg::StA::UNIT : src; \
+                T un[Cfg::StA::UNIT / S];                                                                             \
+                MF_UNROLL for (int k = 0; k < Cfg::StA::UNIT / S; ++k) un[k] = *reinterpret_cast<const T*>(arow + src + k * S); \
+                MF_UNROLL for (int k = 0; k < Cfg::StA::UNIT / S; ++k) *reinterpret_cast<T*>(arow + dst + k * S) = un[k]; \
             }                                                                                                         \
         }                                                                                                             \
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                            \
