@@ -369,6 +369,47 @@ int mf_sde_piecewise_transitions_grad_f32(int64_t B, int64_t n, int ncomp, const
                                           const float* g_cholQ, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Impulse / step mean functions (markovflow/mean_function.py): the response of the kernel's own SDE to interventions at
+ * action_times [B,K] (K >= 1, sorted ascending per series, ties allowed; not checked), evaluated at time_points [B,N] (any order).
+ * Components as for mf_sde_transitions_* (orders, osc: HOST arrays; lam, omega: [ncomp], or [B,ncomp] with per_series; lam may be
+ * NULL when every order is 0, omega when there is no oscillator; no var).  With j(t) = #{k : action_times[k] < t} (strict, in the
+ * call's precision: a point exactly on an action time does not yet see that action):
+ *   j = 0:  state = 0 and f = 0 EXACTLY (the product is skipped, so a point far before the first action gives no inf * 0);
+ *   a NaN time point counts as j = K (it sorts last, as in torch.searchsorted): its gap is NaN, so its state and f are NaN, and in
+ *   the reverse mode it makes g_r of its series (and bin K - 1 of g_a) NaN - a bad query time is not hidden;
+ *   j > 0:  state(t) = a_k + exp(F (t - tau_k)) c_k,  k = j - 1,  with  c_0 = r_0,  c_k = exp(F (tau_k - tau_{k-1})) c_{k-1} + r_k;
+ *   f[.., o] = the sum of the FIRST state of every component c with out_map[c] = o  (out_map: HOST array [ncomp], 0 <= . < m <= ncomp).
+ * r [B,K,d]; a [B,K,d] or NULL (zero); f [B,N,m]; state [B,N,d] optional; c [B,K,d]: caller-owned scratch that receives the
+ * coefficients.  Two launches: a scan sequential in K (one lane per (series, component)) and the evaluation (one lane per point;
+ * every block of exp(F dt) is generated in registers, nothing d x d is held, so ncomp <= 16 is the only limit).
+ * Errors: the negative position of the offending argument, checked before any launch; B = 0 or N = 0 returns 0 without a launch.
+ */
+int mf_mean_response_f64(int64_t B, int64_t K, int64_t N, int ncomp, const int* orders, const int* osc, const double* lam,
+                         const double* omega, int per_series, const double* action_times, const double* r, const double* a,
+                         const double* time_points, int m, const int* out_map, double* f, double* state, double* c, void* stream);
+int mf_mean_response_f32(int64_t B, int64_t K, int64_t N, int ncomp, const int* orders, const int* osc, const float* lam,
+                         const float* omega, int per_series, const float* action_times, const float* r, const float* a,
+                         const float* time_points, int m, const int* out_map, float* f, float* state, float* c, void* stream);
+/*
+ * Reverse mode of mf_mean_response_*, the adjoint of the linear map (r, a) -> f: from g_f [B,N,m] to g_r [B,K,d] and g_a [B,K,d]
+ * (g_a may be NULL).  Per point  exp(F (t - tau_k))^T H^T g_f  goes to bin k of g_c and  H^T g_f  to bin k of g_a; then
+ * lambda_{K-1} = g_c_{K-1},  lambda_{k-1} = g_c_{k-1} + exp(F (tau_k - tau_{k-1}))^T lambda_k,  g_r = lambda.  The sums over the
+ * points of one bin run in a fixed order without floating-point atomics (two launches: per block of 64 points one partial sum per
+ * bin present, then every series' records in block order and the recurrence), so two calls agree bit for bit, for any order of
+ * time_points.  N = 0 gives zeros.
+ * workspace: mf_mean_response_grad_workspace_bytes(B, N, ncomp, d, sizeof(T)) bytes of device memory.
+ */
+size_t mf_mean_response_grad_workspace_bytes(int64_t B, int64_t N, int ncomp, int d, int elem_size);
+int mf_mean_response_grad_f64(int64_t B, int64_t K, int64_t N, int ncomp, const int* orders, const int* osc, const double* lam,
+                              const double* omega, int per_series, const double* action_times, const double* time_points, int m,
+                              const int* out_map, const double* g_f, double* g_r, double* g_a, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int mf_mean_response_grad_f32(int64_t B, int64_t K, int64_t N, int ncomp, const int* orders, const int* osc, const float* lam,
+                              const float* omega, int per_series, const float* action_times, const float* time_points, int m,
+                              const int* out_map, const float* g_f, float* g_r, float* g_a, void* workspace, size_t workspace_bytes,
+                              void* stream);
+
+/*
  * The generator of the LatentExponentiallyGenerated kernel (markovflow/kernels/latent_exp_generated.py): a dense feedback matrix
  * F [d,d] (per_series: [B,d,d]) with steady-state covariance I, 1 <= d <= 16; dt [B,n]; outputs [B,n,d,d], A required, cholQ and Q
  * optional:

@@ -17,10 +17,11 @@ from .kalman_filter import (
     UnivariateGaussianSitesNat,
 )
 from .state_space_model import StateSpaceModel, state_space_model_from_covariances
-from . import conditionals, distributed, kernels, likelihoods, models, spatial_kernels, ssm_gaussian_transformations, ssm_natgrad
+from . import conditionals, distributed, kernels, likelihoods, mean_function, models, spatial_kernels, ssm_gaussian_transformations, ssm_natgrad
 from .kernels import (Constant, HarmonicOscillator, IndependentMultiOutput, LatentExponentiallyGenerated, Matern12, Matern32, Matern52, NonStationaryKernel,
                       PiecewiseKernel, Product, SDEKernel, SparseSpatioTemporalKernel, StationaryKernel, Sum)
 from .likelihoods import Bernoulli, Gaussian, Likelihood, Poisson, StudentT
+from .mean_function import ImpulseMeanFunction, LinearMeanFunction, MeanFunction, StepMeanFunction, ZeroMeanFunction
 from .models import (CVIGaussianProcess, GaussianProcessRegression, ImportanceWeightedVI, PowerExpectationPropagation,
                      SparseCVIGaussianProcess, SparsePowerExpectationPropagation, SparseVariationalGaussianProcess,
                      SpatioTemporalSparseCVI, SpatioTemporalSparseVariational, VariationalGaussianProcess)
@@ -40,4 +41,5 @@ __all__ = [
     "SparsePowerExpectationPropagation", "ImportanceWeightedVI", "ImportanceWeightedPosteriorProcess",
     "VariationalGaussianProcess", "spatial_kernels", "SparseSpatioTemporalKernel", "SpatioTemporalSparseVariational", "SpatioTemporalSparseCVI",
     "NonStationaryKernel", "PiecewiseKernel", "LatentExponentiallyGenerated",
+    "mean_function", "MeanFunction", "ZeroMeanFunction", "LinearMeanFunction", "ImpulseMeanFunction", "StepMeanFunction",
 ]

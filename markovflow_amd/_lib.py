@@ -75,6 +75,10 @@ _SIGS = {
                                                  "Tp", _int, "Tp", "Tp", "T", "Tp", "Tp", "Tp", _vp, _sz, _vp]),
     "mf_sde_leg_transitions": (_int, [_i64, _i64, _int, "Tp", _int, "Tp", "T", "Tp", "Tp", "Tp", _vp]),
     "mf_sde_leg_transitions_grad": (_int, [_i64, _i64, _int, "Tp", _int, "Tp", "T", "Tp", "Tp", "Tp", _vp, _sz, _vp]),
+    "mf_mean_response": (_int, [_i64, _i64, _i64, _int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), "Tp", "Tp", _int,
+                                "Tp", "Tp", "Tp", "Tp", _int, ctypes.POINTER(ctypes.c_int), "Tp", "Tp", "Tp", _vp]),
+    "mf_mean_response_grad": (_int, [_i64, _i64, _i64, _int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), "Tp", "Tp",
+                                     _int, "Tp", "Tp", _int, ctypes.POINTER(ctypes.c_int), "Tp", "Tp", "Tp", _vp, _sz, _vp]),
     "mf_lik_variational_expectations": (_int, [_i64, _int, _hd, _int, _hd, _hd, "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_cvi_site_update": (_int, [_i64, _int, _hd, _int, _hd, _hd, "Tp", "Tp", "Tp", "T", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_predict_log_density": (_int, [_i64, _int, _hd, _int, _hd, _hd, "Tp", "Tp", "Tp", "Tp", _vp]),
@@ -125,6 +129,7 @@ _PLAIN = {
     "mf_btd_grad_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
     "mf_sde_piecewise_transitions_grad_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
     "mf_sde_leg_transitions_grad_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
+    "mf_mean_response_grad_workspace_bytes": (_sz, [_i64, _i64, _int, _int, _int]),
     "mf_lik_sparse_expectations_workspace_bytes": (_sz, [_i64, _int, _int]),
     "mf_lik_iw_log_weights_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
     "mf_lik_dense_expectations_workspace_bytes": (_sz, [_i64, _i64, _int]),

@@ -977,6 +977,340 @@ int run_pw_grad(int64_t B, int64_t n, int ncomp, const int* orders, const int* o
     return hipGetLastError() == hipSuccess ? 0 : -1000;
 }
 
+// ---- mean functions: the response of the kernel's own SDE to impulses / steps at given action times -----------------------------------
+// (markovflow/mean_function.py:117-413.)  For one series with actions at tau_0 <= ... <= tau_{K-1}: j(t) = #{k : tau_k < t}, the state
+// mean is EXACTLY zero for j = 0 and  s(t) = a_k + exp(F (t - tau_k)) c_k  with k = j - 1 otherwise, the coefficients following the
+// affine recurrence  c_0 = r_0,  c_k = exp(F (tau_k - tau_{k-1})) c_{k-1} + r_k  (impulse: r = u, a = 0; step: a = -F^-1 u,
+// r_k = a_{k-1} - a_k).  f(t) = H s(t), H selecting the first state of every component into the component's output.  The reference
+// materialises [.., K, d, d] and [.., N, d, d] transition tensors for this; here every exp(F dt) block lives in the registers of the
+// lane that multiplies with it, built by Comp::build / build_osc above.
+
+// fn(the component's transition block at gap `delta`): THE dispatch over (order, osc) of the kernels below.  Pinf is not used (the
+// compiler drops it)
+template <typename T, typename Fn>
+__device__ __forceinline__ void with_transition(int order, int osc, T l, T w, T delta, Fn&& fn) {
+    const T v = T(1);
+    if (osc == 0) {
+        if (order <= 1) { Comp<T, 1> k; k.build(l, v, delta); fn(k); }
+        else if (order == 3) { Comp<T, 2> k; k.build(l, v, delta); fn(k); }
+        else { Comp<T, 3> k; k.build(l, v, delta); fn(k); }
+    } else if (order <= 1) {
+        Comp<T, 2> k;
+        build_osc<T, 1, false>(l, v, w, delta, k);
+        fn(k);
+    } else if (order == 3) {
+        Comp<T, 4> k;
+        if (osc == 1) build_osc<T, 2, false>(l, v, w, delta, k); else build_osc<T, 2, true>(l, v, w, delta, k);
+        fn(k);
+    } else {
+        Comp<T, 6> k;
+        if (osc == 1) build_osc<T, 3, false>(l, v, w, delta, k); else build_osc<T, 3, true>(l, v, w, delta, k);
+        fn(k);
+    }
+}
+#define MF_COMP_DIM(k) int(sizeof((k).A) / sizeof((k).A[0]))
+
+struct MSpec : GSpec {
+    int out[MAXC];         // the output that the component's first state is added to (H is a 0/1 selector)
+};
+
+__host__ __device__ inline int comp_states(int order, int osc) { return (order == 0 ? 1 : (order + 1) / 2) * (osc ? 2 : 1); }
+
+// number of action times < t (tau sorted ascending): in [0, K] for ANY t.  A NaN time sorts last, as in torch.searchsorted: it
+// lands in the last bin, where its gap t - tau is NaN, so that a bad query time comes out as NaN (and poisons the gradients of its
+// series) instead of hiding behind the exact zero of the points before the first action
+template <typename T> __device__ __forceinline__ int actions_before(const T* __restrict__ tau, int K, T t) {
+    if (t != t) return K;
+    int lo = 0, hi = K;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (tau[mid] < t) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// Forward, launch 1 of 2: the coefficient scan.  F is block diagonal, so the recurrence decouples by component: one lane per
+// (series, component), sequential in K (the number of interventions - small next to N), at most 6 values in registers.
+template <typename T>
+__global__ void __launch_bounds__(64) mean_scan_kernel(long B, long K, MSpec sp, const T* __restrict__ lam, const T* __restrict__ omega,
+                                                       long hstride, const T* __restrict__ tau, const T* __restrict__ r,
+                                                       T* __restrict__ c) {
+    const long id = (long)blockIdx.x * 64 + threadIdx.x;
+    if (id >= B * sp.ncomp) return;
+    const long b = id / sp.ncomp;
+    const int cc = (int)(id % sp.ncomp);
+    const int order = sp.order[cc], osc = sp.osc[cc], off = sp.off[cc], d = sp.d, kk = comp_states(order, osc);
+    const T l = order == 0 ? T(0) : lam[b * hstride + cc], w = osc ? omega[b * hstride + cc] : T(0);
+    const T* tb = tau + b * K;
+    T cur[6];
+    for (int i = 0; i < 6; ++i) cur[i] = i < kk ? r[(b * K) * d + off + i] : T(0);
+    for (int i = 0; i < kk; ++i) c[(b * K) * d + off + i] = cur[i];
+    for (long k = 1; k < K; ++k) {
+        const T* rk = r + (b * K + k) * d + off;
+        T* ck = c + (b * K + k) * d + off;
+        with_transition<T>(order, osc, l, w, tb[k] - tb[k - 1], [&](const auto& blk) {
+            constexpr int KK = MF_COMP_DIM(blk);
+            T nxt[KK];
+            for (int i = 0; i < KK; ++i) {
+                T acc = T(0);
+                for (int j = 0; j < KK; ++j) acc += blk.A[i][j] * cur[j];
+                nxt[i] = acc + rk[i];
+            }
+            for (int i = 0; i < KK; ++i) { cur[i] = nxt[i]; ck[i] = nxt[i]; }
+        });
+    }
+}
+
+// Forward, launch 2 of 2: one lane per (series, time point).  The lane finds its bin by a binary search of the series' action times
+// (global memory, L2-resident: the lanes of a block walk the same few lines), builds every component's block of exp(F (t - tau_k)) in
+// registers, multiplies with the slice of c_k, adds a_k and accumulates the first state into the component's output.  State and f
+// go through an LDS image (odd stride per lane: conflict-free) and leave with coalesced stores, as in sde_transitions_kernel.
+template <typename T>
+__global__ void __launch_bounds__(64) mean_eval_kernel(long B, long K, long N, MSpec sp, int m, const T* __restrict__ lam,
+                                                       const T* __restrict__ omega, long hstride, const T* __restrict__ tau,
+                                                       const T* __restrict__ c, const T* __restrict__ a, const T* __restrict__ tp,
+                                                       T* __restrict__ f, T* __restrict__ state) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    T* buf = reinterpret_cast<T*>(smem_raw);
+    const long base = (long)blockIdx.x * 64, total = B * N;
+    const long id = base + threadIdx.x;
+    const bool valid = id < total;
+    const int d = sp.d, stride = (d + m) | 1;
+    T* mine = buf + threadIdx.x * stride;       // [state d | f m]
+    for (int e = 0; e < d + m; ++e) mine[e] = T(0);
+    if (valid) {
+        const long b = id / N;
+        const T t = tp[id];
+        const int j = actions_before<T>(tau + b * K, (int)K, t);
+        if (j > 0) {
+            const long row = (b * K + (j - 1)) * d;
+            const T delta = t - tau[b * K + (j - 1)];
+            for (int cc = 0; cc < sp.ncomp; ++cc) {
+                const int order = sp.order[cc], osc = sp.osc[cc], off = sp.off[cc];
+                const T l = order == 0 ? T(0) : lam[b * hstride + cc], w = osc ? omega[b * hstride + cc] : T(0);
+                const T* ck = c + row + off;
+                const T* ak = a ? a + row + off : nullptr;
+                T* fo = mine + d + sp.out[cc];
+                with_transition<T>(order, osc, l, w, delta, [&](const auto& blk) {
+                    constexpr int KK = MF_COMP_DIM(blk);
+                    T cv[KK];
+                    for (int i = 0; i < KK; ++i) cv[i] = ck[i];
+                    for (int i = 0; i < KK; ++i) {
+                        T acc = T(0);
+                        for (int jj = 0; jj < KK; ++jj) acc += blk.A[i][jj] * cv[jj];
+                        if (ak) acc = ak[i] + acc;
+                        mine[off + i] = acc;
+                        if (i == 0) *fo += acc;
+                    }
+                });
+            }
+        }
+    }
+    __syncthreads();
+    long nvalid = total - base;
+    if (nvalid > 64) nvalid = 64;
+    if (nvalid < 0) nvalid = 0;
+    for (long e = threadIdx.x; e < nvalid * m; e += 64) f[base * m + e] = buf[(e / m) * stride + d + (e % m)];
+    if (state)
+        for (long e = threadIdx.x; e < nvalid * d; e += 64) state[base * d + e] = buf[(e / d) * stride + (e % d)];
+}
+
+// argument checks shared by the two mean-response entry points (positions in THEIR signatures: both start
+// B, K, N, ncomp, orders, osc, lam, omega, per_series, action_times)
+inline int mean_spec(int64_t B, int64_t K, int64_t N, int ncomp, const int* orders, const int* osc, const void* lam,
+                     const void* omega, const void* tau, MSpec& sp) {
+    if (B < 0) return -1;
+    if (K < 1 || K > (int64_t(1) << 30)) return -2;
+    if (N < 0) return -3;
+    bool any_osc, any_lam = false;
+    const int bad = g_spec(ncomp, orders, osc, sp, any_osc);
+    if (bad) return bad - 1;                                 // (g_spec numbers ncomp, orders, osc 3, 4, 5; here they are 4, 5, 6)
+    for (int c = 0; c < ncomp; ++c) any_lam |= orders[c] != 0;
+    if (B == 0) return 0;
+    if (any_lam && !lam) return -7;
+    if (any_osc && !omega) return -8;
+    if (!tau) return -10;
+    return 0;
+}
+inline int mean_out_map(int ncomp, int m, const int* out_map, int pos_m, MSpec& sp) {
+    if (m < 1 || m > ncomp) return -pos_m;
+    if (!out_map) return -(pos_m + 1);
+    for (int c = 0; c < ncomp; ++c) {
+        if (out_map[c] < 0 || out_map[c] >= m) return -(pos_m + 1);
+        sp.out[c] = out_map[c];
+    }
+    return 0;
+}
+
+template <typename T>
+int run_mean(int64_t B, int64_t K, int64_t N, int ncomp, const int* orders, const int* osc, const T* lam, const T* omega,
+             int per_series, const T* tau, const T* r, const T* a, const T* tp, int m, const int* out_map, T* f, T* state, T* c,
+             void* stream) {
+    MSpec sp;
+    int bad = mean_spec(B, K, N, ncomp, orders, osc, lam, omega, tau, sp);
+    if (bad) return bad;
+    bad = mean_out_map(ncomp, m, out_map, 14, sp);
+    if (bad) return bad;
+    if (B == 0 || N == 0) return 0;
+    if (!r) return -11;
+    if (!tp) return -13;
+    if (!f) return -16;
+    if (!c) return -18;
+    const long hstride = per_series ? (long)ncomp : 0L;
+    hipLaunchKernelGGL((mean_scan_kernel<T>), dim3((unsigned)((B * ncomp + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       (long)B, (long)K, sp, lam, omega, hstride, tau, r, c);
+    if (hipGetLastError() != hipSuccess) return -1000;
+    const size_t lds = size_t(64) * size_t((sp.d + m) | 1) * sizeof(T);      // (at most 64 x 113 x 8 B = 57 KB: inside the default 64 KB)
+    hipLaunchKernelGGL((mean_eval_kernel<T>), dim3((unsigned)((B * N + 63) / 64)), dim3(64), lds, static_cast<hipStream_t>(stream),
+                       (long)B, (long)K, (long)N, sp, m, lam, omega, hstride, tau, c, a, tp, f, state);
+    return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
+// Reverse mode (the adjoint of the linear map (r, a) -> f), launch 1 of 2.  One wavefront per 64 consecutive points OF ONE SERIES
+// (the grid is B x ceil(N / 64)): a lane parks  v = exp(F delta)^T H^T g  (d values: per component g times the first row of its
+// block) and the component's g itself (ncomp values: the rows of H^T g that are not zero) in LDS, and the wave folds the lanes of
+// equal bin together as piecewise_grad_steps_kernel does: record r of block (b, q) is (bin, nv = d + ncomp sums over its lanes IN
+// LANE ORDER); cnt[b, q] records are written.  A point before the first action belongs to no bin.  No atomics.
+template <typename T>
+__global__ void __launch_bounds__(64) mean_grad_points_kernel(long K, long N, long nblk, MSpec sp, int m, const T* __restrict__ lam,
+                                                              const T* __restrict__ omega, long hstride, const T* __restrict__ tau,
+                                                              const T* __restrict__ tp, const T* __restrict__ gf,
+                                                              T* __restrict__ rec_val, int* __restrict__ rec_bin,
+                                                              int* __restrict__ rec_cnt) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    T* park = reinterpret_cast<T*>(smem_raw);
+    const int lane = threadIdx.x, d = sp.d, nv = d + sp.ncomp, pstride = nv | 1;
+    const long blk = blockIdx.x, b = blk / nblk, q = blk % nblk;
+    const long point = q * 64 + lane;
+    int bin = -1;
+    if (point < N) {
+        const long id = b * N + point;
+        const T t = tp[id];
+        bin = actions_before<T>(tau + b * K, (int)K, t) - 1;
+        if (bin >= 0) {
+            const T delta = t - tau[b * K + bin];
+            T* mine = park + lane * pstride;
+            for (int cc = 0; cc < sp.ncomp; ++cc) {
+                const int order = sp.order[cc], osc = sp.osc[cc], off = sp.off[cc];
+                const T l = order == 0 ? T(0) : lam[b * hstride + cc], w = osc ? omega[b * hstride + cc] : T(0);
+                const T g = gf[id * m + sp.out[cc]];
+                mine[d + cc] = g;
+                with_transition<T>(order, osc, l, w, delta, [&](const auto& tr) {
+                    constexpr int KK = MF_COMP_DIM(tr);
+                    for (int i = 0; i < KK; ++i) mine[off + i] = tr.A[0][i] * g;
+                });
+            }
+        }
+    }
+    __syncthreads();
+    const bool binned = bin >= 0;
+    unsigned long long remaining = __ballot(binned);
+    int slot = 0;
+    while (remaining) {                                   // (wave-uniform: one round per bin present in this block)
+        const int leader = __ffsll(remaining) - 1;
+        const int bl = __shfl(bin, leader);
+        const unsigned long long members = __ballot(binned && bin == bl);
+        for (int v = lane; v < nv; v += 64) {
+            T acc = T(0);
+            for (unsigned long long mm = members; mm; mm &= mm - 1) acc += park[(__ffsll(mm) - 1) * pstride + v];
+            rec_val[(blk * 64 + slot) * nv + v] = acc;
+        }
+        if (lane == 0) rec_bin[blk * 64 + slot] = bl;
+        remaining &= ~members;
+        ++slot;
+    }
+    if (lane == 0) rec_cnt[blk] = slot;
+}
+
+// Launch 2 of 2: one lane per (series, component).  It clears its slice of g_r (and of g_a), walks the series' blocks ONCE and adds
+// every record into its bin - O(records), in block and slot order: a fixed order, so two runs agree bit for bit - and then runs the
+// reverse recurrence  lambda_{K-1} = g_c_{K-1},  lambda_{k-1} = g_c_{k-1} + A_k^T lambda_k  in place: g_r = lambda.
+template <typename T>
+__global__ void __launch_bounds__(64) mean_grad_scan_kernel(long B, long K, long nblk, MSpec sp, const T* __restrict__ lam,
+                                                            const T* __restrict__ omega, long hstride, const T* __restrict__ tau,
+                                                            const T* __restrict__ rec_val, const int* __restrict__ rec_bin,
+                                                            const int* __restrict__ rec_cnt, T* g_r, T* g_a) {
+    const long id = (long)blockIdx.x * 64 + threadIdx.x;
+    if (id >= B * sp.ncomp) return;
+    const long b = id / sp.ncomp;
+    const int cc = (int)(id % sp.ncomp);
+    const int order = sp.order[cc], osc = sp.osc[cc], off = sp.off[cc], d = sp.d, kk = comp_states(order, osc), nv = d + sp.ncomp;
+    for (long k = 0; k < K; ++k)
+        for (int i = 0; i < kk; ++i) {
+            g_r[(b * K + k) * d + off + i] = T(0);
+            if (g_a) g_a[(b * K + k) * d + off + i] = T(0);
+        }
+    for (long q = 0; q < nblk; ++q) {
+        const long blk = b * nblk + q;
+        const int cnt = rec_cnt[blk];
+        for (int s = 0; s < cnt; ++s) {
+            const long row = (b * K + rec_bin[blk * 64 + s]) * d + off;
+            const T* rv = rec_val + (blk * 64 + s) * nv;
+            for (int i = 0; i < kk; ++i) g_r[row + i] += rv[off + i];
+            if (g_a) g_a[row] += rv[d + cc];
+        }
+    }
+    const T l = order == 0 ? T(0) : lam[b * hstride + cc], w = osc ? omega[b * hstride + cc] : T(0);
+    const T* tb = tau + b * K;
+    T cur[6];
+    for (int i = 0; i < 6; ++i) cur[i] = i < kk ? g_r[(b * K + K - 1) * d + off + i] : T(0);
+    for (long k = K - 1; k >= 1; --k) {
+        T* gk = g_r + (b * K + k - 1) * d + off;
+        with_transition<T>(order, osc, l, w, tb[k] - tb[k - 1], [&](const auto& tr) {
+            constexpr int KK = MF_COMP_DIM(tr);
+            T nxt[KK];
+            for (int jj = 0; jj < KK; ++jj) {
+                T acc = T(0);
+                for (int i = 0; i < KK; ++i) acc += tr.A[i][jj] * cur[i];
+                nxt[jj] = gk[jj] + acc;
+            }
+            for (int i = 0; i < KK; ++i) { cur[i] = nxt[i]; gk[i] = nxt[i]; }
+        });
+    }
+}
+
+// workspace of the reverse mode: per block of 64 points up to 64 records of d + ncomp values | their bins | the record count
+inline size_t mean_grad_workspace(int64_t B, int64_t N, int ncomp, int d, size_t elem) {
+    if (B <= 0 || N <= 0 || ncomp < 1 || ncomp > MAXC || d < ncomp || d > 6 * MAXC) return 0;
+    const size_t blocks = size_t(B) * size_t((N + 63) / 64);
+    return blocks * (size_t(64) * size_t(d + ncomp) * elem + 64 * sizeof(int) + sizeof(int));
+}
+
+template <typename T>
+int run_mean_grad(int64_t B, int64_t K, int64_t N, int ncomp, const int* orders, const int* osc, const T* lam, const T* omega,
+                  int per_series, const T* tau, const T* tp, int m, const int* out_map, const T* gf, T* g_r, T* g_a, void* ws,
+                  size_t ws_bytes, void* stream) {
+    MSpec sp;
+    int bad = mean_spec(B, K, N, ncomp, orders, osc, lam, omega, tau, sp);
+    if (bad) return bad;
+    bad = mean_out_map(ncomp, m, out_map, 12, sp);
+    if (bad) return bad;
+    if (B == 0) return 0;
+    if (!g_r) return -15;
+    const long hstride = per_series ? (long)ncomp : 0L;
+    const long nblk = (long)((N + 63) / 64), blocks = (long)B * nblk;
+    T* rec_val = static_cast<T*>(ws);
+    int* rec_bin = nullptr;
+    int* rec_cnt = nullptr;
+    if (N > 0) {
+        if (!tp) return -11;
+        if (!gf) return -14;
+        if (!ws) return -17;
+        if (ws_bytes < mean_grad_workspace(B, N, ncomp, sp.d, sizeof(T))) return -18;
+        const int nv = sp.d + ncomp;
+        rec_bin = reinterpret_cast<int*>(rec_val + (size_t)blocks * 64 * nv);
+        rec_cnt = rec_bin + (size_t)blocks * 64;
+        const size_t lds = size_t(64) * size_t(nv | 1) * sizeof(T);
+        hipLaunchKernelGGL((mean_grad_points_kernel<T>), dim3((unsigned)blocks), dim3(64), lds, static_cast<hipStream_t>(stream),
+                           (long)K, (long)N, nblk, sp, m, lam, omega, hstride, tau, tp, gf, rec_val, rec_bin, rec_cnt);
+        if (hipGetLastError() != hipSuccess) return -1000;
+    }
+    hipLaunchKernelGGL((mean_grad_scan_kernel<T>), dim3((unsigned)((B * ncomp + 63) / 64)), dim3(64), 0,
+                       static_cast<hipStream_t>(stream), (long)B, (long)K, nblk, sp, lam, omega, hstride, tau, rec_val, rec_bin,
+                       rec_cnt, g_r, g_a);
+    return hipGetLastError() == hipSuccess ? 0 : -1000;
+}
+
 // R^-1 = (L L^T)^-1 from the Cholesky factor of the observation covariance (KalmanFilter._r_inv, kalman_filter.py:341-348: a
 // tf.linalg.cholesky_solve against the identity).  m <= 32: one wavefront, thread j solves column j of L^-1 by forward
 // substitution, then the threads share the m^2 entries of L^-T L^-1.  ONE launch instead of the eleven small torch / rocBLAS
@@ -1086,6 +1420,36 @@ int mf_sde_piecewise_transitions_grad_f32(int64_t B, int64_t n, int ncomp, const
                                           const float* g_cholQ, float* out, void* workspace, size_t workspace_bytes, void* stream) {
     return run_pw_grad<float>(B, n, ncomp, orders, osc, nseg, change_points, lam, var, omega, per_series, t_start, dt, jitter, g_A,
                               g_cholQ, out, workspace, workspace_bytes, stream);
+}
+
+int mf_mean_response_f64(int64_t B, int64_t K, int64_t N, int ncomp, const int* orders, const int* osc, const double* lam,
+                         const double* omega, int per_series, const double* action_times, const double* r, const double* a,
+                         const double* time_points, int m, const int* out_map, double* f, double* state, double* c, void* stream) {
+    return run_mean<double>(B, K, N, ncomp, orders, osc, lam, omega, per_series, action_times, r, a, time_points, m, out_map, f, state,
+                            c, stream);
+}
+int mf_mean_response_f32(int64_t B, int64_t K, int64_t N, int ncomp, const int* orders, const int* osc, const float* lam,
+                         const float* omega, int per_series, const float* action_times, const float* r, const float* a,
+                         const float* time_points, int m, const int* out_map, float* f, float* state, float* c, void* stream) {
+    return run_mean<float>(B, K, N, ncomp, orders, osc, lam, omega, per_series, action_times, r, a, time_points, m, out_map, f, state,
+                           c, stream);
+}
+size_t mf_mean_response_grad_workspace_bytes(int64_t B, int64_t N, int ncomp, int d, int elem_size) {
+    return (elem_size == 4 || elem_size == 8) ? mean_grad_workspace(B, N, ncomp, d, (size_t)elem_size) : 0;
+}
+int mf_mean_response_grad_f64(int64_t B, int64_t K, int64_t N, int ncomp, const int* orders, const int* osc, const double* lam,
+                              const double* omega, int per_series, const double* action_times, const double* time_points, int m,
+                              const int* out_map, const double* g_f, double* g_r, double* g_a, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    return run_mean_grad<double>(B, K, N, ncomp, orders, osc, lam, omega, per_series, action_times, time_points, m, out_map, g_f, g_r,
+                                 g_a, workspace, workspace_bytes, stream);
+}
+int mf_mean_response_grad_f32(int64_t B, int64_t K, int64_t N, int ncomp, const int* orders, const int* osc, const float* lam,
+                              const float* omega, int per_series, const float* action_times, const float* time_points, int m,
+                              const int* out_map, const float* g_f, float* g_r, float* g_a, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+    return run_mean_grad<float>(B, K, N, ncomp, orders, osc, lam, omega, per_series, action_times, time_points, m, out_map, g_f, g_r,
+                                g_a, workspace, workspace_bytes, stream);
 }
 
 int mf_sde_matern_transitions_grad_f64(int64_t B, int64_t n, int ncomp, const int* orders, const double* lam, const double* var,

@@ -2,7 +2,8 @@
 ``GaussianProcessRegression`` (mirror of ``markovflow/models/gaussian_process_regression.py:29-160``, the direct caller of
 ``KalmanFilter`` in the reference).  Only what drives the hot path is mirrored: construction from ``(time_points, observations)`` and
 an SDE kernel, ``log_likelihood`` / ``loss``, the posterior state space model and ``posterior`` (prediction at new time points,
-``markovflow_amd/posterior.py``); mean functions and training loops belong to the reference's outer layers.  For plain
+``markovflow_amd/posterior.py``) and an optional mean function (``markovflow_amd/mean_function.py``), whose values are subtracted
+from the observations on every path; training loops belong to the reference's outer layers.  For plain
 Matérn components the kernel -> state space model step is fused into the Kalman sweep in both directions
 (``mf_gpr_matern_loglik_*``, ``mf_gpr_matern_loglik_grad_*``, ``mf_gpr_matern_posterior_chain_*``).
 """
@@ -118,11 +119,13 @@ class GaussianProcessRegression:
     """GP regression as a Kalman filter on the kernel's state space model (gaussian_process_regression.py:29-160)."""
 
     def __init__(self, input_data: Tuple[torch.Tensor, torch.Tensor], kernel: SDEKernel,
-                 chol_obs_covariance: Optional[torch.Tensor] = None) -> None:
+                 chol_obs_covariance: Optional[torch.Tensor] = None, mean_function=None) -> None:
         """
         :param input_data: ``(time_points [batch + [num_data]], observations [batch + [num_data, observation_dim]])``.
         :param chol_obs_covariance: ``[observation_dim, observation_dim]`` Cholesky factor of the noise covariance
             (default: identity, as in the reference).
+        :param mean_function: a ``markovflow_amd.mean_function.MeanFunction`` (default: none, a zero mean): the model is fitted to
+            the residuals ``observations - mean_function(time_points)``, evaluated at every call.
         """
         time_points, observations = input_data
         obs_dim = observations.shape[-1]
@@ -136,6 +139,15 @@ class GaussianProcessRegression:
         # float64 kernel would be read past its end)
         _lib.same_dtype_device(observations, "GaussianProcessRegression", time_points=time_points,
                                chol_obs_covariance=chol_obs_covariance)
+        if mean_function is not None:
+            if not callable(mean_function):
+                raise TypeError("mean_function must be a markovflow_amd.mean_function.MeanFunction")
+            mean_dim = getattr(mean_function, "output_dim", None)
+            if mean_dim is None:
+                mean_dim = mean_function(time_points).shape[-1]
+            if mean_dim != obs_dim:
+                raise ValueError(f"mean_function has output dimension {mean_dim}, the observations have {obs_dim}")
+        self._mean_function = mean_function
         self._kernel = kernel
         self._time_points = time_points
         self._observations = observations
@@ -154,12 +166,27 @@ class GaussianProcessRegression:
         return self._kernel
 
     @property
+    def mean_function(self):
+        return self._mean_function
+
+    def _residuals(self) -> torch.Tensor:
+        """``observations - mean_function(time_points)`` (gaussian_process_regression.py:112-124); without a mean function the
+        observations themselves: no launch, no copy."""
+        if self._mean_function is None:
+            return self._observations
+        return self._observations - self._mean_function(self._time_points)
+
+    @property
     def _kalman(self) -> KalmanFilter:
-        """gaussian_process_regression.py:112-124 (no mean function: residuals = observations)."""
+        """gaussian_process_regression.py:112-124."""
+        return self._kalman_on(self._residuals())
+
+    def _kalman_on(self, residuals: torch.Tensor) -> KalmanFilter:
+        """``_kalman`` on residuals that the caller has formed already (the mean function is evaluated once per evaluation)."""
         return KalmanFilter(
             state_space_model=self._kernel.state_space_model(self._time_points),
             emission_model=self._kernel.generate_emission_model(self._time_points),
-            observations=self._observations,
+            observations=residuals,
             chol_obs_covariance=self._chol_obs_covariance,
         )
 
@@ -182,20 +209,20 @@ class GaussianProcessRegression:
 
     fused_backward = True    # set False to force the materialised route whenever a gradient is required
 
-    def _fused_differentiable(self, comps, multi, rows, m, d) -> Optional[torch.Tensor]:
+    def _fused_differentiable(self, comps, multi, rows, m, d, residuals) -> Optional[torch.Tensor]:
         """The fused route when a hyper-parameter or the noise requires a gradient: ``_GprFusedLogLik`` (forward AND backward with the
         kernel -> state space model step fused; d <= 6: one or two components, one output, chains of more than 64 points).  ``None``:
         the materialised, differentiable route runs (row signatures, observations that require a gradient, short chains)."""
         n = self._time_points.shape[-1]
         if not _all_matern(comps):
             return None
-        if (not self.fused_backward or rows or multi or m != 1 or d > 6 or n <= 64 or self._observations.requires_grad
+        if (not self.fused_backward or rows or multi or m != 1 or d > 6 or n <= 64 or residuals.requires_grad
                 or self._time_points.requires_grad):
             return None
         dtype, dev = self._observations.dtype, self._observations.device
         batch = tuple(self._time_points.shape[:-1])
         t = self._time_points.reshape(-1, n).to(dtype).contiguous()
-        y = self._observations.reshape(-1, n).contiguous()
+        y = residuals.reshape(-1, n).contiguous()
         bsz = t.shape[0]
         nt = n - 1
         if bsz == 0 or _gpr_partition(bsz, nt, self._chunks)[1] < 2:
@@ -216,9 +243,10 @@ class GaussianProcessRegression:
         const = -0.5 * math.log(2 * math.pi) * n * m + 0.5 * n * log_det_rinv
         return (out + const).reshape(batch)
 
-    def _fused_log_likelihood_per_series(self) -> Optional[torch.Tensor]:
+    def _fused_log_likelihood_per_series(self, residuals: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
         """Per-series log-likelihood through ``mf_gpr_matern_loglik_*`` (kernel -> SSM generation fused into the Kalman
-        sweep: 16 bytes per step instead of the materialised tensors); ``None`` when the kernel / shapes are not covered."""
+        sweep: 16 bytes per step instead of the materialised tensors); ``None`` when the kernel / shapes are not covered.
+        ``residuals``: ``_residuals()`` where the caller has formed them already."""
         comps = self._kernel._components()
         multi = isinstance(self._kernel, IndependentMultiOutput)
         m = self._observations.shape[-1]
@@ -230,13 +258,15 @@ class GaussianProcessRegression:
         rows = 7 <= d <= 15 and len(comps) <= 15 and (m == len(comps) <= (8 if d >= 10 else 4) if multi else m == 1)
         if not self.fused or not self._observations.is_cuda or not (rows or (not multi and len(comps) <= 2 and m == 1)):
             return None
+        if residuals is None:
+            residuals = self._residuals()
         if torch.is_grad_enabled() and (self._kernel._needs_grad() or self._chol_obs_covariance.requires_grad
-                                        or self._observations.requires_grad):
-            return self._fused_differentiable(comps, multi, rows, m, d)
+                                        or residuals.requires_grad):
+            return self._fused_differentiable(comps, multi, rows, m, d, residuals)
         batch = tuple(self._time_points.shape[:-1])
         n, dtype, dev = self._time_points.shape[-1], self._observations.dtype, self._observations.device
         t = self._time_points.reshape(-1, n).to(dtype).contiguous()
-        y = self._observations.reshape(-1, n, m).contiguous()
+        y = residuals.reshape(-1, n, m).contiguous()
         bsz = t.shape[0]
         if bsz == 0 or n < 1:
             return None
@@ -290,10 +320,11 @@ class GaussianProcessRegression:
 
     def log_likelihood(self) -> torch.Tensor:
         """``log p(y | ϑ)`` summed over the batch (gaussian_process_regression.py:150-160)."""
-        per_series = self._fused_log_likelihood_per_series()
+        residuals = self._residuals()
+        per_series = self._fused_log_likelihood_per_series(residuals)
         if per_series is not None:
             return _lib.checked(torch.sum(per_series))
-        return self._kalman.log_likelihood()
+        return self._kalman_on(residuals).log_likelihood()
 
     def loss(self) -> torch.Tensor:
         return -self.log_likelihood()
@@ -306,9 +337,10 @@ class GaussianProcessRegression:
             kernel=self._kernel,
             conditioning_time_points=self._time_points,
             chol_obs_covariance=self._chol_obs_covariance,
+            mean_function=self._mean_function,
         )
 
-    def _fused_posterior_chain(self) -> Optional[StateSpaceModel]:
+    def _fused_posterior_chain(self, residuals: Optional[torch.Tensor] = None) -> Optional[StateSpaceModel]:
         """The posterior chain with the kernel -> state space model step fused (``mf_gpr_matern_loglik_*`` on an explicit partition
         for its chunk summaries, then ``mf_gpr_matern_posterior_chain_*``): no prior tensors in memory.  ``None`` where the fused
         kernels do not apply (row signatures, several outputs, d > 6, short chains, gradients required)."""
@@ -324,7 +356,11 @@ class GaussianProcessRegression:
         dtype, dev = self._observations.dtype, self._observations.device
         batch = tuple(self._time_points.shape[:-1])
         t = self._time_points.reshape(-1, n).to(dtype).contiguous()
-        y = self._observations.reshape(-1, n).contiguous()
+        if residuals is None:
+            residuals = self._residuals()
+        if self._mean_function is not None and torch.is_grad_enabled() and residuals.requires_grad:
+            return None                     # a learnable mean function: the materialised chain carries its gradient
+        y = residuals.reshape(-1, n).contiguous()
         bsz, nt = t.shape[0], n - 1
         if bsz == 0 or bsz >= 2048:
             return None
@@ -377,5 +413,6 @@ class GaussianProcessRegression:
 
     def posterior_state_space_model(self) -> StateSpaceModel:
         """The smoothed chain on the training time points (what the reference's ``posterior`` is built from, :138-144)."""
-        fused = self._fused_posterior_chain()
-        return fused if fused is not None else self._kalman.posterior_state_space_model()
+        residuals = self._residuals()
+        fused = self._fused_posterior_chain(residuals)
+        return fused if fused is not None else self._kalman_on(residuals).posterior_state_space_model()

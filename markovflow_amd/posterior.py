@@ -9,7 +9,8 @@ conditional statistics + projection + marginalisation run in ONE HIP kernel (``m
 new point).  ``sample_state_trajectories`` / ``sample_state`` / ``sample_f`` (posterior.py:45-138,260-412) draw joint samples by
 Matheron's rule, as the reference does: a joint prior sample at the new and the conditioning points (the kernel's state space
 model on the merged, sorted time points - generated and propagated by the HIP kernels), a posterior sample at the conditioning
-points, and the local conditional-mean correction.  Mean functions are not mirrored (zero mean).
+points, and the local conditional-mean correction.  An optional mean function (``markovflow_amd/mean_function.py``) is added back by
+``predict_f``, ``predict_y`` and ``sample_f``.
 """
 from typing import Optional, Sequence, Tuple, Union
 
@@ -25,10 +26,12 @@ APPROX_INF = 1e10   # markovflow/base.py:46: the "time" of the stationary prior 
 class ConditionalProcess:
     """Posterior process built from the marginals ``q(s(Z))`` and the prior conditional ``p(s(.)|s(Z))`` (posterior.py:160-258)."""
 
-    def __init__(self, posterior_dist: GaussMarkovDistribution, kernel: SDEKernel, conditioning_time_points: torch.Tensor) -> None:
+    def __init__(self, posterior_dist: GaussMarkovDistribution, kernel: SDEKernel, conditioning_time_points: torch.Tensor,
+                 mean_function=None) -> None:
         self.gauss_markov_model = posterior_dist
         self.kernel = kernel
         self.conditioning_time_points = conditioning_time_points
+        self.mean_function = mean_function      # a markovflow_amd.mean_function.MeanFunction, or None (zero mean)
 
     def predict_state(self, new_time_points: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """
@@ -129,16 +132,18 @@ class ConditionalProcess:
         return self.sample_state_trajectories(new_time_points, sample_shape, input_data=input_data)[0]
 
     def sample_f(self, new_time_points: torch.Tensor, sample_shape, *, input_data=None) -> torch.Tensor:
-        """Function samples (projected states), ``sample_shape + batch + [num_new, output_dim]`` (posterior.py:376-412; zero
-        mean function)."""
+        """Function samples (projected states plus the mean function), ``sample_shape + batch + [num_new, output_dim]``
+        (posterior.py:376-412)."""
         states = self.sample_state(new_time_points, sample_shape)
-        return self.kernel.generate_emission_model(new_time_points).project_state_to_f(states)
+        f = self.kernel.generate_emission_model(new_time_points).project_state_to_f(states)
+        return f if self.mean_function is None else f + self.mean_function(new_time_points)
 
     def predict_f(self, new_time_points: torch.Tensor, full_output_cov: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
         """Marginal function values at ``new_time_points``: means ``batch + [num_new, output_dim]`` and variances (or full
-        output covariances) - posterior.py:231-258 (zero mean function)."""
+        output covariances), the mean function added to the means - posterior.py:231-258."""
         emission = self.kernel.generate_emission_model(new_time_points)
-        return emission.project_state_marginals_to_f(*self.predict_state(new_time_points), full_output_cov=full_output_cov)
+        f_mean, f_cov = emission.project_state_marginals_to_f(*self.predict_state(new_time_points), full_output_cov=full_output_cov)
+        return (f_mean if self.mean_function is None else f_mean + self.mean_function(new_time_points)), f_cov
 
 
 def _predict_state_dense(idx, a_mt, q_mt, a_tp, q_tp, means, covs, sub, m0, p0):
@@ -175,8 +180,8 @@ class AnalyticPosteriorProcess(ConditionalProcess):
     """Posterior process of a model with an analytic (Gaussian) likelihood: adds ``predict_y`` (posterior.py:416-470)."""
 
     def __init__(self, posterior_dist: GaussMarkovDistribution, kernel: SDEKernel, conditioning_time_points: torch.Tensor,
-                 chol_obs_covariance: Optional[torch.Tensor] = None) -> None:
-        super().__init__(posterior_dist, kernel, conditioning_time_points)
+                 chol_obs_covariance: Optional[torch.Tensor] = None, mean_function=None) -> None:
+        super().__init__(posterior_dist, kernel, conditioning_time_points, mean_function)
         self._chol_obs_covariance = chol_obs_covariance
 
     def predict_y(self, new_time_points: torch.Tensor, full_output_cov: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
