@@ -1175,6 +1175,60 @@ int mf_lik_st_cvi_site_update_f32(int64_t B, int64_t N, int64_t S, int Ms, int t
                                   size_t workspace_bytes, float learning_rate, float* nat1, float* nat2, float* ve_sum, float* fmu,
                                   float* fvar, void* stream);
 
+/*
+ * Non-linear SDEs  dx = f(x) dt + L dB  (markovflow/sde/sde.py, sde_utils.py; csrc/mf_nlsde.hip).  `drift`: 0 Ornstein-Uhlenbeck,
+ * f(x) = -lambda x, params [lambda]; 1 double well, f(x) = 4 x (1 - x^2), no params (params may be NULL).  Both act element-wise
+ * on the state.  `params`, `chol_l` of the simulation, `nodes` and `weights` are HOST arrays of doubles in both precisions.
+ *
+ * Euler-Maruyama: B paths of dimension 1 <= d <= 4 on a strictly increasing time_grid [T] whose first entry is the start time;
+ * x0 [B, d], noise [B, T - 1, d] standard normal draws, chol_l the d (d + 1) / 2 entries of the lower triangle of L row by row;
+ *   out [B, T, d]:  out[:, 0] = x0 (the same bits),  out[:, k + 1] = out[:, k] + f(out[:, k]) dt_k + sqrt(dt_k) L noise[:, k],
+ * dt_k = time_grid[k + 1] - time_grid[k].  One launch for all T - 1 steps; no atomics, no workspace.  T = 1 writes x0 only.
+ * Returns 0, -(position of the offending argument: 1 B, 2 T < 1, 3 d < 1, 4 drift, 5 params, 6 ... 10 a NULL array), -100 for
+ * d > 4, or -1000 (launch failed); B = 0 returns 0 without a launch.
+ */
+int mf_nlsde_euler_maruyama_f64(int64_t B, int64_t T, int d, int drift, const double* params, const double* chol_l, const double* x0,
+                                const double* time_grid, const double* noise, double* out, void* stream);
+int mf_nlsde_euler_maruyama_f32(int64_t B, int64_t T, int d, int drift, const double* params, const double* chol_l, const float* x0,
+                                const float* time_grid, const float* noise, float* out, void* stream);
+/*
+ * Linearisation along a Gaussian path, state dimension 1 (sde_utils.py:107-158): times [N + 1], mean and var [B, N] the marginals
+ * N(m_k, S_k) of the path, chol_l the scalar L, an nq <= 32 point Gauss-Hermite rule as for mf_lik_variational_expectations.  With
+ * E f = sum_i w_i f(x_i), E f' = sum_i w_i f'(x_i), x_i = m_k + sqrt(2 S_k) node_i, w_i = weights_i / sqrt pi, dt_k = times[k + 1] - times[k]:
+ *   A [B, N] = 1 + E f' dt_k,   b [B, N] = (E f - E f' m_k) dt_k,   cholQ [B, N] = L sqrt(dt_k)
+ * - the element counts of the [B, N, 1, 1], [B, N, 1], [B, N, 1, 1] tensors of a state space model.  A point with S_k <= 0 or NaN
+ * gets NaN in its own A and b.  Returns 0, -(position: 1 B, 2 N, 3 drift, 4 params, 6 nq, 7 nodes, 8 weights, 9 ... 14 a NULL
+ * array) or -1000; B = 0 or N = 0 returns 0 without a launch.
+ */
+int mf_nlsde_linearize_f64(int64_t B, int64_t N, int drift, const double* params, double chol_l, int nq, const double* nodes,
+                           const double* weights, const double* times, const double* mean, const double* var, double* A, double* b,
+                           double* cholQ, void* stream);
+int mf_nlsde_linearize_f32(int64_t B, int64_t N, int drift, const double* params, float chol_l, int nq, const double* nodes,
+                           const double* weights, const float* times, const float* mean, const float* var, float* A, float* b,
+                           float* cholQ, void* stream);
+/*
+ * Expected squared drift difference along a Gaussian path, state dimension 1 (sde_utils.py:161-228): mean, var, A, b [B, N];
+ * per point, with r_i = A_k x_i + b_k - f(x_i) at the nodes x_i above,
+ *   v_k = scale / 2 sum_i w_i r_i^2                                   scale = dt / q
+ *   g_b = scale sum_i w_i r_i,   g_A = scale sum_i w_i r_i x_i,   g_m = scale sum_i w_i r_i (A_k - f'(x_i)),
+ *   g_S = scale sum_i w_i r_i (A_k - f'(x_i)) node_i / sqrt(2 S_k)    - the exact derivatives of the discretised v_k;
+ * sum [B] = sum_k v_k (required); g_m, g_S, g_A, g_b [B, N], each may be NULL.  The sum runs in a fixed order in double in both
+ * precisions - 256 points to one partial by a fixed tree, a series' partials ascending - without floating-point atomics: two calls
+ * agree bit for bit, and so does a series alone and inside a batch.  A point with S_k <= 0 or NaN gets NaN in its own four
+ * derivatives and makes the sum of ITS series NaN.  N = 0 writes zeros.  workspace: mf_nlsde_drift_difference_workspace_bytes
+ * bytes of device memory, 8-byte aligned.  Returns 0, -(position: 1 B, 2 N, 3 drift, 4 params, 5 nq, 6 nodes, 7 weights, 9 ... 12 a
+ * NULL input, 13 a NULL sum, 18 a NULL workspace, 19 one that is too small or misaligned) or -1000; B = 0 returns 0 without a launch.
+ */
+size_t mf_nlsde_drift_difference_workspace_bytes(int64_t B, int64_t N);
+int mf_nlsde_drift_difference_f64(int64_t B, int64_t N, int drift, const double* params, int nq, const double* nodes,
+                                  const double* weights, double scale, const double* mean, const double* var, const double* A,
+                                  const double* b, double* sum, double* g_m, double* g_S, double* g_A, double* g_b, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+int mf_nlsde_drift_difference_f32(int64_t B, int64_t N, int drift, const double* params, int nq, const double* nodes,
+                                  const double* weights, float scale, const float* mean, const float* var, const float* A,
+                                  const float* b, float* sum, float* g_m, float* g_S, float* g_A, float* g_b, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

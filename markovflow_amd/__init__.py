@@ -17,7 +17,7 @@ from .kalman_filter import (
     UnivariateGaussianSitesNat,
 )
 from .state_space_model import StateSpaceModel, state_space_model_from_covariances
-from . import conditionals, distributed, kernels, likelihoods, mean_function, models, spatial_kernels, ssm_gaussian_transformations, ssm_natgrad
+from . import conditionals, distributed, kernels, likelihoods, mean_function, models, sde, spatial_kernels, ssm_gaussian_transformations, ssm_natgrad
 from .kernels import (Constant, HarmonicOscillator, IndependentMultiOutput, LatentExponentiallyGenerated, Matern12, Matern32, Matern52, NonStationaryKernel,
                       PiecewiseKernel, Product, SDEKernel, SparseSpatioTemporalKernel, StationaryKernel, Sum)
 from .likelihoods import Bernoulli, Gaussian, Likelihood, Poisson, StudentT
@@ -25,6 +25,8 @@ from .mean_function import ImpulseMeanFunction, LinearMeanFunction, MeanFunction
 from .models import (CVIGaussianProcess, GaussianProcessRegression, ImportanceWeightedVI, PowerExpectationPropagation,
                      SparseCVIGaussianProcess, SparsePowerExpectationPropagation, SparseVariationalGaussianProcess,
                      SpatioTemporalSparseCVI, SpatioTemporalSparseVariational, VariationalGaussianProcess)
+from .sde import (SDE, DoubleWellSDE, LinearDrift, OrnsteinUhlenbeckSDE, euler_maruyama, linearize_sde,
+                  squared_drift_difference_along_Gaussian_path)
 from .ssm_natgrad import SSMNaturalGradient
 from .posterior import AnalyticPosteriorProcess, ConditionalProcess, ImportanceWeightedPosteriorProcess
 from ._lib import MarkovflowAmdError, check_errors, errors_as_nan, set_synchronous_checks
@@ -42,4 +44,6 @@ __all__ = [
     "VariationalGaussianProcess", "spatial_kernels", "SparseSpatioTemporalKernel", "SpatioTemporalSparseVariational", "SpatioTemporalSparseCVI",
     "NonStationaryKernel", "PiecewiseKernel", "LatentExponentiallyGenerated",
     "mean_function", "MeanFunction", "ZeroMeanFunction", "LinearMeanFunction", "ImpulseMeanFunction", "StepMeanFunction",
+    "sde", "SDE", "OrnsteinUhlenbeckSDE", "DoubleWellSDE", "LinearDrift", "euler_maruyama", "linearize_sde",
+    "squared_drift_difference_along_Gaussian_path",
 ]

@@ -99,6 +99,10 @@ _SIGS = {
                                       _i64, _vp, _vp, _vp, _sz, "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_st_cvi_site_update": (_int, [_i64, _i64, _i64, _int, _int, _int, _hd, _int, _hd, _hd, _vp, "Tp", "Tp", "Tp", "Tp", "Tp",
                                          "Tp", _i64, _vp, _vp, _vp, _sz, "T", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
+    "mf_nlsde_euler_maruyama": (_int, [_i64, _i64, _int, _int, _hd, _hd, "Tp", "Tp", "Tp", "Tp", _vp]),
+    "mf_nlsde_linearize": (_int, [_i64, _i64, _int, _hd, "T", _int, _hd, _hd, "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
+    "mf_nlsde_drift_difference": (_int, [_i64, _i64, _int, _hd, _int, _hd, _hd, "T", "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", "Tp",
+                                         "Tp", _vp, _sz, _vp]),
 }
 _PLAIN = {
     "mf_version": (_int, []),
@@ -135,6 +139,7 @@ _PLAIN = {
     "mf_lik_dense_expectations_workspace_bytes": (_sz, [_i64, _i64, _int]),
     "mf_lik_st_expectations_workspace_bytes": (_sz, [_i64, _int, _int, _int]),
     "mf_lik_st_cvi_site_update_workspace_bytes": (_sz, [_i64, _int, _int, _int]),
+    "mf_nlsde_drift_difference_workspace_bytes": (_sz, [_i64, _i64]),
 }
 
 _lib = None
