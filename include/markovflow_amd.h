@@ -945,6 +945,59 @@ int mf_lik_sparse_expectations_f32(int64_t B, int64_t N, int64_t S, int two_d, i
                                    size_t workspace_bytes, float* ve_sum, float* g_mean, float* g_cov, void* stream);
 
 /*
+ * The data term of the SVGP ELBO for a likelihood with SEVERAL latent functions per observation, and its adjoint onto the pair
+ * marginals (markovflow/models/sparse_variational.py:149-192 with markovflow/likelihoods/mutlistage_likelihood.py underneath;
+ * csrc/mf_lik.hip).  B, N, S, two_d, the rule, seg_offsets, y, pair_mean, pair_cov, the tile table, the workspace and the three
+ * outputs as for mf_lik_sparse_expectations_*; every point carries L = latent_dim DENSE projections of the pair,
+ *   w [B, N, L, 2d]   row l: H_l P_k        c [B, N, L]   H_l T_k H_l^T (the diagonal of the output covariance)
+ * Per point k of segment s and latent l:  mu_l = w_kl . m_s,  s2_l = c_kl + w_kl^T S_s w_kl;  (ve, gm_l, gv_l) of the likelihood
+ * at (mu, s2, y_k);  per segment, over the points in ascending order and within a point over the latents in ascending order,
+ *   ve_sum = sum_k ve_k      g_mean = sum_k sum_l gm_kl w_kl      g_cov = sum_k sum_l gv_kl w_kl w_kl^T
+ * lik = 4, latent_dim = 3 is the multi-stage likelihood (no parameters: params is not read), with the Bernoulli's probit link and
+ * the Poisson's exp link:  y == 0: B1(F0);  y == 1: B0(F0) + B1(F1);  y >= 2: B0(F0) + B0(F1) + Poisson(y - 2 | exp F2);  any other
+ * y (a fraction, a negative number, NaN): exactly 0.  B1 = log sigma and B0 = log(1 - sigma) by the nq-point rule, the Poisson term
+ * in closed form (float32: the link inside B1 / B0 is evaluated from its small side, 0.5 erfc(|f| / sqrt 2), so that the tails
+ * keep their relative accuracy).  A latent that the point's branch does not read has gm = gv = 0 and its s2 is not examined; one that it reads
+ * with s2 <= 0 or NaN makes the three outputs of the point's segment NaN.  Stages that are not read are not evaluated.
+ * Pass 1 is one wavefront per tile of 64 points (LDS: 64 rows of L 2d + 1 elements, the pair marginal, 2 L + 1 rows of 64 values:
+ * 34480 B at 2d = 18 in float64); the workspace row and pass 2 are those of mf_lik_sparse_expectations_*, and so is the size:
+ * mf_lik_sparse_multi_expectations_workspace_bytes(num_tiles, two_d, sizeof(T)).  g_mean and g_cov BOTH NULL: the value only (the
+ * same bits).  No floating-point atomics: the same bits on every launch and for a series alone or inside a batch.  The tile table
+ * is clamped on the device, not validated.  No allocation, no synchronisation.
+ * Returns 0, -(position of the offending argument in THIS signature: 1 B, 2 N, 3 S, 8 nq, 9 nodes, 10 weights, 11 ... 16 a NULL
+ * input, 17 num_tiles negative, above 2^31 - 1 or non-zero for N = 0, 18 / 19 a NULL table, 20 a NULL workspace, 21 a workspace
+ * that is too small, 23 / 24 one of g_mean / g_cov NULL without the other), -101 for a (two_d, latent_dim, lik) that is not
+ * instantiated - two_d in 6, 8, ..., 18 with latent_dim = 3 and lik = 4 are - or -1000 (launch failed).  Nothing is launched on an
+ * error, for B = 0, or when every output is NULL.
+ */
+size_t mf_lik_sparse_multi_expectations_workspace_bytes(int64_t num_tiles, int two_d, int elem_size);
+int mf_lik_sparse_multi_expectations_f64(int64_t B, int64_t N, int64_t S, int two_d, int latent_dim, int lik, const double* params,
+                                         int nq, const double* nodes, const double* weights, const int64_t* seg_offsets,
+                                         const double* w, const double* c, const double* y, const double* pair_mean,
+                                         const double* pair_cov, int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile,
+                                         void* workspace, size_t workspace_bytes, double* ve_sum, double* g_mean, double* g_cov,
+                                         void* stream);
+int mf_lik_sparse_multi_expectations_f32(int64_t B, int64_t N, int64_t S, int two_d, int latent_dim, int lik, const double* params,
+                                         int nq, const double* nodes, const double* weights, const int64_t* seg_offsets,
+                                         const float* w, const float* c, const float* y, const float* pair_mean,
+                                         const float* pair_cov, int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile,
+                                         void* workspace, size_t workspace_bytes, float* ve_sum, float* g_mean, float* g_cov,
+                                         void* stream);
+
+/*
+ * The multi-stage likelihood's variational expectations, element-wise (csrc/mf_lik.hip): a lane per point, fmu, fvar, g_mu and
+ * g_var [N, 3], y and ve [N]; the formulas and the domain rule are those of mf_lik_sparse_multi_expectations_* (a point whose
+ * branch reads a latent with fvar <= 0 or NaN gets NaN in ve and in that latent's two derivatives).  Any output may be NULL.
+ * Returns 0, -(position: 1 N, 2 nq, 3 nodes, 4 weights, 5 ... 7 a NULL input) or -1000 (launch failed).
+ */
+int mf_lik_multistage_variational_expectations_f64(int64_t N, int nq, const double* nodes, const double* weights, const double* fmu,
+                                                   const double* fvar, const double* y, double* ve, double* g_mu, double* g_var,
+                                                   void* stream);
+int mf_lik_multistage_variational_expectations_f32(int64_t N, int nq, const double* nodes, const double* weights, const float* fmu,
+                                                   const float* fvar, const float* y, float* ve, float* g_mu, float* g_var,
+                                                   void* stream);
+
+/*
  * The segmented site update of the sparse power-EP model (markovflow/models/sparse_pep.py:316-487; csrc/mf_lik.hip): B, N, S,
  * two_d, the likelihood, the rule, seg_offsets, w, c, y, the tile table and the workspace as for mf_lik_sparse_expectations_*;
  * alpha in (0, 1] is the power, lr in [0, 1] the damping.  The workspace row has the width of that entry point's, so its size is

@@ -20,7 +20,7 @@ from .state_space_model import StateSpaceModel, state_space_model_from_covarianc
 from . import conditionals, distributed, kernels, likelihoods, mean_function, models, sde, spatial_kernels, ssm_gaussian_transformations, ssm_natgrad
 from .kernels import (Constant, HarmonicOscillator, IndependentMultiOutput, LatentExponentiallyGenerated, Matern12, Matern32, Matern52, NonStationaryKernel,
                       PiecewiseKernel, Product, SDEKernel, SparseSpatioTemporalKernel, StationaryKernel, Sum)
-from .likelihoods import Bernoulli, Gaussian, Likelihood, Poisson, StudentT
+from .likelihoods import Bernoulli, Gaussian, Likelihood, MultiStageLikelihood, Poisson, StudentT
 from .mean_function import ImpulseMeanFunction, LinearMeanFunction, MeanFunction, StepMeanFunction, ZeroMeanFunction
 from .models import (CVIGaussianProcess, GaussianProcessRegression, ImportanceWeightedVI, PowerExpectationPropagation,
                      SparseCVIGaussianProcess, SparsePowerExpectationPropagation, SparseVariationalGaussianProcess,
@@ -38,7 +38,7 @@ __all__ = [
     "state_space_model_from_covariances", "conditionals", "distributed", "kernels", "models", "ssm_gaussian_transformations", "SDEKernel", "StationaryKernel", "Matern12", "Matern32",
     "Matern52", "Sum", "IndependentMultiOutput", "Constant", "HarmonicOscillator", "Product", "GaussianProcessRegression", "AnalyticPosteriorProcess", "ConditionalProcess",
     "MarkovflowAmdError", "check_errors", "errors_as_nan", "set_synchronous_checks",
-    "likelihoods", "Likelihood", "Gaussian", "Bernoulli", "Poisson", "StudentT", "CVIGaussianProcess", "PowerExpectationPropagation",
+    "likelihoods", "Likelihood", "Gaussian", "Bernoulli", "Poisson", "StudentT", "MultiStageLikelihood", "CVIGaussianProcess", "PowerExpectationPropagation",
     "SparseCVIGaussianProcess", "SparseVariationalGaussianProcess", "SSMNaturalGradient", "ssm_natgrad",
     "SparsePowerExpectationPropagation", "ImportanceWeightedVI", "ImportanceWeightedPosteriorProcess",
     "VariationalGaussianProcess", "spatial_kernels", "SparseSpatioTemporalKernel", "SpatioTemporalSparseVariational", "SpatioTemporalSparseCVI",

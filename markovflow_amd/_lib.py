@@ -88,6 +88,9 @@ _SIGS = {
                                       "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_sparse_expectations": (_int, [_i64, _i64, _i64, _int, _int, _hd, _int, _hd, _hd, _vp, "Tp", "Tp", "Tp", "Tp", "Tp", _i64,
                                    _vp, _vp, _vp, _sz, "Tp", "Tp", "Tp", _vp]),
+    "mf_lik_sparse_multi_expectations": (_int, [_i64, _i64, _i64, _int, _int, _int, _hd, _int, _hd, _hd, _vp, "Tp", "Tp", "Tp", "Tp", "Tp",
+                                         _i64, _vp, _vp, _vp, _sz, "Tp", "Tp", "Tp", _vp]),
+    "mf_lik_multistage_variational_expectations": (_int, [_i64, _int, _hd, _hd, "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_sparse_pep_site_update": (_int, [_i64, _i64, _i64, _int, _int, _hd, _int, _hd, _hd, "T", "T", _vp, "Tp", "Tp", "Tp", "Tp",
                                       "Tp", "Tp", _i64, _vp, _vp, _vp, _sz, "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_iw_log_weights": (_int, [_i64, _i64, _i64, _int, _i64, _int, _hd, _vp, "Tp", "Tp", "Tp", "Tp", "Tp", _i64, _vp, _vp, _vp,
@@ -135,6 +138,7 @@ _PLAIN = {
     "mf_sde_leg_transitions_grad_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
     "mf_mean_response_grad_workspace_bytes": (_sz, [_i64, _i64, _int, _int, _int]),
     "mf_lik_sparse_expectations_workspace_bytes": (_sz, [_i64, _int, _int]),
+    "mf_lik_sparse_multi_expectations_workspace_bytes": (_sz, [_i64, _int, _int]),
     "mf_lik_iw_log_weights_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
     "mf_lik_dense_expectations_workspace_bytes": (_sz, [_i64, _i64, _int]),
     "mf_lik_st_expectations_workspace_bytes": (_sz, [_i64, _int, _int, _int]),
@@ -254,6 +258,8 @@ def check(rc: int, what: str):
             f"log_likelihood up to {load().mf_max_state_dim_f32_loglik()} in float32, "
             f"{load().mf_max_state_dim_f64_loglik()} in float64)"
         )
+    if rc == -101:
+        raise NotImplementedError(f"{what}: this signature is not instantiated in this build (see include/markovflow_amd.h)")
     if rc == -1000:
         raise MarkovflowAmdError(f"{what}: kernel launch failed")
     raise ValueError(f"{what}: invalid argument #{-rc} (see include/markovflow_amd.h)")

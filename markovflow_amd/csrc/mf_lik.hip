@@ -324,6 +324,221 @@ __global__ void __launch_bounds__(256) sparse_expect_reduce_kernel(long num_tile
     }
 }
 
+// ---- the multi-stage likelihood (markovflow/likelihoods/mutlistage_likelihood.py): three latents per point, one observation -----
+// A decision tree over the latents: y == 0 reads latent 0 (log sigma), y == 1 latents 0 (log(1 - sigma)) and 1 (log sigma), y >= 2
+// latents 0 and 1 (log(1 - sigma) each) and 2 (Poisson of y - 2); sigma is the Bernoulli's probit link, jitter included.  Any other
+// y - a fraction, a negative number, NaN - reads nothing and contributes exactly 0.  A latent that is not read has derivative 0
+// and its variance is not looked at; one that is read outside the domain (s2 <= 0 or NaN) makes the value and its own two
+// derivatives NaN.  Only the stages that are read are evaluated: one quadrature for y == 0, two otherwise, plus the closed form
+// (bernoulli_stage below; the Poisson stage is expectations<T, 2>).
+// The value is summed over the latents in ascending order.
+constexpr int MULTI_L = 3;         // latents per point
+constexpr int LIK_MULTISTAGE = 4;  // the likelihood id of the multi-latent entry points
+
+__device__ __forceinline__ float m_erfc(float x) { return erfcf(x); }
+__device__ __forceinline__ double m_erfc(double x) { return erfc(x); }
+
+// One Bernoulli stage: the nq-point expectation of log sigma(f) (hit) or log(1 - sigma(f)) (miss) with its two derivatives, s2 > 0.
+// The formulas are expectations<T, 1>'s with y = 1 or 0; the link is evaluated from its SMALL side, 0.5 erfc(|u|), u = f / sqrt 2:
+// sigma = small for u < 0 and 1 - small otherwise, 1 - sigma the other way round.  1 + erf(u) and 1 - sigma cancel in the tails,
+// where an erf good to an ulp of 1 leaves the quotient p' / sigma good to 1e-5 only in float32 (sigma is 1e-3 there, the jitter);
+// a point of this likelihood reads up to two such stages, and the sums of the float32 kernel then miss what the same formulas give
+// with a correctly rounded erf by more than the single-latent kernels do.  erfc keeps the small side to an ulp of ITSELF.
+// Used in float32 only.  In float64 the same cancellation costs 1e-13, far below what a model resolves, and the stage is
+// expectations<T, 1>: what the Bernoulli kernels, the torch route and the tests' closed forms evaluate, operation for operation.
+template <typename T>
+__device__ __forceinline__ void bernoulli_stage(const Rule<T>& q, T mu, T s2, bool hit, T& ve, T& gm, T& gv) {
+    constexpr T JIT = T(1e-3), INV_SQRT2 = T(0.70710678118654752440084436210485), INV_SQRT_2PI = T(0.3989422804014326779399460599343);
+    const T sd = m_sqrt(T(2) * s2);
+    T a0 = T(0), a1 = T(0), a2 = T(0);
+    for (int i = 0; i < q.nq; ++i) {              // wavefront-uniform: q lives in the kernel arguments
+        const T x = q.x[i], w = q.w[i];
+        const T f = mu + sd * x, u = f * INV_SQRT2;
+        const T small = T(0.5) * m_erfc(u < T(0) ? -u : u) * (T(1) - T(2) * JIT) + JIT;
+        const T pr = (u < T(0)) == hit ? small : T(1) - small;      // sigma for a hit, 1 - sigma for a miss
+        const T dp = (T(1) - T(2) * JIT) * INV_SQRT_2PI * m_exp(T(-0.5) * f * f);
+        const T dl = hit ? dp / pr : -dp / pr;
+        a0 += w * m_log(pr);
+        a1 += w * dl;
+        a2 += w * dl * x;
+    }
+    ve = a0;
+    gm = a1;
+    gv = a2 / sd;
+}
+
+template <typename T>
+__device__ __forceinline__ void multistage_expectations(const Rule<T>& q, T y, const T (&mu)[MULTI_L], const T (&s2)[MULTI_L], T& ve,
+                                                        T (&gm)[MULTI_L], T (&gv)[MULTI_L]) {
+    const Par<T> none = {T(0), T(0), T(0)};
+    const int stage = y == T(0) ? 0 : (y == T(1) ? 1 : (y >= T(2) ? 2 : -1));
+    ve = T(0);
+#pragma unroll
+    for (int l = 0; l < MULTI_L; ++l) gm[l] = gv[l] = T(0);
+#pragma unroll
+    for (int l = 0; l < 2; ++l) {
+        if (l <= stage) {
+            if (s2[l] > T(0)) {
+                T v;
+                if constexpr (std::is_same<T, float>::value) {
+                    bernoulli_stage<T>(q, mu[l], s2[l], l == stage, v, gm[l], gv[l]);
+                } else {                           // float64: the Bernoulli kernels' own evaluation, the bits of lik 1
+                    expectations<T, 1>(q, none, mu[l], s2[l], l == stage ? T(1) : T(0), v, gm[l], gv[l]);
+                }
+                ve += v;
+            } else {
+                ve = gm[l] = gv[l] = nan_of<T>();
+            }
+        }
+    }
+    if (stage == 2) {
+        if (s2[2] > T(0)) {
+            T v;
+            expectations<T, 2>(q, none, mu[2], s2[2], y - T(2), v, gm[2], gv[2]);
+            ve += v;
+        } else {
+            ve = gm[2] = gv[2] = nan_of<T>();
+        }
+    }
+}
+
+// element-wise: a lane per point, fmu / fvar / g_mu / g_var [N, 3]
+template <typename T>
+__global__ void __launch_bounds__(256) multistage_ve_kernel(long N, Rule<T> q, const T* __restrict__ fmu, const T* __restrict__ fvar,
+                                                            const T* __restrict__ yobs, T* __restrict__ out_ve,
+                                                            T* __restrict__ out_gm, T* __restrict__ out_gv) {
+    const long id = (long)blockIdx.x * 256 + threadIdx.x;
+    if (id >= N) return;
+    T mu[MULTI_L], s2[MULTI_L], gm[MULTI_L], gv[MULTI_L], ve;
+#pragma unroll
+    for (int l = 0; l < MULTI_L; ++l) {
+        mu[l] = fmu[id * MULTI_L + l];
+        s2[l] = fvar[id * MULTI_L + l];
+    }
+    multistage_expectations<T>(q, yobs[id], mu, s2, ve, gm, gv);
+    if (out_ve) out_ve[id] = ve;
+#pragma unroll
+    for (int l = 0; l < MULTI_L; ++l) {
+        if (out_gm) out_gm[id * MULTI_L + l] = gm[l];
+        if (out_gv) out_gv[id * MULTI_L + l] = gv[l];
+    }
+}
+
+// The multi-latent SVGP data term: pass 1 of the tile-parallel pair above with L = 3 dense rows of w per point (w [B, N, L, 2d],
+// c [B, N, L]); the tile table, the workspace row (lower triangle of g_cov, g_mean, sum ve) and pass 2 are those of
+// sparse_expect_tile_kernel / sparse_expect_reduce_kernel.
+//   phase 1, a lane per point: the tile's L rows per point travel through LDS as one row of L 2d + 1 elements (odd: the lanes' rows
+//            start on distinct banks); per latent mu_l = w_l . m_s, s2_l = c_l + w_l^T S_s w_l; the multi-stage expectation leaves
+//            gv_l (rows 0 .. L - 1 of lg), gm_l (rows L .. 2 L - 1) and ve (row 2 L) in LDS;
+//   phase 2, a lane per accumulator entry: the points in ascending order and, within a point, the latents in ascending order:
+//            g_cov (i, j) += (gv_l w_lj) w_li,  g_mean i += gm_l w_li,  ve_sum += ve.
+// The rows are dense on purpose (a FactorAnalysis emission mixes the states): IndependentMultiOutput's zeros are multiplied through.
+// LDS at L = 3, 2d = 18, fp64: 28160 + 2592 + 144 + 3584 B = 34480 B.
+template <typename T, int D2>
+__global__ void __launch_bounds__(64) sparse_multi_expect_tile_kernel(long N, int S, long BS, Rule<T> q,
+                                                                      const long long* __restrict__ seg,
+                                                                      const long long* __restrict__ tile_seg,
+                                                                      const long long* __restrict__ seg_tile, const T* __restrict__ w,
+                                                                      const T* __restrict__ cvar, const T* __restrict__ yobs,
+                                                                      const T* __restrict__ pair_mean, const T* __restrict__ pair_cov,
+                                                                      int grads, T* __restrict__ ws) {
+    constexpr int L = MULTI_L, W = L * D2 + 1, TRI = D2 * (D2 + 1) / 2, E = seg_entries(D2, 3), R = (E + 63) / 64;
+    __shared__ T lw[64 * W];
+    __shared__ T ls[D2 * D2];
+    __shared__ T lm[D2];
+    __shared__ T lg[(2 * L + 1) * 64];
+    const int lane = threadIdx.x;
+    const long t = blockIdx.x;
+    long bs = (long)tile_seg[t];
+    bs = bs < 0 ? 0 : (bs >= BS ? BS - 1 : bs);
+    const long b = bs / S;
+    const long s = bs - b * S;
+    long k_lo = (long)seg[b * (S + 1) + s], k_hi = (long)seg[b * (S + 1) + s + 1];
+    clamp_range(k_lo, k_hi, N);
+    const long j = t - (long)seg_tile[bs];                          // this tile's number within its segment
+    const long k0 = (j >= 0 && j <= (k_hi - k_lo) / 64) ? k_lo + 64 * j : k_hi;
+    const int npts = k_hi - k0 < 64 ? int(k_hi - k0) : 64;          // (0 only for a table that disagrees with the offsets)
+    int ei[R], ej[R], kind[R];         // this lane's entries: kind 0 = (ei, ej) of the triangle, 1 = ei of the vector, 2 = the scalar,
+    T part[R];                         // 3 = surplus
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int e = lane + 64 * r;
+        part[r] = T(0);
+        ei[r] = ej[r] = 0;
+        kind[r] = e < TRI ? 0 : (e < TRI + D2 ? 1 : (e < E ? 2 : 3));
+        if (kind[r] == 0) tri_decode(e, ei[r], ej[r]);
+        if (kind[r] == 1) ei[r] = e - TRI;
+    }
+    if (npts > 0) {
+        for (int idx = lane; idx < D2 * D2; idx += 64) ls[idx] = pair_cov[bs * (D2 * D2) + idx];
+        if (lane < D2) lm[lane] = pair_mean[bs * D2 + lane];
+        const T* wt = w + (b * N + k0) * (L * D2);                   // npts rows of L 2d elements: coalesced loads
+        for (int idx = lane; idx < npts * (L * D2); idx += 64) lw[(idx / (L * D2)) * W + idx % (L * D2)] = wt[idx];
+        __syncthreads();
+        if (lane < npts) {
+            const long id = b * N + k0 + lane;
+            T wr[L][D2], mu[L], s2[L], gm[L], gv[L], ve;
+#pragma unroll
+            for (int l = 0; l < L; ++l) {
+#pragma unroll
+                for (int i = 0; i < D2; ++i) wr[l][i] = lw[lane * W + l * D2 + i];
+                mu[l] = T(0);
+                s2[l] = cvar[id * L + l];
+            }
+#pragma unroll 1
+            for (int i = 0; i < D2; ++i) {         // (rolled: unrolled, the compiler keeps all of S_s in registers and spills)
+                T acc[L];
+#pragma unroll
+                for (int l = 0; l < L; ++l) acc[l] = T(0);
+#pragma unroll
+                for (int c = 0; c < D2; ++c) {
+                    const T sic = ls[i * D2 + c];
+#pragma unroll
+                    for (int l = 0; l < L; ++l) acc[l] += sic * wr[l][c];
+                }
+                const T mi = lm[i];
+#pragma unroll
+                for (int l = 0; l < L; ++l) {
+                    const T wi = lw[lane * W + l * D2 + i];
+                    s2[l] += wi * acc[l];
+                    mu[l] += wi * mi;
+                }
+            }
+            multistage_expectations<T>(q, yobs[id], mu, s2, ve, gm, gv);
+#pragma unroll
+            for (int l = 0; l < L; ++l) {
+                lg[l * 64 + lane] = gv[l];
+                lg[(L + l) * 64 + lane] = gm[l];
+            }
+            lg[2 * L * 64 + lane] = ve;
+        }
+        __syncthreads();
+        if (grads) {
+            for (int k = 0; k < npts; ++k) {
+#pragma unroll
+                for (int l = 0; l < L; ++l) {
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        const T wi = lw[k * W + l * D2 + ei[r]];
+                        if (kind[r] == 0) part[r] += (lg[l * 64 + k] * lw[k * W + l * D2 + ej[r]]) * wi;
+                        if (kind[r] == 1) part[r] += lg[(L + l) * 64 + k] * wi;
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+                    if (kind[r] == 2) part[r] += lg[2 * L * 64 + k];
+            }
+        } else if (lane == (E - 1) % 64) {         // value only: the one entry, with the bits it has beside the gradients
+            for (int k = 0; k < npts; ++k) part[R - 1] += lg[2 * L * 64 + k];
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int e = lane + 64 * r;
+        if (e < E) ws[t * E + e] = part[r];
+    }
+}
+
 // log of the predictive density  log int p(y | f) N(f | mu, s2) df
 template <typename T, int LIK>
 __global__ void __launch_bounds__(256) lik_pld_kernel(long N, Rule<T> q, Par<T> p, const T* __restrict__ fmu, const T* __restrict__ fvar,
@@ -1073,6 +1288,70 @@ int run_expect(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double
     });
 }
 
+// the multi-latent pair: instantiated for (two_d, latent_dim, lik) = (6 ... 18 even, 3, multi-stage), -101 for any other signature.
+// The likelihood has no parameters (params is not read); the workspace row and pass 2 are the single-latent pair's.
+template <typename F>
+int with_multi_two_d(int two_d, F&& f) {
+    switch (two_d) {
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 10: return f(std::integral_constant<int, 10>{});
+        case 12: return f(std::integral_constant<int, 12>{});
+        case 14: return f(std::integral_constant<int, 14>{});
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 18: return f(std::integral_constant<int, 18>{});
+        default: return -101;
+    }
+}
+
+template <typename T>
+int run_multi_expect(int64_t B, int64_t N, int64_t S, int two_d, int latent_dim, int lik, int nq, const double* nodes,
+                     const double* weights, const int64_t* seg, const T* w, const T* c, const T* y, const T* pm, const T* pc,
+                     int64_t tiles, const int64_t* tile_seg, const int64_t* seg_tile, void* ws, size_t ws_bytes, T* ve_sum, T* g_mean,
+                     T* g_cov, void* stream) {
+    Rule<T> q;
+    Par<T> p;
+    if (B < 0) return -1;
+    if (N < 0) return -2;
+    if (S < 1 || (B > 0 && S > int64_t(0x7fffffff) / B)) return -3;
+    if (latent_dim != MULTI_L || lik != LIK_MULTISTAGE || two_d < 6 || two_d > 18 || (two_d & 1)) return -101;
+    int bad = prepare<T>(0, 1, nullptr, nq, nodes, weights, false, q, p);        // -4 ... -6 there: arguments 8 ... 10 here
+    if (bad) return bad - 4;
+    if (tiles < 0 || tiles > int64_t(0x7fffffff) || (N == 0 && tiles != 0)) return -17;
+    if (!g_mean && g_cov) return -23;
+    if (g_mean && !g_cov) return -24;
+    if (B == 0 || (!ve_sum && !g_mean)) return 0;      // nothing asked for
+    if (tiles > 0) {
+        if ((bad = first_null(11, {seg, w, c, y, pm, pc}))) return bad;
+        if ((bad = first_null(18, {tile_seg, seg_tile, ws}))) return bad;
+        if (ws_bytes < size_t(tiles) * expect_row(two_d) * sizeof(T)) return -21;
+    }
+    return with_multi_two_d(two_d, [&](auto D) {
+        constexpr int D2 = decltype(D)::value;
+        if (tiles > 0) {
+            const int rc = launch(sparse_multi_expect_tile_kernel<T, D2>, tiles, 64, stream, N, S, B * S, q, ll(seg), ll(tile_seg),
+                                  ll(seg_tile), w, c, y, pm, pc, g_mean ? 1 : 0, ws);
+            if (rc) return rc;
+        }
+        return launch(sparse_expect_reduce_kernel<T, D2>, B * S, 256, stream, tiles, tiles > 0 ? ll(seg_tile) : nullptr, ws, ve_sum,
+                      g_mean, g_cov);
+    });
+}
+
+template <typename T>
+int run_multistage_ve(int64_t N, int nq, const double* nodes, const double* weights, const T* fmu, const T* fvar, const T* y, T* ve,
+                      T* g_mu, T* g_var, void* stream) {
+    Rule<T> q;
+    Par<T> p;
+    if (N < 0 || (N + 255) / 256 > int64_t(0x7fffffff)) return -1;
+    const int bad = prepare<T>(0, 1, nullptr, nq, nodes, weights, false, q, p);  // -4 ... -6 there: arguments 2 ... 4 here
+    if (bad) return bad + 2;
+    if (N == 0) return 0;
+    if (const int null = first_null(5, {fmu, fvar, y})) return null;
+    if (!ve && !g_mu && !g_var) return 0;          // nothing asked for
+    return launch(multistage_ve_kernel<T>, (N + 255) / 256, 256, stream, N, q, fmu, fvar, y, ve, g_mu, g_var);
+}
+
 // the sparse power-EP site update: the workspace row is the SVGP kernels' (expect_row), so is the workspace-size function
 template <typename T>
 int run_sparse_pep(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq, const double* nodes,
@@ -1300,6 +1579,39 @@ int mf_lik_sparse_expectations_f32(int64_t B, int64_t N, int64_t S, int two_d, i
                                    size_t workspace_bytes, float* ve_sum, float* g_mean, float* g_cov, void* stream) {
     return run_expect<float>(B, N, S, two_d, lik, params, nq, nodes, weights, seg_offsets, w, c, y, pair_mean, pair_cov, num_tiles,
                              tile_seg, seg_tile, workspace, workspace_bytes, ve_sum, g_mean, g_cov, stream);
+}
+
+size_t mf_lik_sparse_multi_expectations_workspace_bytes(int64_t num_tiles, int two_d, int elem_size) {
+    return mf_lik_sparse_expectations_workspace_bytes(num_tiles, two_d, elem_size);
+}
+int mf_lik_sparse_multi_expectations_f64(int64_t B, int64_t N, int64_t S, int two_d, int latent_dim, int lik, const double* params,
+                                         int nq, const double* nodes, const double* weights, const int64_t* seg, const double* w,
+                                         const double* c, const double* y, const double* pm, const double* pc, int64_t tiles,
+                                         const int64_t* tile_seg, const int64_t* seg_tile, void* ws, size_t ws_bytes, double* ve_sum,
+                                         double* g_mean, double* g_cov, void* stream) {
+    (void)params;
+    return run_multi_expect<double>(B, N, S, two_d, latent_dim, lik, nq, nodes, weights, seg, w, c, y, pm, pc, tiles, tile_seg,
+                                    seg_tile, ws, ws_bytes, ve_sum, g_mean, g_cov, stream);
+}
+int mf_lik_sparse_multi_expectations_f32(int64_t B, int64_t N, int64_t S, int two_d, int latent_dim, int lik, const double* params,
+                                         int nq, const double* nodes, const double* weights, const int64_t* seg, const float* w,
+                                         const float* c, const float* y, const float* pm, const float* pc, int64_t tiles,
+                                         const int64_t* tile_seg, const int64_t* seg_tile, void* ws, size_t ws_bytes, float* ve_sum,
+                                         float* g_mean, float* g_cov, void* stream) {
+    (void)params;
+    return run_multi_expect<float>(B, N, S, two_d, latent_dim, lik, nq, nodes, weights, seg, w, c, y, pm, pc, tiles, tile_seg,
+                                   seg_tile, ws, ws_bytes, ve_sum, g_mean, g_cov, stream);
+}
+
+int mf_lik_multistage_variational_expectations_f64(int64_t N, int nq, const double* nodes, const double* weights, const double* fmu,
+                                                   const double* fvar, const double* y, double* ve, double* g_mu, double* g_var,
+                                                   void* stream) {
+    return run_multistage_ve<double>(N, nq, nodes, weights, fmu, fvar, y, ve, g_mu, g_var, stream);
+}
+int mf_lik_multistage_variational_expectations_f32(int64_t N, int nq, const double* nodes, const double* weights, const float* fmu,
+                                                   const float* fvar, const float* y, float* ve, float* g_mu, float* g_var,
+                                                   void* stream) {
+    return run_multistage_ve<float>(N, nq, nodes, weights, fmu, fvar, y, ve, g_mu, g_var, stream);
 }
 
 int mf_lik_variational_expectations_f64(int64_t N, int lik, const double* params, int nq, const double* nodes, const double* weights,

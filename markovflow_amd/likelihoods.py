@@ -35,6 +35,12 @@ DEVIATION from the reference: its generic ``PEPScalarLikelihood.log_expected_den
 ``alpha log N(y; mu, s2 + var)``, which is not ``log int p^alpha q``; here the integral is computed.  At ``alpha = 1`` all three agree,
 and ``I`` is ``predict_log_density``.
 
+``MultiStageLikelihood`` (``markovflow/likelihoods/mutlistage_likelihood.py``; Seeger et al. 2016, intermittent demand) is the one
+likelihood with more than one latent function: ``latent_dim = 3``, tensors ``batch + [N, 3]`` for the latents and ``batch + [N, 1]``
+for the observations.  It is a decision tree over the three latents - ``y = 0`` with probability ``sigma(F0)``, else ``y = 1`` with
+probability ``sigma(F1)``, else ``y - 2 ~ Poisson(exp(F2))`` - so its expectation is a sum of the Bernoulli and Poisson expectations
+above over the latents the point's branch reads; on HIP tensors it is ONE launch of ``mf_lik_multistage_variational_expectations_*``.
+
 The parameters (``variance``, ``scale``, ``df``) are plain Python floats and are NOT trainable.
 """
 import ctypes
@@ -59,6 +65,7 @@ class Likelihood:
     floats, not trainable."""
 
     _id = -1
+    latent_dim = 1          # latent functions per observation: models ask before they project (MultiStageLikelihood has 3)
 
     def __init__(self, num_gauss_hermite_points: int = 20) -> None:
         nq = int(num_gauss_hermite_points)
@@ -459,3 +466,130 @@ class StudentT(Likelihood):
         if not self.df > 2.0:
             raise ValueError("StudentT.predict_mean_and_var: the variance is finite only for df > 2")
         return fmu, fvar + self.scale * self.scale * self.df / (self.df - 2.0)
+
+
+class MultiStageLikelihood(Likelihood):
+    """The multi-stage likelihood for intermittent, bursty counts (``markovflow/likelihoods/mutlistage_likelihood.py``; Seeger,
+    Salinas and Flunkert 2016): three latent functions ``F = [F0, F1, F2]`` and one observation column.  With ``sigma`` the probit
+    link of ``Bernoulli`` (its 1e-3 jitter included) and the exp link with bin size 1 of ``Poisson``,
+
+        log p(y | F) = [y == 0]  log sigma(F0)
+                     + [y == 1] (log(1 - sigma(F0)) + log sigma(F1))
+                     + [y >= 2] (log(1 - sigma(F0)) + log(1 - sigma(F1)) + log Poisson(y - 2 | exp(F2)))
+
+    An observation that is none of ``0``, ``1``, ``>= 2`` (0.5, a negative number, NaN) contributes exactly 0, as the reference's
+    three masks do; the comparisons are exact floating-point comparisons.  A latent that the point's branch does not read has
+    derivative 0 and its variance is not examined; one that it reads with ``fvar <= 0`` or NaN makes the point's value and that
+    latent's derivatives NaN.  The links are not arguments: the kernels hard-code them.  No parameters."""
+
+    _id = 4
+    latent_dim = 3
+
+    def __init__(self, num_gauss_hermite_points: int = 20) -> None:
+        super().__init__(num_gauss_hermite_points)
+        self._bernoulli = Bernoulli(num_gauss_hermite_points)
+        self._poisson = Poisson(num_gauss_hermite_points)
+
+    def _check(self, what: str, fmu: torch.Tensor, y: torch.Tensor = None, **others: torch.Tensor):
+        if fmu.dim() < 2 or fmu.shape[-1] != self.latent_dim:
+            raise ValueError(f"{type(self).__name__}.{what}: the latents must have shape batch + [N, {self.latent_dim}], got "
+                             f"{tuple(fmu.shape)}")
+        for name, t in others.items():
+            if tuple(t.shape) != tuple(fmu.shape):
+                raise ValueError(f"{type(self).__name__}.{what}: {name} has shape {tuple(t.shape)}, expected {tuple(fmu.shape)}")
+        if y is not None and tuple(y.shape) != tuple(fmu.shape[:-1]) + (1,):
+            raise ValueError(f"{type(self).__name__}.{what}: y has shape {tuple(y.shape)}, expected {tuple(fmu.shape[:-1]) + (1,)}")
+        if fmu.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"markovflow_amd supports float32 and float64 tensors, got {fmu.dtype}")
+        _lib.same_dtype_device(fmu, f"{type(self).__name__}.{what}", y=y, **others)
+
+    def log_prob(self, f: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """``log p(y | F)``, ``batch + [N, 3]``, ``batch + [N, 1] -> batch + [N]`` (element-wise torch on either device)."""
+        self._check("log_prob", f, y=y)
+        obs = y[..., 0]
+        is0, is1, is2 = obs == 0, obs == 1, obs >= 2
+        zero, one = torch.zeros_like(obs), torch.ones_like(obs)
+        yes0, no0 = (self._bernoulli._log_prob_and_grad(f[..., 0], t)[0] for t in (one, zero))
+        yes1, no1 = (self._bernoulli._log_prob_and_grad(f[..., 1], t)[0] for t in (one, zero))
+        count = self._poisson._log_prob_and_grad(f[..., 2], torch.where(is2, obs - 2.0, zero))[0]
+        return torch.where(is0, yes0, zero) + torch.where(is1, no0 + yes1, zero) + torch.where(is2, no0 + no1 + count, zero)
+
+    def variational_expectations(self, fmu: torch.Tensor, fvar: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """``E_{prod_l N(F_l | fmu_l, fvar_l)} log p(y | F)``, ``batch + [N]``, from ``fmu``, ``fvar`` ``batch + [N, 3]`` and ``y``
+        ``batch + [N, 1]``.  Differentiable ONCE in ``fmu`` and ``fvar``: the six derivatives per point are computed beside the value
+        and saved (no second-order support)."""
+        self._check("variational_expectations", fmu, y=y, fvar=fvar)
+        return _MultiStageVariationalExpectations.apply(fmu, fvar, y, self)
+
+    def _expectations(self, fmu, fvar, y):
+        """``(VE [.., N], dVE/dmu [.., N, 3], dVE/dvar [.., N, 3])``: the kernel on HIP tensors, torch on CPU tensors."""
+        if not fmu.is_cuda:
+            return torch_multistage_variational_expectations(self, fmu, fvar, y)
+        mu, var, obs = fmu.contiguous(), fvar.contiguous(), y.contiguous()
+        ve, g_mu, g_var = torch.empty_like(obs[..., 0]), torch.empty_like(mu), torch.empty_like(mu)
+        _lib.call("mf_lik_multistage_variational_expectations", mu.dtype, obs.numel(), self.num_gauss_hermite_points, self._c_nodes,
+                  self._c_weights, _lib.ptr(mu), _lib.ptr(var), _lib.ptr(obs), _lib.ptr(ve), _lib.ptr(g_mu), _lib.ptr(g_var),
+                  _lib.stream_ptr(mu.device))
+        return ve, g_mu, g_var
+
+    def predict_log_density(self, fmu, fvar, y):
+        """Not available, as in the reference (mutlistage_likelihood.py:144-145)."""
+        raise NotImplementedError("MultiStageLikelihood has no predictive density (the reference's raises too)")
+
+    def predict_mean_and_var(self, fmu, fvar):
+        """Not available, as in the reference (mutlistage_likelihood.py:147-148)."""
+        raise NotImplementedError("MultiStageLikelihood has no predictive mean and variance (the reference's raises too)")
+
+    def _one_latent_only(self, *args, **kwargs):
+        raise NotImplementedError("MultiStageLikelihood has three latent functions: the site updates and the power-EP densities "
+                                  "are written for one; use SparseVariationalGaussianProcess")
+
+    cvi_site_update = log_expected_density = grad_log_expected_density = pep_site_update = _one_latent_only
+
+    def sample_y(self, F_samples: torch.Tensor, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """Observations drawn from ``p(y | F)``, ``batch + [3] -> batch + [1]`` (mutlistage_likelihood.py:150-179): ``eta0 ~
+        Bernoulli(sigma(F0))``; ``eta0 = 1`` gives 0, else ``eta1 ~ Bernoulli(sigma(F1)) = 1`` gives 1, else ``Poisson(exp(F2)) + 2``."""
+        if F_samples.dim() < 1 or F_samples.shape[-1] != self.latent_dim:
+            raise ValueError(f"MultiStageLikelihood.sample_y: F_samples must have shape batch + [3], got {tuple(F_samples.shape)}")
+        if F_samples.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"markovflow_amd supports float32 and float64 tensors, got {F_samples.dtype}")
+        eta0 = torch.bernoulli(_inv_probit(F_samples[..., 0]), generator=generator)
+        eta1 = torch.bernoulli(_inv_probit(F_samples[..., 1]), generator=generator)
+        count = torch.poisson(torch.exp(F_samples[..., 2]), generator=generator)
+        return torch.where(eta0 == 1, torch.zeros_like(eta0), torch.where(eta1 == 1, torch.ones_like(eta0), count + 2.0))[..., None]
+
+
+class _MultiStageVariationalExpectations(torch.autograd.Function):
+    """Value ``batch + [N]`` with the six derivatives per point computed in the same pass and saved for the backward."""
+
+    @staticmethod
+    def forward(ctx, fmu, fvar, y, lik):
+        with torch.no_grad():
+            ve, g_mu, g_var = lik._expectations(fmu.detach(), fvar.detach(), y.detach())
+        ctx.save_for_backward(g_mu, g_var)
+        return ve
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if torch.is_grad_enabled():
+            raise RuntimeError("MultiStageLikelihood.variational_expectations is differentiable once: its backward uses the "
+                               "derivatives computed in the forward and has no second-order support (create_graph=True)")
+        g_mu, g_var = ctx.saved_tensors
+        return grad_out[..., None] * g_mu, grad_out[..., None] * g_var, None, None
+
+
+def torch_multistage_variational_expectations(lik: MultiStageLikelihood, fmu: torch.Tensor, fvar: torch.Tensor, y: torch.Tensor):
+    """``(VE [.., N], dVE/dmu [.., N, 3], dVE/dvar [.., N, 3])`` of the multi-stage likelihood from ``torch_variational_expectations``
+    of its Bernoulli and Poisson stages: the CPU route of ``MultiStageLikelihood.variational_expectations``, and the composition
+    ``mf_lik_multistage_variational_expectations_*`` is measured against on the device.  The value is summed over the latents in
+    ascending order, as the kernel sums it; a latent that the branch does not read is evaluated at variance 1 and masked out."""
+    obs = y[..., 0]
+    is0, is1, is2 = obs == 0, obs == 1, obs >= 2
+    read = torch.stack([is0 | is1 | is2, is1 | is2, is2], dim=-1)
+    var = torch.where(read, fvar, torch.ones_like(fvar))
+    mu = torch.where(read, fmu, torch.zeros_like(fmu))
+    target = torch.stack([is0, is1], dim=-1).to(fmu.dtype)                         # sigma(F0) for y = 0, sigma(F1) for y = 1
+    stage = torch_variational_expectations(lik._bernoulli, mu[..., :2], var[..., :2], target)
+    count = torch_variational_expectations(lik._poisson, mu[..., 2:], var[..., 2:], torch.where(is2, obs - 2.0, torch.zeros_like(obs))[..., None])
+    ve, g_mu, g_var = (torch.where(read, torch.cat([s, c], dim=-1), torch.zeros_like(fmu)) for s, c in zip(stage, count))
+    return (ve[..., 0] + ve[..., 1]) + ve[..., 2], g_mu, g_var

@@ -21,9 +21,13 @@ def _refuse_non_stationary(kernel, who: str) -> None:
                                   "supported by GaussianProcessRegression alone")
 
 
-def _require_likelihood(likelihood) -> None:
+def _require_likelihood(likelihood, multi_latent: bool = False) -> None:
+    """``multi_latent``: the caller projects one marginal per latent function; every other model and fused op is written for ONE."""
     if not isinstance(likelihood, Likelihood):
         raise TypeError("likelihood must be a markovflow_amd.likelihoods.Likelihood")
+    if likelihood.latent_dim > 1 and not multi_latent:
+        raise NotImplementedError(f"{type(likelihood).__name__} has {likelihood.latent_dim} latent functions per observation: only "
+                                  "SparseVariationalGaussianProcess supports a likelihood with latent_dim > 1")
 
 
 def _check_dense_data(time_points: torch.Tensor, observations: torch.Tensor) -> None:

@@ -11,6 +11,8 @@ forward launch wrote:
     back-projection and the segmented sum; in place on the sites);
   * ``sparse_pep_site_update_{torch,hip}`` and ``pair_cavity``: ``mf_lik_sparse_pep_site_update_*`` (tile-parallel kernel pair);
   * ``sparse_expected_log_likelihood(_torch)``: ``mf_lik_sparse_expectations_*`` (two passes, tile-parallel), the SVGP data term;
+  * ``sparse_multi_expected_log_likelihood(_torch)``: ``mf_lik_sparse_multi_expectations_*``, the same term for a likelihood with
+    several latent functions per observation (``sparse_multi_site_projections``: one dense projection per latent);
   * ``iw_log_likelihood(_torch)``: ``mf_lik_iw_log_weights_*`` (two passes, tile-parallel, no atomics), the data term of the
     importance weights with Matheron's correction assembled in the kernel.
 """
@@ -28,6 +30,7 @@ from ._common import (_check_shapes, _differentiable_once, _launch, _new_outputs
 
 
 SPARSE_SITE_MAX_TWO_D = 18      # mf_lik_sparse_cvi_site_update_*: 2 d <= 18, the range of the lane-per-point conditional kernels
+SPARSE_MULTI_MIN_TWO_D = 6      # mf_lik_sparse_multi_expectations_*: three latents of one state each at the least
 
 
 def sparse_site_projections(kernel: SDEKernel, time_points: torch.Tensor, inducing_points: torch.Tensor
@@ -317,6 +320,110 @@ def sparse_expected_log_likelihood_torch(likelihood: Likelihood, w: torch.Tensor
     hyper-parameter under the tape, and it is what ``mf_lik_sparse_expectations_*`` is measured against."""
     fmu, fvar, flat = _sparse_point_marginals(w, c, indices, pair_mean, pair_cov, pair_mean.shape[-2])
     ve = likelihood.variational_expectations(fmu[..., None], fvar[..., None], y[..., None])
+    out = torch.zeros(math.prod(pair_mean.shape[:-1]), dtype=ve.dtype, device=ve.device).index_add(0, flat, ve.reshape(-1))
+    return out.reshape(pair_mean.shape[:-1])
+
+
+# ---- SVGP with several latent functions per observation -----------------------------------------------------------------------------
+def sparse_multi_site_projections(kernel: SDEKernel, time_points: torch.Tensor, inducing_points: torch.Tensor
+                                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``sparse_site_projections`` for a kernel with ``L = kernel.output_dim`` outputs: one projection of the pair per latent,
+    ``w [.., N, L, 2d] = H P_k`` and ``c [.., N, L] = diag(H T_k H^T)`` (the reference's ``full_output_cov=False``), with the same
+    ``indices`` and ``offsets``.  The rows are dense: nothing is assumed about the emission matrix."""
+    proj, cov, indices = conditionals._conditional_statistics(time_points, inducing_points, kernel)
+    h = kernel.generate_emission_model(time_points).emission_matrix                         # [.., N, L, d]
+    w = h @ proj
+    c = torch.sum((h @ cov) * h, dim=-1)
+    return w.contiguous(), c.contiguous(), indices, _site_offsets(time_points, inducing_points)
+
+
+def _sparse_multi_point_marginals(w: torch.Tensor, c: torch.Tensor, indices: torch.Tensor, pair_mean: torch.Tensor,
+                                  pair_cov: torch.Tensor, segs: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``_sparse_point_marginals`` per latent: ``fmu``, ``fvar`` ``[.., N, L]`` from ``w [.., N, L, 2d]``, ``c [.., N, L]``."""
+    two_d = w.shape[-1]
+    m = torch.gather(pair_mean, -2, indices[..., None].expand(tuple(indices.shape) + (two_d,)))
+    cov = torch.gather(pair_cov, -3, indices[..., None, None].expand(tuple(indices.shape) + (two_d, two_d)))
+    fmu = torch.sum(w * m[..., None, :], dim=-1)
+    fvar = c + torch.sum(w * (w @ cov.transpose(-1, -2)), dim=-1)
+    series = torch.arange(math.prod(indices.shape[:-1]), device=indices.device).reshape(tuple(indices.shape[:-1]) + (1,))
+    return fmu, fvar, (indices + series * segs).reshape(-1)
+
+
+def _sparse_multi_expectations_launch(likelihood: Likelihood, w, c, y, offsets, tiles, pair_mean, pair_cov, want_grads: bool):
+    """ONE call of ``mf_lik_sparse_multi_expectations_*``: ``(ve_sum [.., S], g_mean [.., S, 2d] | None, g_cov [.., S, 2d, 2d] | None)``."""
+    dtype, dev = w.dtype, w.device
+    n, latents, two_d, segs = w.shape[-3], w.shape[-2], w.shape[-1], offsets.shape[-1] - 1
+    batch = tuple(offsets.shape[:-1])
+    bsz = offsets.numel() // (segs + 1)
+    num_tiles, tile_seg, seg_tile = tiles
+    new = _new_outputs(batch, dtype, dev)
+    ve_sum, g_mean, g_cov = new(True, segs), new(want_grads, segs, two_d), new(want_grads, segs, two_d, two_d)
+    ws, ws_bytes = _workspace(_lib.load().mf_lik_sparse_multi_expectations_workspace_bytes, dev, num_tiles, two_d, w.element_size())
+    _launch("mf_lik_sparse_multi_expectations", dtype, dev, bsz, n, segs, two_d, latents, *likelihood._kernel_args(), offsets, w, c, y,
+            pair_mean, pair_cov, num_tiles, tile_seg, seg_tile, ws, ws_bytes, ve_sum, g_mean, g_cov)
+    return ve_sum, g_mean, g_cov
+
+
+class _SparseMultiExpectedLogLikelihood(torch.autograd.Function):
+    """Value ``batch + [M + 1]``; the adjoints onto the pair marginals come out of the same launch and wait for the backward."""
+
+    @staticmethod
+    def forward(ctx, pair_mean, pair_cov, likelihood, w, c, y, offsets, tiles):
+        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        with torch.no_grad():
+            ve_sum, g_mean, g_cov = _sparse_multi_expectations_launch(likelihood, w.detach(), c.detach(), y.detach(), offsets, tiles,
+                                                                      pair_mean.detach(), pair_cov.detach(), want)
+        if want:
+            ctx.save_for_backward(g_mean, g_cov)
+        return ve_sum
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        _differentiable_once("sparse_multi_expected_log_likelihood", "adjoints")
+        g_mean, g_cov = ctx.saved_tensors
+        return (grad_out[..., None] * g_mean if ctx.needs_input_grad[0] else None,
+                grad_out[..., None, None] * g_cov if ctx.needs_input_grad[1] else None, None, None, None, None, None, None)
+
+
+def sparse_multi_expected_log_likelihood(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor,
+                                         offsets: torch.Tensor, pair_mean: torch.Tensor, pair_cov: torch.Tensor, tiles=None
+                                         ) -> torch.Tensor:
+    """``sparse_expected_log_likelihood`` for a likelihood with ``L = likelihood.latent_dim > 1`` latent functions: per point and
+    latent ``fmu_l = w_kl . m_s`` and ``fvar_l = c_kl + w_kl^T S_s w_kl`` (``w [.., N, L, 2d]``, ``c [.., N, L]``, ``y [.., N]``), the
+    likelihood's expectation over the ``L`` marginals, summed per pair, ``batch + [M + 1]``: ONE call of
+    ``mf_lik_sparse_multi_expectations_*`` on HIP tensors, ``6 <= 2d <= 18``.  Differentiable ONCE in ``pair_mean`` and ``pair_cov``
+    (the backward multiplies the adjoints the forward computed beside the value); not differentiable in ``w`` and ``c``."""
+    _require_likelihood(likelihood, multi_latent=True)
+    what = "sparse_multi_expected_log_likelihood"
+    if w.dim() < 3:
+        raise ValueError(f"{what}: w must have shape batch + [N, L, 2d], got {tuple(w.shape)}")
+    n, latents, two_d, segs = w.shape[-3], w.shape[-2], w.shape[-1], offsets.shape[-1] - 1
+    batch = tuple(offsets.shape[:-1])
+    if latents != likelihood.latent_dim or latents < 2:
+        raise ValueError(f"{what}: w carries {latents} latent rows per point, the likelihood has latent_dim = {likelihood.latent_dim} "
+                         "(a likelihood with one latent takes sparse_expected_log_likelihood)")
+    if two_d > SPARSE_SITE_MAX_TWO_D or two_d < SPARSE_MULTI_MIN_TWO_D or two_d % 2:
+        raise NotImplementedError(f"{what}: 2d = {two_d} is outside {SPARSE_MULTI_MIN_TWO_D}, ..., {SPARSE_SITE_MAX_TWO_D}; use "
+                                  "sparse_multi_expected_log_likelihood_torch")
+    _check_shapes(what, dict(w=(w, batch + (n, latents, two_d)), c=(c, batch + (n, latents)), y=(y, batch + (n,)),
+                             pair_mean=(pair_mean, batch + (segs, two_d)), pair_cov=(pair_cov, batch + (segs, two_d, two_d))))
+    _lib.same_dtype_device(w, what, c=c, y=y, pair_mean=pair_mean, pair_cov=pair_cov)
+    if torch.is_grad_enabled() and (w.requires_grad or c.requires_grad):
+        raise NotImplementedError(f"{what} has no adjoint onto w and c (a kernel hyper-parameter under the tape): use "
+                                  "sparse_multi_expected_log_likelihood_torch")
+    if tiles is None:
+        tiles = sparse_expectation_tiles(offsets)
+    return _SparseMultiExpectedLogLikelihood.apply(pair_mean, pair_cov, likelihood, w, c, y, offsets, tiles)
+
+
+def sparse_multi_expected_log_likelihood_torch(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor,
+                                               indices: torch.Tensor, pair_mean: torch.Tensor, pair_cov: torch.Tensor) -> torch.Tensor:
+    """The same quantity as a torch composition, differentiable by autograd in ``pair_mean``, ``pair_cov``, ``w`` and ``c``: gathers
+    of the pair marginals by the per-point pair index (``indices [.., N]``), ``likelihood.variational_expectations`` on ``[.., N, L]``
+    and ``index_add_`` over the segments.  It runs on CPU tensors, it is the model's route for ``2d > 18`` and for a kernel
+    hyper-parameter under the tape, and it is what ``mf_lik_sparse_multi_expectations_*`` is measured against."""
+    fmu, fvar, flat = _sparse_multi_point_marginals(w, c, indices, pair_mean, pair_cov, pair_mean.shape[-2])
+    ve = likelihood.variational_expectations(fmu, fvar, y[..., None])
     out = torch.zeros(math.prod(pair_mean.shape[:-1]), dtype=ve.dtype, device=ve.device).index_add(0, flat, ve.reshape(-1))
     return out.reshape(pair_mean.shape[:-1])
 
