@@ -998,6 +998,48 @@ int mf_lik_multistage_variational_expectations_f32(int64_t N, int nq, const doub
                                                    void* stream);
 
 /*
+ * The data term of the SVGP ELBO under a FactorAnalysis emission, its adjoint onto the pair marginals and its adjoint onto the
+ * mixing weights (markovflow/kernels/sde_kernel.py:881-941 under markovflow/models/sparse_variational.py:149-192;
+ * csrc/mf_lik_factor.hip): P = num_outputs observed series, each with the scalar likelihood lik, mixed from L = latent_dim latent
+ * processes, f_k = W_k g_k.  B, N, S, two_d, lik, params, the rule, seg_offsets, pair_mean, pair_cov, the tile table, the workspace and
+ * the first three outputs as for mf_lik_sparse_expectations_*; every point carries
+ *   wg  [B, N, L, 2d]  row l: H_inner,l P_k                 cg [B, N, L, L]  H_inner T_k H_inner^T (symmetric: the lower triangle is read)
+ *   mix [B, N, P, L]   W_k = A(t_k) B                       y  [B, N, P]
+ * Per point k of segment s:  mu_g = wg m_s,  Sig_g = cg + wg S_s wg^T;  per output p, ascending:  mu_p = W_p . mu_g,
+ * s2_p = W_p Sig_g W_p^T,  (ve_p, gm_p, gv_p) of the likelihood at (mu_p, s2_p, y_kp);  a = W^T gm,  G = W^T diag(gv) W;  per segment,
+ * over the points in ascending order and within a point over the pairs (l, l' <= l) in the order (0,0), (1,0), (1,1), (2,0), ...,
+ * then over the latents in ascending order,
+ *   ve_sum = sum_k sum_p ve_p      g_mean = sum_k wg^T a      g_cov = sum_k wg^T G wg
+ * and per point, not summed (rows of points outside every segment are not written),
+ *   g_w [B, N, P, L] = gm (x) mu_g + 2 diag(gv) W Sig_g       (may be NULL on its own)
+ * An output with s2_p <= 0 or NaN makes the three outputs of its segment NaN, and row p of that point's g_w.
+ * Pass 1 is one wavefront per tile of 64 points; the outputs are walked in chunks of 4 through LDS, whose footprint does not depend
+ * on P (64 rows of L 2d + 1 elements, the pair marginal, 64 rows of 4 (L + 1) + 1, L (L + 1) / 2 + L + 1 rows of 64 values: 58544 B at
+ * L = 4, 2d = 18 in float64).  The workspace row and pass 2 are those of mf_lik_sparse_expectations_*, and so is the size:
+ * mf_lik_sparse_factor_expectations_workspace_bytes(num_tiles, two_d, sizeof(T)).  g_mean and g_cov BOTH NULL: the value (and g_w when
+ * given) only, the same bits.  No floating-point atomics: the same bits on every launch and for a series alone or inside a batch.  The
+ * tile table is clamped on the device, not validated.  No allocation, no synchronisation.
+ * Returns 0, -(position of the offending argument in THIS signature: 1 B, 2 N, 3 S, 6 num_outputs < 1, 7 lik, 8 params, 9 nq, 10 nodes,
+ * 11 weights, 12 ... 18 a NULL input, 19 num_tiles negative, above 2^31 - 1 or non-zero for N = 0, 20 / 21 a NULL table, 22 a NULL
+ * workspace, 23 a workspace that is too small, 25 / 26 one of g_mean / g_cov NULL without the other), -101 for a signature that is
+ * not instantiated - latent_dim in 2, 3, 4 with two_d even in 2 latent_dim ... 18 and num_outputs <= 1024 are - or -1000 (launch
+ * failed).  Nothing is launched on an error, for B = 0, or when every output is NULL.
+ */
+size_t mf_lik_sparse_factor_expectations_workspace_bytes(int64_t num_tiles, int two_d, int elem_size);
+int mf_lik_sparse_factor_expectations_f64(int64_t B, int64_t N, int64_t S, int two_d, int latent_dim, int64_t num_outputs, int lik,
+                                          const double* params, int nq, const double* nodes, const double* weights,
+                                          const int64_t* seg_offsets, const double* wg, const double* cg, const double* mix,
+                                          const double* y, const double* pair_mean, const double* pair_cov, int64_t num_tiles,
+                                          const int64_t* tile_seg, const int64_t* seg_tile, void* workspace, size_t workspace_bytes,
+                                          double* ve_sum, double* g_mean, double* g_cov, double* g_w, void* stream);
+int mf_lik_sparse_factor_expectations_f32(int64_t B, int64_t N, int64_t S, int two_d, int latent_dim, int64_t num_outputs, int lik,
+                                          const double* params, int nq, const double* nodes, const double* weights,
+                                          const int64_t* seg_offsets, const float* wg, const float* cg, const float* mix,
+                                          const float* y, const float* pair_mean, const float* pair_cov, int64_t num_tiles,
+                                          const int64_t* tile_seg, const int64_t* seg_tile, void* workspace, size_t workspace_bytes,
+                                          float* ve_sum, float* g_mean, float* g_cov, float* g_w, void* stream);
+
+/*
  * The segmented site update of the sparse power-EP model (markovflow/models/sparse_pep.py:316-487; csrc/mf_lik.hip): B, N, S,
  * two_d, the likelihood, the rule, seg_offsets, w, c, y, the tile table and the workspace as for mf_lik_sparse_expectations_*;
  * alpha in (0, 1] is the power, lr in [0, 1] the damping.  The workspace row has the width of that entry point's, so its size is

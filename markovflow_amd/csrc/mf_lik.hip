@@ -21,6 +21,8 @@
 
 // (the rule, the parameters, log p(y | f), the expectation of one point and the host side's argument checks: shared with mf_st.hip)
 #include "mf_lik_math.hpp"
+// (the accumulator row, pass 2 of the tile-parallel SVGP data terms and the launch helper: shared with mf_lik_factor.hip)
+#include "mf_lik_reduce.hpp"
 
 namespace {
 
@@ -60,15 +62,8 @@ __global__ void __launch_bounds__(256) lik_ve_kernel(long N, Rule<T> q, Par<T> p
 // The helpers take the LDS buffers as references to arrays and a point's c as a reference to global memory, not as pointers and a
 // value: inlined, they then index and load exactly as the kernels would, and the register allocation stays what it was.
 
-// entry e of a packed lower triangle is (i, j <= i)
-__device__ __forceinline__ void tri_decode(int e, int& i, int& j) {
-    i = 0;
-    while ((i + 1) * (i + 2) / 2 <= e) ++i;
-    j = e - i * (i + 1) / 2;
-}
-
-// the accumulator has the triangle, the vector and one scalar per row of LDS values beyond the first two
-constexpr int seg_entries(int d2, int rows) { return d2 * (d2 + 1) / 2 + d2 + rows - 2; }
+// (tri_decode and seg_entries - entry e of a packed lower triangle is (i, j <= i); the accumulator has the triangle, the vector and one
+// scalar per row of LDS values beyond the first two - are in mf_lik_reduce.hpp)
 
 // accumulator entry e as (i, j, row of LDS values): e < TRI is (i, j <= i) of the matrix from row 0, then the vector's (j = D2: the
 // column of ones) from row 1, then - ROWS = 3 only - the scalar (i = j = D2) from row 2.  A lane's surplus entry decodes as entry 0.
@@ -295,34 +290,7 @@ __global__ void __launch_bounds__(64) sparse_expect_tile_kernel(long N, int S, l
     }
 }
 
-template <typename T, int D2>
-__global__ void __launch_bounds__(256) sparse_expect_reduce_kernel(long num_tiles, const long long* __restrict__ seg_tile,
-                                                                   const T* __restrict__ ws, T* __restrict__ ve_sum,
-                                                                   T* __restrict__ g_mean, T* __restrict__ g_cov) {
-    constexpr int TRI = D2 * (D2 + 1) / 2, E = seg_entries(D2, 3);
-    const long bs = blockIdx.x;
-    long t_lo = 0, t_hi = 0;
-    if (seg_tile) {                                // (NULL: no points at all)
-        t_lo = (long)seg_tile[bs];
-        t_hi = (long)seg_tile[bs + 1];
-        clamp_range(t_lo, t_hi, num_tiles);
-    }
-    for (int e = threadIdx.x; e < E; e += 256) {
-        if (e < E - 1 ? !g_mean : !ve_sum) continue;
-        T acc = T(0);
-        for (long t = t_lo; t < t_hi; ++t) acc += ws[t * E + e];
-        if (e < TRI) {
-            int i, c;
-            tri_decode(e, i, c);
-            g_cov[bs * (D2 * D2) + i * D2 + c] = acc;
-            g_cov[bs * (D2 * D2) + c * D2 + i] = acc;
-        } else if (e < E - 1) {
-            g_mean[bs * D2 + (e - TRI)] = acc;
-        } else {
-            ve_sum[bs] = acc;
-        }
-    }
-}
+// (pass 2, sparse_expect_reduce_kernel, is in mf_lik_reduce.hpp: mf_lik_factor.hip launches it too)
 
 // ---- the multi-stage likelihood (markovflow/likelihoods/mutlistage_likelihood.py): three latents per point, one observation -----
 // A decision tree over the latents: y == 0 reads latent 0 (log sigma), y == 1 latents 0 (log(1 - sigma)) and 1 (log sigma), y >= 2
@@ -1125,12 +1093,7 @@ int with_two_d(int two_d, F&& f) {
     }
 }
 
-// one launch; the arguments are converted to the kernel's parameter types (NULL to a typed pointer, int64_t to long or int)
-template <typename... Params, typename... Args>
-int launch(void (*kernel)(Params...), int64_t grid, unsigned block, void* stream, const Args&... args) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(block), 0, static_cast<hipStream_t>(stream), static_cast<Params>(args)...);
-    return hipGetLastError() == hipSuccess ? 0 : -1000;
-}
+// (launch - one launch, the arguments converted to the kernel's parameter types - is in mf_lik_reduce.hpp)
 
 // variational expectations (nat1 == NULL) or the CVI site update: the one kernel behind both
 template <typename T>
@@ -1254,7 +1217,7 @@ int run_sparse(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double
     });
 }
 
-constexpr size_t expect_row(int two_d) { return size_t(seg_entries(two_d, 3)); }
+// (expect_row, the workspace row of a tile, is in mf_lik_reduce.hpp)
 
 template <typename T>
 int run_expect(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq, const double* nodes,

@@ -58,3 +58,46 @@ class EmissionModel:
         if full_output_cov:
             return torch.matmul(hs, self._H.transpose(-1, -2))
         return torch.sum(self._H * hs, dim=-1)
+
+
+class ComposedPairEmissionModel(EmissionModel):
+    """Emission through an intermediate space (emission_model.py:157-266): ``g_k = H_inner x_k`` (``inner_dim`` latent functions) and
+    ``f_k = H_outer,k g_k``, so the emission matrix is ``H_outer @ H_inner``.  The ``_f`` methods are ``EmissionModel``'s on the
+    product; the ``_g`` methods project onto the intermediate space with the inner model.  Plain batched products: CPU or HIP
+    tensors, differentiable by autograd.  (``StackEmissionModel`` is not mirrored.)"""
+
+    def __init__(self, outer_emission_model: EmissionModel, inner_emission_model: EmissionModel) -> None:
+        """:param outer_emission_model: ``batch + [num_data, output_dim, inner_dim]``;
+        :param inner_emission_model: ``batch + [num_data, inner_dim, state_dim]``."""
+        outer, inner = outer_emission_model.emission_matrix, inner_emission_model.emission_matrix
+        if outer.shape[-1] != inner.shape[-2] or outer.shape[-3] != inner.shape[-3]:
+            raise ValueError(f"the outer emission matrix {tuple(outer.shape)} does not compose with the inner one {tuple(inner.shape)}")
+        super().__init__(torch.matmul(outer, inner))
+        self._inner_emission_model = inner_emission_model
+
+    @property
+    def state_dim(self) -> int:
+        return self._inner_emission_model.state_dim
+
+    @property
+    def inner_dim(self) -> int:
+        """The dimension of the intermediate space ``g``."""
+        return self._inner_emission_model.output_dim
+
+    @property
+    def inner_emission_matrix(self) -> torch.Tensor:
+        """``batch + [num_data, inner_dim, state_dim]``."""
+        return self._inner_emission_model.emission_matrix
+
+    def project_state_marginals_to_g(
+        self, means: torch.Tensor, covariances: torch.Tensor, full_output_cov: bool = True
+    ) -> Tuple[torch.Tensor, torch.Tensor]:
+        return self._inner_emission_model.project_state_marginals_to_f(means, covariances, full_output_cov)
+
+    def project_state_to_g(self, state: torch.Tensor) -> torch.Tensor:
+        """``H_inner x``."""
+        return self._inner_emission_model.project_state_to_f(state)
+
+    def project_state_covariance_to_g(self, covariance: torch.Tensor, full_output_cov: bool = True) -> torch.Tensor:
+        """``H_inner S H_innerᵀ`` (the default) or its diagonal."""
+        return self._inner_emission_model.project_state_covariance_to_f(covariance, full_output_cov)

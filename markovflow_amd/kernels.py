@@ -26,7 +26,11 @@ The latent exponentially generated kernel: ``LatentExponentiallyGenerated`` (``k
 trainable feedback matrix ``F = −½(N Nᵀ + R − Rᵀ)`` with ``P∞ = I``.  ``mf_sde_leg_transitions_*`` computes ``A_k = expm(Δt_k F)`` and
 ``chol Q_k`` by scaling and squaring on a group of lanes per step; ``mf_sde_leg_transitions_grad_*`` is its reverse mode.
 
-Nothing else of the reference's kernels package (Stack, FactorAnalysis, products of two Matérns) is mirrored.
+The factor-analysis kernel: ``FactorAnalysisKernel`` (``sde_kernel.py:881-941``) - ``P`` observed processes mixed from ``L`` independent
+latent kernels, ``f(t) = A(t) B g(t)``: the chain is ``IndependentMultiOutput``'s, the emission a ``ComposedPairEmissionModel``, and the
+loading matrix ``B`` a trainable hyper-parameter of the emission alone (no generator depends on it).
+
+Nothing else of the reference's kernels package (the Stack kernels, products of two Matérns) is mirrored.
 
 Hyper-parameters are plain tensors / floats (the reference wraps them in ``gpflow.Parameter``); a hyper-parameter may also
 carry ``batch_shape`` (one value per series), which the reference expresses with ``StackKernel``.
@@ -40,7 +44,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 import torch
 
 from . import _lib
-from .emission_model import EmissionModel
+from .emission_model import ComposedPairEmissionModel, EmissionModel
 from .gauss_markov import GaussMarkovDistribution
 from .state_space_model import StateSpaceModel
 
@@ -948,6 +952,86 @@ class IndependentMultiOutput(ConcatKernel):
         return EmissionModel(out)
 
 
+class FactorAnalysisKernel(ConcatKernel):
+    """Observed processes mixed linearly from independent latent GPs (sde_kernel.py:881-941): ``f(t) = A(t) B g(t)`` with ``g`` the
+    ``L = len(kernels)`` single-output children (the state is their concatenation, as ``IndependentMultiOutput``'s), ``A(t)`` a known,
+    possibly time-dependent ``[output_dim, L]`` weight matrix (``weight_function``) and ``B`` the ``[L, L]`` ``loading_matrix``: the
+    identity at construction, trainable unless ``trainable=False``.
+
+    ``loading_matrix`` is a hyper-parameter of the EMISSION, not of the chain: it is not among the leaves of ``_components()``, so
+    ``_needs_grad()`` keeps meaning "a hyper-parameter of the chain is under the tape", and ``SparseVariationalGaussianProcess``
+    trains it on its fused route.  What caches a quantity that depends on it keys on ``_emission_leaves()`` as well."""
+
+    def __init__(self, weight_function, kernels: List[SDEKernel], output_dim: int, trainable: bool = True, jitter: float = 0.0):
+        """
+        :param weight_function: time points ``batch + [num_data]`` -> weights ``batch + [num_data, output_dim, L]`` (a tensor of the
+            time points' dtype and device).
+        :param kernels: the ``L`` latent kernels, ``output_dim == 1`` each.
+        :param output_dim: the number of observed processes.
+        :param trainable: whether ``loading_matrix`` requires a gradient.
+        """
+        super().__init__(kernels, jitter)
+        if any(k.output_dim != 1 for k in kernels):
+            raise ValueError("FactorAnalysisKernel: every child kernel must have output_dim == 1 (one latent process each)")
+        if not callable(weight_function):
+            raise TypeError("FactorAnalysisKernel: weight_function must be callable")
+        assert output_dim > 0, "The output dimension must be positive"
+        self._latent_components = IndependentMultiOutput(kernels, jitter)
+        self._output_dim = int(output_dim)
+        self.latent_dim = self._latent_components.output_dim
+        self._weight_function = weight_function
+        ref = self._components()[0]._variance_t
+        self._loading_matrix = torch.eye(self.latent_dim, dtype=ref.dtype, device=ref.device).requires_grad_(bool(trainable))
+
+    @property
+    def loading_matrix(self) -> torch.Tensor:
+        """``B [L, L]``, a leaf tensor."""
+        return self._loading_matrix
+
+    @property
+    def trainable_variables(self) -> Tuple[torch.Tensor, ...]:
+        """``(loading_matrix,)`` when it is trainable (the children's hyper-parameters are plain tensors of their own)."""
+        return (self._loading_matrix,) if self._loading_matrix.requires_grad else ()
+
+    def _emission_leaves(self) -> Tuple[torch.Tensor, ...]:
+        """The hyper-parameters of the emission that are not hyper-parameters of the chain."""
+        return (self._loading_matrix,)
+
+    def mixing_weights(self, time_points: torch.Tensor) -> torch.Tensor:
+        """``W(t) = A(t) B``, ``time_points.shape + [output_dim, L]``, under the tape of ``loading_matrix`` and of whatever the weight
+        function holds."""
+        a = self._weight_function(time_points)
+        expected = tuple(time_points.shape) + (self._output_dim, self.latent_dim)
+        if not isinstance(a, torch.Tensor) or tuple(a.shape) != expected:
+            got = tuple(a.shape) if isinstance(a, torch.Tensor) else type(a).__name__
+            raise ValueError(f"FactorAnalysisKernel: weight_function returned {got}, expected a tensor of shape {expected} "
+                             "(time_points.shape + (output_dim, latent_dim))")
+        if a.dtype != time_points.dtype or a.device != time_points.device:
+            raise ValueError(f"FactorAnalysisKernel: weight_function returned a tensor of shape {tuple(a.shape)} with "
+                             f"{a.dtype} on {a.device}, expected the time points' {time_points.dtype} on {time_points.device}")
+        # (L scaled copies summed, not ``a @ B``: the backward of that product onto ``B`` is a GEMM with an L x L result whose inner
+        # dimension is every point and output of the batch, which the BLAS runs in ONE workgroup - 344 ms at B = 64, N = 10^4,
+        # P = 5 on an MI355X, beside 0.4 ms for the data term; here it is L reductions)
+        b = self._loading_matrix.to(dtype=a.dtype, device=a.device)
+        return sum(a[..., l:l + 1] * b[l] for l in range(self.latent_dim))
+
+    def latent_emission_model(self, time_points: torch.Tensor) -> EmissionModel:
+        """The emission of the latent processes ``g``: ``IndependentMultiOutput``'s on the children, ``[.., N, L, state_dim]``."""
+        return self._latent_components.generate_emission_model(time_points)
+
+    def generate_emission_model(self, time_points: torch.Tensor) -> ComposedPairEmissionModel:
+        """``H(t) = A(t) B (H_1 ⊕ H_2 ⊕ …)`` as a ``ComposedPairEmissionModel``."""
+        return ComposedPairEmissionModel(EmissionModel(self.mixing_weights(time_points)), self.latent_emission_model(time_points))
+
+
+def _refuse_factor_analysis(kernel, who: str) -> None:
+    """``FactorAnalysisKernel`` mixes several latents into several observed series: the models written for ONE observed series per
+    point refuse it."""
+    if isinstance(kernel, FactorAnalysisKernel):
+        raise NotImplementedError(f"{who} does not support a FactorAnalysisKernel (multi-output observations): use "
+                                  "SparseVariationalGaussianProcess or GaussianProcessRegression")
+
+
 ST_MAX_STATE_DIM = 64           # SparseSpatioTemporalKernel: Ms d_t, the range of the chain kernels and of mf_lik_st_expectations_*
 
 
@@ -966,6 +1050,7 @@ class SparseSpatioTemporalKernel(IndependentMultiOutput):
         if not isinstance(kernel_space, SpatialKernel):
             raise TypeError("kernel_space must be a markovflow_amd.spatial_kernels.SpatialKernel")
         _refuse_non_stationary_children("SparseSpatioTemporalKernel", [kernel_time])
+        _refuse_factor_analysis(kernel_time, "SparseSpatioTemporalKernel")
         if not isinstance(kernel_time, StationaryKernel) or kernel_time.output_dim != 1:
             raise TypeError("kernel_time must be a stationary markovflow_amd.kernels.SDEKernel with one output")
         if not isinstance(inducing_space, torch.Tensor) or inducing_space.dim() != 2 or inducing_space.shape[0] < 1:

@@ -38,11 +38,14 @@ from .. import _lib  # noqa: F401  (with ``KalmanFilter`` and the private names 
 from ..kalman_filter import KalmanFilter  # noqa: F401
 from ._common import back_project_nats, gradient_correction, gradient_transformation_mean_var_to_expectation
 from .gpr import GaussianProcessRegression
-from .segmented_ops import (IW_SAMPLE_CHUNK, SPARSE_EXPECT_TILE, SPARSE_SITE_MAX_TWO_D, _iw_log_weights_launch, _segments_of,
-                            _sparse_expectations_launch, _sparse_multi_expectations_launch, iw_log_likelihood, iw_log_likelihood_torch,
-                            iw_merged_time_points, pair_cavity, sparse_cvi_site_update_hip, sparse_cvi_site_update_torch,
-                            sparse_expectation_tiles, sparse_expected_log_likelihood, sparse_expected_log_likelihood_torch,
-                            sparse_multi_expected_log_likelihood, sparse_multi_expected_log_likelihood_torch,
+from .segmented_ops import (IW_SAMPLE_CHUNK, SPARSE_EXPECT_TILE, SPARSE_FACTOR_LATENTS, SPARSE_FACTOR_MAX_OUTPUTS, SPARSE_SITE_MAX_TWO_D,
+                            _iw_log_weights_launch, _segments_of, _sparse_expectations_launch, _sparse_factor_expectations_launch,
+                            _sparse_multi_expectations_launch, iw_log_likelihood, iw_log_likelihood_torch, iw_merged_time_points,
+                            pair_cavity, sparse_cvi_site_update_hip, sparse_cvi_site_update_torch, sparse_expectation_tiles,
+                            sparse_expected_log_likelihood, sparse_expected_log_likelihood_torch,
+                            sparse_factor_expected_log_likelihood, sparse_factor_expected_log_likelihood_torch,
+                            sparse_factor_site_projections, sparse_multi_expected_log_likelihood,
+                            sparse_multi_expected_log_likelihood_torch, sparse_multi_output_expected_log_likelihood_torch,
                             sparse_multi_site_projections, sparse_pep_site_update_hip, sparse_pep_site_update_torch,
                             sparse_site_projections)
 from .sites import CVIGaussianProcess, PowerExpectationPropagation

@@ -16,7 +16,7 @@ import torch
 
 from .. import _lib
 from ..kalman_filter import KalmanFilter
-from ..kernels import IndependentMultiOutput, SDEKernel, _MaternBase
+from ..kernels import FactorAnalysisKernel, IndependentMultiOutput, SDEKernel, _MaternBase
 from ..posterior import AnalyticPosteriorProcess
 from ..state_space_model import StateSpaceModel
 
@@ -251,7 +251,7 @@ class GaussianProcessRegression:
         multi = isinstance(self._kernel, IndependentMultiOutput)
         m = self._observations.shape[-1]
         d = self._kernel.state_dim
-        if not _all_matern(comps):
+        if not _all_matern(comps) or isinstance(self._kernel, FactorAnalysisKernel):     # (a mixed emission: the generic route)
             return None
         # register kernels (d <= 6): one or two components, one output; row kernels (7 <= d <= 15): any concatenation, one
         # output (Sum) or one per component (IndependentMultiOutput, up to four; eight for d >= 10) - BASELINE config 4 is 3 x Matern-5/2, 3 outputs
@@ -346,7 +346,7 @@ class GaussianProcessRegression:
         kernels do not apply (row signatures, several outputs, d > 6, short chains, gradients required)."""
         comps = self._kernel._components()
         d, m, n = self._kernel.state_dim, self._observations.shape[-1], self._time_points.shape[-1]
-        if not _all_matern(comps):
+        if not _all_matern(comps) or isinstance(self._kernel, FactorAnalysisKernel):
             return None
         if (not self.fused or not self.fused_backward or not self._observations.is_cuda or isinstance(self._kernel, IndependentMultiOutput)
                 or len(comps) > 2 or m != 1 or d > 6 or n <= 64):

@@ -13,6 +13,10 @@ forward launch wrote:
   * ``sparse_expected_log_likelihood(_torch)``: ``mf_lik_sparse_expectations_*`` (two passes, tile-parallel), the SVGP data term;
   * ``sparse_multi_expected_log_likelihood(_torch)``: ``mf_lik_sparse_multi_expectations_*``, the same term for a likelihood with
     several latent functions per observation (``sparse_multi_site_projections``: one dense projection per latent);
+  * ``sparse_factor_expected_log_likelihood(_torch)``: ``mf_lik_sparse_factor_expectations_*``, the same term for ``P`` observed series
+    per point mixed from the ``L`` latents of a ``FactorAnalysisKernel`` (``sparse_factor_site_projections``: the pair projected onto
+    the latents), with the adjoint onto the mixing weights; ``sparse_multi_output_expected_log_likelihood_torch``: the plain
+    multi-output term of any kernel with ``P`` outputs (torch only);
   * ``iw_log_likelihood(_torch)``: ``mf_lik_iw_log_weights_*`` (two passes, tile-parallel, no atomics), the data term of the
     importance weights with Matheron's correction assembled in the kernel.
 """
@@ -424,6 +428,157 @@ def sparse_multi_expected_log_likelihood_torch(likelihood: Likelihood, w: torch.
     hyper-parameter under the tape, and it is what ``mf_lik_sparse_multi_expectations_*`` is measured against."""
     fmu, fvar, flat = _sparse_multi_point_marginals(w, c, indices, pair_mean, pair_cov, pair_mean.shape[-2])
     ve = likelihood.variational_expectations(fmu, fvar, y[..., None])
+    out = torch.zeros(math.prod(pair_mean.shape[:-1]), dtype=ve.dtype, device=ve.device).index_add(0, flat, ve.reshape(-1))
+    return out.reshape(pair_mean.shape[:-1])
+
+
+# ---- SVGP with several observed series per point: multi-output kernels and the FactorAnalysis emission ------------------------------
+SPARSE_FACTOR_LATENTS = (2, 3, 4)   # mf_lik_sparse_factor_expectations_*: the instantiated latent_dim (2d even in 2 L ... 18)
+SPARSE_FACTOR_MAX_OUTPUTS = 1024    # ... and the largest number of observed series
+
+
+def sparse_multi_output_expected_log_likelihood_torch(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor,
+                                                      indices: torch.Tensor, pair_mean: torch.Tensor, pair_cov: torch.Tensor
+                                                      ) -> torch.Tensor:
+    """The SVGP data term for a kernel with ``P`` outputs and a likelihood with ONE latent function, applied per output:
+    ``sum_k sum_p E_q log p(y_kp | f_kp)`` per pair, ``batch + [M + 1]``, with ``fmu_p = w_kp . m_s`` and
+    ``fvar_p = c_kp + w_kp^T S_s w_kp`` from the dense rows ``w [.., N, P, 2d]``, ``c [.., N, P]`` of ``sparse_multi_site_projections``
+    and ``y [.., N, P]``.  A torch composition only (gathers, ``likelihood.variational_expectations``, ``index_add``), differentiable
+    by autograd in ``pair_mean``, ``pair_cov``, ``w`` and ``c``; it runs on CPU tensors.  It is the model's route for multi-output
+    observations on a kernel that is not a ``FactorAnalysisKernel``."""
+    _require_likelihood(likelihood)
+    _check_shapes("sparse_multi_output_expected_log_likelihood_torch", dict(c=(c, tuple(w.shape[:-1])), y=(y, tuple(w.shape[:-1]))))
+    fmu, fvar, flat = _sparse_multi_point_marginals(w, c, indices, pair_mean, pair_cov, pair_mean.shape[-2])
+    ve = torch.sum(likelihood.variational_expectations(fmu[..., None], fvar[..., None], y[..., None]), dim=-1)
+    out = torch.zeros(math.prod(pair_mean.shape[:-1]), dtype=ve.dtype, device=ve.device).index_add(0, flat, ve.reshape(-1))
+    return out.reshape(pair_mean.shape[:-1])
+
+
+def sparse_factor_site_projections(kernel, time_points: torch.Tensor, inducing_points: torch.Tensor
+                                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``sparse_site_projections`` onto the LATENT processes of a ``FactorAnalysisKernel`` with ``L`` latents: ``wg [.., N, L, 2d] =
+    H_inner P_k`` and the full ``cg [.., N, L, L] = H_inner T_k H_inner^T``, with the same ``indices`` and ``offsets``.  None of it
+    depends on the loading matrix or the weight function, so it is computed under ``no_grad`` and a model caches it."""
+    with torch.no_grad():
+        proj, cov, indices = conditionals._conditional_statistics(time_points, inducing_points, kernel)
+        h = kernel.latent_emission_model(time_points).emission_matrix                       # [.., N, L, d]
+        wg = h @ proj
+        cg = h @ cov @ h.transpose(-1, -2)
+        cg = 0.5 * (cg + cg.transpose(-1, -2))
+        return wg.contiguous(), cg.contiguous(), indices, _site_offsets(time_points, inducing_points)
+
+
+def _sparse_factor_check(what: str, likelihood, wg, cg, mix, y, lead, segs, pair_mean, pair_cov) -> None:
+    _require_likelihood(likelihood)
+    if wg.dim() < 3 or mix.dim() < 3:
+        raise ValueError(f"{what}: wg must have shape batch + [N, L, 2d] and mix batch + [N, P, L], got {tuple(wg.shape)} and "
+                         f"{tuple(mix.shape)}")
+    n, latents, two_d, outputs = wg.shape[-3], wg.shape[-2], wg.shape[-1], mix.shape[-2]
+    _check_shapes(what, dict(wg=(wg, lead + (n, latents, two_d)), cg=(cg, lead + (n, latents, latents)),
+                             mix=(mix, lead + (n, outputs, latents)), y=(y, lead + (n, outputs)),
+                             pair_mean=(pair_mean, lead + (segs, two_d)), pair_cov=(pair_cov, lead + (segs, two_d, two_d))))
+    _lib.same_dtype_device(wg, what, cg=cg, mix=mix, y=y, pair_mean=pair_mean, pair_cov=pair_cov)
+
+
+def _sparse_factor_expectations_launch(likelihood: Likelihood, wg, cg, mix, y, offsets, tiles, pair_mean, pair_cov, want_grads: bool,
+                                       want_g_w: bool):
+    """ONE call of ``mf_lik_sparse_factor_expectations_*``: ``(ve_sum [.., S], g_mean [.., S, 2d] | None, g_cov [.., S, 2d, 2d] | None,
+    g_w [.., N, P, L] | None)``."""
+    dtype, dev = wg.dtype, wg.device
+    n, latents, two_d, outputs, segs = wg.shape[-3], wg.shape[-2], wg.shape[-1], mix.shape[-2], offsets.shape[-1] - 1
+    batch = tuple(offsets.shape[:-1])
+    bsz = offsets.numel() // (segs + 1)
+    num_tiles, tile_seg, seg_tile = tiles
+    new = _new_outputs(batch, dtype, dev)
+    ve_sum, g_mean, g_cov = new(True, segs), new(want_grads, segs, two_d), new(want_grads, segs, two_d, two_d)
+    g_w = new(want_g_w, n, outputs, latents)
+    ws, ws_bytes = _workspace(_lib.load().mf_lik_sparse_factor_expectations_workspace_bytes, dev, num_tiles, two_d, wg.element_size())
+    _launch("mf_lik_sparse_factor_expectations", dtype, dev, bsz, n, segs, two_d, latents, outputs, *likelihood._kernel_args(), offsets,
+            wg, cg, mix, y, pair_mean, pair_cov, num_tiles, tile_seg, seg_tile, ws, ws_bytes, ve_sum, g_mean, g_cov, g_w)
+    return ve_sum, g_mean, g_cov, g_w
+
+
+class _SparseFactorExpectedLogLikelihood(torch.autograd.Function):
+    """Value ``batch + [M + 1]``; the adjoints onto the pair marginals and - when ``mix`` requires a gradient - onto the mixing weights
+    come out of the same launch and wait for the backward."""
+
+    @staticmethod
+    def forward(ctx, pair_mean, pair_cov, mix, likelihood, wg, cg, y, offsets, tiles):
+        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        want_w = ctx.needs_input_grad[2]
+        with torch.no_grad():
+            ve_sum, g_mean, g_cov, g_w = _sparse_factor_expectations_launch(likelihood, wg.detach(), cg.detach(), mix.detach(), y.detach(),
+                                                                            offsets, tiles, pair_mean.detach(), pair_cov.detach(), want,
+                                                                            want_w)
+        ctx.want, ctx.want_w = want, want_w
+        saved = ((g_mean, g_cov) if want else ()) + ((g_w, _segments_of(offsets, wg.shape[-3])) if want_w else ())
+        ctx.save_for_backward(*saved)
+        return ve_sum
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        _differentiable_once("sparse_factor_expected_log_likelihood", "adjoints")
+        saved = list(ctx.saved_tensors)
+        g_mean = g_cov = g_mix = None
+        if ctx.want:
+            g_mean, g_cov = saved[:2]
+            saved = saved[2:]
+        if ctx.want_w:
+            g_w, segment = saved
+            g_mix = torch.gather(grad_out, -1, segment)[..., None, None] * g_w       # every point takes its segment's cotangent
+        return (grad_out[..., None] * g_mean if ctx.needs_input_grad[0] else None,
+                grad_out[..., None, None] * g_cov if ctx.needs_input_grad[1] else None, g_mix, None, None, None, None, None, None)
+
+
+def sparse_factor_expected_log_likelihood(likelihood: Likelihood, wg: torch.Tensor, cg: torch.Tensor, mix: torch.Tensor,
+                                          y: torch.Tensor, offsets: torch.Tensor, pair_mean: torch.Tensor, pair_cov: torch.Tensor,
+                                          tiles=None) -> torch.Tensor:
+    """The SVGP data term under a FactorAnalysis emission, ``sum_k sum_p E_q log p(y_kp | f_kp)`` per pair of neighbouring inducing
+    states, ``batch + [M + 1]``: per point ``mu_g = wg m_s``, ``Sig_g = cg + wg S_s wg^T`` (``L`` projections of the pair), then per
+    observed series ``fmu_p = W_p . mu_g``, ``fvar_p = W_p Sig_g W_p^T`` with ``W = mix [.., N, P, L]`` and the likelihood's scalar
+    expectation at ``y [.., N, P]`` (``wg [.., N, L, 2d]``, ``cg [.., N, L, L]`` of ``sparse_factor_site_projections``): ONE call of
+    ``mf_lik_sparse_factor_expectations_*`` on HIP tensors, ``L`` in 2, 3, 4, ``2d`` even in ``2L ... 18``, ``P <= 1024``.
+    Differentiable ONCE in ``pair_mean``, ``pair_cov`` and ``mix``: the backward multiplies the adjoints the forward launch left
+    behind (the adjoint onto ``mix`` is asked of the kernel only when ``mix`` requires a gradient), there is no second launch.  Not
+    differentiable in ``wg`` and ``cg``.  ``tiles``: ``sparse_expectation_tiles(offsets)`` when the caller keeps it."""
+    what = "sparse_factor_expected_log_likelihood"
+    segs = offsets.shape[-1] - 1
+    _sparse_factor_check(what, likelihood, wg, cg, mix, y, tuple(offsets.shape[:-1]), segs, pair_mean, pair_cov)
+    latents, two_d, outputs = wg.shape[-2], wg.shape[-1], mix.shape[-2]
+    if (latents not in SPARSE_FACTOR_LATENTS or two_d > SPARSE_SITE_MAX_TWO_D or two_d < 2 * latents or two_d % 2
+            or not 1 <= outputs <= SPARSE_FACTOR_MAX_OUTPUTS):
+        raise NotImplementedError(f"{what}: L = {latents}, 2d = {two_d}, P = {outputs} is outside L in {SPARSE_FACTOR_LATENTS}, 2d even "
+                                  f"in 2L ... {SPARSE_SITE_MAX_TWO_D}, 1 <= P <= {SPARSE_FACTOR_MAX_OUTPUTS}; use "
+                                  "sparse_factor_expected_log_likelihood_torch")
+    if torch.is_grad_enabled() and (wg.requires_grad or cg.requires_grad):
+        raise NotImplementedError(f"{what} has no adjoint onto wg and cg (a hyper-parameter of the chain under the tape): use "
+                                  "sparse_factor_expected_log_likelihood_torch")
+    if tiles is None:
+        tiles = sparse_expectation_tiles(offsets)
+    return _SparseFactorExpectedLogLikelihood.apply(pair_mean, pair_cov, mix, likelihood, wg, cg, y, offsets, tiles)
+
+
+def sparse_factor_expected_log_likelihood_torch(likelihood: Likelihood, wg: torch.Tensor, cg: torch.Tensor, mix: torch.Tensor,
+                                                y: torch.Tensor, indices: torch.Tensor, pair_mean: torch.Tensor, pair_cov: torch.Tensor
+                                                ) -> torch.Tensor:
+    """The same quantity as a torch composition, differentiable by autograd in everything (``pair_mean``, ``pair_cov``, ``mix``,
+    ``wg``, ``cg``): gathers of the pair marginals by the per-point pair index (``indices [.., N]``), the two projections,
+    ``likelihood.variational_expectations`` per observed series and ``index_add`` over the segments.  It runs on CPU tensors, it is
+    the model's route for ``2d > 18``, for an ``L`` that is not instantiated and for a hyper-parameter of the chain under the tape, and
+    it is what ``mf_lik_sparse_factor_expectations_*`` is measured against."""
+    segs = pair_mean.shape[-2]
+    _sparse_factor_check("sparse_factor_expected_log_likelihood_torch", likelihood, wg, cg, mix, y, tuple(indices.shape[:-1]), segs,
+                         pair_mean, pair_cov)
+    two_d = wg.shape[-1]
+    m = torch.gather(pair_mean, -2, indices[..., None].expand(tuple(indices.shape) + (two_d,)))
+    cov = torch.gather(pair_cov, -3, indices[..., None, None].expand(tuple(indices.shape) + (two_d, two_d)))
+    mu_g = (wg @ m[..., None])[..., 0]                                                     # [.., N, L]
+    sig_g = cg + wg @ cov @ wg.transpose(-1, -2)                                           # [.., N, L, L]
+    fmu = (mix @ mu_g[..., None])[..., 0]                                                  # [.., N, P]
+    fvar = torch.sum((mix @ sig_g) * mix, dim=-1)
+    ve = torch.sum(likelihood.variational_expectations(fmu[..., None], fvar[..., None], y[..., None]), dim=-1)
+    series = torch.arange(math.prod(indices.shape[:-1]), device=indices.device).reshape(tuple(indices.shape[:-1]) + (1,))
+    flat = (indices + series * segs).reshape(-1)
     out = torch.zeros(math.prod(pair_mean.shape[:-1]), dtype=ve.dtype, device=ve.device).index_add(0, flat, ve.reshape(-1))
     return out.reshape(pair_mean.shape[:-1])
 

@@ -23,19 +23,22 @@ import math
 import torch
 
 from .. import _lib, conditionals
-from ..kernels import SDEKernel, _version_key
+from ..kernels import FactorAnalysisKernel, SDEKernel, _version_key
 from ..likelihoods import Likelihood
 from ..posterior import ConditionalProcess, ImportanceWeightedPosteriorProcess
 from ..ssm_gaussian_transformations import naturals_to_ssm_params
 from ..state_space_model import StateSpaceModel
-from ._common import (_PredictLogDensity, _refuse_non_stationary, _require_likelihood, gradient_correction,
+from ._common import (_PredictLogDensity, _refuse_factor_analysis, _refuse_non_stationary, _require_likelihood, gradient_correction,
                       gradient_transformation_mean_var_to_expectation)
-from .segmented_ops import (SPARSE_MULTI_MIN_TWO_D, SPARSE_SITE_MAX_TWO_D, _sparse_point_marginals, iw_log_likelihood,
-                            iw_log_likelihood_torch, iw_merged_time_points, pair_cavity, sparse_cvi_site_update_hip,
-                            sparse_cvi_site_update_torch, sparse_expectation_tiles, sparse_expected_log_likelihood,
-                            sparse_expected_log_likelihood_torch, sparse_multi_expected_log_likelihood,
-                            sparse_multi_expected_log_likelihood_torch, sparse_multi_site_projections, sparse_pep_site_update_hip,
-                            sparse_pep_site_update_torch, sparse_site_projections)
+from .segmented_ops import (SPARSE_FACTOR_LATENTS, SPARSE_FACTOR_MAX_OUTPUTS, SPARSE_MULTI_MIN_TWO_D, SPARSE_SITE_MAX_TWO_D,
+                            _sparse_point_marginals, iw_log_likelihood, iw_log_likelihood_torch, iw_merged_time_points, pair_cavity,
+                            sparse_cvi_site_update_hip, sparse_cvi_site_update_torch, sparse_expectation_tiles,
+                            sparse_expected_log_likelihood, sparse_expected_log_likelihood_torch,
+                            sparse_factor_expected_log_likelihood, sparse_factor_expected_log_likelihood_torch,
+                            sparse_factor_site_projections, sparse_multi_expected_log_likelihood,
+                            sparse_multi_expected_log_likelihood_torch, sparse_multi_output_expected_log_likelihood_torch,
+                            sparse_multi_site_projections, sparse_pep_site_update_hip, sparse_pep_site_update_torch,
+                            sparse_site_projections)
 
 
 class _SparseGaussianProcess(_PredictLogDensity):
@@ -43,11 +46,14 @@ class _SparseGaussianProcess(_PredictLogDensity):
     the cache of the per-point projections, the stationary prior beyond the ends of the chain and ``predict_log_density``."""
 
     _multi_latent = False      # True in the one model that projects a marginal per latent function of the likelihood
+    _multi_output = False      # True in the one model that takes one observed series per output of the kernel
 
     def __init__(self, kernel: SDEKernel, likelihood: Likelihood, inducing_points: torch.Tensor, min_inducing: int) -> None:
         if not isinstance(kernel, SDEKernel):
             raise TypeError("kernel must be a markovflow_amd.kernels.SDEKernel")
         _refuse_non_stationary(kernel, type(self).__name__)
+        if not self._multi_output:
+            _refuse_factor_analysis(kernel, type(self).__name__)
         _require_likelihood(likelihood, multi_latent=self._multi_latent)
         if likelihood.latent_dim > 1 and likelihood.latent_dim != kernel.output_dim:
             raise ValueError(f"the likelihood has latent_dim = {likelihood.latent_dim}, the kernel has output_dim = "
@@ -67,8 +73,13 @@ class _SparseGaussianProcess(_PredictLogDensity):
 
     def _check_data(self, input_data: Tuple[torch.Tensor, torch.Tensor], what: str) -> Tuple[torch.Tensor, torch.Tensor]:
         time_points, observations = input_data
-        if observations.dim() < 2 or observations.shape[-1] != 1:
-            raise ValueError(f"{what}: observations must have shape batch + [num_data, 1], got {tuple(observations.shape)}")
+        outputs = self._kernel.output_dim
+        # one observed series per output of the kernel: the one model that says so, a likelihood with ONE latent function
+        per_output = self._multi_output and outputs > 1 and self._likelihood.latent_dim == 1
+        if observations.dim() < 2 or not (observations.shape[-1] == 1 or (per_output and observations.shape[-1] == outputs)):
+            raise ValueError(f"{what}: observations must have shape batch + [num_data, 1]"
+                             + (f" or batch + [num_data, {outputs}] (one series per output of the kernel)" if per_output else "")
+                             + f", got {tuple(observations.shape)}")
         if tuple(time_points.shape) != tuple(observations.shape[:-1]):
             raise ValueError(f"{what}: time_points must have shape observations.shape[:-1]")
         if tuple(time_points.shape[:-1]) != tuple(self.inducing_inputs.shape[:-1]):
@@ -85,7 +96,8 @@ class _SparseGaussianProcess(_PredictLogDensity):
     def _projections(self, time_points: torch.Tensor):
         """``_compute_projections`` of the data, kept until the data, the inducing points or a hyper-parameter of the kernel is
         replaced or written in place (tensor identity, data pointer and version counter, as the filter caches)."""
-        sources = [time_points, self.inducing_inputs] + [x for comp in self._kernel._components() for x in comp._leaves()]
+        sources = ([time_points, self.inducing_inputs] + [x for comp in self._kernel._components() for x in comp._leaves()]
+                   + list(self._emission_sources()))
         key = tuple(_version_key(x) for x in sources)
         cached = self._projection_cache
         if (cached is not None and None not in key and cached[0] == key and len(cached[1]) == len(sources)
@@ -95,6 +107,11 @@ class _SparseGaussianProcess(_PredictLogDensity):
             out = self._compute_projections(time_points)
         self._projection_cache = (key, sources, out)
         return out
+
+    def _emission_sources(self) -> Tuple[torch.Tensor, ...]:
+        """The hyper-parameters of the kernel's emission that are not hyper-parameters of its chain (a ``FactorAnalysisKernel``'s
+        loading matrix): part of the key of ``_projections`` whenever the projections depend on them."""
+        return tuple(getattr(self._kernel, "_emission_leaves", tuple)())
 
     def _stationary_prior(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """``(m0, P0)`` of the kernel on the inducing points' batch, dtype and device: the outer neighbour of the first and the
@@ -433,9 +450,20 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
     A likelihood with ``L = latent_dim > 1`` latent functions (``MultiStageLikelihood``) takes a kernel with ``output_dim = L``
     (``IndependentMultiOutput``): the observations stay ``batch + [N, 1]``, every point is projected once per latent
     (``sparse_multi_site_projections``), the data term is ONE call of ``mf_lik_sparse_multi_expectations_*`` and ``predict_f`` returns
-    ``batch + [num_new, L]``."""
+    ``batch + [num_new, L]``.
+
+    A likelihood with ONE latent function on a kernel with ``P > 1`` outputs also takes observations ``batch + [N, P]``, one series
+    per output, the likelihood applied to each.  With a ``FactorAnalysisKernel`` (``f = A(t) B g``, ``L`` latents) the projections of
+    the pair onto the latents are cached (``sparse_factor_site_projections``; they do not depend on ``B``), the mixing weights
+    ``kernel.mixing_weights`` are evaluated on every ``elbo`` call under the tape, and the data term with its adjoints onto the pair
+    marginals AND the mixing weights is ONE call of ``mf_lik_sparse_factor_expectations_*`` (HIP tensors, ``L`` in 2, 3, 4,
+    ``2L <= 2d <= 18``, no hyper-parameter of the chain under the tape; otherwise ``sparse_factor_expected_log_likelihood_torch``):
+    the loading matrix trains on the fused path.  Any other multi-output kernel takes
+    ``sparse_multi_output_expected_log_likelihood_torch``.  Observations ``batch + [N, 1]`` keep the single-output path whatever the
+    kernel (a weight function's own parameters are seen on the ``[N, P]`` routes only)."""
 
     _multi_latent = True
+    _multi_output = True
 
     def __init__(self, kernel: SDEKernel, likelihood: Likelihood, inducing_points: torch.Tensor, num_data: Optional[int] = None,
                  initial_distribution: Optional[StateSpaceModel] = None) -> None:
@@ -445,6 +473,7 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
         :param initial_distribution: the initial ``q`` on the inducing points; the prior by default.
         """
         super().__init__(kernel, likelihood, inducing_points, min_inducing=2)
+        self._route = "multi" if likelihood.latent_dim > 1 else "single"    # (``_data_route`` of the data last seen)
         if num_data is not None and not num_data > 0:
             raise ValueError(f"num_data must be positive, got {num_data}")
         self.num_data = num_data
@@ -490,20 +519,70 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
         """A likelihood with several latent functions: the multi-latent projections and data term."""
         return self._likelihood.latent_dim > 1
 
+    def _data_route(self, observations: torch.Tensor) -> str:
+        """What the observations' last dimension selects: ``"single"`` (``[N, 1]``, one latent), ``"multi"`` (``[N, 1]``, a
+        multi-latent likelihood), ``"factor"`` (``[N, P]`` on a ``FactorAnalysisKernel``) or ``"outputs"`` (``[N, P]`` on any other
+        kernel with ``P`` outputs)."""
+        if observations.shape[-1] == 1:
+            return "multi" if self._multi else "single"
+        return "factor" if isinstance(self._kernel, FactorAnalysisKernel) else "outputs"
+
+    def _emission_needs_grad(self) -> bool:
+        """A hyper-parameter of the emission under the tape (the loading matrix of a ``FactorAnalysisKernel``)."""
+        return torch.is_grad_enabled() and any(x.requires_grad for x in super()._emission_sources())
+
+    def _emission_sources(self) -> Tuple[torch.Tensor, ...]:
+        # (the projections onto the latents of a FactorAnalysisKernel do not depend on its loading matrix: a step on it keeps them)
+        return () if self._route == "factor" else super()._emission_sources()
+
     def _fused(self, time_points: torch.Tensor) -> bool:
         two_d = 2 * self._kernel.state_dim
-        return (time_points.is_cuda and two_d <= SPARSE_SITE_MAX_TWO_D and not self._kernel._needs_grad()
-                and not (self._multi and two_d < SPARSE_MULTI_MIN_TWO_D))
+        if not (time_points.is_cuda and two_d <= SPARSE_SITE_MAX_TWO_D and not self._kernel._needs_grad()):
+            return False
+        if self._route == "factor":
+            latents = self._kernel.latent_dim
+            return latents in SPARSE_FACTOR_LATENTS and two_d >= 2 * latents and self._kernel.output_dim <= SPARSE_FACTOR_MAX_OUTPUTS
+        if self._route == "outputs":           # (no fused multi-output term for a kernel that is not a FactorAnalysisKernel)
+            return False
+        if self._route == "single":            # the loading matrix under the tape: w and c are part of the graph
+            return not self._emission_needs_grad()
+        return two_d >= SPARSE_MULTI_MIN_TWO_D
 
     def _compute_projections(self, time_points: torch.Tensor):
         """``(order | None, w, c, indices, offsets, tiles)`` of the data: the permutation that sorts each series (None for sorted
-        data), ``sparse_site_projections`` of the sorted points (``sparse_multi_site_projections`` for a multi-latent likelihood: ``w``
-        and ``c`` carry one row per latent) and the tile table."""
+        data), ``sparse_site_projections`` of the sorted points (``sparse_multi_site_projections`` for a multi-latent likelihood or
+        multi-output observations: ``w`` and ``c`` carry one row per latent or output; ``sparse_factor_site_projections`` for a
+        ``FactorAnalysisKernel`` with multi-output observations: ``wg``, ``cg`` of the latents) and the tile table."""
         order, time_points = _sorted_series(time_points)
-        project = sparse_multi_site_projections if self._multi else sparse_site_projections
+        project = {"single": sparse_site_projections, "multi": sparse_multi_site_projections,
+                   "outputs": sparse_multi_site_projections, "factor": sparse_factor_site_projections}[self._route]
         w, c, indices, offsets = project(self._kernel, time_points, self.inducing_inputs)
         tiles = sparse_expectation_tiles(offsets) if time_points.is_cuda else None
         return order, w, c, indices, offsets, tiles
+
+    def _multi_output_expected_log_likelihood(self, time_points: torch.Tensor, observations: torch.Tensor, pair_mean, pair_cov
+                                              ) -> torch.Tensor:
+        """The data term for observations ``batch + [N, P]``, ``P`` the kernel's output dimension."""
+        kernel, factor = self._kernel, self._route == "factor"
+        fused = self._fused(time_points)
+        if not fused and kernel._needs_grad():
+            # a hyper-parameter of the chain under the tape: the projections are part of the graph
+            order, x = _sorted_series(time_points)
+            proj, cov, indices = conditionals._conditional_statistics(x, self.inducing_inputs, kernel)
+            h = (kernel.latent_emission_model(x) if factor else kernel.generate_emission_model(x)).emission_matrix
+            w, c = h @ proj, (h @ cov @ h.transpose(-1, -2) if factor else torch.sum((h @ cov) * h, dim=-1))
+        else:
+            order, w, c, indices, offsets, tiles = self._projections(time_points)
+            x = time_points if order is None else torch.gather(time_points, -1, order)
+        y = observations
+        if order is not None:
+            y = torch.gather(y, -2, order[..., None].expand(y.shape))
+        if not factor:
+            return sparse_multi_output_expected_log_likelihood_torch(self._likelihood, w, c, y, indices, pair_mean, pair_cov)
+        mix = kernel.mixing_weights(x)             # on every call, under the tape of the loading matrix and the weight function
+        if fused:
+            return sparse_factor_expected_log_likelihood(self._likelihood, w, c, mix, y, offsets, pair_mean, pair_cov, tiles=tiles)
+        return sparse_factor_expected_log_likelihood_torch(self._likelihood, w, c, mix, y, indices, pair_mean, pair_cov)
 
     def _pair_marginals(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """``(m_pair [.., M+1, 2d], S_pair [.., M+1, 2d, 2d])`` of ``dist_q`` - under the tape when its leaves require a gradient -
@@ -514,6 +593,11 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
         """``sum_i E_q log p(y_i | f_i)`` per pair, ``batch + [M + 1]``."""
         pair_mean, pair_cov = self._pair_marginals()
         multi = self._multi
+        route = self._data_route(observations)
+        if route != self._route:                   # the cached projections are the other route's
+            self._route, self._projection_cache = route, None
+        if route in ("factor", "outputs"):
+            return self._multi_output_expected_log_likelihood(time_points, observations, pair_mean, pair_cov)
         if self._fused(time_points):
             order, w, c, _, offsets, tiles = self._projections(time_points)
             y = observations[..., 0]
@@ -521,7 +605,7 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
                 y = torch.gather(y, -1, order)
             fused = sparse_multi_expected_log_likelihood if multi else sparse_expected_log_likelihood
             return fused(self._likelihood, w, c, y, offsets, pair_mean, pair_cov, tiles=tiles)
-        if self._kernel._needs_grad():
+        if self._kernel._needs_grad() or self._emission_needs_grad():
             # a hyper-parameter under the tape: w and c are part of the graph
             order, time_points = _sorted_series(time_points)
             proj, cov, indices = conditionals._conditional_statistics(time_points, self.inducing_inputs, self._kernel)
@@ -559,11 +643,18 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
 
     def predict_f(self, new_time_points: torch.Tensor, full_output_cov: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
         """Posterior mean and variance of ``f`` at ``new_time_points`` (sorted), ``batch + [num_new, L]`` each, ``L`` the kernel's
-        output dimension (1 for every likelihood but a multi-latent one)."""
+        output dimension (1 unless the likelihood is a multi-latent one or the kernel has several outputs).  The latent processes
+        of a ``FactorAnalysisKernel``: ``posterior.predict_state`` and
+        ``kernel.latent_emission_model(t).project_state_marginals_to_f``."""
         with torch.no_grad():
             return self._posterior.predict_f(new_time_points, full_output_cov)
 
     _predict_f = predict_f          # (``predict_log_density`` predicts outside the tape here, as ``predict_f`` does)
+
+    def predict_log_density(self, input_data: Tuple[torch.Tensor, torch.Tensor], full_output_cov: bool = False) -> torch.Tensor:
+        if input_data[1].dim() >= 1 and input_data[1].shape[-1] != 1:
+            raise NotImplementedError("predict_log_density: observations with several outputs per point are not supported")
+        return super().predict_log_density(input_data, full_output_cov)
 
 
 class ImportanceWeightedVI(SparseVariationalGaussianProcess):
@@ -573,7 +664,8 @@ class ImportanceWeightedVI(SparseVariationalGaussianProcess):
     hyper-parameter under the tape their assembly, the ``K`` evaluations of the likelihood at every data point and the adjoint onto
     the draw from ``q`` are ONE call of ``mf_lik_iw_log_weights_*``."""
 
-    _multi_latent = False      # (the importance weights are written for one latent function)
+    _multi_latent = False      # (the importance weights are written for one latent function ...
+    _multi_output = False      # ... and one observed series)
 
     def __init__(self, kernel: SDEKernel, inducing_points: torch.Tensor, likelihood: Likelihood, num_importance_samples: int,
                  initial_distribution: Optional[StateSpaceModel] = None) -> None:
