@@ -1040,6 +1040,51 @@ int mf_lik_sparse_factor_expectations_f32(int64_t B, int64_t N, int64_t S, int t
                                           float* ve_sum, float* g_mean, float* g_cov, float* g_w, void* stream);
 
 /*
+ * The data term of the SVGP ELBO for a likelihood with K = latent_dim latent functions per observation on K STACKED chains, and its
+ * adjoints onto every chain's pair marginals (markovflow/kernels/sde_kernel.py:945-1279 and markovflow/emission_model.py:270-378
+ * under markovflow/models/sparse_variational.py:149-192; csrc/mf_lik_stack.hip).  Every latent has a chain of its own - K is the last
+ * batch dimension of the chains - and the K chains of a series share ONE segmentation: B series, N points, S = M + 1 segments,
+ * two_d = 2 d (d the padded state dimension), the rule, seg_offsets [B, S + 1] and the tile table over the B S segments as for
+ * mf_lik_sparse_expectations_*.  The data arrays are in the stacked layout, no transposes:
+ *   w [B, K, N, 2d]  row n of chain k: H_k P_kn        c [B, K, N]  H_k T_kn H_k^T        y [B, N]
+ *   pair_mean [B, K, S, 2d]        pair_cov [B, K, S, 2d, 2d]
+ * Per point n of segment s and latent k, ascending:  mu_k = w_kn . m_ks,  s2_k = c_kn + w_kn^T S_ks w_kn;  (ve, gm_k, gv_k) of the
+ * likelihood at (mu, s2, y_n);  per segment, over the points in ascending order,
+ *   ve_sum [B, S] = sum ve      g_mean [B, K, S, 2d] = sum gm_k w_kn      g_cov [B, K, S, 2d, 2d] = sum gv_k w_kn w_kn^T
+ * (g_cov symmetric, both triangles written from one sum).  lik = 4, latent_dim = 3 is the multi-stage likelihood of
+ * mf_lik_sparse_multi_expectations_* (the same evaluation); lik = 5, latent_dim = 2 is the heteroscedastic Gaussian
+ * y ~ N(F0, exp F1) in closed form: with e = exp(-mu_1 + s2_1 / 2) and E = e ((mu_0 - y)^2 + s2_0), ve = -(log 2 pi + mu_1 + E) / 2,
+ * gm_0 = -e (mu_0 - y), gv_0 = -e / 2, gm_1 = -(1 - E) / 2, gv_1 = -E / 4 (the rule is checked, not used).  Neither has parameters:
+ * params is not read.  A latent that the point's branch does not read has gm = gv = 0 and its s2 is not examined; one that it reads
+ * with s2 <= 0 or NaN makes ve_sum [b, s], g_mean [b, :, s] and g_cov [b, :, s] NaN - all K chains of that segment, no other
+ * segment.  The heteroscedastic Gaussian reads both latents at every point.  The zero columns of w in the padded state dimensions
+ * of a chain shorter than d are multiplied through.
+ * Pass 1 is one wavefront per tile of 64 points (LDS: 64 rows of K 2d + 1 elements, the K pair marginals, 2 K + 1 rows of 64 values:
+ * 39952 B at K = 3, 2d = 18 in float64); a workspace row is K (2d (2d + 1) / 2 + 2d) + 1 values - per latent the lower triangle of
+ * g_cov and g_mean, then sum ve - and pass 2 adds a segment's rows in ascending tile order.  The workspace holds
+ * mf_lik_stack_expectations_workspace_bytes(num_tiles, two_d, latent_dim, sizeof(T)) bytes (0 for an argument out of range).
+ * g_mean and g_cov BOTH NULL: the value only (the same bits); ve_sum NULL: the adjoints only (the same bits).  Empty segments and
+ * N = 0 give exact zeros.  No floating-point atomics: the same bits on every launch and for a series alone or inside a batch.
+ * The tile table is clamped on the device, not validated.  No allocation, no synchronisation.
+ * Returns 0, -(position of the offending argument in THIS signature: 1 B, 3 N, 4 S, 8 nq, 9 nodes, 10 weights, 11 ... 16 a NULL
+ * input, 17 num_tiles negative, above 2^31 - 1 or non-zero for N = 0, 18 / 19 a NULL table, 20 a NULL workspace, 21 a workspace
+ * that is too small, 23 / 24 one of g_mean / g_cov NULL without the other), -101 for a (two_d, latent_dim, lik) that is not
+ * instantiated - two_d in 2, 4, ..., 18 with (latent_dim, lik) = (3, 4) or (2, 5) are - or -1000 (launch failed).  Nothing is
+ * launched and nothing written on an error, for B = 0, or when every output is NULL.
+ */
+size_t mf_lik_stack_expectations_workspace_bytes(int64_t num_tiles, int two_d, int latent_dim, int elem_size);
+int mf_lik_stack_expectations_f64(int64_t B, int latent_dim, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq,
+                                  const double* nodes, const double* weights, const int64_t* seg_offsets, const double* w,
+                                  const double* c, const double* y, const double* pair_mean, const double* pair_cov,
+                                  int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile, void* workspace,
+                                  size_t workspace_bytes, double* ve_sum, double* g_mean, double* g_cov, void* stream);
+int mf_lik_stack_expectations_f32(int64_t B, int latent_dim, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq,
+                                  const double* nodes, const double* weights, const int64_t* seg_offsets, const float* w,
+                                  const float* c, const float* y, const float* pair_mean, const float* pair_cov,
+                                  int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile, void* workspace,
+                                  size_t workspace_bytes, float* ve_sum, float* g_mean, float* g_cov, void* stream);
+
+/*
  * The segmented site update of the sparse power-EP model (markovflow/models/sparse_pep.py:316-487; csrc/mf_lik.hip): B, N, S,
  * two_d, the likelihood, the rule, seg_offsets, w, c, y, the tile table and the workspace as for mf_lik_sparse_expectations_*;
  * alpha in (0, 1] is the power, lr in [0, 1] the damping.  The workspace row has the width of that entry point's, so its size is

@@ -6,7 +6,7 @@ Drop-in for the hot path of secondmind-labs/markovflow (``kalman_filter.py``, ``
 torch HIP tensors in place of TensorFlow tensors, hand-written gfx950 kernels underneath.
 """
 from .block_tri_diag import BlockTriDiagonal, LowerTriangularBlockTriDiagonal, SymmetricBlockTriDiagonal
-from .emission_model import ComposedPairEmissionModel, EmissionModel
+from .emission_model import ComposedPairEmissionModel, EmissionModel, StackEmissionModel
 from .gauss_markov import GaussMarkovDistribution, check_compatible
 from .kalman_filter import (
     BaseKalmanFilter,
@@ -18,9 +18,9 @@ from .kalman_filter import (
 )
 from .state_space_model import StateSpaceModel, state_space_model_from_covariances
 from . import conditionals, distributed, kernels, likelihoods, mean_function, models, sde, spatial_kernels, ssm_gaussian_transformations, ssm_natgrad
-from .kernels import (Constant, FactorAnalysisKernel, HarmonicOscillator, IndependentMultiOutput, LatentExponentiallyGenerated, Matern12, Matern32, Matern52, NonStationaryKernel,
-                      PiecewiseKernel, Product, SDEKernel, SparseSpatioTemporalKernel, StationaryKernel, Sum)
-from .likelihoods import Bernoulli, Gaussian, Likelihood, MultiStageLikelihood, Poisson, StudentT
+from .kernels import (Constant, FactorAnalysisKernel, HarmonicOscillator, IndependentMultiOutput, IndependentMultiOutputStack, LatentExponentiallyGenerated, Matern12, Matern32, Matern52, NonStationaryKernel,
+                      PiecewiseKernel, Product, SDEKernel, SparseSpatioTemporalKernel, StackKernel, StationaryKernel, Sum)
+from .likelihoods import Bernoulli, Gaussian, HeteroscedasticGaussian, Likelihood, MultiStageLikelihood, Poisson, StudentT
 from .mean_function import ImpulseMeanFunction, LinearMeanFunction, MeanFunction, StepMeanFunction, ZeroMeanFunction
 from .models import (CVIGaussianProcess, GaussianProcessRegression, ImportanceWeightedVI, PowerExpectationPropagation,
                      SparseCVIGaussianProcess, SparsePowerExpectationPropagation, SparseVariationalGaussianProcess,
@@ -38,7 +38,7 @@ __all__ = [
     "state_space_model_from_covariances", "conditionals", "distributed", "kernels", "models", "ssm_gaussian_transformations", "SDEKernel", "StationaryKernel", "Matern12", "Matern32",
     "Matern52", "Sum", "IndependentMultiOutput", "FactorAnalysisKernel", "ComposedPairEmissionModel", "Constant", "HarmonicOscillator", "Product", "GaussianProcessRegression", "AnalyticPosteriorProcess", "ConditionalProcess",
     "MarkovflowAmdError", "check_errors", "errors_as_nan", "set_synchronous_checks",
-    "likelihoods", "Likelihood", "Gaussian", "Bernoulli", "Poisson", "StudentT", "MultiStageLikelihood", "CVIGaussianProcess", "PowerExpectationPropagation",
+    "likelihoods", "Likelihood", "Gaussian", "Bernoulli", "Poisson", "StudentT", "MultiStageLikelihood", "HeteroscedasticGaussian", "StackKernel", "IndependentMultiOutputStack", "StackEmissionModel", "CVIGaussianProcess", "PowerExpectationPropagation",
     "SparseCVIGaussianProcess", "SparseVariationalGaussianProcess", "SSMNaturalGradient", "ssm_natgrad",
     "SparsePowerExpectationPropagation", "ImportanceWeightedVI", "ImportanceWeightedPosteriorProcess",
     "VariationalGaussianProcess", "spatial_kernels", "SparseSpatioTemporalKernel", "SpatioTemporalSparseVariational", "SpatioTemporalSparseCVI",

@@ -92,6 +92,8 @@ _SIGS = {
                                          _i64, _vp, _vp, _vp, _sz, "Tp", "Tp", "Tp", _vp]),
     "mf_lik_sparse_factor_expectations": (_int, [_i64, _i64, _i64, _int, _int, _i64, _int, _hd, _int, _hd, _hd, _vp, "Tp", "Tp", "Tp", "Tp",
                                           "Tp", "Tp", _i64, _vp, _vp, _vp, _sz, "Tp", "Tp", "Tp", "Tp", _vp]),
+    "mf_lik_stack_expectations": (_int, [_i64, _int, _i64, _i64, _int, _int, _hd, _int, _hd, _hd, _vp, "Tp", "Tp", "Tp", "Tp", "Tp", _i64, _vp,
+                                  _vp, _vp, _sz, "Tp", "Tp", "Tp", _vp]),
     "mf_lik_multistage_variational_expectations": (_int, [_i64, _int, _hd, _hd, "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_sparse_pep_site_update": (_int, [_i64, _i64, _i64, _int, _int, _hd, _int, _hd, _hd, "T", "T", _vp, "Tp", "Tp", "Tp", "Tp",
                                       "Tp", "Tp", _i64, _vp, _vp, _vp, _sz, "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
@@ -142,6 +144,7 @@ _PLAIN = {
     "mf_lik_sparse_expectations_workspace_bytes": (_sz, [_i64, _int, _int]),
     "mf_lik_sparse_multi_expectations_workspace_bytes": (_sz, [_i64, _int, _int]),
     "mf_lik_sparse_factor_expectations_workspace_bytes": (_sz, [_i64, _int, _int]),
+    "mf_lik_stack_expectations_workspace_bytes": (_sz, [_i64, _int, _int, _int]),
     "mf_lik_iw_log_weights_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
     "mf_lik_dense_expectations_workspace_bytes": (_sz, [_i64, _i64, _int]),
     "mf_lik_st_expectations_workspace_bytes": (_sz, [_i64, _int, _int, _int]),

@@ -560,19 +560,21 @@ class MultiStageLikelihood(Likelihood):
 
 
 class _MultiStageVariationalExpectations(torch.autograd.Function):
-    """Value ``batch + [N]`` with the six derivatives per point computed in the same pass and saved for the backward."""
+    """Value ``batch + [N]`` with the ``2 latent_dim`` derivatives per point computed in the same pass and saved for the backward
+    (``MultiStageLikelihood``, ``HeteroscedasticGaussian``)."""
 
     @staticmethod
     def forward(ctx, fmu, fvar, y, lik):
         with torch.no_grad():
             ve, g_mu, g_var = lik._expectations(fmu.detach(), fvar.detach(), y.detach())
         ctx.save_for_backward(g_mu, g_var)
+        ctx.who = type(lik).__name__
         return ve
 
     @staticmethod
     def backward(ctx, grad_out):
         if torch.is_grad_enabled():
-            raise RuntimeError("MultiStageLikelihood.variational_expectations is differentiable once: its backward uses the "
+            raise RuntimeError(f"{ctx.who}.variational_expectations is differentiable once: its backward uses the "
                                "derivatives computed in the forward and has no second-order support (create_graph=True)")
         g_mu, g_var = ctx.saved_tensors
         return grad_out[..., None] * g_mu, grad_out[..., None] * g_var, None, None
@@ -593,3 +595,78 @@ def torch_multistage_variational_expectations(lik: MultiStageLikelihood, fmu: to
     count = torch_variational_expectations(lik._poisson, mu[..., 2:], var[..., 2:], torch.where(is2, obs - 2.0, torch.zeros_like(obs))[..., None])
     ve, g_mu, g_var = (torch.where(read, torch.cat([s, c], dim=-1), torch.zeros_like(fmu)) for s, c in zip(stage, count))
     return (ve[..., 0] + ve[..., 1]) + ve[..., 2], g_mu, g_var
+
+
+class HeteroscedasticGaussian(Likelihood):
+    """A Gaussian whose mean AND log-variance are latent functions (the second half of the reference's stacked-kernels notebook):
+    ``latent_dim = 2``, ``F = [F0, F1]``, ``y ~ N(F0, exp(F1))``; tensors ``batch + [N, 2]`` for the latents and ``batch + [N, 1]`` for
+    the observations.  Everything is in closed form: with ``E = exp(-m1 + v1 / 2) ((m0 - y)^2 + v0)``,
+
+        E_q log p(y | F) = -(log 2 pi + m1 + E) / 2
+
+    with the derivatives ``-exp(-m1 + v1 / 2) (m0 - y)``, ``-exp(-m1 + v1 / 2) / 2`` (latent 0: mean, variance) and ``-(1 - E) / 2``,
+    ``-E / 4`` (latent 1).  Both latents are read at every point: a variance that is ``<= 0`` or NaN makes the point's value and all
+    four derivatives NaN.  No parameters; the quadrature rule is not used.  On stacked chains (``IndependentMultiOutputStack``) the
+    SVGP data term of this likelihood is ONE call of ``mf_lik_stack_expectations_*``."""
+
+    _id = 5
+    latent_dim = 2
+
+    _check = MultiStageLikelihood._check
+
+    def log_prob(self, f: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """``log N(y | F0, exp F1)``, ``batch + [N, 2]``, ``batch + [N, 1] -> batch + [N]``."""
+        self._check("log_prob", f, y=y)
+        r = y[..., 0] - f[..., 0]
+        return -0.5 * (math.log(2.0 * math.pi) + f[..., 1] + r * r * torch.exp(-f[..., 1]))
+
+    def variational_expectations(self, fmu: torch.Tensor, fvar: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """``E_{N(F0 | m0, v0) N(F1 | m1, v1)} log p(y | F)``, ``batch + [N]``.  Differentiable ONCE in ``fmu`` and ``fvar``: the four
+        derivatives per point are computed beside the value and saved (no second-order support)."""
+        self._check("variational_expectations", fmu, y=y, fvar=fvar)
+        return _MultiStageVariationalExpectations.apply(fmu, fvar, y, self)
+
+    def _expectations(self, fmu, fvar, y):
+        """``(VE [.., N], dVE/dmu [.., N, 2], dVE/dvar [.., N, 2])`` in closed form: element-wise torch on either device."""
+        m0, m1, v0, v1 = fmu[..., 0], fmu[..., 1], fvar[..., 0], fvar[..., 1]
+        r = m0 - y[..., 0]
+        e = torch.exp(0.5 * v1 - m1)
+        big = e * (r * r + v0)
+        ve = -0.5 * (math.log(2.0 * math.pi) + m1 + big)
+        g_mu = torch.stack([-e * r, -0.5 * (1.0 - big)], dim=-1)
+        g_var = torch.stack([-0.5 * e, -0.25 * big], dim=-1)
+        bad = ~((v0 > 0) & (v1 > 0))
+        nan = float("nan")
+        return ve.masked_fill(bad, nan), g_mu.masked_fill(bad[..., None], nan), g_var.masked_fill(bad[..., None], nan)
+
+    def predict_mean_and_var(self, fmu: torch.Tensor, fvar: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(m0, v0 + E exp F1) = (m0, v0 + exp(m1 + v1 / 2))``, ``batch + [N, 1]`` each."""
+        self._check("predict_mean_and_var", fmu, fvar=fvar)
+        return fmu[..., :1], fvar[..., :1] + torch.exp(fmu[..., 1:] + 0.5 * fvar[..., 1:])
+
+    def predict_log_density(self, fmu, fvar, y):
+        """Not available: the predictive density of a Gaussian with a log-normal variance has no closed form."""
+        raise NotImplementedError("HeteroscedasticGaussian has no predictive density in closed form")
+
+    def _one_latent_only(self, *args, **kwargs):
+        raise NotImplementedError("HeteroscedasticGaussian has two latent functions: the site updates and the power-EP densities "
+                                  "are written for one; use SparseVariationalGaussianProcess")
+
+    cvi_site_update = log_expected_density = grad_log_expected_density = pep_site_update = _one_latent_only
+
+    def sample_y(self, F_samples: torch.Tensor, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """Observations drawn from ``p(y | F)``, ``batch + [2] -> batch + [1]``."""
+        if F_samples.dim() < 1 or F_samples.shape[-1] != self.latent_dim:
+            raise ValueError(f"HeteroscedasticGaussian.sample_y: F_samples must have shape batch + [2], got {tuple(F_samples.shape)}")
+        if F_samples.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"markovflow_amd supports float32 and float64 tensors, got {F_samples.dtype}")
+        noise = torch.randn(F_samples.shape[:-1], dtype=F_samples.dtype, device=F_samples.device, generator=generator)
+        return (F_samples[..., 0] + torch.exp(0.5 * F_samples[..., 1]) * noise)[..., None]
+
+
+def torch_heteroscedastic_variational_expectations(fmu: torch.Tensor, fvar: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """The statement of ``HeteroscedasticGaussian.variational_expectations`` in plain torch operations, ``batch + [N]``,
+    differentiable by autograd to any order (no domain rule): what the closed-form derivatives are checked against."""
+    r = fmu[..., 0] - y[..., 0]
+    big = torch.exp(0.5 * fvar[..., 1] - fmu[..., 1]) * (r * r + fvar[..., 0])
+    return -0.5 * (math.log(2.0 * math.pi) + fmu[..., 1] + big)

@@ -36,7 +36,7 @@ import torch
 
 from . import _lib
 from .kernels import (Constant, IndependentMultiOutput, LatentExponentiallyGenerated, NonStationaryKernel, Product, SDEKernel,
-                      SparseSpatioTemporalKernel, Sum, _MaternBase, to_delta_time)
+                      SparseSpatioTemporalKernel, Sum, _MaternBase, _refuse_stack, to_delta_time)
 from .models._common import _differentiable_once, _launch, _workspace
 
 fused = True    # set False to force the torch route (the same mathematics in differentiable torch operations)
@@ -167,6 +167,7 @@ class _ResponseMeanFunction(MeanFunction):
                                       "has no single feedback matrix to propagate the actions with")
         if isinstance(kernel, SparseSpatioTemporalKernel):
             raise NotImplementedError(f"{who} does not support a SparseSpatioTemporalKernel")
+        _refuse_stack(kernel, who)
         if not (isinstance(action_times, torch.Tensor) and isinstance(state_perturbations, torch.Tensor)):
             raise TypeError(f"{who}: action_times and state_perturbations must be tensors")
         if state_perturbations.dim() < 2 or tuple(action_times.shape) != tuple(state_perturbations.shape[:-1]):

@@ -18,7 +18,8 @@ components the kernel -> state space model step is fused into the sweep, ``mf_gp
 ``mf_lik_sparse_pep_site_update_*``.
 
 ``SparseVariationalGaussianProcess`` (``sparse.py``): SVGP, ``q`` a trainable chain on the inducing points;
-``mf_lik_sparse_expectations_*``.
+``mf_lik_sparse_expectations_*``; on the stacked chains of an ``IndependentMultiOutputStack`` with a multi-latent likelihood,
+``mf_lik_stack_expectations_*``.
 
 ``ImportanceWeightedVI`` (``sparse.py``): SVGP with the importance-weighted bound, proposals by Matheron's rule;
 ``mf_lik_iw_log_weights_*``.
@@ -47,7 +48,8 @@ from .segmented_ops import (IW_SAMPLE_CHUNK, SPARSE_EXPECT_TILE, SPARSE_FACTOR_L
                             sparse_factor_site_projections, sparse_multi_expected_log_likelihood,
                             sparse_multi_expected_log_likelihood_torch, sparse_multi_output_expected_log_likelihood_torch,
                             sparse_multi_site_projections, sparse_pep_site_update_hip, sparse_pep_site_update_torch,
-                            sparse_site_projections)
+                            sparse_site_projections, sparse_stack_expected_log_likelihood,
+                            sparse_stack_expected_log_likelihood_torch)
 from .sites import CVIGaussianProcess, PowerExpectationPropagation
 from .sparse import (ImportanceWeightedVI, SparseCVIGaussianProcess, SparsePowerExpectationPropagation,
                      SparseVariationalGaussianProcess, _SparseSitesGaussianProcess)

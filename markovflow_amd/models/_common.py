@@ -9,7 +9,7 @@ from typing import Tuple
 import torch
 
 from .. import _lib
-from ..kernels import NonStationaryKernel, SDEKernel, _refuse_factor_analysis  # noqa: F401  (the models import it from here)
+from ..kernels import NonStationaryKernel, SDEKernel, _refuse_factor_analysis, _refuse_stack  # noqa: F401  (the models import them from here)
 from ..likelihoods import Likelihood
 
 

@@ -13,6 +13,8 @@ forward launch wrote:
   * ``sparse_expected_log_likelihood(_torch)``: ``mf_lik_sparse_expectations_*`` (two passes, tile-parallel), the SVGP data term;
   * ``sparse_multi_expected_log_likelihood(_torch)``: ``mf_lik_sparse_multi_expectations_*``, the same term for a likelihood with
     several latent functions per observation (``sparse_multi_site_projections``: one dense projection per latent);
+  * ``sparse_stack_expected_log_likelihood(_torch)``: ``mf_lik_stack_expectations_*``, the same term on ``K`` STACKED chains
+    (``IndependentMultiOutputStack``: ``w [.., K, N, 2d]``, one pair marginal of ``2d`` per chain, not one of ``K 2d``);
   * ``sparse_factor_expected_log_likelihood(_torch)``: ``mf_lik_sparse_factor_expectations_*``, the same term for ``P`` observed series
     per point mixed from the ``L`` latents of a ``FactorAnalysisKernel`` (``sparse_factor_site_projections``: the pair projected onto
     the latents), with the adjoint onto the mixing weights; ``sparse_multi_output_expected_log_likelihood_torch``: the plain
@@ -430,6 +432,135 @@ def sparse_multi_expected_log_likelihood_torch(likelihood: Likelihood, w: torch.
     ve = likelihood.variational_expectations(fmu, fvar, y[..., None])
     out = torch.zeros(math.prod(pair_mean.shape[:-1]), dtype=ve.dtype, device=ve.device).index_add(0, flat, ve.reshape(-1))
     return out.reshape(pair_mean.shape[:-1])
+
+
+# ---- SVGP with several latent functions per observation on STACKED chains (IndependentMultiOutputStack) ----------------------------
+SPARSE_STACK_SIGNATURES = ((3, 4), (2, 5))      # mf_lik_stack_expectations_*: the instantiated (latent_dim, likelihood id)
+
+
+def sparse_stack_instantiated(likelihood: Likelihood, latents: int, two_d: int) -> bool:
+    """Whether ``mf_lik_stack_expectations_*`` is instantiated for this likelihood on ``latents`` chains of ``2d = two_d``."""
+    return ((latents, likelihood._id) in SPARSE_STACK_SIGNATURES and latents == likelihood.latent_dim
+            and 2 <= two_d <= SPARSE_SITE_MAX_TWO_D and two_d % 2 == 0)
+
+
+def _sparse_stack_check(what: str, likelihood, w, c, y, lead, segs, pair_mean, pair_cov, segmentation, per_chain: bool) -> None:
+    _require_likelihood(likelihood, multi_latent=True)
+    if w.dim() < 3:
+        raise ValueError(f"{what}: w must have shape batch + [K, N, 2d], got {tuple(w.shape)}")
+    latents, n, two_d = w.shape[-3], w.shape[-2], w.shape[-1]
+    if latents != likelihood.latent_dim or latents < 2:
+        raise ValueError(f"{what}: w carries {latents} chains, the likelihood has latent_dim = {likelihood.latent_dim} (a likelihood "
+                         "with one latent takes sparse_expected_log_likelihood on the batch of chains)")
+    name, seg = segmentation
+    _check_shapes(what, {"w": (w, lead + (latents, n, two_d)), "c": (c, lead + (latents, n)), "y": (y, lead + (n,)),
+                         "pair_mean": (pair_mean, lead + (latents, segs, two_d)),
+                         "pair_cov": (pair_cov, lead + (latents, segs, two_d, two_d))})
+    if per_chain and tuple(seg.shape) not in (lead + (n,), lead + (latents, n)):
+        raise ValueError(f"{what}: {name} has shape {tuple(seg.shape)}, expected {lead + (n,)} or {lead + (latents, n)}")
+    if not per_chain and tuple(seg.shape) != lead + (segs + 1,):
+        raise ValueError(f"{what}: {name} has shape {tuple(seg.shape)}, expected {lead + (segs + 1,)}")
+    _lib.same_dtype_device(w, what, c=c, y=y, pair_mean=pair_mean, pair_cov=pair_cov)
+
+
+def _sparse_stack_expectations_launch(likelihood: Likelihood, w, c, y, offsets, tiles, pair_mean, pair_cov, want_grads: bool):
+    """ONE call of ``mf_lik_stack_expectations_*``: ``(ve_sum [.., S], g_mean [.., K, S, 2d] | None, g_cov [.., K, S, 2d, 2d] | None)``."""
+    dtype, dev = w.dtype, w.device
+    latents, n, two_d, segs = w.shape[-3], w.shape[-2], w.shape[-1], offsets.shape[-1] - 1
+    lead = tuple(offsets.shape[:-1])
+    bsz = offsets.numel() // (segs + 1)
+    num_tiles, tile_seg, seg_tile = tiles
+    ve_sum = torch.empty(lead + (segs,), dtype=dtype, device=dev)
+    new = _new_outputs(lead + (latents,), dtype, dev)
+    g_mean, g_cov = new(want_grads, segs, two_d), new(want_grads, segs, two_d, two_d)
+    ws, ws_bytes = _workspace(_lib.load().mf_lik_stack_expectations_workspace_bytes, dev, num_tiles, two_d, latents, w.element_size())
+    _launch("mf_lik_stack_expectations", dtype, dev, bsz, latents, n, segs, two_d, *likelihood._kernel_args(), offsets, w, c, y,
+            pair_mean, pair_cov, num_tiles, tile_seg, seg_tile, ws, ws_bytes, ve_sum, g_mean, g_cov)
+    return ve_sum, g_mean, g_cov
+
+
+class _SparseStackExpectedLogLikelihood(torch.autograd.Function):
+    """Value ``lead + [M + 1]``; the adjoints onto the ``K`` chains' pair marginals come out of the same launch and wait for the
+    backward."""
+
+    @staticmethod
+    def forward(ctx, pair_mean, pair_cov, likelihood, w, c, y, offsets, tiles):
+        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        with torch.no_grad():
+            ve_sum, g_mean, g_cov = _sparse_stack_expectations_launch(likelihood, w.detach(), c.detach(), y.detach(), offsets, tiles,
+                                                                      pair_mean.detach(), pair_cov.detach(), want)
+        if want:
+            ctx.save_for_backward(g_mean, g_cov)
+        return ve_sum
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        _differentiable_once("sparse_stack_expected_log_likelihood", "adjoints")
+        g_mean, g_cov = ctx.saved_tensors
+        g = grad_out[..., None, :]                  # a segment's cotangent goes to every chain of it
+        return (g[..., None] * g_mean if ctx.needs_input_grad[0] else None,
+                g[..., None, None] * g_cov if ctx.needs_input_grad[1] else None, None, None, None, None, None, None)
+
+
+def sparse_stack_expected_log_likelihood(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor,
+                                         offsets: torch.Tensor, pair_mean: torch.Tensor, pair_cov: torch.Tensor, tiles=None
+                                         ) -> torch.Tensor:
+    """The SVGP data term of a likelihood with ``K = likelihood.latent_dim > 1`` latent functions on ``K`` STACKED chains that share
+    one segmentation, ``sum_n E_q log p(y_n | f_n)`` per pair of neighbouring inducing points, ``lead + [M + 1]``: per point and
+    latent ``fmu_k = w_kn . m_ks`` and ``fvar_k = c_kn + w_kn^T S_ks w_kn`` with the pair marginals of chain ``k``
+    (``w [.., K, N, 2d]``, ``c [.., K, N]`` - ``sparse_site_projections`` on the stacked batch -, ``y [.., N]``,
+    ``offsets [.., M + 2]``, ``pair_mean [.., K, M + 1, 2d]``, ``pair_cov [.., K, M + 1, 2d, 2d]``): ONE call of
+    ``mf_lik_stack_expectations_*`` on HIP tensors, ``2d <= 18``, ``MultiStageLikelihood`` (``K = 3``) or ``HeteroscedasticGaussian``
+    (``K = 2``).  Differentiable ONCE in ``pair_mean`` and ``pair_cov`` (the backward multiplies the adjoints the forward computed
+    beside the value, there is no second launch); not differentiable in ``w`` and ``c``.  ``tiles``:
+    ``sparse_expectation_tiles(offsets)`` when the caller keeps it."""
+    what = "sparse_stack_expected_log_likelihood"
+    segs = offsets.shape[-1] - 1
+    lead = tuple(offsets.shape[:-1])
+    _sparse_stack_check(what, likelihood, w, c, y, lead, segs, pair_mean, pair_cov, ("offsets", offsets), per_chain=False)
+    latents, two_d = w.shape[-3], w.shape[-1]
+    if not sparse_stack_instantiated(likelihood, latents, two_d):
+        raise NotImplementedError(f"{what}: K = {latents}, 2d = {two_d}, {type(likelihood).__name__} is outside the instantiated "
+                                  f"signatures (2d even in 2 ... {SPARSE_SITE_MAX_TWO_D}; MultiStageLikelihood, "
+                                  "HeteroscedasticGaussian); use sparse_stack_expected_log_likelihood_torch")
+    if torch.is_grad_enabled() and (w.requires_grad or c.requires_grad):
+        raise NotImplementedError(f"{what} has no adjoint onto w and c (a kernel hyper-parameter under the tape): use "
+                                  "sparse_stack_expected_log_likelihood_torch")
+    if tiles is None:
+        tiles = sparse_expectation_tiles(offsets)
+    return _SparseStackExpectedLogLikelihood.apply(pair_mean, pair_cov, likelihood, w, c, y, offsets, tiles)
+
+
+def sparse_stack_expected_log_likelihood_torch(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor,
+                                               indices: torch.Tensor, pair_mean: torch.Tensor, pair_cov: torch.Tensor,
+                                               orders: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The same quantity as a torch composition, differentiable by autograd in everything (``pair_mean``, ``pair_cov``, ``w``, ``c``):
+    per chain the gathers of its pair marginals by the per-point pair index, ``likelihood.variational_expectations`` on
+    ``[.., N, K]`` and ``index_add`` over the segments.  ``indices`` is ``[.., N]`` (one segmentation for the ``K`` chains) or
+    ``[.., K, N]``: the chains need NOT share inducing points.  The data term of a point is then booked on the pair of chain 0 - the
+    split over the pairs is chain 0's, the sum over them is the ELBO's data term whatever the chains' segmentations.
+    ``orders [.., K, N]`` (optional): chain ``k``'s rows of ``w``, ``c`` and ``indices`` are in the order ``orders[.., k, :]`` of the
+    data (each chain sorted on its own time points); the per-chain marginals are brought back to the data's order, that of ``y``,
+    before the likelihood sees them.  It runs on CPU tensors, it is the model's route for ``2d > 18``, for a hyper-parameter under
+    the tape and for chains that do not share their inducing or data times, and it is what ``mf_lik_stack_expectations_*`` is
+    measured against."""
+    what = "sparse_stack_expected_log_likelihood_torch"
+    lead = tuple(y.shape[:-1])
+    latents, segs = w.shape[-3], pair_mean.shape[-2]
+    _sparse_stack_check(what, likelihood, w, c, y, lead, segs, pair_mean, pair_cov, ("indices", indices), per_chain=True)
+    if indices.dim() == len(lead) + 1:
+        indices = indices[..., None, :].expand(lead + (latents, indices.shape[-1]))
+    fmu, fvar, _ = _sparse_point_marginals(w, c, indices, pair_mean, pair_cov, segs)            # [.., K, N] on the batch of chains
+    booked = indices[..., 0, :]
+    if orders is not None:
+        inverse = torch.argsort(orders, dim=-1)
+        fmu, fvar = torch.gather(fmu, -1, inverse), torch.gather(fvar, -1, inverse)
+        booked = torch.gather(booked, -1, inverse[..., 0, :])
+    ve = likelihood.variational_expectations(fmu.transpose(-1, -2), fvar.transpose(-1, -2), y[..., None])
+    series = torch.arange(math.prod(lead), device=indices.device).reshape(lead + (1,))
+    flat = (booked + series * segs).reshape(-1)
+    out = torch.zeros(math.prod(lead) * segs, dtype=ve.dtype, device=ve.device).index_add(0, flat, ve.reshape(-1))
+    return out.reshape(lead + (segs,))
 
 
 # ---- SVGP with several observed series per point: multi-output kernels and the FactorAnalysis emission ------------------------------

@@ -22,7 +22,7 @@ from ..likelihoods import Likelihood
 from ..posterior import ConditionalProcess
 from ..ssm_gaussian_transformations import naturals_to_ssm_params
 from ..state_space_model import StateSpaceModel
-from ._common import (_PredictLogDensity, _check_dense_data, _refuse_factor_analysis, _refuse_non_stationary, _require_likelihood,
+from ._common import (_PredictLogDensity, _check_dense_data, _refuse_factor_analysis, _refuse_non_stationary, _refuse_stack, _require_likelihood,
                       back_project_nats, gradient_correction, gradient_transformation_mean_var_to_expectation)
 
 
@@ -40,6 +40,7 @@ class _GaussianProcessWithSites(_PredictLogDensity):
             raise ValueError(f"learning_rate must lie in [0, 1], got {learning_rate}")
         _refuse_non_stationary(kernel, type(self).__name__)
         _refuse_factor_analysis(kernel, type(self).__name__)
+        _refuse_stack(kernel, type(self).__name__)
         _lib.same_dtype_device(observations, type(self).__name__, time_points=time_points)
         self._kernel = kernel
         self._likelihood = likelihood

@@ -23,12 +23,12 @@ import math
 import torch
 
 from .. import _lib, conditionals
-from ..kernels import FactorAnalysisKernel, SDEKernel, _version_key
+from ..kernels import FactorAnalysisKernel, IndependentMultiOutputStack, SDEKernel, StackKernel, _version_key
 from ..likelihoods import Likelihood
 from ..posterior import ConditionalProcess, ImportanceWeightedPosteriorProcess
 from ..ssm_gaussian_transformations import naturals_to_ssm_params
 from ..state_space_model import StateSpaceModel
-from ._common import (_PredictLogDensity, _refuse_factor_analysis, _refuse_non_stationary, _require_likelihood, gradient_correction,
+from ._common import (_PredictLogDensity, _refuse_factor_analysis, _refuse_non_stationary, _refuse_stack, _require_likelihood, gradient_correction,
                       gradient_transformation_mean_var_to_expectation)
 from .segmented_ops import (SPARSE_FACTOR_LATENTS, SPARSE_FACTOR_MAX_OUTPUTS, SPARSE_MULTI_MIN_TWO_D, SPARSE_SITE_MAX_TWO_D,
                             _sparse_point_marginals, iw_log_likelihood, iw_log_likelihood_torch, iw_merged_time_points, pair_cavity,
@@ -38,7 +38,8 @@ from .segmented_ops import (SPARSE_FACTOR_LATENTS, SPARSE_FACTOR_MAX_OUTPUTS, SP
                             sparse_factor_site_projections, sparse_multi_expected_log_likelihood,
                             sparse_multi_expected_log_likelihood_torch, sparse_multi_output_expected_log_likelihood_torch,
                             sparse_multi_site_projections, sparse_pep_site_update_hip, sparse_pep_site_update_torch,
-                            sparse_site_projections)
+                            sparse_site_projections, sparse_stack_expected_log_likelihood,
+                            sparse_stack_expected_log_likelihood_torch, sparse_stack_instantiated)
 
 
 class _SparseGaussianProcess(_PredictLogDensity):
@@ -54,6 +55,10 @@ class _SparseGaussianProcess(_PredictLogDensity):
         _refuse_non_stationary(kernel, type(self).__name__)
         if not self._multi_output:
             _refuse_factor_analysis(kernel, type(self).__name__)
+            _refuse_stack(kernel, type(self).__name__)
+        elif isinstance(kernel, StackKernel) and not isinstance(kernel, IndependentMultiOutputStack):
+            raise NotImplementedError(f"{type(self).__name__} takes a StackKernel with its multi-output emission only: use "
+                                      "IndependentMultiOutputStack")
         _require_likelihood(likelihood, multi_latent=self._multi_latent)
         if likelihood.latent_dim > 1 and likelihood.latent_dim != kernel.output_dim:
             raise ValueError(f"the likelihood has latent_dim = {likelihood.latent_dim}, the kernel has output_dim = "
@@ -66,6 +71,8 @@ class _SparseGaussianProcess(_PredictLogDensity):
             raise TypeError(f"markovflow_amd supports float32 and float64 tensors, got {inducing_points.dtype}")
         if bool((inducing_points[..., 1:] < inducing_points[..., :-1]).any()):
             raise ValueError("inducing_points must be sorted")
+        if isinstance(kernel, StackKernel):        # lead + [K, M]: one set of inducing points per chain
+            kernel._check_batch(inducing_points.shape[:-1], "inducing_points")
         self._kernel = kernel
         self._likelihood = likelihood
         self.inducing_inputs = inducing_points
@@ -73,6 +80,8 @@ class _SparseGaussianProcess(_PredictLogDensity):
 
     def _check_data(self, input_data: Tuple[torch.Tensor, torch.Tensor], what: str) -> Tuple[torch.Tensor, torch.Tensor]:
         time_points, observations = input_data
+        if isinstance(self._kernel, StackKernel):
+            return self._check_stack_data(time_points, observations, what)
         outputs = self._kernel.output_dim
         # one observed series per output of the kernel: the one model that says so, a likelihood with ONE latent function
         per_output = self._multi_output and outputs > 1 and self._likelihood.latent_dim == 1
@@ -85,6 +94,25 @@ class _SparseGaussianProcess(_PredictLogDensity):
         if tuple(time_points.shape[:-1]) != tuple(self.inducing_inputs.shape[:-1]):
             raise ValueError(f"{what}: the data must carry the batch shape of the inducing points, "
                              f"{tuple(self.inducing_inputs.shape[:-1])}, got {tuple(time_points.shape[:-1])}")
+        _lib.same_dtype_device(self.inducing_inputs, f"{type(self).__name__}.{what}", time_points=time_points,
+                               observations=observations)
+        return time_points, observations
+
+    def _check_stack_data(self, time_points: torch.Tensor, observations: torch.Tensor, what: str):
+        """The data of a stack kernel with ``K`` chains: time points ``lead + [K, N]`` - every chain has its own, as it has its own
+        inducing points - and observations ``lead + [N, 1]`` under a ``K``-latent likelihood or ``lead + [N, K]`` (one series per
+        output) under a one-latent likelihood."""
+        chains = self._kernel.num_kernels
+        batch = tuple(self.inducing_inputs.shape[:-1])
+        if time_points.dim() < 2 or tuple(time_points.shape[:-1]) != batch:
+            raise ValueError(f"{what}: time_points must have shape {batch} + [num_data] (the batch shape of the inducing points, "
+                             f"which ends in the {chains} chains of the kernel), got {tuple(time_points.shape)}")
+        columns = 1 if self._likelihood.latent_dim > 1 else chains
+        expected = batch[:-1] + (time_points.shape[-1], columns)
+        if tuple(observations.shape) != expected:
+            raise ValueError(f"{what}: observations must have shape {expected} (" + ("one column under a likelihood with "
+                             f"{chains} latent functions" if columns == 1 else "one series per output of the kernel")
+                             + f"), got {tuple(observations.shape)}")
         _lib.same_dtype_device(self.inducing_inputs, f"{type(self).__name__}.{what}", time_points=time_points,
                                observations=observations)
         return time_points, observations
@@ -460,7 +488,16 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
     ``2L <= 2d <= 18``, no hyper-parameter of the chain under the tape; otherwise ``sparse_factor_expected_log_likelihood_torch``):
     the loading matrix trains on the fused path.  Any other multi-output kernel takes
     ``sparse_multi_output_expected_log_likelihood_torch``.  Observations ``batch + [N, 1]`` keep the single-output path whatever the
-    kernel (a weight function's own parameters are seen on the ``[N, P]`` routes only)."""
+    kernel (a weight function's own parameters are seen on the ``[N, P]`` routes only).
+
+    An ``IndependentMultiOutputStack`` of ``K`` kernels keeps ``K`` independent chains of dimension ``d = max d_k`` with ``K`` as the
+    last batch dimension: inducing points ``lead + [K, M]``, time points ``lead + [K, N]``, ``dist_q`` / ``dist_p`` / the KL /
+    ``SSMNaturalGradient`` on batch ``lead + [K]``, ``predict_f`` ``lead + [num_new, K]``.  Observations ``lead + [N, 1]`` under a
+    ``K``-latent likelihood couple the chains at every point: the data term is ONE call of ``mf_lik_stack_expectations_*`` when the
+    tensors are HIP tensors, ``2d <= 18``, the likelihood is instantiated (``MultiStageLikelihood``, ``HeteroscedasticGaussian``), no
+    kernel hyper-parameter is under the tape and the chains of every series share their inducing points and data times;
+    otherwise ``sparse_stack_expected_log_likelihood_torch``.  Observations ``lead + [N, K]`` under a one-latent likelihood are
+    ``K`` decoupled problems: ``mf_lik_sparse_expectations_*`` on the batch of chains, per-output inducing points allowed."""
 
     _multi_latent = True
     _multi_output = True
@@ -474,6 +511,8 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
         """
         super().__init__(kernel, likelihood, inducing_points, min_inducing=2)
         self._route = "multi" if likelihood.latent_dim > 1 else "single"    # (``_data_route`` of the data last seen)
+        if isinstance(kernel, StackKernel):
+            self._route = "stack" if likelihood.latent_dim > 1 else "stack_outputs"
         if num_data is not None and not num_data > 0:
             raise ValueError(f"num_data must be positive, got {num_data}")
         self.num_data = num_data
@@ -523,6 +562,8 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
         """What the observations' last dimension selects: ``"single"`` (``[N, 1]``, one latent), ``"multi"`` (``[N, 1]``, a
         multi-latent likelihood), ``"factor"`` (``[N, P]`` on a ``FactorAnalysisKernel``) or ``"outputs"`` (``[N, P]`` on any other
         kernel with ``P`` outputs)."""
+        if isinstance(self._kernel, StackKernel):
+            return "stack" if self._multi else "stack_outputs"
         if observations.shape[-1] == 1:
             return "multi" if self._multi else "single"
         return "factor" if isinstance(self._kernel, FactorAnalysisKernel) else "outputs"
@@ -553,12 +594,66 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
         data), ``sparse_site_projections`` of the sorted points (``sparse_multi_site_projections`` for a multi-latent likelihood or
         multi-output observations: ``w`` and ``c`` carry one row per latent or output; ``sparse_factor_site_projections`` for a
         ``FactorAnalysisKernel`` with multi-output observations: ``wg``, ``cg`` of the latents) and the tile table."""
+        if self._route in ("stack", "stack_outputs"):
+            return self._compute_stack_projections(time_points)
         order, time_points = _sorted_series(time_points)
         project = {"single": sparse_site_projections, "multi": sparse_multi_site_projections,
                    "outputs": sparse_multi_site_projections, "factor": sparse_factor_site_projections}[self._route]
         w, c, indices, offsets = project(self._kernel, time_points, self.inducing_inputs)
         tiles = sparse_expectation_tiles(offsets) if time_points.is_cuda else None
         return order, w, c, indices, offsets, tiles
+
+    def _compute_stack_projections(self, time_points: torch.Tensor):
+        """``(order | None, w, c, indices, offsets, tiles, shared)`` of data ``lead + [K, N]`` on a stack kernel:
+        ``sparse_site_projections`` on the stacked batch (every chain sorted on its own time points), ``w [.., K, N, 2d]``,
+        ``c [.., K, N]``.  ``shared``: the ``K`` chains of every series have equal inducing points, equal data times and one sorting
+        permutation, so they share ONE segmentation (one read-back, kept with the projections) - the coupled route's tile table is
+        then that of chain 0's offsets; the per-output route's is that of the batch of chains."""
+        order, x = _sorted_series(time_points)
+        w, c, indices, offsets = sparse_site_projections(self._kernel, x, self.inducing_inputs)
+        shared, tiles = False, None
+        if self._route == "stack":
+            z = self.inducing_inputs
+            same = (z == z[..., :1, :]).all() & (x == x[..., :1, :]).all()
+            if order is not None:
+                same = same & (order == order[..., :1, :]).all()
+            shared = bool(same)
+            if shared and time_points.is_cuda:
+                tiles = sparse_expectation_tiles(offsets[..., 0, :].contiguous())
+        elif time_points.is_cuda:
+            tiles = sparse_expectation_tiles(offsets)
+        return order, w, c, indices, offsets, tiles, shared
+
+    def _stack_expected_log_likelihood(self, time_points: torch.Tensor, observations: torch.Tensor, pair_mean, pair_cov
+                                       ) -> torch.Tensor:
+        """The data term on a stack kernel, ``lead + [M + 1]`` (coupled) or ``lead + [K, M + 1]`` (one series per output)."""
+        kernel, lik = self._kernel, self._likelihood
+        two_d = 2 * kernel.state_dim
+        on_device = time_points.is_cuda and two_d <= SPARSE_SITE_MAX_TWO_D and not kernel._needs_grad()
+        if kernel._needs_grad():
+            # a hyper-parameter under the tape: w and c are part of the graph
+            order, x = _sorted_series(time_points)
+            proj, cov, indices = conditionals._conditional_statistics(x, self.inducing_inputs, kernel)
+            h = kernel.generate_emission_model(x).emission_matrix
+            w, c = (h @ proj)[..., 0, :], (h @ cov @ h.transpose(-1, -2))[..., 0, 0]
+            offsets = tiles = None
+            shared = False
+        else:
+            order, w, c, indices, offsets, tiles, shared = self._projections(time_points)
+        if self._route == "stack_outputs":
+            # K decoupled chains: the single-latent term on the batch lead + [K]
+            y = observations.transpose(-1, -2)
+            if order is not None:
+                y = torch.gather(y, -1, order)
+            if on_device:
+                return sparse_expected_log_likelihood(lik, w, c, y.contiguous(), offsets, pair_mean, pair_cov, tiles=tiles)
+            return sparse_expected_log_likelihood_torch(lik, w, c, y, indices, pair_mean, pair_cov)
+        y = observations[..., 0]
+        if on_device and shared and sparse_stack_instantiated(lik, kernel.num_kernels, two_d):
+            if order is not None:
+                y = torch.gather(y, -1, order[..., 0, :])
+            return sparse_stack_expected_log_likelihood(lik, w, c, y, offsets[..., 0, :].contiguous(), pair_mean, pair_cov, tiles=tiles)
+        return sparse_stack_expected_log_likelihood_torch(lik, w, c, y, indices, pair_mean, pair_cov, orders=order)
 
     def _multi_output_expected_log_likelihood(self, time_points: torch.Tensor, observations: torch.Tensor, pair_mean, pair_cov
                                               ) -> torch.Tensor:
@@ -596,6 +691,8 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
         route = self._data_route(observations)
         if route != self._route:                   # the cached projections are the other route's
             self._route, self._projection_cache = route, None
+        if route in ("stack", "stack_outputs"):
+            return self._stack_expected_log_likelihood(time_points, observations, pair_mean, pair_cov)
         if route in ("factor", "outputs"):
             return self._multi_output_expected_log_likelihood(time_points, observations, pair_mean, pair_cov)
         if self._fused(time_points):
@@ -652,6 +749,9 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
     _predict_f = predict_f          # (``predict_log_density`` predicts outside the tape here, as ``predict_f`` does)
 
     def predict_log_density(self, input_data: Tuple[torch.Tensor, torch.Tensor], full_output_cov: bool = False) -> torch.Tensor:
+        if isinstance(self._kernel, StackKernel):
+            raise NotImplementedError("predict_log_density is not supported on a stack kernel (several latents or several outputs "
+                                      "per point)")
         if input_data[1].dim() >= 1 and input_data[1].shape[-1] != 1:
             raise NotImplementedError("predict_log_density: observations with several outputs per point are not supported")
         return super().predict_log_density(input_data, full_output_cov)

@@ -16,7 +16,7 @@ from ..likelihoods import Likelihood
 from ..posterior import ConditionalProcess
 from ..state_space_model import StateSpaceModel
 from ._common import (_PredictLogDensity, _check_dense_data, _check_shapes, _differentiable_once, _launch, _new_outputs,
-                      _refuse_factor_analysis, _refuse_non_stationary, _require_likelihood, _workspace)
+                      _refuse_factor_analysis, _refuse_non_stationary, _refuse_stack, _require_likelihood, _workspace)
 
 
 # ---- VGP: the dense ELBO data term -------------------------------------------------------------------------------------------------
@@ -113,6 +113,7 @@ class VariationalGaussianProcess(_PredictLogDensity):
             raise TypeError("kernel must be a markovflow_amd.kernels.SDEKernel")
         _refuse_non_stationary(kernel, "VariationalGaussianProcess")
         _refuse_factor_analysis(kernel, "VariationalGaussianProcess")
+        _refuse_stack(kernel, "VariationalGaussianProcess")
         _require_likelihood(likelihood)
         _check_dense_data(time_points, observations)
         if time_points.shape[-1] < 2:
