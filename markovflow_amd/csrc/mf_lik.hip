@@ -21,8 +21,9 @@
 
 // (the rule, the parameters, log p(y | f), the expectation of one point and the host side's argument checks: shared with mf_st.hip)
 #include "mf_lik_math.hpp"
-// (the accumulator row, pass 2 of the tile-parallel SVGP data terms and the launch helper: shared with mf_lik_factor.hip)
-#include "mf_lik_reduce.hpp"
+// (the front end of the tile-parallel kernels - tile locator, staging, workspace row -, pass 2 of the SVGP terms and the
+// host side's dispatch and tile-table checks: shared with mf_lik_factor.hip, mf_lik_stack.hip and mf_st.hip)
+#include "mf_lik_tile.hpp"
 // (the multi-stage likelihood's expectation of one point: shared with mf_lik_stack.hip)
 #include "mf_lik_multistage.hpp"
 
@@ -65,7 +66,7 @@ __global__ void __launch_bounds__(256) lik_ve_kernel(long N, Rule<T> q, Par<T> p
 // value: inlined, they then index and load exactly as the kernels would, and the register allocation stays what it was.
 
 // (tri_decode and seg_entries - entry e of a packed lower triangle is (i, j <= i); the accumulator has the triangle, the vector and one
-// scalar per row of LDS values beyond the first two - are in mf_lik_reduce.hpp)
+// scalar per row of LDS values beyond the first two - are in mf_lik_tile.hpp)
 
 // accumulator entry e as (i, j, row of LDS values): e < TRI is (i, j <= i) of the matrix from row 0, then the vector's (j = D2: the
 // column of ones) from row 1, then - ROWS = 3 only - the scalar (i = j = D2) from row 2.  A lane's surplus entry decodes as entry 0.
@@ -96,11 +97,7 @@ __device__ __forceinline__ void stage_pair(int lane, long bs, const T* pair_mean
     lw[lane * (D2 + 1) + D2] = T(1);
 }
 
-// npts rows of w into LDS: coalesced global loads, row stride 2d + 1 elements - odd, so the lanes' rows start on distinct banks
-template <typename T, int D2>
-__device__ __forceinline__ void stage_tile(int lane, int npts, const T* wt, T (&lw)[64 * (D2 + 1)]) {
-    for (int idx = lane; idx < npts * D2; idx += 64) lw[(idx / D2) * (D2 + 1) + idx % D2] = wt[idx];
-}
+// (stage_tile - npts rows of w into LDS at the odd row stride 2d + 1 - is in mf_lik_tile.hpp)
 
 // this lane's point: mu = w . m_s, s2 = c + w^T S_s w
 template <typename T, int D2>
@@ -226,8 +223,8 @@ __global__ void __launch_bounds__(64) sparse_site_kernel(long N, int S, Rule<T> 
 //   pass 2, one block per (series, segment), a lane per entry: the segment's rows are added in ascending tile order, the outputs
 //            are written and the triangle mirrored.  An empty segment writes zeros.
 // The tile table comes from the caller: tile_seg[t] = series * S + segment of tile t, seg_tile[series * S + segment] = the first
-// tile of the segment (a prefix sum, B S + 1 entries).  It is clamped here, not trusted: a wrong table gives wrong numbers and no
-// access outside the buffers.  No floating-point atomics; every sum's order is fixed by the point order alone.
+// tile of the segment (a prefix sum, B S + 1 entries).  It is clamped (locate_tile: mf_lik_tile.hpp), not trusted: a wrong table gives
+// wrong numbers and no access outside the buffers.  No floating-point atomics; every sum's order is fixed by the point order alone.
 template <typename T, int LIK, int D2>
 __global__ void __launch_bounds__(64) sparse_expect_tile_kernel(long N, int S, long BS, Rule<T> q, Par<T> p,
                                                                 const long long* __restrict__ seg,
@@ -243,15 +240,9 @@ __global__ void __launch_bounds__(64) sparse_expect_tile_kernel(long N, int S, l
     __shared__ T lg[3 * 64];           // gv of the tile's points, then gm, then ve
     const int lane = threadIdx.x;
     const long t = blockIdx.x;
-    long bs = (long)tile_seg[t];
-    bs = bs < 0 ? 0 : (bs >= BS ? BS - 1 : bs);
-    const long b = bs / S;
-    const long s = bs - b * S;
-    long k_lo = (long)seg[b * (S + 1) + s], k_hi = (long)seg[b * (S + 1) + s + 1];
-    clamp_range(k_lo, k_hi, N);
-    const long j = t - (long)seg_tile[bs];                          // this tile's number within its segment
-    const long k0 = (j >= 0 && j <= (k_hi - k_lo) / 64) ? k_lo + 64 * j : k_hi;
-    const int npts = k_hi - k0 < 64 ? int(k_hi - k0) : 64;          // (0 only for a table that disagrees with the offsets)
+    const TileAt at = locate_tile<64>(t, N, S, BS, seg, tile_seg, seg_tile);
+    const long bs = at.bs, b = at.b, k0 = at.k0;
+    const int npts = at.npts;
     int ei[R], ej[R], es[R];           // this lane's entries
     T part[R];
 #pragma unroll
@@ -285,14 +276,10 @@ __global__ void __launch_bounds__(64) sparse_expect_tile_kernel(long N, int S, l
             for (int k = 0; k < npts; ++k) part[R - 1] += lg[128 + k];
         }
     }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int e = lane + 64 * r;
-        if (e < E) ws[t * E + e] = part[r];
-    }
+    store_row<E>(ws + t * E, lane, part);
 }
 
-// (pass 2, sparse_expect_reduce_kernel, is in mf_lik_reduce.hpp: mf_lik_factor.hip launches it too)
+// (pass 2, expect_reduce_kernel at K = 1, is in mf_lik_tile.hpp: mf_lik_factor.hip and mf_lik_stack.hip launch it too)
 
 // ---- the multi-stage likelihood: three latents per point, one observation (multistage_expectations: mf_lik_multistage.hpp) -------
 // element-wise: a lane per point, fmu / fvar / g_mu / g_var [N, 3]
@@ -319,7 +306,7 @@ __global__ void __launch_bounds__(256) multistage_ve_kernel(long N, Rule<T> q, c
 
 // The multi-latent SVGP data term: pass 1 of the tile-parallel pair above with L = 3 dense rows of w per point (w [B, N, L, 2d],
 // c [B, N, L]); the tile table, the workspace row (lower triangle of g_cov, g_mean, sum ve) and pass 2 are those of
-// sparse_expect_tile_kernel / sparse_expect_reduce_kernel.
+// sparse_expect_tile_kernel / expect_reduce_kernel.
 //   phase 1, a lane per point: the tile's L rows per point travel through LDS as one row of L 2d + 1 elements (odd: the lanes' rows
 //            start on distinct banks); per latent mu_l = w_l . m_s, s2_l = c_l + w_l^T S_s w_l; the multi-stage expectation leaves
 //            gv_l (rows 0 .. L - 1 of lg), gm_l (rows L .. 2 L - 1) and ve (row 2 L) in LDS;
@@ -335,22 +322,16 @@ __global__ void __launch_bounds__(64) sparse_multi_expect_tile_kernel(long N, in
                                                                       const T* __restrict__ cvar, const T* __restrict__ yobs,
                                                                       const T* __restrict__ pair_mean, const T* __restrict__ pair_cov,
                                                                       int grads, T* __restrict__ ws) {
-    constexpr int L = MULTI_L, W = L * D2 + 1, TRI = D2 * (D2 + 1) / 2, E = seg_entries(D2, 3), R = (E + 63) / 64;
+    constexpr int L = MULTI_L, W = L * D2 + 1, TRI = D2 * (D2 + 1) / 2, E = expect_entries(1, D2), R = (E + 63) / 64;
     __shared__ T lw[64 * W];
     __shared__ T ls[D2 * D2];
     __shared__ T lm[D2];
     __shared__ T lg[(2 * L + 1) * 64];
     const int lane = threadIdx.x;
     const long t = blockIdx.x;
-    long bs = (long)tile_seg[t];
-    bs = bs < 0 ? 0 : (bs >= BS ? BS - 1 : bs);
-    const long b = bs / S;
-    const long s = bs - b * S;
-    long k_lo = (long)seg[b * (S + 1) + s], k_hi = (long)seg[b * (S + 1) + s + 1];
-    clamp_range(k_lo, k_hi, N);
-    const long j = t - (long)seg_tile[bs];                          // this tile's number within its segment
-    const long k0 = (j >= 0 && j <= (k_hi - k_lo) / 64) ? k_lo + 64 * j : k_hi;
-    const int npts = k_hi - k0 < 64 ? int(k_hi - k0) : 64;          // (0 only for a table that disagrees with the offsets)
+    const TileAt at = locate_tile<64>(t, N, S, BS, seg, tile_seg, seg_tile);
+    const long bs = at.bs, b = at.b, k0 = at.k0;
+    const int npts = at.npts;
     int ei[R], ej[R], kind[R];         // this lane's entries: kind 0 = (ei, ej) of the triangle, 1 = ei of the vector, 2 = the scalar,
     T part[R];                         // 3 = surplus
 #pragma unroll
@@ -365,8 +346,7 @@ __global__ void __launch_bounds__(64) sparse_multi_expect_tile_kernel(long N, in
     if (npts > 0) {
         for (int idx = lane; idx < D2 * D2; idx += 64) ls[idx] = pair_cov[bs * (D2 * D2) + idx];
         if (lane < D2) lm[lane] = pair_mean[bs * D2 + lane];
-        const T* wt = w + (b * N + k0) * (L * D2);                   // npts rows of L 2d elements: coalesced loads
-        for (int idx = lane; idx < npts * (L * D2); idx += 64) lw[(idx / (L * D2)) * W + idx % (L * D2)] = wt[idx];
+        stage_tile<T, L * D2>(lane, npts, w + (b * N + k0) * (L * D2), lw);      // npts rows of L 2d elements
         __syncthreads();
         if (lane < npts) {
             const long id = b * N + k0 + lane;
@@ -425,11 +405,7 @@ __global__ void __launch_bounds__(64) sparse_multi_expect_tile_kernel(long N, in
             for (int k = 0; k < npts; ++k) part[R - 1] += lg[2 * L * 64 + k];
         }
     }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int e = lane + 64 * r;
-        if (e < E) ws[t * E + e] = part[r];
-    }
+    store_row<E>(ws + t * E, lane, part);
 }
 
 // log of the predictive density  log int p(y | f) N(f | mu, s2) df
@@ -597,15 +573,9 @@ __global__ void __launch_bounds__(64) sparse_pep_tile_kernel(long N, int S, long
     __shared__ T lg[3 * 64];           // L2 of the tile's points, then L1, then I
     const int lane = threadIdx.x;
     const long t = blockIdx.x;
-    long bs = (long)tile_seg[t];
-    bs = bs < 0 ? 0 : (bs >= BS ? BS - 1 : bs);
-    const long b = bs / S;
-    const long s = bs - b * S;
-    long k_lo = (long)seg[b * (S + 1) + s], k_hi = (long)seg[b * (S + 1) + s + 1];
-    clamp_range(k_lo, k_hi, N);
-    const long j = t - (long)seg_tile[bs];                          // this tile's number within its segment
-    const long k0 = (j >= 0 && j <= (k_hi - k_lo) / 64) ? k_lo + 64 * j : k_hi;
-    const int npts = k_hi - k0 < 64 ? int(k_hi - k0) : 64;          // (0 only for a table that disagrees with the offsets)
+    const TileAt at = locate_tile<64>(t, N, S, BS, seg, tile_seg, seg_tile);
+    const long bs = at.bs, b = at.b, k0 = at.k0;
+    const int npts = at.npts;
     int ei[R], ej[R], es[R];           // this lane's entries
     T part[R];
 #pragma unroll
@@ -649,11 +619,7 @@ __global__ void __launch_bounds__(64) sparse_pep_tile_kernel(long N, int S, long
             for (int k = 0; k < npts; ++k) part[R - 1] += lg[128 + k];
         }
     }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int e = lane + 64 * r;
-        if (e < E) ws[t * E + e] = part[r];
-    }
+    store_row<E>(ws + t * E, lane, part);
 }
 
 template <typename T, int D2>
@@ -742,15 +708,9 @@ __global__ void __launch_bounds__(64) iw_tile_kernel(long N, int S, long BS, lon
     const long t = blockIdx.x / chunks;
     const long k_base = (blockIdx.x - t * chunks) * IW_CHUNK;
     const int kc = K - k_base < IW_CHUNK ? int(K - k_base) : IW_CHUNK;
-    long bs = (long)tile_seg[t];
-    bs = bs < 0 ? 0 : (bs >= BS ? BS - 1 : bs);
-    const long b = bs / S;
-    const int s = int(bs - b * S);
-    long k_lo = (long)seg[b * (S + 1) + s], k_hi = (long)seg[b * (S + 1) + s + 1];
-    clamp_range(k_lo, k_hi, N);
-    const long j = t - (long)seg_tile[bs];                          // this tile's number within its segment
-    const long k0 = (j >= 0 && j <= (k_hi - k_lo) / 64) ? k_lo + 64 * j : k_hi;
-    const int npts = k_hi - k0 < 64 ? int(k_hi - k0) : 64;          // (0 only for a table that disagrees with the offsets)
+    const TileAt at = locate_tile<64>(t, N, S, BS, seg, tile_seg, seg_tile);
+    const long b = at.b, k_lo = at.k_lo, k_hi = at.k_hi, k0 = at.k0;
+    const int s = int(at.s), npts = at.npts;
     const long rows = u_post ? N + (S - 1) : N;                     // rows of one (sample, series) of states
     const long row0 = u_post ? k0 + s : k0;                         // the row of the tile's first point
     T part[R];
@@ -1001,24 +961,8 @@ __global__ void __launch_bounds__(256) dense_adjoint_kernel(long BN, long N, con
 
 // (prepare, first_null and with_lik - the argument checks shared by every entry point - are in mf_lik_math.hpp)
 
-// the same as with_lik for the pair dimension of the segmented kernels: 2, 4, ..., 18, -100 for any other
-template <typename F>
-int with_two_d(int two_d, F&& f) {
-    switch (two_d) {
-        case 2: return f(std::integral_constant<int, 2>{});
-        case 4: return f(std::integral_constant<int, 4>{});
-        case 6: return f(std::integral_constant<int, 6>{});
-        case 8: return f(std::integral_constant<int, 8>{});
-        case 10: return f(std::integral_constant<int, 10>{});
-        case 12: return f(std::integral_constant<int, 12>{});
-        case 14: return f(std::integral_constant<int, 14>{});
-        case 16: return f(std::integral_constant<int, 16>{});
-        case 18: return f(std::integral_constant<int, 18>{});
-        default: return -100;
-    }
-}
-
-// (launch - one launch, the arguments converted to the kernel's parameter types - is in mf_lik_reduce.hpp)
+// (with_even_two_d - the same as with_lik for the pair dimension of the segmented kernels - and launch - one launch, the arguments
+// converted to the kernel's parameter types - are in mf_lik_tile.hpp)
 
 // variational expectations (nat1 == NULL) or the CVI site update: the one kernel behind both
 template <typename T>
@@ -1107,15 +1051,14 @@ int run_pep(int64_t N, int lik, const double* params, int nq, const double* node
 }
 
 // the leading argument checks of the segmented entry points: the (negative) position of the offending argument in THEIR
-// signature, -100 for a two_d outside 2, 4, ..., 18
+// signature (check_segmentation: mf_lik_tile.hpp), -100 for a two_d outside 2, 4, ..., 18
 template <typename T>
 int prepare_segmented(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq, const double* nodes,
                       const double* weights, Rule<T>& q, Par<T>& p, bool log_weights = false) {
-    if (B < 0) return -1;
-    if (N < 0) return -2;
-    if (S < 1 || (B > 0 && S > int64_t(0x7fffffff) / B)) return -3;
+    int bad = check_segmentation(B, N, S);
+    if (bad) return bad;
     if (two_d < 2 || two_d > 18 || (two_d & 1)) return -100;
-    const int bad = prepare<T>(0, lik, params, nq, nodes, weights, log_weights, q, p);      // -2 ... -6 there: arguments 5 ... 9 here
+    bad = prepare<T>(0, lik, params, nq, nodes, weights, log_weights, q, p);                // -2 ... -6 there: arguments 5 ... 9 here
     return bad ? bad - 3 : 0;
 }
 
@@ -1134,7 +1077,7 @@ int run_sparse(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double
     if (!nat1 && (N == 0 || (!fmu && !fvar && !ve))) return 0;      // nothing asked for
     if (!seg) return -10;
     if (N > 0 && (bad = first_null(11, {w, c, y, pm, pc}))) return bad;
-    return with_two_d(two_d, [&](auto D) {
+    return with_even_two_d<2>(two_d, -100, [&](auto D) {
         return with_lik(lik, [&](auto L) {
             return launch(sparse_site_kernel<T, decltype(L)::value, decltype(D)::value>, B * S, 64, stream, N, S, q, p, ll(seg), w, c,
                           y, pm, pc, lr, nat1, nat2, fmu, fvar, ve);
@@ -1142,7 +1085,7 @@ int run_sparse(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double
     });
 }
 
-// (expect_row, the workspace row of a tile, is in mf_lik_reduce.hpp)
+// (expect_row, the workspace row of a tile, and check_tile_count / check_tile_table are in mf_lik_tile.hpp)
 
 template <typename T>
 int run_expect(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq, const double* nodes,
@@ -1153,16 +1096,15 @@ int run_expect(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double
     Par<T> p;
     int bad = prepare_segmented<T>(B, N, S, two_d, lik, params, nq, nodes, weights, q, p);
     if (bad) return bad;
-    if (tiles < 0 || tiles > int64_t(0x7fffffff) || (N == 0 && tiles != 0)) return -16;
+    if ((bad = check_tile_count(16, N, tiles))) return bad;
     if (!g_mean && g_cov) return -22;
     if (g_mean && !g_cov) return -23;
     if (B == 0 || (!ve_sum && !g_mean)) return 0;      // nothing asked for
     if (tiles > 0) {
         if ((bad = first_null(10, {seg, w, c, y, pm, pc}))) return bad;
-        if ((bad = first_null(17, {tile_seg, seg_tile, ws}))) return bad;
-        if (ws_bytes < size_t(tiles) * expect_row(two_d) * sizeof(T)) return -20;
+        if ((bad = check_tile_table(16, tiles, tile_seg, seg_tile, ws, ws_bytes, expect_row(two_d), sizeof(T)))) return bad;
     }
-    return with_two_d(two_d, [&](auto D) {
+    return with_even_two_d<2>(two_d, -100, [&](auto D) {
         constexpr int D2 = decltype(D)::value;
         if (tiles > 0) {
             const int rc = with_lik(lik, [&](auto L) {
@@ -1171,27 +1113,13 @@ int run_expect(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double
             });
             if (rc) return rc;
         }
-        return launch(sparse_expect_reduce_kernel<T, D2>, B * S, 256, stream, tiles, tiles > 0 ? ll(seg_tile) : nullptr, ws, ve_sum,
+        return launch(expect_reduce_kernel<T, 1, D2>, B * S, 256, stream, tiles, S, tiles > 0 ? ll(seg_tile) : nullptr, ws, ve_sum,
                       g_mean, g_cov);
     });
 }
 
 // the multi-latent pair: instantiated for (two_d, latent_dim, lik) = (6 ... 18 even, 3, multi-stage), -101 for any other signature.
 // The likelihood has no parameters (params is not read); the workspace row and pass 2 are the single-latent pair's.
-template <typename F>
-int with_multi_two_d(int two_d, F&& f) {
-    switch (two_d) {
-        case 6: return f(std::integral_constant<int, 6>{});
-        case 8: return f(std::integral_constant<int, 8>{});
-        case 10: return f(std::integral_constant<int, 10>{});
-        case 12: return f(std::integral_constant<int, 12>{});
-        case 14: return f(std::integral_constant<int, 14>{});
-        case 16: return f(std::integral_constant<int, 16>{});
-        case 18: return f(std::integral_constant<int, 18>{});
-        default: return -101;
-    }
-}
-
 template <typename T>
 int run_multi_expect(int64_t B, int64_t N, int64_t S, int two_d, int latent_dim, int lik, int nq, const double* nodes,
                      const double* weights, const int64_t* seg, const T* w, const T* c, const T* y, const T* pm, const T* pc,
@@ -1199,29 +1127,27 @@ int run_multi_expect(int64_t B, int64_t N, int64_t S, int two_d, int latent_dim,
                      T* g_cov, void* stream) {
     Rule<T> q;
     Par<T> p;
-    if (B < 0) return -1;
-    if (N < 0) return -2;
-    if (S < 1 || (B > 0 && S > int64_t(0x7fffffff) / B)) return -3;
+    int bad = check_segmentation(B, N, S);
+    if (bad) return bad;
     if (latent_dim != MULTI_L || lik != LIK_MULTISTAGE || two_d < 6 || two_d > 18 || (two_d & 1)) return -101;
-    int bad = prepare<T>(0, 1, nullptr, nq, nodes, weights, false, q, p);        // -4 ... -6 there: arguments 8 ... 10 here
+    bad = prepare<T>(0, 1, nullptr, nq, nodes, weights, false, q, p);            // -4 ... -6 there: arguments 8 ... 10 here
     if (bad) return bad - 4;
-    if (tiles < 0 || tiles > int64_t(0x7fffffff) || (N == 0 && tiles != 0)) return -17;
+    if ((bad = check_tile_count(17, N, tiles))) return bad;
     if (!g_mean && g_cov) return -23;
     if (g_mean && !g_cov) return -24;
     if (B == 0 || (!ve_sum && !g_mean)) return 0;      // nothing asked for
     if (tiles > 0) {
         if ((bad = first_null(11, {seg, w, c, y, pm, pc}))) return bad;
-        if ((bad = first_null(18, {tile_seg, seg_tile, ws}))) return bad;
-        if (ws_bytes < size_t(tiles) * expect_row(two_d) * sizeof(T)) return -21;
+        if ((bad = check_tile_table(17, tiles, tile_seg, seg_tile, ws, ws_bytes, expect_row(two_d), sizeof(T)))) return bad;
     }
-    return with_multi_two_d(two_d, [&](auto D) {
+    return with_even_two_d<6>(two_d, -101, [&](auto D) {
         constexpr int D2 = decltype(D)::value;
         if (tiles > 0) {
             const int rc = launch(sparse_multi_expect_tile_kernel<T, D2>, tiles, 64, stream, N, S, B * S, q, ll(seg), ll(tile_seg),
                                   ll(seg_tile), w, c, y, pm, pc, g_mean ? 1 : 0, ws);
             if (rc) return rc;
         }
-        return launch(sparse_expect_reduce_kernel<T, D2>, B * S, 256, stream, tiles, tiles > 0 ? ll(seg_tile) : nullptr, ws, ve_sum,
+        return launch(expect_reduce_kernel<T, 1, D2>, B * S, 256, stream, tiles, S, tiles > 0 ? ll(seg_tile) : nullptr, ws, ve_sum,
                       g_mean, g_cov);
     });
 }
@@ -1252,17 +1178,16 @@ int run_sparse_pep(int64_t B, int64_t N, int64_t S, int two_d, int lik, const do
     if (bad) return bad;
     if (!(alpha > T(0)) || !(alpha <= T(1))) return -10;
     if (!(lr >= T(0)) || !(lr <= T(1))) return -11;
-    if (tiles < 0 || tiles > int64_t(0x7fffffff) || (N == 0 && tiles != 0)) return -19;
+    if ((bad = check_tile_count(19, N, tiles))) return bad;
     if (nat1 || nat2 || log_norm) {                // all three, or none (evaluation only)
         if ((bad = first_null(24, {nat1, nat2, log_norm}))) return bad;
     }
     if (B == 0 || (!nat1 && !led_sum && !fmu && !fvar && !led)) return 0;      // nothing asked for
     if (tiles > 0) {
         if ((bad = first_null(12, {seg, w, c, y, cm, cc}))) return bad;
-        if ((bad = first_null(20, {tile_seg, seg_tile, ws}))) return bad;
-        if (ws_bytes < size_t(tiles) * expect_row(two_d) * sizeof(T)) return -23;
+        if ((bad = check_tile_table(19, tiles, tile_seg, seg_tile, ws, ws_bytes, expect_row(two_d), sizeof(T)))) return bad;
     }
-    return with_two_d(two_d, [&](auto D) {
+    return with_even_two_d<2>(two_d, -100, [&](auto D) {
         constexpr int D2 = decltype(D)::value;
         if (tiles > 0) {
             const int rc = with_lik(lik, [&](auto L) {
@@ -1284,29 +1209,26 @@ template <typename T>
 int run_iw(int64_t B, int64_t N, int64_t S, int two_d, int64_t K, int lik, const double* params, const int64_t* seg, const T* w,
            const T* y, const T* h, const T* states, const T* u_post, int64_t tiles, const int64_t* tile_seg, const int64_t* seg_tile,
            void* ws, size_t ws_bytes, T* log_lik, T* g_u, void* stream) {
-    if (B < 0) return -1;
-    if (N < 0) return -2;
-    if (S < 1 || (B > 0 && S > int64_t(0x7fffffff) / B)) return -3;
+    int bad = check_segmentation(B, N, S);
+    if (bad) return bad;
     if (two_d < 2 || two_d > 18 || (two_d & 1)) return -100;
     if (K < 0 || K > int64_t(0x7fffffff)) return -5;
     Rule<T> q;                         // no quadrature: the density is evaluated point-wise (a one-node rule satisfies prepare)
     Par<T> p;
     const double node = 0.0, weight = 1.0;
-    int bad = prepare<T>(0, lik, params, 1, &node, &weight, false, q, p);      // -2, -3 there: arguments 6, 7 here
+    bad = prepare<T>(0, lik, params, 1, &node, &weight, false, q, p);          // -2, -3 there: arguments 6, 7 here
     if (bad) return bad - 4;
     const int64_t chunks = (K + IW_CHUNK - 1) / IW_CHUNK;
-    if (tiles < 0 || tiles > int64_t(0x7fffffff) || (N == 0 && tiles != 0) || (chunks > 0 && tiles > int64_t(0x7fffffff) / chunks))
-        return -14;
+    if ((bad = check_tile_count(14, N, tiles, chunks))) return bad;            // (a block per tile and chunk of samples)
     if (g_u && !u_post) return -20;
     if (B == 0 || K == 0 || (!log_lik && !g_u)) return 0;      // nothing asked for
     if (tiles > 0) {
         if (!seg) return -8;
         if (u_post && !w) return -9;
         if ((bad = first_null(10, {y, h, states}))) return bad;
-        if ((bad = first_null(15, {tile_seg, seg_tile, ws}))) return bad;
-        if (ws_bytes < size_t(tiles) * size_t(K) * iw_row(two_d) * sizeof(T)) return -18;
+        if ((bad = check_tile_table(14, tiles, tile_seg, seg_tile, ws, ws_bytes, size_t(K) * iw_row(two_d), sizeof(T)))) return bad;
     }
-    return with_two_d(two_d, [&](auto D) {
+    return with_even_two_d<2>(two_d, -100, [&](auto D) {
         constexpr int D2 = decltype(D)::value;
         if (tiles > 0) {
             const int rc = with_lik(lik, [&](auto L) {

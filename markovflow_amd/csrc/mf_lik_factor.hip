@@ -8,8 +8,9 @@
 //   a = W^T gm   G = W^T diag(gv) W                                                 (L and L x L, G symmetric)
 //   ve_sum[s] = sum_k sum_p ve_p     g_mean[s] = sum_k wg^T a     g_cov[s] = sum_k wg^T G wg
 //   g_w[k]    = gm (x) mu_g + 2 diag(gv) W Sig_g                                    ([P, L] per point: the adjoint onto W_k)
-// Two passes, tile-parallel, as mf_lik_sparse_multi_expectations_* (mf_lik.hip): the tile table, the tile of 64 points per wavefront,
-// the workspace row and pass 2 (mf_lik_reduce.hpp) are the siblings'.  New is pass 1:
+// Two passes, tile-parallel, as mf_lik_sparse_multi_expectations_* (mf_lik.hip): the tile table and its locator, the tile of 64 points
+// per wavefront, the staging of wg, the workspace row and pass 2 at K = 1 (all in mf_lik_tile.hpp) are the siblings'.
+// New is pass 1:
 //   phase 1, a lane per point.  The point's L rows of wg travel through LDS as ONE row of L 2d + 1 elements (odd: the lanes' rows
 //            start on distinct banks) into registers.  The projection is the rolled walk over the rows i of S_s:
 //            acc_l = sum_c S_ic wg_lc (c ascending),  Sig_g[l][l'] += wg_l'i acc_l for l' <= l,  mu_g[l] += wg_li m_i,
@@ -32,7 +33,7 @@
 // remarks: DESIGN.md 4.23), nothing was cut.  1 <= P <= FACTOR_MAX_OUTPUTS = 1024.
 #include "../../include/markovflow_amd.h"
 
-#include "mf_lik_reduce.hpp"
+#include "mf_lik_tile.hpp"
 
 namespace {
 
@@ -49,7 +50,7 @@ __global__ void __launch_bounds__(64) sparse_factor_expect_tile_kernel(long N, i
                                                                        const T* __restrict__ pair_mean, const T* __restrict__ pair_cov,
                                                                        int grads, T* __restrict__ gw, T* __restrict__ ws) {
     constexpr int C = FACTOR_CHUNK, W = L * D2 + 1, CW = C * (L + 1) + 1, TL = L * (L + 1) / 2, NG = TL + L + 1;
-    constexpr int TRI = D2 * (D2 + 1) / 2, E = seg_entries(D2, 3), R = (E + 63) / 64;
+    constexpr int TRI = D2 * (D2 + 1) / 2, E = expect_entries(1, D2), R = (E + 63) / 64;
     __shared__ T lw[64 * W];
     __shared__ T ls[D2 * D2];
     __shared__ T lm[D2];
@@ -57,15 +58,9 @@ __global__ void __launch_bounds__(64) sparse_factor_expect_tile_kernel(long N, i
     __shared__ T lg[NG * 64];          // G of the tile's points (TL rows), then a (L rows), then ve
     const int lane = threadIdx.x;
     const long t = blockIdx.x;
-    long bs = (long)tile_seg[t];
-    bs = bs < 0 ? 0 : (bs >= BS ? BS - 1 : bs);
-    const long b = bs / S;
-    const long s = bs - b * S;
-    long k_lo = (long)seg[b * (S + 1) + s], k_hi = (long)seg[b * (S + 1) + s + 1];
-    clamp_range(k_lo, k_hi, N);
-    const long j = t - (long)seg_tile[bs];                          // this tile's number within its segment
-    const long k0 = (j >= 0 && j <= (k_hi - k_lo) / 64) ? k_lo + 64 * j : k_hi;
-    const int npts = k_hi - k0 < 64 ? int(k_hi - k0) : 64;          // (0 only for a table that disagrees with the offsets)
+    const TileAt at = locate_tile<64>(t, N, S, BS, seg, tile_seg, seg_tile);
+    const long bs = at.bs, b = at.b, k0 = at.k0;
+    const int npts = at.npts;
     int ei[R], ej[R], kind[R];         // this lane's entries: kind 0 = (ei, ej) of the triangle, 1 = ei of the vector, 2 = the scalar,
     T part[R];                         // 3 = surplus
 #pragma unroll
@@ -81,8 +76,7 @@ __global__ void __launch_bounds__(64) sparse_factor_expect_tile_kernel(long N, i
         const long id0 = b * N + k0;                                 // the tile's first point
         for (int idx = lane; idx < D2 * D2; idx += 64) ls[idx] = pair_cov[bs * (D2 * D2) + idx];
         if (lane < D2) lm[lane] = pair_mean[bs * D2 + lane];
-        const T* wt = wg + id0 * (L * D2);                           // npts rows of L 2d elements: coalesced loads
-        for (int idx = lane; idx < npts * (L * D2); idx += 64) lw[(idx / (L * D2)) * W + idx % (L * D2)] = wt[idx];
+        stage_tile<T, L * D2>(lane, npts, wg + id0 * (L * D2), lw);  // npts rows of L 2d elements
         __syncthreads();
         T mug[L], sig[L][L], a[L], g[TL], ve_pt = T(0);
 #pragma unroll
@@ -230,36 +224,17 @@ __global__ void __launch_bounds__(64) sparse_factor_expect_tile_kernel(long N, i
             for (int k = 0; k < npts; ++k) part[R - 1] += lg[(TL + L) * 64 + k];
         }
     }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int e = lane + 64 * r;
-        if (e < E) ws[t * E + e] = part[r];
-    }
+    store_row<E>(ws + t * E, lane, part);
 }
 
 // (latent_dim, two_d) as compile-time constants: latent_dim in 2, 3, 4 and two_d even in 2 latent_dim ... 18; -101 for any other
-template <int L, typename F>
-int with_factor_two_d(int two_d, F&& f) {
-    if (two_d < 2 * L) return -101;
-    switch (two_d) {
-        case 4: if constexpr (L <= 2) return f(std::integral_constant<int, L>{}, std::integral_constant<int, 4>{}); else return -101;
-        case 6: if constexpr (L <= 3) return f(std::integral_constant<int, L>{}, std::integral_constant<int, 6>{}); else return -101;
-        case 8: return f(std::integral_constant<int, L>{}, std::integral_constant<int, 8>{});
-        case 10: return f(std::integral_constant<int, L>{}, std::integral_constant<int, 10>{});
-        case 12: return f(std::integral_constant<int, L>{}, std::integral_constant<int, 12>{});
-        case 14: return f(std::integral_constant<int, L>{}, std::integral_constant<int, 14>{});
-        case 16: return f(std::integral_constant<int, L>{}, std::integral_constant<int, 16>{});
-        case 18: return f(std::integral_constant<int, L>{}, std::integral_constant<int, 18>{});
-        default: return -101;
-    }
-}
-
 template <typename F>
 int with_factor_dims(int latent_dim, int two_d, F&& f) {
+    auto at = [&](auto L) { return with_even_two_d<2 * decltype(L)::value>(two_d, -101, [&](auto D) { return f(L, D); }); };
     switch (latent_dim) {
-        case 2: return with_factor_two_d<2>(two_d, f);
-        case 3: return with_factor_two_d<3>(two_d, f);
-        case 4: return with_factor_two_d<4>(two_d, f);
+        case 2: return at(std::integral_constant<int, 2>{});
+        case 3: return at(std::integral_constant<int, 3>{});
+        case 4: return at(std::integral_constant<int, 4>{});
         default: return -101;
     }
 }
@@ -271,21 +246,19 @@ int run_factor_expect(int64_t B, int64_t N, int64_t S, int two_d, int latent_dim
                       size_t ws_bytes, T* ve_sum, T* g_mean, T* g_cov, T* g_w, void* stream) {
     Rule<T> q;
     Par<T> p;
-    if (B < 0) return -1;
-    if (N < 0) return -2;
-    if (S < 1 || (B > 0 && S > int64_t(0x7fffffff) / B)) return -3;
+    int bad = check_segmentation(B, N, S);
+    if (bad) return bad;
     if (P < 1) return -6;
     if (latent_dim < 2 || latent_dim > 4 || two_d < 2 * latent_dim || two_d > 18 || (two_d & 1) || P > FACTOR_MAX_OUTPUTS) return -101;
-    int bad = prepare<T>(0, lik, params, nq, nodes, weights, false, q, p);       // -2 ... -6 there: arguments 7 ... 11 here
+    bad = prepare<T>(0, lik, params, nq, nodes, weights, false, q, p);           // -2 ... -6 there: arguments 7 ... 11 here
     if (bad) return bad - 5;
-    if (tiles < 0 || tiles > int64_t(0x7fffffff) || (N == 0 && tiles != 0)) return -19;
+    if ((bad = check_tile_count(19, N, tiles))) return bad;
     if (!g_mean && g_cov) return -25;
     if (g_mean && !g_cov) return -26;
     if (B == 0 || (!ve_sum && !g_mean && !g_w)) return 0;      // nothing asked for
     if (tiles > 0) {
         if ((bad = first_null(12, {seg, wg, cg, mix, y, pm, pc}))) return bad;
-        if ((bad = first_null(20, {tile_seg, seg_tile, ws}))) return bad;
-        if (ws_bytes < size_t(tiles) * expect_row(two_d) * sizeof(T)) return -23;
+        if ((bad = check_tile_table(19, tiles, tile_seg, seg_tile, ws, ws_bytes, expect_row(two_d), sizeof(T)))) return bad;
     }
     return with_factor_dims(latent_dim, two_d, [&](auto LL, auto D) {
         constexpr int L = decltype(LL)::value, D2 = decltype(D)::value;
@@ -296,7 +269,7 @@ int run_factor_expect(int64_t B, int64_t N, int64_t S, int two_d, int latent_dim
             });
             if (rc) return rc;
         }
-        return launch(sparse_expect_reduce_kernel<T, D2>, B * S, 256, stream, tiles, tiles > 0 ? ll(seg_tile) : nullptr, ws, ve_sum,
+        return launch(expect_reduce_kernel<T, 1, D2>, B * S, 256, stream, tiles, S, tiles > 0 ? ll(seg_tile) : nullptr, ws, ve_sum,
                       g_mean, g_cov);
     });
 }

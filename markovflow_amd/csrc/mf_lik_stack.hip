@@ -6,8 +6,8 @@
 // Per point n of segment s and latent k, ascending:  mu_k = w_kn . m_ks,  s2_k = c_kn + w_kn^T S_ks w_kn;  (ve, gm_k, gv_k) of the
 // likelihood at (mu, s2, y_n);  per segment, over the points in ascending order,
 //   ve_sum = sum ve      g_mean[k] = sum gm_k w_kn      g_cov[k] = sum gv_k w_kn w_kn^T
-// Two passes, tile-parallel, as mf_lik_sparse_multi_expectations_* (mf_lik.hip): the tile table and the tile of 64 points per
-// wavefront are the siblings'.
+// Two passes, tile-parallel, as mf_lik_sparse_multi_expectations_* (mf_lik.hip): the tile table and its locator, the tile of 64 points
+// per wavefront, the staging of a chain's rows, the workspace row and pass 2 (mf_lik_tile.hpp) are the siblings' at K chains.
 //   pass 1, phase 1, a lane per point.  The point's K rows of w travel through LDS as ONE row of K 2d + 1 elements (odd: the lanes'
 //            rows start on distinct banks); a chain's npts rows are contiguous in global memory, so the loads are coalesced runs.
 //            The latents are walked one after the other, so a lane holds ONE row of w in registers, not K: the rolled walk over the
@@ -26,15 +26,14 @@
 // Instantiated: (K, lik) = (3, multi-stage) and (2, heteroscedastic Gaussian), 2d even in 2 ... 18, both dtypes.
 #include "../../include/markovflow_amd.h"
 
-#include "mf_lik_reduce.hpp"
+#include "mf_lik_tile.hpp"
 #include "mf_lik_multistage.hpp"
 
 namespace {
 
 constexpr int LIK_HETEROSCEDASTIC = 5;     // mean and log-variance latents, K = 2 (LIK_MULTISTAGE = 4 has K = 3)
 
-// a workspace row: per latent the triangle of g_cov and g_mean, then sum ve
-constexpr int stack_entries(int k, int d2) { return k * (d2 * (d2 + 1) / 2 + d2) + 1; }
+// (a workspace row is expect_entries(K, 2d) values - per latent the triangle of g_cov and g_mean, then sum ve: mf_lik_tile.hpp)
 
 template <int LIK> struct StackLatents;
 template <> struct StackLatents<LIK_MULTISTAGE> { static constexpr int value = MULTI_L; };
@@ -85,22 +84,16 @@ __global__ void __launch_bounds__(64) stack_expect_tile_kernel(long N, int S, lo
                                                                const T* __restrict__ cvar, const T* __restrict__ yobs,
                                                                const T* __restrict__ pair_mean, const T* __restrict__ pair_cov,
                                                                int grads, T* __restrict__ ws) {
-    constexpr int W = K * D2 + 1, TRI = D2 * (D2 + 1) / 2, PER = TRI + D2, E = stack_entries(K, D2), R = (E + 63) / 64;
+    constexpr int W = K * D2 + 1, TRI = D2 * (D2 + 1) / 2, PER = TRI + D2, E = expect_entries(K, D2), R = (E + 63) / 64;
     __shared__ T lw[64 * W];
     __shared__ T ls[K * D2 * D2];
     __shared__ T lm[K * D2];
     __shared__ T lg[(2 * K + 1) * 64];
     const int lane = threadIdx.x;
     const long t = blockIdx.x;
-    long bs = (long)tile_seg[t];
-    bs = bs < 0 ? 0 : (bs >= BS ? BS - 1 : bs);
-    const long b = bs / S;
-    const long s = bs - b * S;
-    long k_lo = (long)seg[b * (S + 1) + s], k_hi = (long)seg[b * (S + 1) + s + 1];
-    clamp_range(k_lo, k_hi, N);
-    const long j = t - (long)seg_tile[bs];                          // this tile's number within its segment
-    const long k0 = (j >= 0 && j <= (k_hi - k_lo) / 64) ? k_lo + 64 * j : k_hi;
-    const int npts = k_hi - k0 < 64 ? int(k_hi - k0) : 64;          // (0 only for a table that disagrees with the offsets)
+    const TileAt at = locate_tile<64>(t, N, S, BS, seg, tile_seg, seg_tile);
+    const long b = at.b, s = at.s, k0 = at.k0;
+    const int npts = at.npts;
     // this lane's entries: kind 0 = (oi, oj) of a triangle, 1 = oi of a vector, 2 = the scalar, 3 = surplus; oi / oj are offsets into
     // a point's row of lw (latent * 2d + state), og the row of lg that holds the entry's factor
     int oi[R], oj[R], og[R], kind[R];
@@ -136,10 +129,8 @@ __global__ void __launch_bounds__(64) stack_expect_tile_kernel(long N, int S, lo
             lm[idx] = pair_mean[((b * K + k) * S + s) * D2 + (idx - k * D2)];
         }
 #pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const T* wt = w + ((b * K + k) * N + k0) * D2;           // npts rows of 2d elements of chain k: coalesced loads
-            for (int idx = lane; idx < npts * D2; idx += 64) lw[(idx / D2) * W + k * D2 + idx % D2] = wt[idx];
-        }
+        for (int k = 0; k < K; ++k)                                   // npts rows of 2d elements of chain k, at column k 2d
+            stage_tile<T, D2, W>(lane, npts, w + ((b * K + k) * N + k0) * D2, lw, k * D2);
         __syncthreads();
         if (lane < npts) {
             T mu[K], s2[K], gm[K], gv[K], ve;
@@ -184,63 +175,13 @@ __global__ void __launch_bounds__(64) stack_expect_tile_kernel(long N, int S, lo
         }
     }
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
+    for (int r = 0; r < R; ++r) {                  // (not store_row: through it four float64 instantiations spill two more SGPRs)
         const int e = lane + 64 * r;
         if (e < E) ws[t * E + e] = part[r];
     }
 }
 
-template <typename T, int K, int D2>
-__global__ void __launch_bounds__(256) stack_expect_reduce_kernel(long num_tiles, int S, const long long* __restrict__ seg_tile,
-                                                                  const T* __restrict__ ws, T* __restrict__ ve_sum,
-                                                                  T* __restrict__ g_mean, T* __restrict__ g_cov) {
-    constexpr int TRI = D2 * (D2 + 1) / 2, PER = TRI + D2, E = stack_entries(K, D2);
-    const long bs = blockIdx.x;
-    const long b = bs / S;
-    const long s = bs - b * S;
-    long t_lo = 0, t_hi = 0;
-    if (seg_tile) {                                // (NULL: no points at all)
-        t_lo = (long)seg_tile[bs];
-        t_hi = (long)seg_tile[bs + 1];
-        clamp_range(t_lo, t_hi, num_tiles);
-    }
-    for (int e = threadIdx.x; e < E; e += 256) {
-        if (e < E - 1 ? !g_mean : !ve_sum) continue;
-        T acc = T(0);
-        for (long t = t_lo; t < t_hi; ++t) acc += ws[t * E + e];
-        if (e == E - 1) {
-            ve_sum[bs] = acc;
-            continue;
-        }
-        const int k = e / PER, f = e - k * PER;
-        const long row = (b * K + k) * S + s;
-        if (f < TRI) {
-            int i, c;
-            tri_decode(f, i, c);
-            g_cov[row * (D2 * D2) + i * D2 + c] = acc;
-            g_cov[row * (D2 * D2) + c * D2 + i] = acc;
-        } else {
-            g_mean[row * D2 + (f - TRI)] = acc;
-        }
-    }
-}
-
-// two_d (even in 2 ... 18) as a compile-time constant; -101 for any other
-template <typename F>
-int with_stack_two_d(int two_d, F&& f) {
-    switch (two_d) {
-        case 2: return f(std::integral_constant<int, 2>{});
-        case 4: return f(std::integral_constant<int, 4>{});
-        case 6: return f(std::integral_constant<int, 6>{});
-        case 8: return f(std::integral_constant<int, 8>{});
-        case 10: return f(std::integral_constant<int, 10>{});
-        case 12: return f(std::integral_constant<int, 12>{});
-        case 14: return f(std::integral_constant<int, 14>{});
-        case 16: return f(std::integral_constant<int, 16>{});
-        case 18: return f(std::integral_constant<int, 18>{});
-        default: return -101;
-    }
-}
+// (pass 2 is expect_reduce_kernel<T, K, D2> of mf_lik_tile.hpp)
 
 inline bool stack_instantiated(int two_d, int latent_dim, int lik) {
     if (two_d < 2 || two_d > 18 || (two_d & 1)) return false;
@@ -255,22 +196,21 @@ int run_stack_expect(int64_t B, int latent_dim, int64_t N, int64_t S, int two_d,
                      T* g_cov, void* stream) {
     Rule<T> q;
     Par<T> p;
-    if (B < 0) return -1;
-    if (N < 0) return -3;
-    if (S < 1 || (B > 0 && S > int64_t(0x7fffffff) / B)) return -4;
+    int bad = check_segmentation(B, N, S, 3, 4);                                 // (latent_dim is the second argument here)
+    if (bad) return bad;
     if (!stack_instantiated(two_d, latent_dim, lik)) return -101;
-    int bad = prepare<T>(0, 1, nullptr, nq, nodes, weights, false, q, p);        // -4 ... -6 there: arguments 8 ... 10 here
+    bad = prepare<T>(0, 1, nullptr, nq, nodes, weights, false, q, p);            // -4 ... -6 there: arguments 8 ... 10 here
     if (bad) return bad - 4;
-    if (tiles < 0 || tiles > int64_t(0x7fffffff) || (N == 0 && tiles != 0)) return -17;
+    if ((bad = check_tile_count(17, N, tiles))) return bad;
     if (!g_mean && g_cov) return -23;
     if (g_mean && !g_cov) return -24;
     if (B == 0 || (!ve_sum && !g_mean)) return 0;      // nothing asked for
     if (tiles > 0) {
         if ((bad = first_null(11, {seg, w, c, y, pm, pc}))) return bad;
-        if ((bad = first_null(18, {tile_seg, seg_tile, ws}))) return bad;
-        if (ws_bytes < size_t(tiles) * size_t(stack_entries(latent_dim, two_d)) * sizeof(T)) return -21;
+        if ((bad = check_tile_table(17, tiles, tile_seg, seg_tile, ws, ws_bytes, size_t(expect_entries(latent_dim, two_d)), sizeof(T))))
+            return bad;
     }
-    return with_stack_two_d(two_d, [&](auto D) {
+    return with_even_two_d<2>(two_d, -101, [&](auto D) {
         constexpr int D2 = decltype(D)::value;
         auto run = [&](auto LK) {
             constexpr int LIK = decltype(LK)::value, K = StackLatents<LIK>::value;
@@ -279,7 +219,7 @@ int run_stack_expect(int64_t B, int latent_dim, int64_t N, int64_t S, int two_d,
                                       ll(tile_seg), ll(seg_tile), w, c, y, pm, pc, g_mean ? 1 : 0, ws);
                 if (rc) return rc;
             }
-            return launch(stack_expect_reduce_kernel<T, K, D2>, B * S, 256, stream, tiles, S, tiles > 0 ? ll(seg_tile) : nullptr, ws,
+            return launch(expect_reduce_kernel<T, K, D2>, B * S, 256, stream, tiles, S, tiles > 0 ? ll(seg_tile) : nullptr, ws,
                           ve_sum, g_mean, g_cov);
         };
         return lik == LIK_MULTISTAGE ? run(std::integral_constant<int, LIK_MULTISTAGE>{})
@@ -293,7 +233,7 @@ extern "C" {
 
 size_t mf_lik_stack_expectations_workspace_bytes(int64_t num_tiles, int two_d, int latent_dim, int elem_size) {
     if (num_tiles <= 0 || two_d < 2 || two_d > 18 || (two_d & 1) || latent_dim < 1 || elem_size < 1) return 0;
-    return size_t(num_tiles) * size_t(stack_entries(latent_dim, two_d)) * size_t(elem_size);
+    return size_t(num_tiles) * size_t(expect_entries(latent_dim, two_d)) * size_t(elem_size);
 }
 int mf_lik_stack_expectations_f64(int64_t B, int latent_dim, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq,
                                   const double* nodes, const double* weights, const int64_t* seg, const double* w, const double* c,

@@ -24,10 +24,11 @@
 // ST_WANT_SITES - g1 = gm - 2 gv fmu rides into the vector sum in place of gm - and a pass 2 of its own, st_cvi_reduce_kernel, which
 // adds the rows in the same order and blends the sums into nat1 and nat2 in place.
 // Every sum starts from 0 and grows by one fused multiply-add per term, index ascending (include/markovflow_amd.h has the list); no
-// floating-point atomics.  The tile table is clamped here, not trusted.
+// floating-point atomics.  The tile table is clamped (locate_tile at ST_TILE points a tile: mf_lik_tile.hpp), not trusted.
 #include "../../include/markovflow_amd.h"
 
-#include "mf_lik_math.hpp"
+// (the tile locator and the checks of the segmentation: shared with the other tile-parallel kernels)
+#include "mf_lik_tile.hpp"
 
 namespace {
 
@@ -97,16 +98,10 @@ __global__ void __launch_bounds__(ST_THREADS) st_expect_tile_kernel(
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ti = tid >> 4, tj = tid & 15;
     const bool want_lik = want != 0 || g_a != nullptr;          // (g_a, g_wt, g_c come together)
 
-    const long t = blockIdx.x;
-    long bs = (long)tile_seg[t];
-    bs = bs < 0 ? 0 : (bs >= BS ? BS - 1 : bs);
-    const long b = bs / S;
-    const long s_seg = bs - b * S;
-    long k_lo = (long)seg[b * (S + 1) + s_seg], k_hi = (long)seg[b * (S + 1) + s_seg + 1];
-    clamp_range(k_lo, k_hi, N);
-    const long jrow = t - (long)seg_tile[bs];                   // this row's number within its segment
-    const long k0 = (jrow >= 0 && jrow <= (k_hi - k_lo) / ST_TILE) ? k_lo + ST_TILE * jrow : k_hi;
-    const int npts_row = k_hi - k0 < ST_TILE ? int(k_hi - k0) : ST_TILE;      // (0 only for a table that disagrees with the offsets)
+    const long t = blockIdx.x;                                  // this row of the table: ST_TILE points a tile
+    const TileAt at = locate_tile<ST_TILE>(t, N, S, BS, seg, tile_seg, seg_tile);
+    const long bs = at.bs, b = at.b, k0 = at.k0;
+    const int npts_row = at.npts;
 
     T acc[ST_REG * (ST_REG + 1) / 2];
 #pragma unroll
@@ -417,13 +412,12 @@ int run_st_cvi(int64_t B, int64_t N, int64_t S, int Ms, int two_dt, int lik, con
                T* nat2, T* ve_sum, T* fmu, T* fvar, void* stream) {
     Rule<T> q;
     Par<T> p;
-    if (B < 0) return -1;
-    if (N < 0) return -2;
-    if (S < 1 || (B > 0 && S > int64_t(0x7fffffff) / B)) return -3;
+    int bad = check_segmentation(B, N, S);
+    if (bad) return bad;
     if (!st_in_range(Ms, two_dt)) return -100;
-    int bad = prepare<T>(0, lik, params, nq, nodes, weights, false, q, p);      // -2 ... -6 there: arguments 6 ... 10 here
+    bad = prepare<T>(0, lik, params, nq, nodes, weights, false, q, p);          // -2 ... -6 there: arguments 6 ... 10 here
     if (bad) return bad - 4;
-    if (tiles < 0 || tiles > int64_t(0x7fffffff) || (N == 0 && tiles != 0)) return -18;
+    if ((bad = check_tile_count(18, N, tiles))) return bad;
     if (!(learning_rate >= 0.0 && learning_rate <= 1.0)) return -23;           // (NaN fails both)
     if ((bad = first_null(24, {nat1, nat2}))) return bad;
     if (B == 0) return 0;
@@ -457,13 +451,12 @@ int run_st(int64_t B, int64_t N, int64_t S, int Ms, int two_dt, int lik, const d
            T* g_a, T* g_wt, T* g_c, T* fmu, T* fvar, void* stream) {
     Rule<T> q;
     Par<T> p;
-    if (B < 0) return -1;
-    if (N < 0) return -2;
-    if (S < 1 || (B > 0 && S > int64_t(0x7fffffff) / B)) return -3;
+    int bad = check_segmentation(B, N, S);
+    if (bad) return bad;
     if (!st_in_range(Ms, two_dt)) return -100;
-    int bad = prepare<T>(0, lik, params, nq, nodes, weights, false, q, p);      // -2 ... -6 there: arguments 6 ... 10 here
+    bad = prepare<T>(0, lik, params, nq, nodes, weights, false, q, p);          // -2 ... -6 there: arguments 6 ... 10 here
     if (bad) return bad - 4;
-    if (tiles < 0 || tiles > int64_t(0x7fffffff) || (N == 0 && tiles != 0)) return -18;
+    if ((bad = check_tile_count(18, N, tiles))) return bad;
     if (!g_mean && g_cov) return -24;
     if (g_mean && !g_cov) return -25;
     if (g_a || g_wt || g_c) {                      // all three, or none

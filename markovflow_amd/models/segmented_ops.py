@@ -21,6 +21,11 @@ forward launch wrote:
     multi-output term of any kernel with ``P`` outputs (torch only);
   * ``iw_log_likelihood(_torch)``: ``mf_lik_iw_log_weights_*`` (two passes, tile-parallel, no atomics), the data term of the
     importance weights with Matheron's correction assembled in the kernel.
+
+The four tile-parallel SVGP terms share their plumbing: ``_expectations_launch`` is the body of the four
+``_sparse_*_expectations_launch`` (outputs, workspace, ONE call), ``_ExpectedLogLikelihood`` the autograd function of the single,
+multi and stack terms (the factor term's sibling adds the ``mix`` adjoint), and the compositions are built from ``_gather_pairs``,
+``_flat_segments`` and ``_segment_sum``.
 """
 from typing import Optional, Tuple
 
@@ -62,17 +67,32 @@ def _site_offsets(time_points: torch.Tensor, inducing_points: torch.Tensor) -> t
     return offsets.contiguous()
 
 
+def _gather_pairs(pair_mean: torch.Tensor, pair_cov: torch.Tensor, indices: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(m_s [.., N, 2d], S_s [.., N, 2d, 2d])``: the marginal of the pair every point belongs to (``indices [.., N]``)."""
+    two_d = pair_mean.shape[-1]
+    return (torch.gather(pair_mean, -2, indices[..., None].expand(tuple(indices.shape) + (two_d,))),
+            torch.gather(pair_cov, -3, indices[..., None, None].expand(tuple(indices.shape) + (two_d, two_d))))
+
+
+def _flat_segments(indices: torch.Tensor, segs: int) -> torch.Tensor:
+    """One flat segment index over the batch, ``series * segs + pair`` (``[B N]``), from the per-point pair index ``[.., N]``."""
+    series = torch.arange(math.prod(indices.shape[:-1]), device=indices.device).reshape(tuple(indices.shape[:-1]) + (1,))
+    return (indices + series * segs).reshape(-1)
+
+
+def _segment_sum(ve: torch.Tensor, flat: torch.Tensor, shape) -> torch.Tensor:
+    """The per-point values ``ve`` added per segment (``flat``: ``_flat_segments`` of the points), as a tensor of ``shape``."""
+    return torch.zeros(math.prod(shape), dtype=ve.dtype, device=ve.device).index_add(0, flat, ve.reshape(-1)).reshape(tuple(shape))
+
+
 def _sparse_point_marginals(w: torch.Tensor, c: torch.Tensor, indices: torch.Tensor, pair_mean: torch.Tensor, pair_cov: torch.Tensor,
                             segs: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Per point ``fmu = w . m_s`` and ``fvar = c + w^T S_s w`` (``[.., N]`` each) with ``(m_s, S_s)`` the marginal of the pair the
     point belongs to (``indices [.., N]``), and one flat segment index over the batch, ``series * segs + pair`` (``[B N]``)."""
-    two_d = w.shape[-1]
-    m = torch.gather(pair_mean, -2, indices[..., None].expand(tuple(indices.shape) + (two_d,)))
-    cov = torch.gather(pair_cov, -3, indices[..., None, None].expand(tuple(indices.shape) + (two_d, two_d)))
+    m, cov = _gather_pairs(pair_mean, pair_cov, indices)
     fmu = torch.sum(w * m, dim=-1)
     fvar = c + torch.sum(w * torch.sum(cov * w[..., None, :], dim=-1), dim=-1)
-    series = torch.arange(math.prod(indices.shape[:-1]), device=indices.device).reshape(tuple(indices.shape[:-1]) + (1,))
-    return fmu, fvar, (indices + series * segs).reshape(-1)
+    return fmu, fvar, _flat_segments(indices, segs)
 
 
 def _segments_of(offsets: torch.Tensor, n: int) -> torch.Tensor:
@@ -255,40 +275,58 @@ def pair_cavity(pair_mean: torch.Tensor, pair_cov: torch.Tensor, nat1: torch.Ten
             (g_cav - g_marg).masked_fill(bad, nan))
 
 
+def _expectations_launch(base: str, likelihood: Likelihood, dims, inputs, offsets, tiles, pair_mean, pair_cov, want_grads: bool,
+                         chains=(), ws_dims=(), extra=None):
+    """ONE call of the tile-parallel SVGP entry point ``base``, the body of the four launchers below.  ``dims``: its dimension
+    arguments after the batch size; ``inputs``: its per-point tensors, the projection ``[.., 2d]`` first; ``chains``: the axes of the
+    adjoints between the series and the segments (the stack's ``K``); ``ws_dims``: what ``base_workspace_bytes`` takes between ``2d``
+    and the element size; ``extra``: ``(want, *shape)`` of a per-series output after ``g_cov``.  Returns ``(ve_sum [.., S],
+    g_mean [.., chains, S, 2d] | None, g_cov [.., chains, S, 2d, 2d] | None)`` and the extra output, if any."""
+    first = inputs[0]
+    dtype, dev = first.dtype, first.device
+    two_d, segs = first.shape[-1], offsets.shape[-1] - 1
+    batch = tuple(offsets.shape[:-1])
+    num_tiles, tile_seg, seg_tile = tiles
+    new, new_adjoint = _new_outputs(batch, dtype, dev), _new_outputs(batch + tuple(chains), dtype, dev)
+    outs = (new(True, segs), new_adjoint(want_grads, segs, two_d), new_adjoint(want_grads, segs, two_d, two_d))
+    if extra is not None:
+        outs += (new(*extra),)
+    ws, ws_bytes = _workspace(getattr(_lib.load(), base + "_workspace_bytes"), dev, num_tiles, two_d, *ws_dims, first.element_size())
+    _launch(base, dtype, dev, offsets.numel() // (segs + 1), *dims, *likelihood._kernel_args(), offsets, *inputs, pair_mean, pair_cov,
+            num_tiles, tile_seg, seg_tile, ws, ws_bytes, *outs)
+    return outs
+
+
 def _sparse_expectations_launch(likelihood: Likelihood, w, c, y, offsets, tiles, pair_mean, pair_cov, want_grads: bool):
     """ONE call of ``mf_lik_sparse_expectations_*``: ``(ve_sum [.., S], g_mean [.., S, 2d] | None, g_cov [.., S, 2d, 2d] | None)``."""
-    dtype, dev = w.dtype, w.device
-    n, two_d, segs = w.shape[-2], w.shape[-1], offsets.shape[-1] - 1
-    batch = tuple(offsets.shape[:-1])
-    bsz = offsets.numel() // (segs + 1)
-    num_tiles, tile_seg, seg_tile = tiles
-    new = _new_outputs(batch, dtype, dev)
-    ve_sum, g_mean, g_cov = new(True, segs), new(want_grads, segs, two_d), new(want_grads, segs, two_d, two_d)
-    ws, ws_bytes = _workspace(_lib.load().mf_lik_sparse_expectations_workspace_bytes, dev, num_tiles, two_d, w.element_size())
-    _launch("mf_lik_sparse_expectations", dtype, dev, bsz, n, segs, two_d, *likelihood._kernel_args(), offsets, w, c, y, pair_mean,
-            pair_cov, num_tiles, tile_seg, seg_tile, ws, ws_bytes, ve_sum, g_mean, g_cov)
-    return ve_sum, g_mean, g_cov
+    return _expectations_launch("mf_lik_sparse_expectations", likelihood, (w.shape[-2], offsets.shape[-1] - 1, w.shape[-1]), (w, c, y),
+                                offsets, tiles, pair_mean, pair_cov, want_grads)
 
 
-class _SparseExpectedLogLikelihood(torch.autograd.Function):
-    """Value ``batch + [M + 1]``; the adjoints onto the pair marginals come out of the same launch and wait for the backward."""
+class _ExpectedLogLikelihood(torch.autograd.Function):
+    """The single-latent, multi-latent and stacked SVGP data terms: value ``batch + [M + 1]``; the adjoints onto the pair marginals
+    come out of the same launch and wait for the backward.  ``launcher``: one of the ``_sparse_*_expectations_launch``; ``name``: the
+    public function, for the messages; ``chains``: the number of axes of the pair marginals between the series and the segments
+    (the stack's ``K``: 1), over which a segment's cotangent is broadcast."""
 
     @staticmethod
-    def forward(ctx, pair_mean, pair_cov, likelihood, w, c, y, offsets, tiles):
+    def forward(ctx, pair_mean, pair_cov, launcher, name, chains, likelihood, w, c, y, offsets, tiles):
         want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         with torch.no_grad():
-            ve_sum, g_mean, g_cov = _sparse_expectations_launch(likelihood, w.detach(), c.detach(), y.detach(), offsets, tiles,
-                                                                pair_mean.detach(), pair_cov.detach(), want)
+            ve_sum, g_mean, g_cov = launcher(likelihood, w.detach(), c.detach(), y.detach(), offsets, tiles, pair_mean.detach(),
+                                             pair_cov.detach(), want)
         if want:
             ctx.save_for_backward(g_mean, g_cov)
+        ctx.name, ctx.chains = name, chains
         return ve_sum
 
     @staticmethod
     def backward(ctx, grad_out):
-        _differentiable_once("sparse_expected_log_likelihood", "adjoints")
+        _differentiable_once(ctx.name, "adjoints")
         g_mean, g_cov = ctx.saved_tensors
-        return (grad_out[..., None] * g_mean if ctx.needs_input_grad[0] else None,
-                grad_out[..., None, None] * g_cov if ctx.needs_input_grad[1] else None, None, None, None, None, None, None)
+        g = grad_out[(Ellipsis,) + (None,) * ctx.chains + (slice(None),)]       # a segment's cotangent goes to every chain of it
+        return (g[..., None] * g_mean if ctx.needs_input_grad[0] else None,
+                g[..., None, None] * g_cov if ctx.needs_input_grad[1] else None) + (None,) * 9
 
 
 def sparse_expected_log_likelihood(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor, offsets: torch.Tensor,
@@ -315,7 +353,8 @@ def sparse_expected_log_likelihood(likelihood: Likelihood, w: torch.Tensor, c: t
                                   "tape): use sparse_expected_log_likelihood_torch")
     if tiles is None:
         tiles = sparse_expectation_tiles(offsets)
-    return _SparseExpectedLogLikelihood.apply(pair_mean, pair_cov, likelihood, w, c, y, offsets, tiles)
+    return _ExpectedLogLikelihood.apply(pair_mean, pair_cov, _sparse_expectations_launch, "sparse_expected_log_likelihood", 0,
+                                        likelihood, w, c, y, offsets, tiles)
 
 
 def sparse_expected_log_likelihood_torch(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor,
@@ -326,8 +365,7 @@ def sparse_expected_log_likelihood_torch(likelihood: Likelihood, w: torch.Tensor
     hyper-parameter under the tape, and it is what ``mf_lik_sparse_expectations_*`` is measured against."""
     fmu, fvar, flat = _sparse_point_marginals(w, c, indices, pair_mean, pair_cov, pair_mean.shape[-2])
     ve = likelihood.variational_expectations(fmu[..., None], fvar[..., None], y[..., None])
-    out = torch.zeros(math.prod(pair_mean.shape[:-1]), dtype=ve.dtype, device=ve.device).index_add(0, flat, ve.reshape(-1))
-    return out.reshape(pair_mean.shape[:-1])
+    return _segment_sum(ve, flat, pair_mean.shape[:-1])
 
 
 # ---- SVGP with several latent functions per observation -----------------------------------------------------------------------------
@@ -346,49 +384,17 @@ def sparse_multi_site_projections(kernel: SDEKernel, time_points: torch.Tensor, 
 def _sparse_multi_point_marginals(w: torch.Tensor, c: torch.Tensor, indices: torch.Tensor, pair_mean: torch.Tensor,
                                   pair_cov: torch.Tensor, segs: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """``_sparse_point_marginals`` per latent: ``fmu``, ``fvar`` ``[.., N, L]`` from ``w [.., N, L, 2d]``, ``c [.., N, L]``."""
-    two_d = w.shape[-1]
-    m = torch.gather(pair_mean, -2, indices[..., None].expand(tuple(indices.shape) + (two_d,)))
-    cov = torch.gather(pair_cov, -3, indices[..., None, None].expand(tuple(indices.shape) + (two_d, two_d)))
+    m, cov = _gather_pairs(pair_mean, pair_cov, indices)
     fmu = torch.sum(w * m[..., None, :], dim=-1)
     fvar = c + torch.sum(w * (w @ cov.transpose(-1, -2)), dim=-1)
-    series = torch.arange(math.prod(indices.shape[:-1]), device=indices.device).reshape(tuple(indices.shape[:-1]) + (1,))
-    return fmu, fvar, (indices + series * segs).reshape(-1)
+    return fmu, fvar, _flat_segments(indices, segs)
 
 
 def _sparse_multi_expectations_launch(likelihood: Likelihood, w, c, y, offsets, tiles, pair_mean, pair_cov, want_grads: bool):
     """ONE call of ``mf_lik_sparse_multi_expectations_*``: ``(ve_sum [.., S], g_mean [.., S, 2d] | None, g_cov [.., S, 2d, 2d] | None)``."""
-    dtype, dev = w.dtype, w.device
-    n, latents, two_d, segs = w.shape[-3], w.shape[-2], w.shape[-1], offsets.shape[-1] - 1
-    batch = tuple(offsets.shape[:-1])
-    bsz = offsets.numel() // (segs + 1)
-    num_tiles, tile_seg, seg_tile = tiles
-    new = _new_outputs(batch, dtype, dev)
-    ve_sum, g_mean, g_cov = new(True, segs), new(want_grads, segs, two_d), new(want_grads, segs, two_d, two_d)
-    ws, ws_bytes = _workspace(_lib.load().mf_lik_sparse_multi_expectations_workspace_bytes, dev, num_tiles, two_d, w.element_size())
-    _launch("mf_lik_sparse_multi_expectations", dtype, dev, bsz, n, segs, two_d, latents, *likelihood._kernel_args(), offsets, w, c, y,
-            pair_mean, pair_cov, num_tiles, tile_seg, seg_tile, ws, ws_bytes, ve_sum, g_mean, g_cov)
-    return ve_sum, g_mean, g_cov
-
-
-class _SparseMultiExpectedLogLikelihood(torch.autograd.Function):
-    """Value ``batch + [M + 1]``; the adjoints onto the pair marginals come out of the same launch and wait for the backward."""
-
-    @staticmethod
-    def forward(ctx, pair_mean, pair_cov, likelihood, w, c, y, offsets, tiles):
-        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        with torch.no_grad():
-            ve_sum, g_mean, g_cov = _sparse_multi_expectations_launch(likelihood, w.detach(), c.detach(), y.detach(), offsets, tiles,
-                                                                      pair_mean.detach(), pair_cov.detach(), want)
-        if want:
-            ctx.save_for_backward(g_mean, g_cov)
-        return ve_sum
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        _differentiable_once("sparse_multi_expected_log_likelihood", "adjoints")
-        g_mean, g_cov = ctx.saved_tensors
-        return (grad_out[..., None] * g_mean if ctx.needs_input_grad[0] else None,
-                grad_out[..., None, None] * g_cov if ctx.needs_input_grad[1] else None, None, None, None, None, None, None)
+    return _expectations_launch("mf_lik_sparse_multi_expectations", likelihood,
+                                (w.shape[-3], offsets.shape[-1] - 1, w.shape[-1], w.shape[-2]), (w, c, y), offsets, tiles, pair_mean,
+                                pair_cov, want_grads)
 
 
 def sparse_multi_expected_log_likelihood(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor,
@@ -419,7 +425,8 @@ def sparse_multi_expected_log_likelihood(likelihood: Likelihood, w: torch.Tensor
                                   "sparse_multi_expected_log_likelihood_torch")
     if tiles is None:
         tiles = sparse_expectation_tiles(offsets)
-    return _SparseMultiExpectedLogLikelihood.apply(pair_mean, pair_cov, likelihood, w, c, y, offsets, tiles)
+    return _ExpectedLogLikelihood.apply(pair_mean, pair_cov, _sparse_multi_expectations_launch, what, 0, likelihood, w, c, y, offsets,
+                                        tiles)
 
 
 def sparse_multi_expected_log_likelihood_torch(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor,
@@ -430,8 +437,7 @@ def sparse_multi_expected_log_likelihood_torch(likelihood: Likelihood, w: torch.
     hyper-parameter under the tape, and it is what ``mf_lik_sparse_multi_expectations_*`` is measured against."""
     fmu, fvar, flat = _sparse_multi_point_marginals(w, c, indices, pair_mean, pair_cov, pair_mean.shape[-2])
     ve = likelihood.variational_expectations(fmu, fvar, y[..., None])
-    out = torch.zeros(math.prod(pair_mean.shape[:-1]), dtype=ve.dtype, device=ve.device).index_add(0, flat, ve.reshape(-1))
-    return out.reshape(pair_mean.shape[:-1])
+    return _segment_sum(ve, flat, pair_mean.shape[:-1])
 
 
 # ---- SVGP with several latent functions per observation on STACKED chains (IndependentMultiOutputStack) ----------------------------
@@ -465,41 +471,9 @@ def _sparse_stack_check(what: str, likelihood, w, c, y, lead, segs, pair_mean, p
 
 def _sparse_stack_expectations_launch(likelihood: Likelihood, w, c, y, offsets, tiles, pair_mean, pair_cov, want_grads: bool):
     """ONE call of ``mf_lik_stack_expectations_*``: ``(ve_sum [.., S], g_mean [.., K, S, 2d] | None, g_cov [.., K, S, 2d, 2d] | None)``."""
-    dtype, dev = w.dtype, w.device
-    latents, n, two_d, segs = w.shape[-3], w.shape[-2], w.shape[-1], offsets.shape[-1] - 1
-    lead = tuple(offsets.shape[:-1])
-    bsz = offsets.numel() // (segs + 1)
-    num_tiles, tile_seg, seg_tile = tiles
-    ve_sum = torch.empty(lead + (segs,), dtype=dtype, device=dev)
-    new = _new_outputs(lead + (latents,), dtype, dev)
-    g_mean, g_cov = new(want_grads, segs, two_d), new(want_grads, segs, two_d, two_d)
-    ws, ws_bytes = _workspace(_lib.load().mf_lik_stack_expectations_workspace_bytes, dev, num_tiles, two_d, latents, w.element_size())
-    _launch("mf_lik_stack_expectations", dtype, dev, bsz, latents, n, segs, two_d, *likelihood._kernel_args(), offsets, w, c, y,
-            pair_mean, pair_cov, num_tiles, tile_seg, seg_tile, ws, ws_bytes, ve_sum, g_mean, g_cov)
-    return ve_sum, g_mean, g_cov
-
-
-class _SparseStackExpectedLogLikelihood(torch.autograd.Function):
-    """Value ``lead + [M + 1]``; the adjoints onto the ``K`` chains' pair marginals come out of the same launch and wait for the
-    backward."""
-
-    @staticmethod
-    def forward(ctx, pair_mean, pair_cov, likelihood, w, c, y, offsets, tiles):
-        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        with torch.no_grad():
-            ve_sum, g_mean, g_cov = _sparse_stack_expectations_launch(likelihood, w.detach(), c.detach(), y.detach(), offsets, tiles,
-                                                                      pair_mean.detach(), pair_cov.detach(), want)
-        if want:
-            ctx.save_for_backward(g_mean, g_cov)
-        return ve_sum
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        _differentiable_once("sparse_stack_expected_log_likelihood", "adjoints")
-        g_mean, g_cov = ctx.saved_tensors
-        g = grad_out[..., None, :]                  # a segment's cotangent goes to every chain of it
-        return (g[..., None] * g_mean if ctx.needs_input_grad[0] else None,
-                g[..., None, None] * g_cov if ctx.needs_input_grad[1] else None, None, None, None, None, None, None)
+    latents = w.shape[-3]
+    return _expectations_launch("mf_lik_stack_expectations", likelihood, (latents, w.shape[-2], offsets.shape[-1] - 1, w.shape[-1]),
+                                (w, c, y), offsets, tiles, pair_mean, pair_cov, want_grads, chains=(latents,), ws_dims=(latents,))
 
 
 def sparse_stack_expected_log_likelihood(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor,
@@ -528,7 +502,8 @@ def sparse_stack_expected_log_likelihood(likelihood: Likelihood, w: torch.Tensor
                                   "sparse_stack_expected_log_likelihood_torch")
     if tiles is None:
         tiles = sparse_expectation_tiles(offsets)
-    return _SparseStackExpectedLogLikelihood.apply(pair_mean, pair_cov, likelihood, w, c, y, offsets, tiles)
+    return _ExpectedLogLikelihood.apply(pair_mean, pair_cov, _sparse_stack_expectations_launch, what, 1, likelihood, w, c, y, offsets,
+                                        tiles)
 
 
 def sparse_stack_expected_log_likelihood_torch(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor,
@@ -557,10 +532,7 @@ def sparse_stack_expected_log_likelihood_torch(likelihood: Likelihood, w: torch.
         fmu, fvar = torch.gather(fmu, -1, inverse), torch.gather(fvar, -1, inverse)
         booked = torch.gather(booked, -1, inverse[..., 0, :])
     ve = likelihood.variational_expectations(fmu.transpose(-1, -2), fvar.transpose(-1, -2), y[..., None])
-    series = torch.arange(math.prod(lead), device=indices.device).reshape(lead + (1,))
-    flat = (booked + series * segs).reshape(-1)
-    out = torch.zeros(math.prod(lead) * segs, dtype=ve.dtype, device=ve.device).index_add(0, flat, ve.reshape(-1))
-    return out.reshape(lead + (segs,))
+    return _segment_sum(ve, _flat_segments(booked, segs), lead + (segs,))
 
 
 # ---- SVGP with several observed series per point: multi-output kernels and the FactorAnalysis emission ------------------------------
@@ -581,8 +553,7 @@ def sparse_multi_output_expected_log_likelihood_torch(likelihood: Likelihood, w:
     _check_shapes("sparse_multi_output_expected_log_likelihood_torch", dict(c=(c, tuple(w.shape[:-1])), y=(y, tuple(w.shape[:-1]))))
     fmu, fvar, flat = _sparse_multi_point_marginals(w, c, indices, pair_mean, pair_cov, pair_mean.shape[-2])
     ve = torch.sum(likelihood.variational_expectations(fmu[..., None], fvar[..., None], y[..., None]), dim=-1)
-    out = torch.zeros(math.prod(pair_mean.shape[:-1]), dtype=ve.dtype, device=ve.device).index_add(0, flat, ve.reshape(-1))
-    return out.reshape(pair_mean.shape[:-1])
+    return _segment_sum(ve, flat, pair_mean.shape[:-1])
 
 
 def sparse_factor_site_projections(kernel, time_points: torch.Tensor, inducing_points: torch.Tensor
@@ -615,18 +586,10 @@ def _sparse_factor_expectations_launch(likelihood: Likelihood, wg, cg, mix, y, o
                                        want_g_w: bool):
     """ONE call of ``mf_lik_sparse_factor_expectations_*``: ``(ve_sum [.., S], g_mean [.., S, 2d] | None, g_cov [.., S, 2d, 2d] | None,
     g_w [.., N, P, L] | None)``."""
-    dtype, dev = wg.dtype, wg.device
-    n, latents, two_d, outputs, segs = wg.shape[-3], wg.shape[-2], wg.shape[-1], mix.shape[-2], offsets.shape[-1] - 1
-    batch = tuple(offsets.shape[:-1])
-    bsz = offsets.numel() // (segs + 1)
-    num_tiles, tile_seg, seg_tile = tiles
-    new = _new_outputs(batch, dtype, dev)
-    ve_sum, g_mean, g_cov = new(True, segs), new(want_grads, segs, two_d), new(want_grads, segs, two_d, two_d)
-    g_w = new(want_g_w, n, outputs, latents)
-    ws, ws_bytes = _workspace(_lib.load().mf_lik_sparse_factor_expectations_workspace_bytes, dev, num_tiles, two_d, wg.element_size())
-    _launch("mf_lik_sparse_factor_expectations", dtype, dev, bsz, n, segs, two_d, latents, outputs, *likelihood._kernel_args(), offsets,
-            wg, cg, mix, y, pair_mean, pair_cov, num_tiles, tile_seg, seg_tile, ws, ws_bytes, ve_sum, g_mean, g_cov, g_w)
-    return ve_sum, g_mean, g_cov, g_w
+    n, latents, outputs = wg.shape[-3], wg.shape[-2], mix.shape[-2]
+    return _expectations_launch("mf_lik_sparse_factor_expectations", likelihood,
+                                (n, offsets.shape[-1] - 1, wg.shape[-1], latents, outputs), (wg, cg, mix, y), offsets, tiles,
+                                pair_mean, pair_cov, want_grads, extra=(want_g_w, n, outputs, latents))
 
 
 class _SparseFactorExpectedLogLikelihood(torch.autograd.Function):
@@ -700,18 +663,13 @@ def sparse_factor_expected_log_likelihood_torch(likelihood: Likelihood, wg: torc
     segs = pair_mean.shape[-2]
     _sparse_factor_check("sparse_factor_expected_log_likelihood_torch", likelihood, wg, cg, mix, y, tuple(indices.shape[:-1]), segs,
                          pair_mean, pair_cov)
-    two_d = wg.shape[-1]
-    m = torch.gather(pair_mean, -2, indices[..., None].expand(tuple(indices.shape) + (two_d,)))
-    cov = torch.gather(pair_cov, -3, indices[..., None, None].expand(tuple(indices.shape) + (two_d, two_d)))
+    m, cov = _gather_pairs(pair_mean, pair_cov, indices)
     mu_g = (wg @ m[..., None])[..., 0]                                                     # [.., N, L]
     sig_g = cg + wg @ cov @ wg.transpose(-1, -2)                                           # [.., N, L, L]
     fmu = (mix @ mu_g[..., None])[..., 0]                                                  # [.., N, P]
     fvar = torch.sum((mix @ sig_g) * mix, dim=-1)
     ve = torch.sum(likelihood.variational_expectations(fmu[..., None], fvar[..., None], y[..., None]), dim=-1)
-    series = torch.arange(math.prod(indices.shape[:-1]), device=indices.device).reshape(tuple(indices.shape[:-1]) + (1,))
-    flat = (indices + series * segs).reshape(-1)
-    out = torch.zeros(math.prod(pair_mean.shape[:-1]), dtype=ve.dtype, device=ve.device).index_add(0, flat, ve.reshape(-1))
-    return out.reshape(pair_mean.shape[:-1])
+    return _segment_sum(ve, _flat_segments(indices, segs), pair_mean.shape[:-1])
 
 
 # ---- importance-weighted VI: the data term of the log weights ----------------------------------------------------------------------
