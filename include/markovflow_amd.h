@@ -1128,6 +1128,32 @@ int mf_lik_sparse_pep_site_update_f32(int64_t B, int64_t N, int64_t S, int two_d
                                       float* led, void* stream);
 
 /*
+ * The pair cavity of the sparse power-EP model (markovflow/models/sparse_pep.py:251-293; csrc/mf_pair_cavity.hip): what the site
+ * update above takes as cav_mean / cav_cov and the model adds to its normaliser.  For every pair (b, s) of a [B, S] batch, with
+ * n = two_d in 2, 4, ..., 18:
+ *   pair_mean [B, S, n], pair_cov [B, S, n, n]   the marginal N(m, Sig) of q on the pair; the LOWER triangle of Sig is read
+ *   nat1 [B, S, n], nat2 [B, S, n, n]            the site; nat2 need not be symmetric, sym(X) = (X + X^T) / 2 is what enters
+ *   beta [B, S]                                  the fraction of the site to remove
+ *   cav_cov [B, S, n, n]  = (Sig^-1 + 2 beta sym(nat2))^-1, symmetric bit for bit
+ *   cav_mean [B, S, n]    = cav_cov (Sig^-1 m - beta nat1)
+ *   gamma [B, S]          = G(cav_mean, cav_cov) - G(m, Sig),  G(m, S) = (log det S + m^T S^-1 m) / 2
+ * No inverse is formed: Sig = L L^T,  M = I + 2 beta L^T sym(nat2) L = C C^T,  a = L^-1 m,  u = a - beta L^T nat1,  b = C^-1 u,
+ * W = L C^-T;  cav_cov = W W^T,  cav_mean = W b,  gamma = -sum_i log C_ii + (|b|^2 - |a|^2) / 2.  A pair for which a pivot of
+ * either factorisation is not > 0 - Sig or the cavity precision is not positive definite, or holds a NaN - gets NaN in all three
+ * outputs; no other pair is touched, nothing is raised and there is no info word.  beta = 0: gamma = 0 exactly.
+ * One launch, a group of 4 ... 32 lanes per pair and one wavefront of 16 ... 2 pairs per workgroup; the inputs are staged into LDS
+ * with coalesced loads and the outputs leave the same way.  No workspace, no allocation, no synchronisation, no atomics: the same
+ * bits on every launch, for a pair alone or inside a batch.  All eight pointers are required.
+ * Returns 0, -(position of the offending argument in THIS signature: 1 B, 2 S negative or B S above 2^31 - 1, 4 ... 8 a NULL
+ * input, 9 ... 11 a NULL output), -100 for an n that is odd, < 2 or > 18, or -1000 (launch failed).  Nothing is launched and nothing
+ * written on an error or for B S = 0.
+ */
+int mf_pair_cavity_f64(int64_t B, int64_t S, int n, const double* pair_mean, const double* pair_cov, const double* nat1,
+                           const double* nat2, const double* beta, double* cav_mean, double* cav_cov, double* gamma, void* stream);
+int mf_pair_cavity_f32(int64_t B, int64_t S, int n, const float* pair_mean, const float* pair_cov, const float* nat1,
+                           const float* nat2, const float* beta, float* cav_mean, float* cav_cov, float* gamma, void* stream);
+
+/*
  * The data term of the log importance weights of importance-weighted VI and its adjoint onto the posterior draw at the inducing
  * points (markovflow/models/iwvi.py:109-173, markovflow/posterior.py:522-580; csrc/mf_lik.hip): K Monte-Carlo evaluations of
  * log p(y_n | f_n) at every data point.  B, N, S = M + 1, two_d = 2 d, the likelihood, seg_offsets, w = H [D E], y, the tile table

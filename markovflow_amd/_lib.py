@@ -97,6 +97,7 @@ _SIGS = {
     "mf_lik_multistage_variational_expectations": (_int, [_i64, _int, _hd, _hd, "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_sparse_pep_site_update": (_int, [_i64, _i64, _i64, _int, _int, _hd, _int, _hd, _hd, "T", "T", _vp, "Tp", "Tp", "Tp", "Tp",
                                       "Tp", "Tp", _i64, _vp, _vp, _vp, _sz, "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
+    "mf_pair_cavity": (_int, [_i64, _i64, _int, "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_iw_log_weights": (_int, [_i64, _i64, _i64, _int, _i64, _int, _hd, _vp, "Tp", "Tp", "Tp", "Tp", "Tp", _i64, _vp, _vp, _vp,
                                      _sz, "Tp", "Tp", _vp]),
     "mf_lik_dense_expectations": (_int, [_i64, _i64, _int, _int, _hd, _int, _hd, _hd, "Tp", "Tp", "Tp", "Tp", _vp, _sz, "Tp", "Tp", "Tp",

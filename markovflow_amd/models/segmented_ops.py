@@ -9,7 +9,8 @@ forward launch wrote:
 
   * ``sparse_cvi_site_update_{torch,hip}``: ``mf_lik_sparse_cvi_site_update_*`` (projection onto the bracketing pair, expectations,
     back-projection and the segmented sum; in place on the sites);
-  * ``sparse_pep_site_update_{torch,hip}`` and ``pair_cavity``: ``mf_lik_sparse_pep_site_update_*`` (tile-parallel kernel pair);
+  * ``sparse_pep_site_update_{torch,hip}``: ``mf_lik_sparse_pep_site_update_*`` (tile-parallel kernel pair), and the cavity it
+    takes, ``pair_cavity_{torch,hip}``: ``mf_pair_cavity_*`` (a group of lanes per pair, one launch);
   * ``sparse_expected_log_likelihood(_torch)``: ``mf_lik_sparse_expectations_*`` (two passes, tile-parallel), the SVGP data term;
   * ``sparse_multi_expected_log_likelihood(_torch)``: ``mf_lik_sparse_multi_expectations_*``, the same term for a likelihood with
     several latent functions per observation (``sparse_multi_site_projections``: one dense projection per latent);
@@ -254,9 +255,43 @@ def pair_cavity(pair_mean: torch.Tensor, pair_cov: torch.Tensor, nat1: torch.Ten
     ``q`` on a pair (``pair_mean [.., S, 2d]``, ``pair_cov [.., S, 2d, 2d]``), its site ``t(v) = exp(nat1 . v + v^T nat2 v + ...)`` and
     the fraction ``beta [.., S]`` of the site to remove, the cavity ``N(m_c, S_c)`` has precision ``S^-1 + 2 beta nat2`` and linear
     term ``S^-1 m - beta nat1`` (sparse_pep.py:251-293), and ``Gamma = G(m_c, S_c) - G(m, S)`` with
-    ``G(m, S) = (log det S + m^T S^-1 m) / 2``.  Batched torch: two Cholesky factorisations per pair, none of which raises - a pair
-    whose marginal or cavity precision is not positive definite gets NaN in all three results.
+    ``G(m, S) = (log det S + m^T S^-1 m) / 2``.  Nothing raises: a pair whose marginal or cavity precision is not positive definite
+    gets NaN in all three results.  HIP tensors with ``2d`` even and ``<= 18``: ``pair_cavity_hip`` (ONE launch of
+    ``mf_pair_cavity_*``); anything else - CPU tensors, ``2d > 18``, an input under the tape - : ``pair_cavity_torch``.
     Returns ``(cav_mean, cav_cov, gamma [.., S])``."""
+    two_d = pair_cov.shape[-1]
+    taped = torch.is_grad_enabled() and any(t.requires_grad for t in (pair_mean, pair_cov, nat1, nat2, beta))
+    if pair_cov.is_cuda and two_d <= SPARSE_SITE_MAX_TWO_D and two_d % 2 == 0 and not taped:
+        return pair_cavity_hip(pair_mean, pair_cov, nat1, nat2, beta)
+    return pair_cavity_torch(pair_mean, pair_cov, nat1, nat2, beta)
+
+
+def pair_cavity_hip(pair_mean: torch.Tensor, pair_cov: torch.Tensor, nat1: torch.Tensor, nat2: torch.Tensor, beta: torch.Tensor
+                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """ONE launch of ``mf_pair_cavity_*`` on HIP tensors (``2d`` even, ``<= 18``), any leading batch shape: what
+    ``pair_cavity_torch`` computes, without an explicit inverse - ``S = L L^T``, ``M = I + 2 beta L^T sym(nat2) L = C C^T``,
+    ``W = L C^-T``, ``cav_cov = W W^T`` (symmetric bit for bit), ``cav_mean = W C^-1 (L^-1 m - beta L^T nat1)`` - on a group of lanes
+    per pair with the blocks in LDS.  ``beta`` is broadcast to ``[.., S]``."""
+    what = "pair_cavity_hip"
+    lead, two_d = tuple(pair_mean.shape[:-1]), pair_mean.shape[-1]
+    if two_d > SPARSE_SITE_MAX_TWO_D or two_d % 2 or two_d < 2:
+        raise NotImplementedError(f"{what}: 2d = {two_d} is outside 2, 4, ..., {SPARSE_SITE_MAX_TWO_D}; use pair_cavity_torch")
+    beta = beta.expand(lead)
+    _check_shapes(what, dict(pair_cov=(pair_cov, lead + (two_d, two_d)), nat1=(nat1, lead + (two_d,)),
+                             nat2=(nat2, lead + (two_d, two_d))))
+    _lib.same_dtype_device(pair_mean, what, pair_cov=pair_cov, nat1=nat1, nat2=nat2, beta=beta)
+    dtype, dev = pair_mean.dtype, pair_mean.device
+    new = _new_outputs(lead, dtype, dev)
+    outs = (new(True, two_d), new(True, two_d, two_d), new(True))
+    _launch("mf_pair_cavity", dtype, dev, math.prod(lead), 1, two_d, pair_mean, pair_cov, nat1, nat2, beta, *outs)
+    return outs
+
+
+def pair_cavity_torch(pair_mean: torch.Tensor, pair_cov: torch.Tensor, nat1: torch.Tensor, nat2: torch.Tensor, beta: torch.Tensor
+                      ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``pair_cavity`` as a batched torch composition by explicit inverses: two ``cholesky_ex`` (``check_errors=False``) and eight
+    triangular solves per pair.  It runs on CPU tensors, it is the route for ``2d > 18``, and it is what ``mf_pair_cavity_*`` is
+    measured against."""
     eye = torch.eye(pair_cov.shape[-1], dtype=pair_cov.dtype, device=pair_cov.device).expand(pair_cov.shape)
     chol_s, info_s = torch.linalg.cholesky_ex(pair_cov, check_errors=False)
     prec = _lib.chol_solve(chol_s, eye)

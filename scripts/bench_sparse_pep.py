@@ -2,8 +2,10 @@
 points, Sum(Matern52, Matern52) (d = 6, pairs of 2d = 12), fp64, Bernoulli likelihood, 20 Gauss-Hermite points, alpha = lr = 1/2 -
 with M = 100 inducing points per series and with M = 2 (three long segments per series):
 
-  * one ``update_sites()`` (posterior chain on the M inducing points, its pair marginals, the batched pair cavity, the cached
-    per-point projections and ONE ``mf_lik_sparse_pep_site_update`` call of two launches),
+  * one ``update_sites()`` (posterior chain on the M inducing points, its pair marginals, the pair cavity - ONE launch of
+    ``mf_pair_cavity`` -, the cached per-point projections and ONE ``mf_lik_sparse_pep_site_update`` call of two launches), and the
+    same step with the cavity on its previous route, the batched torch composition ``models.pair_cavity_torch``,
+  * the cavity kernel alone (``models.pair_cavity_hip``) against that composition on the same device tensors,
   * the kernel pair alone against the torch composition of the same step (``models.sparse_pep_site_update_torch``) on the same device
     tensors,
   * the kernel pair against ``mf_lik_sparse_expectations`` (value and adjoints: SVGP's pair, the same front end and workspace row) at
@@ -25,6 +27,7 @@ import torch  # noqa: E402
 
 import markovflow_amd as mfa  # noqa: E402
 from markovflow_amd import models as MM  # noqa: E402
+from markovflow_amd.models import sparse as sparse_module  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=64)
@@ -92,21 +95,43 @@ def measure(m):
     err = max(float((s - t).abs().max()) for s, t in zip(a, b))
     scale = max(float(t.abs().max()) for t in b)
     assert err <= 1e-10 * scale, (err, scale)
-    t_pair, t_torch, t_svgp, t_update = [], [], [], []
+    # the cavity: one launch against the batched torch composition, on the pair marginals and sites of the model
+    cavity_args = (pair_mean, pair_cov, model.nat1.clone(), model.nat2.clone(), (alpha * model.fraction_sites(x)).contiguous())
+    cavity = lambda: MM.pair_cavity_hip(*cavity_args)           # noqa: E731
+    cavity_composed = lambda: MM.pair_cavity_torch(*cavity_args)        # noqa: E731
+    cav_err = max(float((s - t).abs().max() / (1.0 + t.abs().max())) for s, t in zip(cavity(), cavity_composed()))
+    assert cav_err <= 1e-9, cav_err
+    t_pair, t_torch, t_svgp, t_update, t_before, t_cav, t_cav_torch = [], [], [], [], [], [], []
     for _ in range(2):                                  # warm-up windows
-        timed(pair)
-        timed(composed)
-        timed(svgp)
+        for fn in (pair, composed, svgp, cavity, cavity_composed):
+            timed(fn)
     for _ in range(rounds):                             # alternating, one process
         t_pair.append(timed(pair))
         t_torch.append(timed(composed))
         t_svgp.append(timed(svgp))
+        t_cav.append(timed(cavity))
+        t_cav_torch.append(timed(cavity_composed))
     update = lambda: model.update_sites((x, y))          # noqa: E731
+
+    def update_before():                                 # the step as it was: the model's cavity through the torch composition
+        sparse_module.pair_cavity = MM.pair_cavity_torch
+        try:
+            model.update_sites((x, y))
+        finally:
+            sparse_module.pair_cavity = MM.pair_cavity
+
     timed(update)
+    timed(update_before)
     for _ in range(rounds):
         t_update.append(timed(update))
+        t_before.append(timed(update_before))
     assert bool(torch.isfinite(model.energy((x, y))).all())          # the sites stayed in the domain
-    return {"update_sites_ms": stats(t_update), "kernel_pair_ms": stats(t_pair), "torch_composition_ms": stats(t_torch),
+    two_d, pairs = pair_mean.shape[-1], pair_mean.numel() // pair_mean.shape[-1]
+    cavity_bytes = pairs * (3 * two_d * two_d + 3 * two_d + 2) * pair_mean.element_size()      # five inputs, three outputs
+    return {"update_sites_ms": stats(t_update), "update_sites_torch_cavity_ms": stats(t_before), "pair_cavity_hip_ms": stats(t_cav),
+            "pair_cavity_torch_ms": stats(t_cav_torch), "pair_cavity_pairs": pairs, "pair_cavity_bytes": cavity_bytes,
+            "pair_cavity_hip_vs_torch_max_scaled_diff": cav_err,
+            "kernel_pair_ms": stats(t_pair), "torch_composition_ms": stats(t_torch),
             "svgp_pair_ms": stats(t_svgp), "kernel_pair_ns_per_point": statistics.median(t_pair) * 1e6 / (bsz * n),
             "svgp_pair_ns_per_point": statistics.median(t_svgp) * 1e6 / (bsz * n), "num_tiles": tiles[0],
             "kernel_vs_torch_max_abs_diff": err}
@@ -126,7 +151,9 @@ with torch.no_grad():
 
 for m in (100, 2):
     r = res[f"M{m}"]
-    for label, key in (("update_sites()", "update_sites_ms"), ("mf_lik_sparse_pep_site_update", "kernel_pair_ms"),
+    for label, key in (("update_sites()", "update_sites_ms"), ("update_sites(), torch cavity", "update_sites_torch_cavity_ms"),
+                       ("mf_pair_cavity", "pair_cavity_hip_ms"), ("pair_cavity_torch", "pair_cavity_torch_ms"),
+                       ("mf_lik_sparse_pep_site_update", "kernel_pair_ms"),
                        ("torch composition", "torch_composition_ms"), ("mf_lik_sparse_expectations", "svgp_pair_ms")):
         print(f"M = {m:3d}  {label:32s} median {r[key]['median']:.3f} ms   min {r[key]['min']:.3f} ms")
     print(f"M = {m:3d}  kernel pair {r['kernel_pair_ns_per_point']:.3f} ns per point, SVGP pair {r['svgp_pair_ns_per_point']:.3f} ns per point, "
