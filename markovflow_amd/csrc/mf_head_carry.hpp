@@ -3,8 +3,9 @@
 // A row of ROWB bytes is fetched as the UNIT-byte units that Keep flags.  When a row starts inside a line, that line was already
 // touched by the fetch of the previous row (whose last unit ends where this row starts).  If ALL kept units of the row that lie in
 // this first line belong to a small fixed set - the "tail units", at most MAXT of them - the previous row's fetch brings them
-// along (as extra units past its own end, out of a line it moves anyway), the consumer takes them from there - chol Q: copied to
-// registers and held across the step boundary; A: moved inside LDS from the tail slots to the row's own head slots, which the
+// along (as extra units past its own end, out of a line it moves anyway), the consumer takes them from there - first generation
+// (chol Q wherever KfLdsCfg::QMOVE does not hold): copied to registers and held across the step boundary; second generation (A,
+// chol Q and b of the fp64 d = 6, m = 1 kernel): moved inside LDS from the tail slots to the row's own head slots, which the
 // row's fetch masks out (MovedSchedule below) - and the row's own fetch leaves the first line alone: one line less on the fabric for that row.
 //
 // Everything here is integer arithmetic on BYTE ADDRESSES modulo 128 (base offsets, batch slices and chunk starts all shift the
@@ -17,7 +18,10 @@
 
 namespace mf {
 
-template <int ROWB, int UNIT, typename Keep, int MAXT_ = 2> struct HeadCarry {
+// SHORT: rows shorter than a line are admitted too (b, 48-byte rows): the line a row starts in then holds more than one earlier row,
+// which changes nothing as long as the previous row's last unit - the one that ends where this row starts - is never a head unit
+// itself, so that the previous row's fetch always touches the shared line.
+template <int ROWB, int UNIT, typename Keep, int MAXT_ = 2, bool SHORT = false> struct HeadCarry {
     static constexpr int LINE = 128;
     static constexpr int MAXT = MAXT_;                              // tail units per row (each costs 64 x UNIT bytes of LDS)
     static_assert(MAXT >= 1 && MAXT <= 4, "one bit table per tail unit: TAB0 ... TAB3");
@@ -58,10 +62,11 @@ template <int ROWB, int UNIT, typename Keep, int MAXT_ = 2> struct HeadCarry {
     // the decisions repeat with this period in the step index (a power of two, at most 32 for rows of whole dwords)
     static constexpr int period() { int p = 1, r = STEP; while (r % LINE) { r += STEP; ++p; } return p; }
     static constexpr int PERIOD = (ROWB % 4 == 0) ? period() : 0;
-    // Usable: rows of whole dwords that span at least a line (the line before a row then belongs to the previous row alone) but
+    // Usable: rows of whole dwords that span at least a line (the line before a row then belongs to the previous row alone; SHORT
+    // waives this where the row's last unit is no head unit) but
     // not a whole number of lines (such rows share no line unless the base is misaligned), whose last unit is fetched (so the
     // previous row's fetch does touch the shared line), and some phase that carries at all.
-    static constexpr bool USABLE = ROWB % 4 == 0 && ROWB >= LINE && STEP != 0 && Keep::keep(UG - 1, UNIT) && (TAB0 | TAB1 | TAB2 | TAB3) != 0u;
+    static constexpr bool USABLE = ROWB % 4 == 0 && (ROWB >= LINE || (SHORT && tail_index(UG - 1) < 0)) && STEP != 0 && Keep::keep(UG - 1, UNIT) && (TAB0 | TAB1 | TAB2 | TAB3) != 0u;
     static constexpr int NT = USABLE ? count_cand() : 0;
     static constexpr int tail_unit(int t) { return cand(t); }
 
@@ -101,7 +106,7 @@ template <int ROWB, int UNIT, typename Keep, int MAXT_ = 2> struct HeadCarry {
 // the kernel reads ~600 B per lane per step, nowhere near LDS bandwidth, while padding would push the
 // fp64 d=6 image over a quarter of the CU's 160 KB and cost a wave of occupancy.)
 // TAIL: the row's image ends with tail slots that hold the NEXT row's head units (chol Q; A where KfLdsCfg::ATAIL holds).
-template <int ROWB, typename Keep, bool TAIL = false, int MAXT = 2> struct Stream {
+template <int ROWB, typename Keep, bool TAIL = false, int MAXT = 2, bool SHORT = false> struct Stream {
     // 16-B granules whenever a row holds at least one; a row that is not a whole number of them (odd d) is fetched up
     // to the next 16-B boundary: the extra 4..12 bytes belong to the next row (or lie past the end of the tensor, where
     // the buffer range check returns zeros) and are never read.  Rows then start 4- or 8-byte aligned, which the DMA
@@ -109,7 +114,7 @@ template <int ROWB, typename Keep, bool TAIL = false, int MAXT = 2> struct Strea
     static constexpr int UNIT = (ROWB >= 16) ? 16 : 4;
     static constexpr int UG = (ROWB + UNIT - 1) / UNIT;          // units per row in global memory
     static constexpr int count_kept() { int n = 0; for (int u = 0; u < UG; ++u) n += Keep::keep(u, UNIT) ? 1 : 0; return n; }
-    using HC = HeadCarry<ROWB, UNIT, Keep, MAXT>;
+    using HC = HeadCarry<ROWB, UNIT, Keep, MAXT, SHORT>;
     static constexpr int UB = count_kept();                       // the row's own units kept in LDS
     static constexpr int NT = TAIL ? HC::NT : 0;                  // tail slots: the next row's units HC::tail_unit(t)
     static constexpr int U = UB + NT;                             // units per row of the LDS image
@@ -187,46 +192,61 @@ template <typename St> struct MaskedSchedule {
     static constexpr bool carried(unsigned sch, int t, unsigned p) { return ((sch >> (SH_C + t * PB + (int)p)) & 1u) != 0u; }
 };
 
-// Packed per-lane schedule of a stream with tail slots whose carried head is MOVED back into the row's own slots (mf_kf_lds.hpp, A
-// with up to four tail units): at the top of step j, once row j is in registers, the lane copies the tail units that row j + 1
-// carries from its tail slots to its head slots, inside LDS.  The head slots are dead then, the fetch of row j + 1 leaves them out
-// through the EXEC mask, and the same fetch may refill the tail slots with the head of row j + 2: rows may carry on consecutive
-// steps with ONE tail set, and the consumer reads every unit of a row from the row's own slots.
+// Packed per-lane schedule of a stream with tail slots whose carried head is MOVED back into the row's own slots (mf_kf_lds.hpp: A
+// with up to four tail units, chol Q with two, b with one): at the top of step j, once row j is in registers, the lane copies the
+// tail units that row j + 1 carries from its tail slots to its head slots, inside LDS.  The head slots are dead then, the fetch of
+// row j + 1 leaves them out through the EXEC mask, and the same fetch may refill the tail slots with the head of row j + 2: rows may
+// carry on consecutive steps with ONE tail set, and the consumer reads every unit of a row from the row's own slots.
 // A lane meets the units of one residue mod G = gcd(64, U), each once per block of PER = U / G instructions, advancing by 64 % U
-// units per instruction.  Head and tail units together are a cyclic run of the image (..., U - 1, 0, 1, ...), so the NS of them
-// that a lane meets in a block sit at NS consecutive block positions (cyclically) starting at a position `idx` that is the same in
-// every block (runs_consecutive() checks both).  Two words describe the lane:
+// units per instruction.  The NS head and tail units ("special" units) that a lane meets in a block sit at the block positions
+// idx, idx + GAP, ..., idx + (NS - 1) GAP (cyclically), with `idx` the same in every block; a residue may also hold no special unit
+// at all (runs_consecutive() checks all of this).  The meeting patterns:
+//   A      U = 22, G = 2, PER = 11, 64 % 22 = 20: heads (0 ... 3) and tails (18 ... 21) are a cyclic run of the image and a lane
+//          steps two units down per instruction: residue 0 walks 2 -> 0 -> 20 -> 18, residue 1 walks 3 -> 1 -> 21 -> 19, two heads
+//          then two tails at consecutive instructions: NS = 4, GAP = 1, 2 blocks;
+//   chol Q U = 14 (12 kept units, the heads are image units 0 and 1, the tails 12 and 13), G = 2, PER = 7, 64 % 14 = 8: a lane of
+//          residue 0 walks 12 -> 6 -> 0 -> 8 -> 2 -> 10 -> 4 (-> 12), one of residue 1 walks 13 -> 7 -> 1 -> 9 -> 3 -> 11 -> 5: the
+//          tail slot first, one ordinary unit, then the head it pairs with: NS = 2, GAP = 2, 2 blocks;
+//   b      U = 4 (3 + 1 tail), G = 4, PER = 1: a lane moves the same unit of 4 different rows; lanes 0 mod 4 hold the head, lanes
+//          3 mod 4 the tail slot, the others nothing special: NS = 1, 4 blocks, period 8: 32 fetch bits.
+// Two words describe the lane:
 //   w0  bit (p NB NS + b NS + k) = fetch the k-th special unit of block b with the rows of step jn, jn % PB == p
-//       (HeadCarry::producer_bits of the row the unit belongs to);
+//       (HeadCarry::producer_bits of the row the unit belongs to; all ones for a lane without special units);
 //   w1  bits 0..3 = idx, bits SH_C + t PB + p = HeadCarry::consumer_bits of the lane's OWN row.
-// (The one-word form of MaskedSchedule holds one special unit per block; here there are NS = 4, i.e. PB NB NS = 32 fetch bits.)
-template <typename St> struct MovedSchedule {
+// (The one-word form of MaskedSchedule holds one special unit per block; A has NS = 4, i.e. PB NB NS = 32 fetch bits.)
+template <typename St, int GAP = 1> struct MovedSchedule {
     using HC = typename St::HC;
     static constexpr int PB = HC::PERIOD > 0 ? HC::PERIOD : 1;
     static constexpr int gcd(int a, int b) { return b == 0 ? a : gcd(b, a % b); }
     static constexpr int G = gcd(64, St::U), PER = St::U / G, NB = (St::NI + PER - 1) / PER, ADV = 64 % St::U;
     static constexpr int count_special(int c) { int n = 0; for (int u = c; u < St::U; u += G) n += St::unit_kind(u) != 0 ? 1 : 0; return n; }
-    static constexpr int NS = count_special(0);
+    static constexpr int max_special() { int n = 0; for (int c = 0; c < G; ++c) n = count_special(c) > n ? count_special(c) : n; return n; }
+    static constexpr int NS = max_special();
     static constexpr int SH_C = 4;
     // block position, relative to the position of unit (cu % G), at which a lane meets unit cu
     static constexpr int rel(int cu) { int q = 0, u = cu % G; while (u != cu) { u = (u + ADV) % St::U; ++q; } return q; }
-    // the special unit of cu's residue that a lane meets first: every other one follows within NS - 1 positions (-1: no such unit)
+    // the special unit of cu's residue that a lane meets first: every other one follows at a multiple of GAP within (NS - 1) GAP
+    // positions (-1: no such unit)
     static constexpr int first_special(int c) {
         for (int s = c; s < St::U; s += G) {
             if (St::unit_kind(s) == 0) continue;
             bool ok = true;
-            for (int x = c; x < St::U; x += G) if (St::unit_kind(x) != 0 && (rel(x) - rel(s) + PER) % PER >= NS) ok = false;
+            for (int x = c; x < St::U; x += G) {
+                const int d = (rel(x) - rel(s) + PER) % PER;
+                if (St::unit_kind(x) != 0 && (d % GAP != 0 || d / GAP >= NS)) ok = false;
+            }
             if (ok) return s;
         }
         return -1;
     }
     static constexpr bool runs_consecutive() {
-        for (int c = 0; c < G; ++c) if (count_special(c) != NS || first_special(c) < 0) return false;
+        for (int c = 0; c < G; ++c) if (count_special(c) != 0 && (count_special(c) != NS || first_special(c) < 0)) return false;
         return St::NI % PER == 0;
     }
+    // the source offset of image unit c is c units from the row's start (else the fetch takes it from a table: chol Q)
     static constexpr bool linear() { for (int c = 0; c < St::U; ++c) if (St::global_offset(c) != c * St::UNIT) return false; return true; }
-    static constexpr bool USABLE = St::NT > 0 && PER <= 15 && NS >= 1 && NS <= PER && PB * NB * NS <= 32 && SH_C + St::NT * PB <= 32 &&
-                                   runs_consecutive() && linear();
+    static constexpr bool USABLE = St::NT > 0 && PER <= 15 && NS >= 1 && (NS - 1) * GAP < PER && PB * NB * NS <= 32 &&
+                                   SH_C + St::NT * PB <= 32 && runs_consecutive();
     // the PB bits `bits` (bit p = phase p) spread to the positions of special k of block b
     static constexpr unsigned spread(unsigned bits, int b, int k) {
         unsigned m = 0u;
@@ -234,23 +254,29 @@ template <typename St> struct MovedSchedule {
         return m;
     }
     template <int C> static constexpr int FIRST_SPECIAL = first_special(C);
-    // the first special unit of residue c (a run-time value)
+    // the first special unit of residue c (a run-time value; -1: the residue has none)
     template <int C = 0> static constexpr int first_of(int c) {
         if constexpr (C + 1 < G) return c == C ? FIRST_SPECIAL<C> : first_of<C + 1>(c);
         else return FIRST_SPECIAL<C>;
     }
     // HeadCarry::producer_bits of the K-th special unit that a lane of residue c meets in a block, for a row at step-0 address addr
+    template <int K, int C> static constexpr unsigned bits_at(unsigned addr) {
+        if constexpr (FIRST_SPECIAL<C> < 0) return (1u << PB) - 1u;
+        else {
+            constexpr int KIND = St::unit_kind((FIRST_SPECIAL<C> + ADV * K * GAP) % St::U);
+            static_assert(KIND != 0, "a special unit");
+            return HC::producer_bits(addr, KIND);
+        }
+    }
     template <int K, int C = 0> static constexpr unsigned bits_of(unsigned addr, int c) {
-        constexpr int KIND = St::unit_kind((FIRST_SPECIAL<C> + ADV * K) % St::U);
-        static_assert(KIND != 0, "a special unit");
-        const unsigned mine = HC::producer_bits(addr, KIND);
+        const unsigned mine = bits_at<K, C>(addr);
         if constexpr (C + 1 < G) return c == C ? mine : bits_of<K, C + 1>(addr, c);
         else return mine;
     }
     template <int BK, typename F> static constexpr void build_special(unsigned& w0, int idx, int lane, F row_addr) {
         if constexpr (BK < NB * NS) {
             constexpr int B = BK / NS, K = BK % NS;
-            int q = idx + K;
+            int q = idx + K * GAP;
             q -= q >= PER ? PER : 0;
             const int row = (64 * (B * PER + q) + lane) / St::U;                // DMA instruction i, lane l moves unit 64 i + l
             w0 |= spread(bits_of<K>(row_addr(row), lane % G), B, K);
@@ -258,6 +284,7 @@ template <typename St> struct MovedSchedule {
         }
     }
     // The words of DMA lane `lane`, branch-free (the kernel runs this per lane): row_addr(r) = step-0 byte address of image row r.
+    // It walks the lane's NB NS special units, not the instructions: a compare per unit and instruction would not stay in registers.
     template <typename F> static constexpr void build(unsigned& w0, unsigned& w1, int lane, F row_addr) {
         const int c0 = lane % St::U, first = first_of(lane % G);
         int idx = 0;
@@ -268,10 +295,14 @@ template <typename St> struct MovedSchedule {
     }
     // bit i = the lane's unit of instruction i is fetched with the rows of a step of phase p (= jn % PB, jn >= 1)
     static constexpr unsigned fetch_mask(unsigned w0, unsigned w1, unsigned p) {
+        if constexpr (PER == 1) return w0 >> (p * (unsigned)(NB * NS));                         // one unit per lane: block = instruction
         const unsigned left = ~(w0 >> (p * (unsigned)(NB * NS))), idx = w1 & 0xFu;
         unsigned out = 0u;
         for (int b = 0; b < NB; ++b) {
-            unsigned x = ((left >> (b * NS)) & ((1u << NS) - 1u)) << idx;                       // the run, from block position idx on
+            unsigned x = 0u;
+            if constexpr (GAP == 1) x = (left >> (b * NS)) & ((1u << NS) - 1u);
+            else for (int k = 0; k < NS; ++k) x |= ((left >> (b * NS + k)) & 1u) << (k * GAP);
+            x <<= idx;                                                                          // the run, from block position idx on
             x = (x | (x >> PER)) & ((1u << PER) - 1u);                                          // ... cyclically
             out |= x << (b * PER);
         }

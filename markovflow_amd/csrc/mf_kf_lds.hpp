@@ -87,28 +87,32 @@ template <bool WIDE, int N> MF_DEV void dma_b128_group(mf_v4i srd, unsigned lds_
 // what it held (the out-of-range offset would put zeros there).  EXEC is saved and restored inside the statement.
 #define MF_DMA_HEAD_X "s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b64 %1, exec\n\ts_mov_b32 m0, %3\n\t"
 #define MF_DMA_TAIL_X "s_mov_b64 exec, %1\n\ts_mov_b32 m0, %0"
-#define MF_DMA_X4_X(v, e) "s_mov_b64 exec, " e "\n\ts_nop 0\n\tbuffer_load_dwordx4 " v ", %2, 0 offen" MF_POLICY_WIDE " lds\n\t"
+#define MF_DMA_X4_X(v, e, pol) "s_mov_b64 exec, " e "\n\ts_nop 0\n\tbuffer_load_dwordx4 " v ", %2, 0 offen" pol " lds\n\t"
 #define MF_DMA_STEP4_X "s_add_u32 m0, m0, 0x400\n\t"
-template <int N> MF_DEV void dma_b128_group_masked(mf_v4i srd, unsigned lds_addr, const unsigned* v, const unsigned long long* em) {
+template <bool WIDE, int N> MF_DEV void dma_b128_group_masked(mf_v4i srd, unsigned lds_addr, const unsigned* v, const unsigned long long* em) {
     unsigned keep;
     unsigned long long keepx;
     static_assert(N >= 1 && N <= 4, "group size");
-    if constexpr (N == 1)
-        asm volatile(MF_DMA_HEAD_X MF_DMA_X4_X("%4", "%5") MF_DMA_TAIL_X
-                     : "=&s"(keep), "=&s"(keepx) : "s"(srd), "s"(lds_addr), "v"(v[0]), "s"(em[0]) : "memory", "scc");
-    else if constexpr (N == 2)
-        asm volatile(MF_DMA_HEAD_X MF_DMA_X4_X("%4", "%6") MF_DMA_STEP4_X MF_DMA_X4_X("%5", "%7") MF_DMA_TAIL_X
-                     : "=&s"(keep), "=&s"(keepx) : "s"(srd), "s"(lds_addr), "v"(v[0]), "v"(v[1]), "s"(em[0]), "s"(em[1]) : "memory", "scc");
-    else if constexpr (N == 3)
-        asm volatile(MF_DMA_HEAD_X MF_DMA_X4_X("%4", "%7") MF_DMA_STEP4_X MF_DMA_X4_X("%5", "%8") MF_DMA_STEP4_X MF_DMA_X4_X("%6", "%9") MF_DMA_TAIL_X
-                     : "=&s"(keep), "=&s"(keepx) : "s"(srd), "s"(lds_addr), "v"(v[0]), "v"(v[1]), "v"(v[2]), "s"(em[0]), "s"(em[1]), "s"(em[2])
+#define MF_DMA_B128_MASKED_BODY(POL)                                                                                                \
+    if constexpr (N == 1)                                                                                                           \
+        asm volatile(MF_DMA_HEAD_X MF_DMA_X4_X("%4", "%5", POL) MF_DMA_TAIL_X                                                       \
+                     : "=&s"(keep), "=&s"(keepx) : "s"(srd), "s"(lds_addr), "v"(v[0]), "s"(em[0]) : "memory", "scc");               \
+    else if constexpr (N == 2)                                                                                                      \
+        asm volatile(MF_DMA_HEAD_X MF_DMA_X4_X("%4", "%6", POL) MF_DMA_STEP4_X MF_DMA_X4_X("%5", "%7", POL) MF_DMA_TAIL_X           \
+                     : "=&s"(keep), "=&s"(keepx) : "s"(srd), "s"(lds_addr), "v"(v[0]), "v"(v[1]), "s"(em[0]), "s"(em[1]) : "memory", "scc"); \
+    else if constexpr (N == 3)                                                                                                      \
+        asm volatile(MF_DMA_HEAD_X MF_DMA_X4_X("%4", "%7", POL) MF_DMA_STEP4_X MF_DMA_X4_X("%5", "%8", POL) MF_DMA_STEP4_X          \
+                     MF_DMA_X4_X("%6", "%9", POL) MF_DMA_TAIL_X                                                                     \
+                     : "=&s"(keep), "=&s"(keepx) : "s"(srd), "s"(lds_addr), "v"(v[0]), "v"(v[1]), "v"(v[2]), "s"(em[0]), "s"(em[1]), "s"(em[2]) \
+                     : "memory", "scc");                                                                                            \
+    else                                                                                                                            \
+        asm volatile(MF_DMA_HEAD_X MF_DMA_X4_X("%4", "%8", POL) MF_DMA_STEP4_X MF_DMA_X4_X("%5", "%9", POL) MF_DMA_STEP4_X          \
+                     MF_DMA_X4_X("%6", "%10", POL) MF_DMA_STEP4_X MF_DMA_X4_X("%7", "%11", POL) MF_DMA_TAIL_X                       \
+                     : "=&s"(keep), "=&s"(keepx)                                                                                    \
+                     : "s"(srd), "s"(lds_addr), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "s"(em[0]), "s"(em[1]), "s"(em[2]), "s"(em[3]) \
                      : "memory", "scc");
-    else
-        asm volatile(MF_DMA_HEAD_X MF_DMA_X4_X("%4", "%8") MF_DMA_STEP4_X MF_DMA_X4_X("%5", "%9") MF_DMA_STEP4_X MF_DMA_X4_X("%6", "%10")
-                     MF_DMA_STEP4_X MF_DMA_X4_X("%7", "%11") MF_DMA_TAIL_X
-                     : "=&s"(keep), "=&s"(keepx)
-                     : "s"(srd), "s"(lds_addr), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "s"(em[0]), "s"(em[1]), "s"(em[2]), "s"(em[3])
-                     : "memory", "scc");
+    if (WIDE) { MF_DMA_B128_MASKED_BODY(MF_POLICY_WIDE) } else { MF_DMA_B128_MASKED_BODY(MF_POLICY_NARROW) }
+#undef MF_DMA_B128_MASKED_BODY
 }
 template <int N> MF_DEV void dma_b32_group(mf_v4i srd, unsigned lds_addr, const unsigned* v) {
     unsigned keep;
@@ -221,19 +225,19 @@ template <typename St> struct DmaStream {
     }
 };
 
-// DmaStream for a stream with tail slots that keeps every unit (A with KfLdsCfg::ATAIL), a type of its own so that DmaStream
-// stays what it was for every other stream.  A unit the schedule leaves out is left out by the EXEC mask of its instruction, so
+// DmaStream for a stream with tail slots on the moved scheme (A with KfLdsCfg::ATAIL, chol Q with QMOVE, b with BHEAD), a type of
+// its own so that DmaStream stays what it was for every other stream.  GAP: MovedSchedule's.  A unit the schedule leaves out is left out by the EXEC mask of its instruction, so
 // its slot keeps what it held: a head slot keeps the carried unit that the consumer moved there from the tail slot (see
 // MovedSchedule, mf_head_carry.hpp, and the top of MF_KF_LDS_STEP) - no carried values held in registers across the step.  The
 // schedule is two packed words per lane, consumer bits included.
-template <typename St> struct DmaStreamMoved {
-    using MS = MovedSchedule<St>;
-    static_assert(MS::USABLE && St::UNIT == 16 && St::UG >= 8, "moved schedule: see MovedSchedule; a wide stream");
+template <typename St, int GAP = 1> struct DmaStreamMoved {
+    using MS = MovedSchedule<St, GAP>;
+    static_assert(MS::USABLE && St::UNIT == 16, "moved schedule: see MovedSchedule");
     unsigned vo[St::NI];           // this lane's source byte offset for DMA instruction i
     unsigned sch0, sch1;           // the lane's packed schedule
-    // base_lo: low 32 bits of the address the row offsets are relative to (the phase of a row); the lane-to-unit arithmetic is
-    // DmaStream::init's
-    MF_DEV void init(const char* smem, int lane, int rel_tab, int, unsigned base_lo) {
+    // base_lo: low 32 bits of the address the row offsets are relative to (the phase of a row); the lane-to-unit arithmetic and
+    // gtab (a stream that drops units: chol Q) are DmaStream::init's
+    MF_DEV void init(const char* smem, int lane, int rel_tab, int gtab, unsigned base_lo) {
         const int q0 = lane / St::U, c0 = lane - q0 * St::U;
         MS::build(sch0, sch1, lane,
                   [&](int row) { return base_lo + *reinterpret_cast<const unsigned*>(smem + rel_tab + row * 4); });
@@ -244,7 +248,9 @@ template <typename St> struct DmaStreamMoved {
             cu -= carry * St::U;
             const int row = q0 + a + carry;
             const unsigned rel = *reinterpret_cast<const unsigned*>(smem + rel_tab + row * 4);
-            const unsigned off = (unsigned)cu * St::UNIT;          // (MovedSchedule::linear)
+            unsigned off;
+            if constexpr (MS::linear()) off = (unsigned)cu * St::UNIT;
+            else off = *reinterpret_cast<const unsigned*>(smem + gtab + cu * 4);
             vo[i] = rel + off;
 #ifdef MF_EXPERIMENT
             if (pack_base != 0xffffffffu && rel < MF_DMA_INVALID)
@@ -281,8 +287,8 @@ template <typename St> struct DmaStreamMoved {
                 const unsigned mask = MS::fetch_mask(sch0, sch1, phase);
                 unsigned long long em[N];
                 MF_UNROLL for (int k = 0; k < N; ++k) em[k] = __builtin_amdgcn_ballot_w64(MS::fetch(mask, I0 + k));
-                dma_b128_group_masked<N>(srd, lds_base + I0 * 1024, voff, em);
-            } else dma_b128_group<true, N>(srd, lds_base + I0 * 1024, voff);
+                dma_b128_group_masked<(St::UG >= 8), N>(srd, lds_base + I0 * 1024, voff, em);
+            } else dma_b128_group<(St::UG >= 8), N>(srd, lds_base + I0 * 1024, voff);
             issue<I0 + N, I1, SCHED>(srd, lds_base, phase);
         }
     }
@@ -349,6 +355,34 @@ template <typename T, typename St> struct RowReader {
     MF_DEV T tail_at(int t, int k) const { return *reinterpret_cast<const T*>(row + (St::UB + t) * St::UNIT + k * (int)sizeof(T)); }
 };
 
+// The move of the moved head carry (MovedSchedule, mf_head_carry.hpp) for this lane's row of the image at `row`: the head units that
+// the NEXT row carries (phase = (j + 1) % period) go from the tail slots, where this step's fetch left them, to the row's head
+// slots, which are dead once the row is in registers: the fetch of the next row masks exactly those out and may refill the tail
+// slots.  A unit that is not carried is written back to its own tail slot: no branch.  (Copied as values of T, the type the row
+// was read with: the stores stay behind those reads.)
+template <typename T, typename St, int GAP> MF_DEV void move_carried_heads(char* row, unsigned sch1, unsigned phase) {
+    constexpr int UEL = St::UNIT / (int)sizeof(T);
+    MF_UNROLL for (int t = 0; t < St::NT; ++t) {
+        const bool mv = MovedSchedule<St, GAP>::carried(sch1, t, phase);
+        const int src = (St::UB + t) * St::UNIT, dst = mv ? St::compact_unit(St::HC::tail_unit(t)) * St::UNIT : src;
+        T un[UEL];
+        MF_UNROLL for (int k = 0; k < UEL; ++k) un[k] = *reinterpret_cast<const T*>(row + src + k * (int)sizeof(T));
+        MF_UNROLL for (int k = 0; k < UEL; ++k) *reinterpret_cast<T*>(row + dst + k * (int)sizeof(T)) = un[k];
+    }
+}
+
+// MovedSchedule<St, GAP>::USABLE where ON holds (the schedule of a stream without tail slots is not even formed)
+template <bool ON, typename St, int GAP> struct MovedUsable { static constexpr bool value = false; };
+template <typename St, int GAP> struct MovedUsable<true, St, GAP> { static constexpr bool value = MovedSchedule<St, GAP>::USABLE; };
+
+// Switches of the two parts of the second-generation carry of chol Q and b (KfLdsCfg::QMOVE, BHEAD): 0 builds the kernel without.
+#ifndef MF_QMOVE
+#define MF_QMOVE 1
+#endif
+#ifndef MF_BHEAD
+#define MF_BHEAD 1
+#endif
+
 // RSTEP: the observation precision is a per-step stream [B, T, M, M] (KalmanFilterWithSites / WithSparseSites) instead of
 // one shared [M, M] matrix held in registers.
 // BG: rows of b and H fetched per DMA batch (the same remedy as YG below, for kernels that have the LDS: the passes of the streamed
@@ -366,7 +400,8 @@ template <typename T, int D, int M, bool RSTEP = false, int BG = 1, bool CARRY =
     using StAT = Stream<D * D * S, KeepAll, true, 4>;
     using StC0 = Stream<D * D * S, KeepLower<D, S>>;
     using StCT = Stream<D * D * S, KeepLower<D, S>, true>;
-    using Stb = Stream<BG * D * S, KeepAll>;
+    using Stb0 = Stream<BG * D * S, KeepAll>;
+    using StbT = Stream<BG * D * S, KeepAll, true, 1, true>;
     using StH = Stream<BG * M * D * S, KeepAll>;
     // y rows are tiny (M S bytes): with one output they are fetched YG steps at a time, so a 128-B line of y is
     // touched every YG-th step instead of every step (the memory side moves whole lines whatever part is used)
@@ -376,11 +411,11 @@ template <typename T, int D, int M, bool RSTEP = false, int BG = 1, bool CARRY =
     static constexpr bool RS = RSTEP;
     static constexpr int QUARTER_CU = (160 * 1024) / 4;
     static constexpr int TABLE_BYTES = 5 * 256 + ((StCT::U * 4 + 15) / 16) * 16;
-    static constexpr int IMAGE_T = StA0::LDS_BYTES + StCT::LDS_BYTES + Stb::LDS_BYTES + StH::LDS_BYTES + ((Sty::LDS_BYTES + 15) / 16) * 16 +
+    static constexpr int IMAGE_T = StA0::LDS_BYTES + StCT::LDS_BYTES + Stb0::LDS_BYTES + StH::LDS_BYTES + ((Sty::LDS_BYTES + 15) / 16) * 16 +
                                    (RSTEP ? ((StR::LDS_BYTES + 15) / 16) * 16 : 0);
     static constexpr bool TAIL = CARRY && StCT::NT > 0 && !StC0::ALL && StCT::NI * StCT::HC::PERIOD <= 64 &&
                                  StCT::NT * StCT::HC::PERIOD <= 32 && IMAGE_T <= QUARTER_CU && TABLE_BYTES <= IMAGE_T &&
-                                 (StA0::NI + StCT::NI + Stb::NI + StH::NI + Sty::NI + (RSTEP ? StR::NI : 0)) < 64;
+                                 (StA0::NI + StCT::NI + Stb0::NI + StH::NI + Sty::NI + (RSTEP ? StR::NI : 0)) < 64;
     using StC = Stream<D * D * S, KeepLower<D, S>, TAIL>;
     // ATAIL (one output, shared precision, where chol Q carries): y and H leave LDS and the room their images took becomes tail
     // slots of A.  HeadCarry<rows of A, KeepAll> with four tail units carries the whole of a row's part of its first line where
@@ -392,13 +427,28 @@ template <typename T, int D, int M, bool RSTEP = false, int BG = 1, bool CARRY =
     // of the row's first use (Obs::apply) instead of at its end.
     static constexpr int Y_IMAGE = ((Sty::LDS_BYTES + 15) / 16) * 16;
     static constexpr bool ATAIL = TAIL && M == 1 && !RSTEP && sizeof(T) == 8 && StAT::NT > 0 && StAT::HC::PERIOD == StCT::HC::PERIOD &&
-                                  (M * D * S) % 16 == 0 && StAT::LDS_BYTES + StCT::LDS_BYTES + Stb::LDS_BYTES <= QUARTER_CU &&
-                                  (StAT::NI + StCT::NI + Stb::NI + (M * D * S) / 16 + (YG * M * S) / 16) < 64;
+                                  (M * D * S) % 16 == 0 && StAT::LDS_BYTES + StCT::LDS_BYTES + Stb0::LDS_BYTES <= QUARTER_CU &&
+                                  (StAT::NI + StCT::NI + Stb0::NI + (M * D * S) / 16 + (YG * M * S) / 16) < 64;
     static constexpr bool YREG = ATAIL, HREG = ATAIL;
     // (groups of two - one dwordx4, a y line touched every second step - were measured and lost the whole gain)
     static_assert(YG % 2 == 0 || !YREG, "whole dwordx4 loads");
     using DA = std::conditional_t<ATAIL, DmaStreamMoved<StAT>, DmaStream<StA0>>;
     using StA = std::conditional_t<ATAIL, StAT, StA0>;
+    // QMOVE (where ATAIL holds): chol Q's two tail units take A's scheme as well - moved inside LDS to the head slots, the fetch
+    // masked through EXEC - instead of three doubles held in registers across the step and a select per entry.  A lane meets chol
+    // Q's tail and head units two instructions apart (MovedSchedule's GAP).
+    // BHEAD (likewise): the image's last spare unit per lane becomes a tail slot of b.  A 48-byte row that starts 112 bytes into a
+    // line has its unit 0 brought along by the fetch of the row before (whose last unit lies in that line) and moved to its head
+    // slot; its own fetch then touches one line, not two: 9 line requests per 8 steps instead of 10.  (It pays only with the
+    // registers that QMOVE frees: BHEAD without QMOVE spills to scratch and runs 21 % slower than neither.)
+    static constexpr bool QMOVE = MF_QMOVE && MovedUsable<ATAIL, StCT, 2>::value;
+    static constexpr int QGAP = 2;
+    static constexpr bool BHEAD = MF_BHEAD && BG == 1 && MovedUsable<(ATAIL && StbT::NT == 1), StbT, 1>::value &&
+                                  StAT::LDS_BYTES + StCT::LDS_BYTES + StbT::LDS_BYTES <= QUARTER_CU &&
+                                  (StAT::NI + StCT::NI + StbT::NI + (M * D * S) / 16 + (YG * M * S) / 16) < 64;
+    using Stb = std::conditional_t<BHEAD, StbT, Stb0>;
+    using DC = std::conditional_t<QMOVE, DmaStreamMoved<StC, QGAP>, DmaStream<StC>>;
+    using Db = std::conditional_t<BHEAD, DmaStreamMoved<StbT>, DmaStream<Stb0>>;
     static constexpr int NI_y = YREG ? 0 : Sty::NI;
     static constexpr int NI_H = HREG ? 0 : StH::NI;
     static constexpr int OFF_A = 0;
@@ -424,12 +474,19 @@ template <typename T, int D, int M, bool RSTEP = false, int BG = 1, bool CARRY =
 
 template <typename T, int D, int M, bool RSTEP = false> using KfChunkCfg = KfLdsCfg<T, D, M, RSTEP, 1, true>;
 static_assert(KfChunkCfg<double, 6, 1>::TAIL && KfChunkCfg<double, 6, 1>::LDS_TOTAL <= 40960, "fp64 d = 6: four wavefronts per CU");
-static_assert(KfChunkCfg<double, 6, 1>::ATAIL && KfChunkCfg<double, 6, 1>::StA::U == 22 && KfChunkCfg<double, 6, 1>::LDS_TOTAL == 39936,
-              "fp64 d = 6, m = 1: A's four tail slots take the place of the y and H images, one unit per lane to spare");
-static_assert(KfChunkCfg<double, 6, 1>::StA::NI + KfChunkCfg<double, 6, 1>::StC::NI + KfChunkCfg<double, 6, 1>::Stb::NI == 39,
-              "39 LDS-DMA instructions, 3 loads of H and 2 of y per step: 44 in flight, below the 6-bit counter's 63");
+static_assert(KfChunkCfg<double, 6, 1>::ATAIL && KfChunkCfg<double, 6, 1>::StA::U == 22 &&
+              KfChunkCfg<double, 6, 1>::LDS_TOTAL == (KfChunkCfg<double, 6, 1>::BHEAD ? 40960 : 39936),
+              "fp64 d = 6, m = 1: A's four tail slots take the place of the y and H images; the unit per lane that is left is b's tail slot");
+static_assert(KfChunkCfg<double, 6, 1>::StA::NI + KfChunkCfg<double, 6, 1>::StC::NI + KfChunkCfg<double, 6, 1>::Stb::NI ==
+              (KfChunkCfg<double, 6, 1>::BHEAD ? 40 : 39),
+              "40 LDS-DMA instructions, 3 loads of H and 2 of y per step: 45 in flight, below the 6-bit counter's 63");
+static_assert((KfChunkCfg<double, 6, 1>::QMOVE || !MF_QMOVE) && (KfChunkCfg<double, 6, 1>::BHEAD || !MF_BHEAD) &&
+              KfChunkCfg<double, 6, 1>::StC::U == 14 && KfChunkCfg<double, 6, 1>::StbT::HC::PERIOD == 8,
+              "fp64 d = 6, m = 1: chol Q (12 + 2 units) and b (3 + 1 units, period 8) on the moved scheme");
 static_assert(!KfChunkCfg<double, 6, 2>::ATAIL && !KfChunkCfg<double, 6, 1, true>::ATAIL && !KfChunkCfg<float, 6, 1>::ATAIL &&
               !KfLdsCfg<double, 6, 1>::ATAIL && !KfLdsCfg<double, 6, 1, false, 2>::ATAIL, "every other instantiation keeps its streams");
+static_assert(!KfChunkCfg<double, 6, 2>::QMOVE && !KfChunkCfg<double, 6, 2>::BHEAD && !KfChunkCfg<float, 6, 1>::QMOVE &&
+              !KfChunkCfg<float, 6, 1>::BHEAD && !KfLdsCfg<double, 6, 1>::BHEAD && !KfLdsCfg<double, 6, 1>::QMOVE, "... and its schedules");
 
 // DMA batches of one step.  All of a step's data is pulled into registers at the top of the step behind ONE
 // `s_waitcnt vmcnt(0)`; the batches of the next step are then issued between the arithmetic phases.
@@ -439,14 +496,15 @@ template <typename Cfg> struct KfPump {
     static constexpr int N_SMALL = Cfg::StC::NI + Cfg::Stb::NI + Cfg::NI_H + Cfg::NI_y + (Cfg::RS ? Cfg::StR::NI : 0);
     static constexpr bool HREG = Cfg::HREG;   // kf_lds_step drains the vector-memory counter in front of the first use of H
     static constexpr int N_BIG = Cfg::StA::NI;
-    const typename Cfg::DA& dA; const DmaStream<typename Cfg::StC>& dC;
-    const DmaStream<typename Cfg::Stb>& db; const DmaStream<typename Cfg::StH>& dH;
+    const typename Cfg::DA& dA; const typename Cfg::DC& dC;
+    const typename Cfg::Db& db; const DmaStream<typename Cfg::StH>& dH;
     const DmaStream<typename Cfg::Sty>& dy; const DmaStream<typename Cfg::StR>& dR;
     mf_v4i sA, sC, sb, sH, sy, sR;
     unsigned lds0;
     bool more;
     bool yfetch = true;     // this step's batch includes the next group of y rows
     unsigned cphase = 0;    // head carry: (index of the step being fetched) % period
+    unsigned bphase = 0;    // ... % period of b's schedule (BHEAD)
     template <int K> MF_DEV void small() const {
         if (!((MF_PUMPMASK >> K) & 1)) return;
         small_do<K>();
@@ -457,7 +515,8 @@ template <typename Cfg> struct KfPump {
         if (K == 0) dC.template issue<0, HC, true>(sC, lds0 + Cfg::OFF_C, cphase);
         else {
             dC.template issue<HC, 64, true>(sC, lds0 + Cfg::OFF_C, cphase);
-            db.template issue<0, 64>(sb, lds0 + Cfg::OFF_b);
+            if constexpr (Cfg::BHEAD) db.template issue<0, 64, true>(sb, lds0 + Cfg::OFF_b, bphase);
+            else db.template issue<0, 64>(sb, lds0 + Cfg::OFF_b);
             if constexpr (!Cfg::HREG) dH.template issue<0, 64>(sH, lds0 + Cfg::OFF_H);
             if constexpr (!Cfg::YREG) { if (yfetch) dy.template issue<0, 64>(sy, lds0 + Cfg::OFF_y); }
             if (Cfg::RS) dR.template issue<0, 64>(sR, lds0 + Cfg::OFF_R);
@@ -625,8 +684,8 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
         }
     }
     typename Cfg::DA dA;
-    DmaStream<typename Cfg::StC> dC;
-    DmaStream<typename Cfg::Stb> db;
+    typename Cfg::DC dC;
+    typename Cfg::Db db;
     DmaStream<typename Cfg::StH> dH;
     DmaStream<typename Cfg::Sty> dy;
     DmaStream<typename Cfg::StR> dR;
@@ -682,15 +741,17 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
     if constexpr (Cfg::ATAIL) dA.init(smem, lane, Cfg::OFF_relA, 0, (unsigned)pA);
     else dA.init(smem, lane, Cfg::OFF_relA, 0);
     dC.init(smem, lane, Cfg::OFF_relA, Cfg::OFF_gtabC, (unsigned)pC);
-    db.init(smem, lane, Cfg::OFF_relb, 0);
+    if constexpr (Cfg::BHEAD) db.init(smem, lane, Cfg::OFF_relb, 0, (unsigned)pb);
+    else db.init(smem, lane, Cfg::OFF_relb, 0);
     if constexpr (!Cfg::HREG) dH.init(smem, lane, Cfg::OFF_relH, 0);
     if constexpr (!Cfg::YREG) dy.init(smem, lane, Cfg::OFF_rely, 0);
     if (RSTEP) dR.init(smem, lane, Cfg::OFF_relR, 0);
     // (with the head carry the tables lie over the image: the last table read is done before the first DMA writes there)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    // head carry: this lane's consumer schedule, and the carried entries of the next row's chol Q (tail slot t, element k)
+    // head carry, first generation (not QMOVE): this lane's consumer schedule, and the carried entries of the next row's chol Q
+    // (tail slot t, element k)
     using HC = typename Cfg::StC::HC;
-    constexpr int NTAIL = Cfg::StC::NT, CPER = NTAIL > 0 ? HC::PERIOD : 1, UEL = Cfg::StC::UNIT / S;
+    constexpr int NTAIL = Cfg::QMOVE ? 0 : Cfg::StC::NT, CPER = Cfg::StC::NT > 0 ? HC::PERIOD : 1, UEL = Cfg::StC::UNIT / S;
     const unsigned cbits = NTAIL > 0 ? HC::consumer_bits((unsigned)((unsigned long long)a.cholQ + offA)) : 0u;
     T cv[NTAIL > 0 ? NTAIL : 1][UEL];
     MF_UNROLL for (int t = 0; t < (NTAIL > 0 ? NTAIL : 1); ++t) MF_UNROLL for (int k = 0; k < UEL; ++k) cv[t][k] = T(0);
@@ -703,6 +764,12 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
         static_assert(HCA::PERIOD == CPER, "one phase for both schedules");
         dA.sch1 = MovedSchedule<typename Cfg::StA>::with_consumer(dA.sch1, (unsigned)((unsigned long long)a.A + offA));
     }
+    // chol Q's (QMOVE) and b's (BHEAD) likewise; b's schedule has a period of its own
+    constexpr int BPER = Cfg::BHEAD ? Cfg::Stb::HC::PERIOD : 1;
+    if constexpr (Cfg::QMOVE)
+        dC.sch1 = MovedSchedule<typename Cfg::StC, Cfg::QGAP>::with_consumer(dC.sch1, (unsigned)((unsigned long long)a.cholQ + offA));
+    if constexpr (Cfg::BHEAD)
+        db.sch1 = MovedSchedule<typename Cfg::Stb>::with_consumer(db.sch1, (unsigned)((unsigned long long)a.b + offb));
     // YREG: this lane's group of y values (steps YG g ... YG g + YG - 1 of its chunk) and its offset from the wave's descriptor base
     YRegs<T, Cfg::YG * M, Cfg::YREG> yr;
     if constexpr (Cfg::YREG) {
@@ -777,7 +844,14 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
                 MF_UNROLL for (int k = 0; k < UEL; ++k) cv[t][k] = rC.tail_at(t, k);                                  \
             }                                                                                                         \
         }                                                                                                             \
+        /* QMOVE, BHEAD: the next row's carried head units go from the tail slots to the head slots (move_carried_heads) */ \
+        if constexpr (Cfg::QMOVE)                                                                                     \
+            move_carried_heads<T, typename Cfg::StC, Cfg::QGAP>(smem + Cfg::OFF_C + lane * (Cfg::StC::U * Cfg::StC::UNIT), dC.sch1, \
+                                                                (unsigned)((j + 1) & (CPER - 1)));                    \
         MF_UNROLL for (int i = 0; i < D; ++i) mvec[i] = rb.at(i);                                                     \
+        if constexpr (Cfg::BHEAD)                                                                                     \
+            move_carried_heads<T, typename Cfg::Stb, 1>(smem + Cfg::OFF_b + lane * (Cfg::Stb::U * Cfg::Stb::UNIT), db.sch1, \
+                                                        (unsigned)((j + 1) & (BPER - 1)));                            \
         /* HREG: this step's row of H (pH is a row ahead by now), straight into hk; first used, behind a full drain, */ \
         /* in front of Obs::apply                                                                                    */ \
         if constexpr (Cfg::HREG) yreg_load(pH - M * D * S, eH, a.debug | ((a.debug >> 1) & 1), hvoff, hk);            \
@@ -797,18 +871,9 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
         T Bm[D][D];                                                                                                   \
         MF_UNROLL for (int i = 0; i < D; ++i) MF_UNROLL for (int jj = 0; jj < D; ++jj) Bm[i][jj] = rA.at(i * D + jj); \
         if constexpr (NTA > 0) {                                                                                      \
-            /* the head units that the NEXT row carries go from the tail slots, where this step's fetch left them, to  */ \
-            /* the row's head slots, which are dead now: the fetch of the next row masks exactly those out and may    */ \
-            /* refill the tail slots.  A unit that is not carried is written back to its own tail slot: no branch.    */ \
-            /* (copied as values of T, the type the row was read with: the stores stay behind those reads)            */ \
-            char* arow = smem + Cfg::OFF_A + lane * (Cfg::StA::U * Cfg::StA::UNIT);                                   \
-            MF_UNROLL for (int t = 0; t < NTA; ++t) {                                                                 \
-                const bool mv = MovedSchedule<typename Cfg::StA>::carried(dA.sch1, t, (unsigned)((j + 1) & (CPER - 1))); \
-                const int src = (Cfg::StA::UB + t) * Cfg::StA::UNIT, dst = mv ? HCA::tail_unit(t) * Cfg::StA::UNIT : src; \
-                T un[Cfg::StA::UNIT / S];                                                                             \
-                MF_UNROLL for (int k = 0; k < Cfg::StA::UNIT / S; ++k) un[k] = *reinterpret_cast<const T*>(arow + src + k * S); \
-                MF_UNROLL for (int k = 0; k < Cfg::StA::UNIT / S; ++k) *reinterpret_cast<T*>(arow + dst + k * S) = un[k]; \
-            }                                                                                                         \
+            /* the head units that the NEXT row carries go to the row's head slots, which are dead now                */ \
+            move_carried_heads<T, typename Cfg::StA, 1>(smem + Cfg::OFF_A + lane * (Cfg::StA::U * Cfg::StA::UNIT), dA.sch1,  \
+                                                        (unsigned)((j + 1) & (CPER - 1)));                            \
         }                                                                                                             \
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                            \
         MF_CHECKSUM_ACC                                                                                               \
@@ -819,7 +884,7 @@ __global__ void __launch_bounds__(64) kf_chunk_lds_kernel(KfArgs<T> a, long L, R
                         make_srd(pH, eH, a.debug | ((a.debug >> 1) & 1)),                                             \
                         make_srd(py, ey, a.debug | ((a.debug >> 1) & 1)),                                             \
                         make_srd(pR, eR, a.debug | ((a.debug >> 1) & 1)), lds0, more, yfetch,                         \
-                        (unsigned)((j + 1) & (CPER - 1))};                                                            \
+                        (unsigned)((j + 1) & (CPER - 1)), (unsigned)((j + 1) & (BPER - 1))};                       \
         MF_EXP_STEP_NEXT                                                                                              \
         MF_NOPUMP_ISSUE                                                                                               \
         const bool active = j < len;                                                                                  \
