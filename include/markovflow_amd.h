@@ -1040,6 +1040,44 @@ int mf_lik_sparse_factor_expectations_f32(int64_t B, int64_t N, int64_t S, int t
                                           float* ve_sum, float* g_mean, float* g_cov, float* g_w, void* stream);
 
 /*
+ * The data term of the SVGP ELBO under a MultivariateGaussian likelihood, its adjoints onto the pair marginals and its adjoint onto
+ * the likelihood's precision (markovflow/likelihoods/multivariate_gaussian.py under markovflow/models/sparse_variational.py:149-192;
+ * csrc/mf_lik_mvn.hip): P = num_outputs observed series per point with noise correlated across them, p(y_k | f_k) = N(y_k; f_k, Sigma).
+ * B, N, S, two_d, seg_offsets, pair_mean, pair_cov and the tile table as for mf_lik_sparse_expectations_*; every point carries
+ *   w [B, N, P, 2d]  row p: H_p P_k        c [B, N, P, P]  the FULL H T_k H^T (symmetric: the lower triangle is read)        y [B, N, P]
+ * and the launch ONE matrix  prec [P, P] = Sigma^-1  on the device (symmetric: the lower triangle is read).
+ * Per point k of segment s:  mu = w m_s,  F = c + w S_s w^T,  r = y - mu,  v = prec r,  quad_k = r . v + <prec, F>;  per segment, over
+ * the points in ascending order and within a point over the pairs (p, q <= p) in the order (0,0), (1,0), (1,1), (2,0), ..., then over
+ * the outputs in ascending order,
+ *   quad_sum [B, S]       = sum_k quad_k            (E_q log p = -(n_s (P log 2 pi + log det Sigma) + quad_sum) / 2: the constants are
+ *                                                    the caller's)
+ *   g_mean [B, S, 2d]     = sum_k w^T v             the adjoint of -quad_sum / 2 onto pair_mean
+ *   g_cov  [B, S, 2d, 2d] = -1/2 sum_k w^T prec w   ... onto pair_cov (symmetric: both triangles are written from one sum)
+ *   m_sum  [B, S, P, P]   = sum_k (r r^T + F)       mirrored; -m_sum / 2 is the adjoint onto prec (may be NULL on its own)
+ * Pass 1 is one wavefront per tile of 64 points (LDS: 64 rows of P 2d + 1 elements, the pair marginal, P + P (P + 1) / 2 + 1 rows of 64
+ * values: 47792 B at P = 4, 2d = 18 in float64); a workspace row holds 2d (2d + 1) / 2 + 2d + P (P + 1) / 2 + 1 values:
+ * mf_lik_sparse_mvn_expectations_workspace_bytes(num_tiles, two_d, num_outputs, sizeof(T)).  Pass 2 is one block per (series, segment).
+ * g_mean, g_cov and m_sum ALL NULL: the value only, the same bits.  An empty segment writes exact zeros.  No floating-point atomics:
+ * the same bits on every launch and for a series alone or inside a batch.  The tile table is clamped on the device, not validated.
+ * No allocation, no synchronisation.
+ * Returns 0, -(position of the offending argument in THIS signature: 1 B, 2 N, 3 S, 6 ... 12 a NULL input, 13 num_tiles negative,
+ * above 2^31 - 1 or non-zero for N = 0, 14 / 15 a NULL table, 16 a NULL workspace, 17 a workspace that is too small, 19 / 20 one of
+ * g_mean / g_cov NULL without the other), -101 for a shape that is not instantiated - num_outputs in 2, 3, 4 with two_d even in
+ * 2 ... 18 are - or -1000 (launch failed).  Nothing is launched on an error, for B = 0, or when every output is NULL.
+ */
+size_t mf_lik_sparse_mvn_expectations_workspace_bytes(int64_t num_tiles, int two_d, int num_outputs, int elem_size);
+int mf_lik_sparse_mvn_expectations_f64(int64_t B, int64_t N, int64_t S, int two_d, int num_outputs, const int64_t* seg_offsets,
+                                       const double* w, const double* c, const double* y, const double* prec, const double* pair_mean,
+                                       const double* pair_cov, int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile,
+                                       void* workspace, size_t workspace_bytes, double* quad_sum, double* g_mean, double* g_cov,
+                                       double* m_sum, void* stream);
+int mf_lik_sparse_mvn_expectations_f32(int64_t B, int64_t N, int64_t S, int two_d, int num_outputs, const int64_t* seg_offsets,
+                                       const float* w, const float* c, const float* y, const float* prec, const float* pair_mean,
+                                       const float* pair_cov, int64_t num_tiles, const int64_t* tile_seg, const int64_t* seg_tile,
+                                       void* workspace, size_t workspace_bytes, float* quad_sum, float* g_mean, float* g_cov,
+                                       float* m_sum, void* stream);
+
+/*
  * The data term of the SVGP ELBO for a likelihood with K = latent_dim latent functions per observation on K STACKED chains, and its
  * adjoints onto every chain's pair marginals (markovflow/kernels/sde_kernel.py:945-1279 and markovflow/emission_model.py:270-378
  * under markovflow/models/sparse_variational.py:149-192; csrc/mf_lik_stack.hip).  Every latent has a chain of its own - K is the last

@@ -41,7 +41,9 @@ for the observations.  It is a decision tree over the three latents - ``y = 0`` 
 probability ``sigma(F1)``, else ``y - 2 ~ Poisson(exp(F2))`` - so its expectation is a sum of the Bernoulli and Poisson expectations
 above over the latents the point's branch reads; on HIP tensors it is ONE launch of ``mf_lik_multistage_variational_expectations_*``.
 
-The parameters (``variance``, ``scale``, ``df``) are plain Python floats and are NOT trainable.
+The parameters (``variance``, ``scale``, ``df``) are plain Python floats and are NOT trainable.  The one trainable likelihood
+parameter is the Cholesky factor of ``MultivariateGaussian`` (``p(y_k | f_k) = N(y_k; f_k, L L^T)``, ``P`` outputs per point with
+correlated noise; tensors ``batch + [N, P]``, covariances ``batch + [N, P, P]``), a torch leaf.
 """
 import ctypes
 import math
@@ -670,3 +672,104 @@ def torch_heteroscedastic_variational_expectations(fmu: torch.Tensor, fvar: torc
     r = fmu[..., 0] - y[..., 0]
     big = torch.exp(0.5 * fvar[..., 1] - fmu[..., 1]) * (r * r + fvar[..., 0])
     return -0.5 * (math.log(2.0 * math.pi) + fmu[..., 1] + big)
+
+
+class MultivariateGaussian(Likelihood):
+    """``p(y_k | f_k) = N(y_k; f_k, Sigma)``, ``Sigma = L L^T`` (markovflow/likelihoods/multivariate_gaussian.py): ``P`` observed
+    series per point with noise that is correlated ACROSS the series.  ``chol_covariance`` is ``L [P, P]``, a torch tensor kept as a
+    leaf that may carry ``requires_grad=True`` - the one TRAINABLE likelihood parameter (``trainable_variables``); only its lower
+    triangle is ever read (``L.tril()``: the gradient that reaches the leaf is lower-triangular) and its diagonal must be non-zero.
+    ``obs_dim = latent_dim = P``; tensors are ``batch + [N, P]`` and covariances ``batch + [N, P, P]``.  Everything is in closed
+    form in torch on either device and differentiable by autograd in everything; the SVGP data term on HIP tensors is ONE call of
+    ``mf_lik_sparse_mvn_expectations_*`` (``models.sparse_mvn_expected_log_likelihood``)."""
+
+    _id = 6
+    _full_covariance = True        # the marginal of f_k it needs is the full P x P one: no scalar entry point can serve it
+
+    def __init__(self, chol_covariance: torch.Tensor) -> None:
+        super().__init__(1)
+        if not isinstance(chol_covariance, torch.Tensor) or chol_covariance.dim() != 2 or chol_covariance.shape[0] != chol_covariance.shape[1] \
+                or chol_covariance.shape[0] < 1:
+            raise ValueError("MultivariateGaussian: chol_covariance must be a [P, P] tensor with P >= 1")
+        if chol_covariance.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"markovflow_amd supports float32 and float64 tensors, got {chol_covariance.dtype}")
+        if bool((torch.diagonal(chol_covariance.detach()) == 0).any()):
+            raise ValueError("MultivariateGaussian: the diagonal of chol_covariance must be non-zero")
+        self.chol_covariance = chol_covariance
+        self.obs_dim = self.latent_dim = int(chol_covariance.shape[0])
+
+    @property
+    def trainable_variables(self) -> Tuple[torch.Tensor, ...]:
+        return (self.chol_covariance,)
+
+    def _kernel_args(self):
+        return ()                  # (no id, no parameters, no rule: the precision travels as a device tensor)
+
+    def _chol(self, ref: torch.Tensor) -> torch.Tensor:
+        """``L.tril()`` on the dtype and device of ``ref``, under the tape."""
+        return self.chol_covariance.tril().to(dtype=ref.dtype, device=ref.device)
+
+    def precision(self, ref: torch.Tensor) -> torch.Tensor:
+        """``Sigma^-1 [P, P]`` from ``L.tril()`` by two triangular solves, symmetric, under the tape."""
+        chol = self._chol(ref)
+        prec = _lib.chol_solve(chol, torch.eye(self.obs_dim, dtype=ref.dtype, device=ref.device))
+        return 0.5 * (prec + prec.transpose(-1, -2))
+
+    def log_normaliser(self, ref: torch.Tensor) -> torch.Tensor:
+        """``P log 2 pi + log det Sigma`` (a scalar tensor, under the tape)."""
+        return self.obs_dim * math.log(2.0 * math.pi) + 2.0 * torch.sum(torch.log(torch.abs(torch.diagonal(self._chol(ref)))))
+
+    def _check(self, what: str, fmu: torch.Tensor, fcov: Optional[torch.Tensor] = None, **others: torch.Tensor):
+        p = self.obs_dim
+        if fmu.dim() < 2 or fmu.shape[-1] != p:
+            raise ValueError(f"MultivariateGaussian.{what}: tensors must have shape batch + [N, {p}], got {tuple(fmu.shape)}")
+        if fcov is not None and tuple(fcov.shape) != tuple(fmu.shape) + (p,):
+            raise ValueError(f"MultivariateGaussian.{what}: the covariances have shape {tuple(fcov.shape)}, expected "
+                             f"{tuple(fmu.shape) + (p,)}")
+        for name, t in others.items():
+            if tuple(t.shape) != tuple(fmu.shape):
+                raise ValueError(f"MultivariateGaussian.{what}: {name} has shape {tuple(t.shape)}, expected {tuple(fmu.shape)}")
+        if fmu.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"markovflow_amd supports float32 and float64 tensors, got {fmu.dtype}")
+        _lib.same_dtype_device(fmu, f"MultivariateGaussian.{what}", fcov=fcov, **others)
+
+    @staticmethod
+    def _log_density(chol: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
+        """``log N(r; 0, chol chol^T)``, ``[.., P] -> [..]``; ``chol`` is ``[P, P]`` or ``[.., P, P]``, lower."""
+        z = torch.linalg.solve_triangular(chol, r[..., None], upper=False)[..., 0]
+        logdet = 2.0 * torch.sum(torch.log(torch.abs(torch.diagonal(chol, dim1=-2, dim2=-1))), dim=-1)
+        return -0.5 * (torch.sum(z * z, dim=-1) + logdet + r.shape[-1] * math.log(2.0 * math.pi))
+
+    def log_prob(self, f: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """``log N(y; f, Sigma)``, ``batch + [N, P] -> batch + [N]``."""
+        self._check("log_prob", f, y=y)
+        return self._log_density(self._chol(f), y - f)
+
+    def variational_expectations(self, fmu: torch.Tensor, fcov: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """``E_{N(f | fmu, fcov)} log p(y | f) = -tr(Sigma^-1 fcov) / 2 + log N(y; fmu, Sigma)``, ``batch + [N]``, in the form the
+        kernel computes: ``-(P log 2 pi + log det Sigma + r^T Lam r + <Lam, fcov>) / 2`` with ``Lam = Sigma^-1``, ``r = y - fmu``."""
+        self._check("variational_expectations", fmu, fcov, y=y)
+        prec = self.precision(fmu)
+        r = y - fmu
+        quad = torch.sum(r * (r @ prec), dim=-1) + torch.sum(prec * fcov, dim=(-1, -2))
+        return -0.5 * (self.log_normaliser(fmu) + quad)
+
+    def predict_mean_and_var(self, fmu: torch.Tensor, fcov: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(fmu, Sigma + fcov)``: mean ``batch + [N, P]`` and FULL covariance ``batch + [N, P, P]`` of ``y``."""
+        self._check("predict_mean_and_var", fmu, fcov)
+        chol = self._chol(fmu)
+        return fmu, chol @ chol.transpose(-1, -2) + fcov
+
+    def predict_log_density(self, fmu: torch.Tensor, fcov: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """``log N(y; fmu, Sigma + fcov)``, ``batch + [N]``."""
+        self._check("predict_log_density", fmu, fcov, y=y)
+        chol = self._chol(fmu)
+        total = chol @ chol.transpose(-1, -2) + fcov
+        return self._log_density(_lib.checked_cholesky(0.5 * (total + total.transpose(-1, -2)), "MultivariateGaussian.predict_log_density"),
+                                 y - fmu)
+
+    def _one_latent_only(self, *args, **kwargs):
+        raise NotImplementedError(f"MultivariateGaussian couples its {self.obs_dim} outputs through a full covariance: the site updates "
+                                  "and the power-EP densities are written for one latent function; use SparseVariationalGaussianProcess")
+
+    cvi_site_update = log_expected_density = grad_log_expected_density = pep_site_update = _expectations = _one_latent_only

@@ -19,7 +19,8 @@ components the kernel -> state space model step is fused into the sweep, ``mf_gp
 
 ``SparseVariationalGaussianProcess`` (``sparse.py``): SVGP, ``q`` a trainable chain on the inducing points;
 ``mf_lik_sparse_expectations_*``; on the stacked chains of an ``IndependentMultiOutputStack`` with a multi-latent likelihood,
-``mf_lik_stack_expectations_*``.
+``mf_lik_stack_expectations_*``; under a ``MultivariateGaussian`` likelihood (noise correlated across the observed series, a trainable
+Cholesky factor), ``mf_lik_sparse_mvn_expectations_*``.
 
 ``ImportanceWeightedVI`` (``sparse.py``): SVGP with the importance-weighted bound, proposals by Matheron's rule;
 ``mf_lik_iw_log_weights_*``.
@@ -39,7 +40,8 @@ from .. import _lib  # noqa: F401  (with ``KalmanFilter`` and the private names 
 from ..kalman_filter import KalmanFilter  # noqa: F401
 from ._common import back_project_nats, gradient_correction, gradient_transformation_mean_var_to_expectation
 from .gpr import GaussianProcessRegression
-from .segmented_ops import (IW_SAMPLE_CHUNK, SPARSE_EXPECT_TILE, SPARSE_FACTOR_LATENTS, SPARSE_FACTOR_MAX_OUTPUTS, SPARSE_SITE_MAX_TWO_D,
+from .segmented_ops import (IW_SAMPLE_CHUNK, SPARSE_EXPECT_TILE, SPARSE_FACTOR_LATENTS, SPARSE_FACTOR_MAX_OUTPUTS, SPARSE_MVN_OUTPUTS,
+                            SPARSE_SITE_MAX_TWO_D, _sparse_mvn_expectations_launch,
                             _iw_log_weights_launch, _segments_of, _sparse_expectations_launch, _sparse_factor_expectations_launch,
                             _sparse_multi_expectations_launch, iw_log_likelihood, iw_log_likelihood_torch, iw_merged_time_points,
                             pair_cavity, pair_cavity_hip, pair_cavity_torch, sparse_cvi_site_update_hip, sparse_cvi_site_update_torch, sparse_expectation_tiles,
@@ -47,7 +49,8 @@ from .segmented_ops import (IW_SAMPLE_CHUNK, SPARSE_EXPECT_TILE, SPARSE_FACTOR_L
                             sparse_factor_expected_log_likelihood, sparse_factor_expected_log_likelihood_torch,
                             sparse_factor_site_projections, sparse_multi_expected_log_likelihood,
                             sparse_multi_expected_log_likelihood_torch, sparse_multi_output_expected_log_likelihood_torch,
-                            sparse_multi_site_projections, sparse_pep_site_update_hip, sparse_pep_site_update_torch,
+                            sparse_full_site_projections, sparse_multi_site_projections, sparse_mvn_expected_log_likelihood,
+                            sparse_mvn_expected_log_likelihood_torch, sparse_pep_site_update_hip, sparse_pep_site_update_torch,
                             sparse_site_projections, sparse_stack_expected_log_likelihood,
                             sparse_stack_expected_log_likelihood_torch)
 from .sites import CVIGaussianProcess, PowerExpectationPropagation

@@ -17,6 +17,7 @@ import torch
 from .. import _lib
 from ..kalman_filter import KalmanFilter
 from ..kernels import FactorAnalysisKernel, IndependentMultiOutput, SDEKernel, _MaternBase, _refuse_stack
+from ..likelihoods import MultivariateGaussian
 from ..posterior import AnalyticPosteriorProcess
 from ..state_space_model import StateSpaceModel
 
@@ -169,6 +170,12 @@ class GaussianProcessRegression:
     @property
     def mean_function(self):
         return self._mean_function
+
+    @property
+    def likelihood(self) -> MultivariateGaussian:
+        """The observation noise as a likelihood, ``N(y; f, chol_obs_covariance chol_obs_covariance^T)``
+        (gaussian_process_regression.py:126-131).  Read-only: the Kalman path takes the Cholesky factor itself."""
+        return MultivariateGaussian(self._chol_obs_covariance)
 
     def _residuals(self) -> torch.Tensor:
         """``observations - mean_function(time_points)`` (gaussian_process_regression.py:112-124); without a mean function the

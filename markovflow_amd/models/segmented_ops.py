@@ -20,6 +20,9 @@ forward launch wrote:
     per point mixed from the ``L`` latents of a ``FactorAnalysisKernel`` (``sparse_factor_site_projections``: the pair projected onto
     the latents), with the adjoint onto the mixing weights; ``sparse_multi_output_expected_log_likelihood_torch``: the plain
     multi-output term of any kernel with ``P`` outputs (torch only);
+  * ``sparse_mvn_expected_log_likelihood(_torch)``: ``mf_lik_sparse_mvn_expectations_*``, the same term under a
+    ``MultivariateGaussian`` likelihood - the full ``P x P`` marginal per point (``sparse_full_site_projections``), closed form, with
+    the adjoint onto the likelihood's precision;
   * ``iw_log_likelihood(_torch)``: ``mf_lik_iw_log_weights_*`` (two passes, tile-parallel, no atomics), the data term of the
     importance weights with Matheron's correction assembled in the kernel.
 
@@ -704,6 +707,120 @@ def sparse_factor_expected_log_likelihood_torch(likelihood: Likelihood, wg: torc
     fmu = (mix @ mu_g[..., None])[..., 0]                                                  # [.., N, P]
     fvar = torch.sum((mix @ sig_g) * mix, dim=-1)
     ve = torch.sum(likelihood.variational_expectations(fmu[..., None], fvar[..., None], y[..., None]), dim=-1)
+    return _segment_sum(ve, _flat_segments(indices, segs), pair_mean.shape[:-1])
+
+
+# ---- SVGP with noise correlated across the observed series: the MultivariateGaussian likelihood ------------------------------------
+SPARSE_MVN_OUTPUTS = (2, 3, 4)      # mf_lik_sparse_mvn_expectations_*: the instantiated P (2d even in 2 ... 18)
+
+
+def sparse_full_site_projections(kernel: SDEKernel, time_points: torch.Tensor, inducing_points: torch.Tensor
+                                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``sparse_site_projections`` for a kernel with ``P = kernel.output_dim`` outputs whose likelihood needs their joint marginal:
+    ``w [.., N, P, 2d] = H P_k`` and the FULL ``c [.., N, P, P] = H T_k H^T`` (symmetric bit for bit), with the same ``indices`` and
+    ``offsets``; the kernel's own emission (a ``FactorAnalysisKernel``'s composed one), under ``no_grad``: a model caches it."""
+    with torch.no_grad():
+        proj, cov, indices = conditionals._conditional_statistics(time_points, inducing_points, kernel)
+        h = kernel.generate_emission_model(time_points).emission_matrix                     # [.., N, P, d]
+        w = h @ proj
+        c = h @ cov @ h.transpose(-1, -2)
+        c = 0.5 * (c + c.transpose(-1, -2))
+        return w.contiguous(), c.contiguous(), indices, _site_offsets(time_points, inducing_points)
+
+
+def _sparse_mvn_check(what: str, likelihood, w, c, y, lead, segs, pair_mean, pair_cov) -> None:
+    if not getattr(likelihood, "_full_covariance", False):
+        raise TypeError(f"{what}: likelihood must be a markovflow_amd.likelihoods.MultivariateGaussian")
+    if w.dim() < 3:
+        raise ValueError(f"{what}: w must have shape batch + [N, P, 2d], got {tuple(w.shape)}")
+    n, outputs, two_d = w.shape[-3], w.shape[-2], w.shape[-1]
+    if outputs != likelihood.obs_dim:
+        raise ValueError(f"{what}: w carries {outputs} rows per point, the likelihood has obs_dim = {likelihood.obs_dim}")
+    _check_shapes(what, dict(w=(w, lead + (n, outputs, two_d)), c=(c, lead + (n, outputs, outputs)), y=(y, lead + (n, outputs)),
+                             pair_mean=(pair_mean, lead + (segs, two_d)), pair_cov=(pair_cov, lead + (segs, two_d, two_d))))
+    _lib.same_dtype_device(w, what, c=c, y=y, pair_mean=pair_mean, pair_cov=pair_cov)
+
+
+def _sparse_mvn_expectations_launch(likelihood: Likelihood, w, c, y, prec, offsets, tiles, pair_mean, pair_cov, want_grads: bool,
+                                    want_m_sum: bool):
+    """ONE call of ``mf_lik_sparse_mvn_expectations_*``: ``(quad_sum [.., S], g_mean [.., S, 2d] | None, g_cov [.., S, 2d, 2d] | None,
+    m_sum [.., S, P, P] | None)``."""
+    n, outputs, segs = w.shape[-3], w.shape[-2], offsets.shape[-1] - 1
+    return _expectations_launch("mf_lik_sparse_mvn_expectations", likelihood, (n, segs, w.shape[-1], outputs), (w, c, y, prec), offsets,
+                                tiles, pair_mean, pair_cov, want_grads, ws_dims=(outputs,), extra=(want_m_sum, segs, outputs, outputs))
+
+
+class _SparseMvnQuadraticTerm(torch.autograd.Function):
+    """``-quad_sum / 2``, ``batch + [M + 1]``: the part of the data term that depends on the pair marginals and on the precision.  Its
+    adjoints onto the pair marginals and - when ``prec`` requires a gradient - onto the precision come out of the same launch and wait
+    for the backward."""
+
+    @staticmethod
+    def forward(ctx, pair_mean, pair_cov, prec, likelihood, w, c, y, offsets, tiles):
+        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        want_m = ctx.needs_input_grad[2]
+        with torch.no_grad():
+            quad_sum, g_mean, g_cov, m_sum = _sparse_mvn_expectations_launch(likelihood, w.detach(), c.detach(), y.detach(), prec.detach(),
+                                                                             offsets, tiles, pair_mean.detach(), pair_cov.detach(), want,
+                                                                             want_m)
+        ctx.want, ctx.want_m = want, want_m
+        ctx.save_for_backward(*(((g_mean, g_cov) if want else ()) + ((m_sum,) if want_m else ())))
+        return -0.5 * quad_sum
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        _differentiable_once("sparse_mvn_expected_log_likelihood", "adjoints")
+        saved = list(ctx.saved_tensors)
+        g_prec = None
+        if ctx.want_m:
+            m_sum = saved.pop()
+            g_prec = torch.sum((grad_out[..., None, None] * (-0.5 * m_sum)).reshape((-1,) + tuple(m_sum.shape[-2:])), dim=0)
+        return (grad_out[..., None] * saved[0] if ctx.needs_input_grad[0] else None,
+                grad_out[..., None, None] * saved[1] if ctx.needs_input_grad[1] else None, g_prec, None, None, None, None, None, None)
+
+
+def sparse_mvn_expected_log_likelihood(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor, offsets: torch.Tensor,
+                                       pair_mean: torch.Tensor, pair_cov: torch.Tensor, tiles=None) -> torch.Tensor:
+    """The SVGP data term under a ``MultivariateGaussian`` likelihood, ``sum_k E_q log N(y_k; f_k, Sigma)`` per pair of neighbouring
+    inducing states, ``batch + [M + 1]``: per point ``mu = w m_s``, ``F = c + w S_s w^T`` (the FULL ``P x P`` marginal), ``r = y - mu``
+    and ``-(P log 2 pi + log det Sigma + r^T Lam r + <Lam, F>) / 2`` with ``Lam = Sigma^-1`` (``w [.., N, P, 2d]``, ``c [.., N, P, P]`` of
+    ``sparse_full_site_projections``, ``y [.., N, P]``): ONE call of ``mf_lik_sparse_mvn_expectations_*`` on HIP tensors, ``P`` in
+    2, 3, 4, ``2d`` even in ``2 ... 18``.  Differentiable ONCE in ``pair_mean``, ``pair_cov`` and ``likelihood.chol_covariance``: the
+    precision and the log-determinant are built from ``chol_covariance.tril()`` under the tape here, and the backward multiplies the
+    adjoints the forward launch left behind (the one onto the precision is asked of the kernel only when ``chol_covariance`` requires
+    a gradient); there is no second launch.  Not differentiable in ``w`` and ``c``.  ``tiles``:
+    ``sparse_expectation_tiles(offsets)`` when the caller keeps it."""
+    what = "sparse_mvn_expected_log_likelihood"
+    segs = offsets.shape[-1] - 1
+    _sparse_mvn_check(what, likelihood, w, c, y, tuple(offsets.shape[:-1]), segs, pair_mean, pair_cov)
+    outputs, two_d = w.shape[-2], w.shape[-1]
+    if outputs not in SPARSE_MVN_OUTPUTS or two_d > SPARSE_SITE_MAX_TWO_D or two_d % 2:
+        raise NotImplementedError(f"{what}: P = {outputs}, 2d = {two_d} is outside P in {SPARSE_MVN_OUTPUTS}, 2d even in 2 ... "
+                                  f"{SPARSE_SITE_MAX_TWO_D}; use sparse_mvn_expected_log_likelihood_torch")
+    if torch.is_grad_enabled() and (w.requires_grad or c.requires_grad):
+        raise NotImplementedError(f"{what} has no adjoint onto w and c (a hyper-parameter of the kernel under the tape): use "
+                                  "sparse_mvn_expected_log_likelihood_torch")
+    if tiles is None:
+        tiles = sparse_expectation_tiles(offsets)
+    counts = (offsets[..., 1:] - offsets[..., :-1]).to(w.dtype)
+    quad = _SparseMvnQuadraticTerm.apply(pair_mean, pair_cov, likelihood.precision(w), likelihood, w, c, y, offsets, tiles)
+    return quad - 0.5 * counts * likelihood.log_normaliser(w)
+
+
+def sparse_mvn_expected_log_likelihood_torch(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor,
+                                             indices: torch.Tensor, pair_mean: torch.Tensor, pair_cov: torch.Tensor) -> torch.Tensor:
+    """The same quantity as a torch composition, differentiable by autograd in everything (``pair_mean``, ``pair_cov``,
+    ``chol_covariance``, ``w``, ``c``): gathers of the pair marginals by the per-point pair index (``indices [.., N]``), the projection,
+    ``likelihood.variational_expectations`` and ``index_add`` over the segments.  It runs on CPU tensors, it is the model's route for
+    every shape the kernel does not take and for a hyper-parameter of the kernel under the tape, and it is what
+    ``mf_lik_sparse_mvn_expectations_*`` is measured against."""
+    segs = pair_mean.shape[-2]
+    _sparse_mvn_check("sparse_mvn_expected_log_likelihood_torch", likelihood, w, c, y, tuple(indices.shape[:-1]), segs, pair_mean,
+                      pair_cov)
+    m, cov = _gather_pairs(pair_mean, pair_cov, indices)
+    fmu = (w @ m[..., None])[..., 0]                                                       # [.., N, P]
+    fcov = c + w @ cov @ w.transpose(-1, -2)                                               # [.., N, P, P]
+    ve = likelihood.variational_expectations(fmu, fcov, y)
     return _segment_sum(ve, _flat_segments(indices, segs), pair_mean.shape[:-1])
 
 

@@ -24,20 +24,22 @@ import torch
 
 from .. import _lib, conditionals
 from ..kernels import FactorAnalysisKernel, IndependentMultiOutputStack, SDEKernel, StackKernel, _version_key
-from ..likelihoods import Likelihood
+from ..likelihoods import Likelihood, MultivariateGaussian
 from ..posterior import ConditionalProcess, ImportanceWeightedPosteriorProcess
 from ..ssm_gaussian_transformations import naturals_to_ssm_params
 from ..state_space_model import StateSpaceModel
 from ._common import (_PredictLogDensity, _refuse_factor_analysis, _refuse_non_stationary, _refuse_stack, _require_likelihood, gradient_correction,
                       gradient_transformation_mean_var_to_expectation)
-from .segmented_ops import (SPARSE_FACTOR_LATENTS, SPARSE_FACTOR_MAX_OUTPUTS, SPARSE_MULTI_MIN_TWO_D, SPARSE_SITE_MAX_TWO_D,
+from .segmented_ops import (SPARSE_FACTOR_LATENTS, SPARSE_FACTOR_MAX_OUTPUTS, SPARSE_MULTI_MIN_TWO_D, SPARSE_MVN_OUTPUTS,
+                            SPARSE_SITE_MAX_TWO_D,
                             _sparse_point_marginals, iw_log_likelihood, iw_log_likelihood_torch, iw_merged_time_points, pair_cavity,
                             sparse_cvi_site_update_hip, sparse_cvi_site_update_torch, sparse_expectation_tiles,
                             sparse_expected_log_likelihood, sparse_expected_log_likelihood_torch,
                             sparse_factor_expected_log_likelihood, sparse_factor_expected_log_likelihood_torch,
-                            sparse_factor_site_projections, sparse_multi_expected_log_likelihood,
+                            sparse_factor_site_projections, sparse_full_site_projections, sparse_multi_expected_log_likelihood,
                             sparse_multi_expected_log_likelihood_torch, sparse_multi_output_expected_log_likelihood_torch,
-                            sparse_multi_site_projections, sparse_pep_site_update_hip, sparse_pep_site_update_torch,
+                            sparse_multi_site_projections, sparse_mvn_expected_log_likelihood,
+                            sparse_mvn_expected_log_likelihood_torch, sparse_pep_site_update_hip, sparse_pep_site_update_torch,
                             sparse_site_projections, sparse_stack_expected_log_likelihood,
                             sparse_stack_expected_log_likelihood_torch, sparse_stack_instantiated)
 
@@ -60,7 +62,7 @@ class _SparseGaussianProcess(_PredictLogDensity):
             raise NotImplementedError(f"{type(self).__name__} takes a StackKernel with its multi-output emission only: use "
                                       "IndependentMultiOutputStack")
         _require_likelihood(likelihood, multi_latent=self._multi_latent)
-        if likelihood.latent_dim > 1 and likelihood.latent_dim != kernel.output_dim:
+        if (likelihood.latent_dim > 1 or isinstance(likelihood, MultivariateGaussian)) and likelihood.latent_dim != kernel.output_dim:
             raise ValueError(f"the likelihood has latent_dim = {likelihood.latent_dim}, the kernel has output_dim = "
                              f"{kernel.output_dim}: a multi-latent likelihood needs one output of the kernel per latent function")
         if (not isinstance(inducing_points, torch.Tensor) or inducing_points.dim() < 1
@@ -85,7 +87,11 @@ class _SparseGaussianProcess(_PredictLogDensity):
         outputs = self._kernel.output_dim
         # one observed series per output of the kernel: the one model that says so, a likelihood with ONE latent function
         per_output = self._multi_output and outputs > 1 and self._likelihood.latent_dim == 1
-        if observations.dim() < 2 or not (observations.shape[-1] == 1 or (per_output and observations.shape[-1] == outputs)):
+        if isinstance(self._likelihood, MultivariateGaussian):     # one observed series per output, jointly: [N, P] and nothing else
+            if observations.dim() < 2 or observations.shape[-1] != outputs:
+                raise ValueError(f"{what}: observations must have shape batch + [num_data, {outputs}] (one series per output of the "
+                                 f"kernel, under a MultivariateGaussian likelihood), got {tuple(observations.shape)}")
+        elif observations.dim() < 2 or not (observations.shape[-1] == 1 or (per_output and observations.shape[-1] == outputs)):
             raise ValueError(f"{what}: observations must have shape batch + [num_data, 1]"
                              + (f" or batch + [num_data, {outputs}] (one series per output of the kernel)" if per_output else "")
                              + f", got {tuple(observations.shape)}")
@@ -490,6 +496,16 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
     ``sparse_multi_output_expected_log_likelihood_torch``.  Observations ``batch + [N, 1]`` keep the single-output path whatever the
     kernel (a weight function's own parameters are seen on the ``[N, P]`` routes only).
 
+    A ``MultivariateGaussian`` likelihood (``p(y_k | f_k) = N(y_k; f_k, L L^T)``, ``L [P, P]`` a trainable leaf) takes any kernel with
+    ``output_dim = P`` (``IndependentMultiOutput``, ``FactorAnalysisKernel`` through its composed emission,
+    ``SparseSpatioTemporalKernel``) and observations ``batch + [N, P]``: noise correlated ACROSS the observed series.  The term is not
+    a sum over the outputs - it needs the full ``P x P`` marginal of ``f_k`` (``sparse_full_site_projections``) - and is ONE call of
+    ``mf_lik_sparse_mvn_expectations_*``, which also leaves the adjoint onto ``Sigma^-1`` behind: ``L`` trains on the fused path (HIP
+    tensors, ``P`` in 2, 3, 4, ``2d <= 18``, no hyper-parameter of the chain or of the emission under the tape; otherwise
+    ``sparse_mvn_expected_log_likelihood_torch``).  ``SSMNaturalGradient`` on ``dist_q`` alternates with a torch optimiser on
+    ``likelihood.trainable_variables``; neither step invalidates the cached projections.  ``predict_log_density`` takes ``[N, P]``
+    observations under this likelihood only.
+
     An ``IndependentMultiOutputStack`` of ``K`` kernels keeps ``K`` independent chains of dimension ``d = max d_k`` with ``K`` as the
     last batch dimension: inducing points ``lead + [K, M]``, time points ``lead + [K, N]``, ``dist_q`` / ``dist_p`` / the KL /
     ``SSMNaturalGradient`` on batch ``lead + [K]``, ``predict_f`` ``lead + [num_new, K]``.  Observations ``lead + [N, 1]`` under a
@@ -511,7 +527,12 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
         """
         super().__init__(kernel, likelihood, inducing_points, min_inducing=2)
         self._route = "multi" if likelihood.latent_dim > 1 else "single"    # (``_data_route`` of the data last seen)
-        if isinstance(kernel, StackKernel):
+        if isinstance(likelihood, MultivariateGaussian):
+            if isinstance(kernel, StackKernel):
+                raise NotImplementedError("a MultivariateGaussian likelihood couples the outputs at every point through their joint "
+                                          "marginal: a stack kernel keeps one independent chain per output; use IndependentMultiOutput")
+            self._route = "mvn"
+        elif isinstance(kernel, StackKernel):
             self._route = "stack" if likelihood.latent_dim > 1 else "stack_outputs"
         if num_data is not None and not num_data > 0:
             raise ValueError(f"num_data must be positive, got {num_data}")
@@ -561,7 +582,9 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
     def _data_route(self, observations: torch.Tensor) -> str:
         """What the observations' last dimension selects: ``"single"`` (``[N, 1]``, one latent), ``"multi"`` (``[N, 1]``, a
         multi-latent likelihood), ``"factor"`` (``[N, P]`` on a ``FactorAnalysisKernel``) or ``"outputs"`` (``[N, P]`` on any other
-        kernel with ``P`` outputs)."""
+        kernel with ``P`` outputs); ``"mvn"`` whatever the observations under a ``MultivariateGaussian`` likelihood."""
+        if isinstance(self._likelihood, MultivariateGaussian):
+            return "mvn"
         if isinstance(self._kernel, StackKernel):
             return "stack" if self._multi else "stack_outputs"
         if observations.shape[-1] == 1:
@@ -585,6 +608,8 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
             return latents in SPARSE_FACTOR_LATENTS and two_d >= 2 * latents and self._kernel.output_dim <= SPARSE_FACTOR_MAX_OUTPUTS
         if self._route == "outputs":           # (no fused multi-output term for a kernel that is not a FactorAnalysisKernel)
             return False
+        if self._route == "mvn":               # the loading matrix under the tape: w and c are part of the graph
+            return self._likelihood.obs_dim in SPARSE_MVN_OUTPUTS and not self._emission_needs_grad()
         if self._route == "single":            # the loading matrix under the tape: w and c are part of the graph
             return not self._emission_needs_grad()
         return two_d >= SPARSE_MULTI_MIN_TWO_D
@@ -593,12 +618,14 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
         """``(order | None, w, c, indices, offsets, tiles)`` of the data: the permutation that sorts each series (None for sorted
         data), ``sparse_site_projections`` of the sorted points (``sparse_multi_site_projections`` for a multi-latent likelihood or
         multi-output observations: ``w`` and ``c`` carry one row per latent or output; ``sparse_factor_site_projections`` for a
-        ``FactorAnalysisKernel`` with multi-output observations: ``wg``, ``cg`` of the latents) and the tile table."""
+        ``FactorAnalysisKernel`` with multi-output observations: ``wg``, ``cg`` of the latents; ``sparse_full_site_projections`` under a
+        ``MultivariateGaussian`` likelihood: ``c`` is the full ``P x P`` block) and the tile table."""
         if self._route in ("stack", "stack_outputs"):
             return self._compute_stack_projections(time_points)
         order, time_points = _sorted_series(time_points)
         project = {"single": sparse_site_projections, "multi": sparse_multi_site_projections,
-                   "outputs": sparse_multi_site_projections, "factor": sparse_factor_site_projections}[self._route]
+                   "outputs": sparse_multi_site_projections, "factor": sparse_factor_site_projections,
+                   "mvn": sparse_full_site_projections}[self._route]
         w, c, indices, offsets = project(self._kernel, time_points, self.inducing_inputs)
         tiles = sparse_expectation_tiles(offsets) if time_points.is_cuda else None
         return order, w, c, indices, offsets, tiles
@@ -679,6 +706,26 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
             return sparse_factor_expected_log_likelihood(self._likelihood, w, c, mix, y, offsets, pair_mean, pair_cov, tiles=tiles)
         return sparse_factor_expected_log_likelihood_torch(self._likelihood, w, c, mix, y, indices, pair_mean, pair_cov)
 
+    def _mvn_expected_log_likelihood(self, time_points: torch.Tensor, observations: torch.Tensor, pair_mean, pair_cov) -> torch.Tensor:
+        """The data term under a ``MultivariateGaussian`` likelihood, observations ``batch + [N, P]``.  Neither route's projections
+        depend on the likelihood's Cholesky factor: a step on it keeps the cache."""
+        kernel = self._kernel
+        fused = self._fused(time_points)
+        if not fused and (kernel._needs_grad() or self._emission_needs_grad()):
+            # a hyper-parameter of the chain or of the emission under the tape: the projections are part of the graph
+            order, x = _sorted_series(time_points)
+            proj, cov, indices = conditionals._conditional_statistics(x, self.inducing_inputs, kernel)
+            h = kernel.generate_emission_model(x).emission_matrix
+            w, c = h @ proj, h @ cov @ h.transpose(-1, -2)
+        else:
+            order, w, c, indices, offsets, tiles = self._projections(time_points)
+        y = observations
+        if order is not None:
+            y = torch.gather(y, -2, order[..., None].expand(y.shape))
+        if fused:
+            return sparse_mvn_expected_log_likelihood(self._likelihood, w, c, y, offsets, pair_mean, pair_cov, tiles=tiles)
+        return sparse_mvn_expected_log_likelihood_torch(self._likelihood, w, c, y, indices, pair_mean, pair_cov)
+
     def _pair_marginals(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """``(m_pair [.., M+1, 2d], S_pair [.., M+1, 2d, 2d])`` of ``dist_q`` - under the tape when its leaves require a gradient -
         with the stationary prior beyond both ends."""
@@ -695,6 +742,8 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
             return self._stack_expected_log_likelihood(time_points, observations, pair_mean, pair_cov)
         if route in ("factor", "outputs"):
             return self._multi_output_expected_log_likelihood(time_points, observations, pair_mean, pair_cov)
+        if route == "mvn":
+            return self._mvn_expected_log_likelihood(time_points, observations, pair_mean, pair_cov)
         if self._fused(time_points):
             order, w, c, _, offsets, tiles = self._projections(time_points)
             y = observations[..., 0]
@@ -752,6 +801,12 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
         if isinstance(self._kernel, StackKernel):
             raise NotImplementedError("predict_log_density is not supported on a stack kernel (several latents or several outputs "
                                       "per point)")
+        if isinstance(self._likelihood, MultivariateGaussian):
+            # the one likelihood with a joint predictive density over the outputs: from the FULL output covariance
+            new_times, new_obs = input_data
+            f_mean, f_cov = self.predict_f(new_times, full_output_cov=True)
+            with torch.no_grad():
+                return self._likelihood.predict_log_density(f_mean, f_cov, new_obs)
         if input_data[1].dim() >= 1 and input_data[1].shape[-1] != 1:
             raise NotImplementedError("predict_log_density: observations with several outputs per point are not supported")
         return super().predict_log_density(input_data, full_output_cov)
