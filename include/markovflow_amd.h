@@ -945,6 +945,50 @@ int mf_lik_sparse_expectations_f32(int64_t B, int64_t N, int64_t S, int two_d, i
                                    size_t workspace_bytes, float* ve_sum, float* g_mean, float* g_cov, void* stream);
 
 /*
+ * The same data term with the likelihood's parameter theta in DEVICE memory, and its adjoint onto theta out of the same launch
+ * (gpflow's trainable Gaussian.variance / StudentT.scale; csrc/mf_lik_theta.hip).  B, N, S, two_d, the rule, seg_offsets, w, c, y,
+ * pair_mean, pair_cov, the tile table and the first three outputs as for mf_lik_sparse_expectations_*.
+ *   lik 0  Gaussian    theta = variance   params is not read
+ *   lik 3  Student-t   theta = scale      params [df, const],  const = lgamma((df+1)/2) - lgamma(df/2) - log(df pi)/2: the part of
+ *                                         the normaliser that is free of theta; the kernel subtracts log theta itself
+ *   theta, theta_stride   device memory of T;  stride 0: theta[0] for every series,  stride 1: theta[b] for series b
+ * Per point, beside (ve, gm, gv):  gt = d ve / d theta  - Gaussian:  (1 / 2 theta) ((r^2 + fvar) / theta - 1),  r = y - fmu;  Student-t:
+ * sum_i w_i ((df + 1) r_i^2 / (theta (a + r_i^2)) - 1 / theta),  a = df theta^2, over the nodes of the rule -  and per segment
+ *   g_theta [B, S]          sum_k gt_k                d ve_sum_s / d theta  (the caller adds the segments, and the series for stride 0)
+ * The outputs are three groups, each asked for or not on its own: (g_mean, g_cov) - both or neither -, g_theta, ve_sum; every output
+ * has the same bits whichever of the others is asked for, and without (g_mean, g_cov) pass 1 accumulates the two scalars only.
+ * theta is NOT checked on the host (that would be a synchronisation): a theta that is <= 0, NaN or infinite makes all four outputs
+ * of EVERY segment of THAT series NaN, the empty ones included, and changes no other series.
+ * Pass 1 is one wavefront per tile of 64 points: theta is loaded once per tile (the tile's series is wavefront-uniform) and the
+ * constants derived from it are formed once; four rows of 64 values in LDS (gv, gm, ve, gt); a workspace row holds
+ * 2d (2d + 1) / 2 + 2d + 2 values: mf_lik_sparse_expectations_theta_workspace_bytes(num_tiles, two_d, sizeof(T)) bytes (0 for
+ * num_tiles = 0).  Pass 2 is one block per (series, segment): ascending tile order, the triangle mirrored.
+ * No floating-point atomics: every sum runs over the points in ascending order, the same bits on every launch and for a series
+ * alone or inside a batch.  A point with fvar <= 0 or NaN makes the four outputs of ITS segment NaN; no other segment is touched.
+ * An empty segment, and every segment for N = 0, gets zeros (under a valid theta).  The tile table is clamped on the device, not
+ * validated.  No allocation, no synchronisation.
+ * Returns 0, -(position of the offending argument in THIS signature: 1 B, 2 N, 3 S, 6 params (Student-t: NULL, df not positive and
+ * finite, const not finite), 7 nq, 8 nodes, 9 weights, 10 theta NULL, 11 theta_stride not 0 or 1, 12 ... 17 a NULL input, 18 num_tiles
+ * negative, above 2^31 - 1 or non-zero for N = 0, 19 / 20 a NULL table, 21 a NULL workspace, 22 a workspace that is too small,
+ * 24 / 25 one of g_mean / g_cov NULL without the other), -100 for a two_d that is odd, < 2 or > 18, -101 for a lik other than 0 and 3
+ * (signature not covered: use mf_lik_sparse_expectations_*), or -1000 (launch failed).  Nothing is launched on an error, for B = 0,
+ * or when every output is NULL.
+ */
+size_t mf_lik_sparse_expectations_theta_workspace_bytes(int64_t num_tiles, int two_d, int elem_size);
+int mf_lik_sparse_expectations_theta_f64(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq,
+                                         const double* nodes, const double* weights, const double* theta, int64_t theta_stride,
+                                         const int64_t* seg_offsets, const double* w, const double* c, const double* y,
+                                         const double* pair_mean, const double* pair_cov, int64_t num_tiles, const int64_t* tile_seg,
+                                         const int64_t* seg_tile, void* workspace, size_t workspace_bytes, double* ve_sum,
+                                         double* g_mean, double* g_cov, double* g_theta, void* stream);
+int mf_lik_sparse_expectations_theta_f32(int64_t B, int64_t N, int64_t S, int two_d, int lik, const double* params, int nq,
+                                         const double* nodes, const double* weights, const float* theta, int64_t theta_stride,
+                                         const int64_t* seg_offsets, const float* w, const float* c, const float* y,
+                                         const float* pair_mean, const float* pair_cov, int64_t num_tiles, const int64_t* tile_seg,
+                                         const int64_t* seg_tile, void* workspace, size_t workspace_bytes, float* ve_sum, float* g_mean,
+                                         float* g_cov, float* g_theta, void* stream);
+
+/*
  * The data term of the SVGP ELBO for a likelihood with SEVERAL latent functions per observation, and its adjoint onto the pair
  * marginals (markovflow/models/sparse_variational.py:149-192 with markovflow/likelihoods/mutlistage_likelihood.py underneath;
  * csrc/mf_lik.hip).  B, N, S, two_d, the rule, seg_offsets, y, pair_mean, pair_cov, the tile table, the workspace and the three

@@ -88,6 +88,8 @@ _SIGS = {
                                       "Tp", "Tp", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_sparse_expectations": (_int, [_i64, _i64, _i64, _int, _int, _hd, _int, _hd, _hd, _vp, "Tp", "Tp", "Tp", "Tp", "Tp", _i64,
                                    _vp, _vp, _vp, _sz, "Tp", "Tp", "Tp", _vp]),
+    "mf_lik_sparse_expectations_theta": (_int, [_i64, _i64, _i64, _int, _int, _hd, _int, _hd, _hd, "Tp", _i64, _vp, "Tp", "Tp", "Tp", "Tp",
+                                         "Tp", _i64, _vp, _vp, _vp, _sz, "Tp", "Tp", "Tp", "Tp", _vp]),
     "mf_lik_sparse_multi_expectations": (_int, [_i64, _i64, _i64, _int, _int, _int, _hd, _int, _hd, _hd, _vp, "Tp", "Tp", "Tp", "Tp", "Tp",
                                          _i64, _vp, _vp, _vp, _sz, "Tp", "Tp", "Tp", _vp]),
     "mf_lik_sparse_factor_expectations": (_int, [_i64, _i64, _i64, _int, _int, _i64, _int, _hd, _int, _hd, _hd, _vp, "Tp", "Tp", "Tp", "Tp",
@@ -145,6 +147,7 @@ _PLAIN = {
     "mf_sde_leg_transitions_grad_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
     "mf_mean_response_grad_workspace_bytes": (_sz, [_i64, _i64, _int, _int, _int]),
     "mf_lik_sparse_expectations_workspace_bytes": (_sz, [_i64, _int, _int]),
+    "mf_lik_sparse_expectations_theta_workspace_bytes": (_sz, [_i64, _int, _int]),
     "mf_lik_sparse_multi_expectations_workspace_bytes": (_sz, [_i64, _int, _int]),
     "mf_lik_sparse_factor_expectations_workspace_bytes": (_sz, [_i64, _int, _int]),
     "mf_lik_sparse_mvn_expectations_workspace_bytes": (_sz, [_i64, _int, _int, _int]),

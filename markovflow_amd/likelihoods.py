@@ -41,9 +41,15 @@ for the observations.  It is a decision tree over the three latents - ``y = 0`` 
 probability ``sigma(F1)``, else ``y - 2 ~ Poisson(exp(F2))`` - so its expectation is a sum of the Bernoulli and Poisson expectations
 above over the latents the point's branch reads; on HIP tensors it is ONE launch of ``mf_lik_multistage_variational_expectations_*``.
 
-The parameters (``variance``, ``scale``, ``df``) are plain Python floats and are NOT trainable.  The one trainable likelihood
-parameter is the Cholesky factor of ``MultivariateGaussian`` (``p(y_k | f_k) = N(y_k; f_k, L L^T)``, ``P`` outputs per point with
-correlated noise; tensors ``batch + [N, P]``, covariances ``batch + [N, P, P]``), a torch leaf.
+``Gaussian(variance=...)`` and ``StudentT(scale=...)`` take a plain Python float - a constant - or a ``torch.Tensor`` of shape ``()``
+or of the model's batch shape (one value per series), which makes the parameter TRAINABLE as in gpflow: the likelihood then owns an
+unconstrained leaf (``trainable_variables``) with ``value = lower + softplus(leaf)``, its torch methods are differentiable in it by
+plain autograd on either device, and ``SparseVariationalGaussianProcess`` trains it on the fused path
+(``mf_lik_sparse_expectations_theta_*``: the parameter is read from device memory, its adjoint comes out of the same launch).  The
+element-wise ``mf_lik_*`` entry points take the parameters as host doubles: a tensor-parameter likelihood takes torch there, and the
+power-EP methods raise.  ``df`` stays a float.  The other trainable likelihood parameter is the Cholesky factor of
+``MultivariateGaussian`` (``p(y_k | f_k) = N(y_k; f_k, L L^T)``, ``P`` outputs per point with correlated noise; tensors
+``batch + [N, P]``, covariances ``batch + [N, P, P]``), a torch leaf.
 """
 import ctypes
 import math
@@ -64,9 +70,11 @@ def _inv_probit(f: torch.Tensor) -> torch.Tensor:
 
 class Likelihood:
     """Base class: the id and parameters the kernels take, the Gauss-Hermite rule, and the four methods.  Parameters are plain
-    floats, not trainable."""
+    floats; ``Gaussian`` and ``StudentT`` may own ONE trainable parameter instead (``_init_theta``)."""
 
     _id = -1
+    _theta_leaf = None      # the unconstrained leaf of a tensor parameter (Gaussian's variance, StudentT's scale); None: plain floats
+    _theta_lower = 0.0
     latent_dim = 1          # latent functions per observation: models ask before they project (MultiStageLikelihood has 3)
 
     def __init__(self, num_gauss_hermite_points: int = 20) -> None:
@@ -106,6 +114,49 @@ class Likelihood:
         """Mean and variance of ``y`` under ``f ~ N(fmu, fvar)`` (closed forms), shapes of ``fmu``."""
         raise NotImplementedError
 
+    # ---- a trainable parameter ---------------------------------------------------------------------------------------------------
+    def _init_theta(self, value, lower: float, name: str, df=None) -> Optional[float]:
+        """``value`` as a positive float, returned - or, a ``torch.Tensor`` of shape ``()`` or of the model's batch shape, as the
+        start of a trainable parameter ``lower + softplus(leaf)``: the leaf lives on that tensor's dtype and device (returns None)."""
+        who = type(self).__name__
+        if not isinstance(value, torch.Tensor):
+            if not float(value) > 0.0:
+                raise ValueError(f"{who}: {name} must be positive, got {value}" if df is None else
+                                 f"{who}: {name} and df must be positive, got {name}={value}, df={df}")
+            return float(value)
+        if value.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"markovflow_amd supports float32 and float64 tensors, got {value.dtype}")
+        x = value.detach() - lower
+        if not bool((x > 0).all()) or not bool(torch.isfinite(x).all()):
+            raise ValueError(f"{who}: {name} must be finite and above {lower}, got {value}")
+        self._theta_lower = lower
+        # softplus^-1 (torch's softplus is the identity above its threshold of 20)
+        self._theta_leaf = torch.where(x > 20.0, x, x + torch.log(-torch.expm1(-x))).clone().requires_grad_(True)
+        return None
+
+    def _theta(self) -> torch.Tensor:
+        """The tensor parameter under the tape: ``lower + softplus(leaf)``."""
+        return self._theta_lower + torch.nn.functional.softplus(self._theta_leaf)
+
+    def _theta_like(self, value, ref: torch.Tensor):
+        """A parameter as the element-wise formulas take it: a float as it is, a tensor (``()`` or the batch shape) with trailing
+        axes of one up to the rank of ``ref`` (``batch + [N, 1]``, or that with the rule's nodes behind)."""
+        return value.reshape(tuple(value.shape) + (1,) * (ref.dim() - value.dim())) if isinstance(value, torch.Tensor) else value
+
+    @property
+    def trainable_variables(self) -> Tuple[torch.Tensor, ...]:
+        """The unconstrained leaf of a tensor parameter; empty for plain floats."""
+        return () if self._theta_leaf is None else (self._theta_leaf,)
+
+    def _float_parameters(self, what: str) -> None:
+        if self._theta_leaf is not None:
+            raise NotImplementedError(f"{type(self).__name__}.{what} takes the likelihood's parameters as host numbers: construct the "
+                                      "likelihood with a float (a tensor parameter is trained by SparseVariationalGaussianProcess)")
+
+    def _on_torch(self, fmu: torch.Tensor) -> bool:
+        """CPU tensors, or a tensor parameter (the element-wise entry points take host doubles): the torch statement."""
+        return not fmu.is_cuda or self._theta_leaf is not None
+
     # ---- shared ----------------------------------------------------------------------------------------------------------------
     def _c_params(self):
         p = self._params()
@@ -113,7 +164,16 @@ class Likelihood:
 
     def _kernel_args(self):
         """What every ``mf_lik_*`` entry point takes behind its sizes: the id, the parameters and the Gauss-Hermite rule."""
+        self._float_parameters("_kernel_args")
         return self._id, self._c_params(), self.num_gauss_hermite_points, self._c_nodes, self._c_weights
+
+    def _theta_kernel_args(self):
+        """The same run of arguments for ``mf_lik_sparse_expectations_theta_*``, whose ``params`` hold what does NOT train."""
+        p = self._theta_params()
+        return self._id, (ctypes.c_double * len(p))(*p) if p else None, self.num_gauss_hermite_points, self._c_nodes, self._c_weights
+
+    def _theta_params(self) -> Tuple[float, ...]:
+        return ()
 
     def _check(self, what: str, fmu: torch.Tensor, **others: torch.Tensor):
         if fmu.dim() < 2 or fmu.shape[-1] != 1:
@@ -132,15 +192,18 @@ class Likelihood:
 
     def variational_expectations(self, fmu: torch.Tensor, fvar: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """``E_{N(f | fmu, fvar)} log p(y | f)``, ``batch + [N]``.  Differentiable ONCE in ``fmu`` and ``fvar``: the backward
-        multiplies the derivatives the forward computed alongside the value (no second-order support)."""
+        multiplies the derivatives the forward computed alongside the value (no second-order support).  With a tensor parameter:
+        the torch statement on either device, differentiable by plain autograd in the parameter too."""
         self._check("variational_expectations", fmu, fvar=fvar, y=y)
+        if self._theta_leaf is not None:
+            return torch_variational_expectations(self, fmu, fvar, y)[0][..., 0]
         return _VariationalExpectations.apply(fmu, fvar, y, self)[..., 0]
 
     def predict_log_density(self, fmu: torch.Tensor, fvar: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """``log int p(y | f) N(f | fmu, fvar) df``, ``batch + [N]`` (not differentiable)."""
         self._check("predict_log_density", fmu, fvar=fvar, y=y)
         with torch.no_grad():
-            if not fmu.is_cuda:
+            if self._on_torch(fmu):
                 return torch_predict_log_density(self, fmu, fvar, y)[..., 0]
             mu, var, obs = fmu.contiguous(), fvar.contiguous(), y.contiguous()
             out = torch.empty_like(mu)
@@ -150,7 +213,7 @@ class Likelihood:
 
     def _expectations(self, fmu, fvar, y):
         """``(VE, dVE/dmu, dVE/dvar)``, each of ``fmu``'s shape: the kernel on HIP tensors, torch on CPU tensors."""
-        if not fmu.is_cuda:
+        if self._on_torch(fmu):
             return torch_variational_expectations(self, fmu, fvar, y)
         mu, var, obs = fmu.contiguous(), fvar.contiguous(), y.contiguous()
         ve, g_mu, g_var = torch.empty_like(mu), torch.empty_like(mu), torch.empty_like(mu)
@@ -172,7 +235,7 @@ class Likelihood:
             raise ValueError(f"cvi_site_update: learning_rate must lie in [0, 1], got {learning_rate}")
         lr = float(learning_rate)
         with torch.no_grad():
-            if not fmu.is_cuda:
+            if self._on_torch(fmu):
                 _, g_mu, g_var = torch_variational_expectations(self, fmu, fvar, y)
                 nat1.mul_(1.0 - lr).add_(lr * (g_mu - 2.0 * g_var * fmu).reshape(nat1.shape))
                 nat2.mul_(1.0 - lr).add_(lr * g_var.reshape(nat2.shape))
@@ -194,6 +257,7 @@ class Likelihood:
     def _log_expected_density(self, fmu, fvar, y, alpha: float, want=(True, True, True)):
         """``(I, g1, g2)``, each of ``fmu``'s shape or None where not wanted: ONE launch of ``mf_lik_log_expected_density_*`` on HIP
         tensors, ``torch_log_expected_density`` on CPU tensors."""
+        self._float_parameters("log_expected_density")
         if not fmu.is_cuda:
             return tuple(o if w else None for o, w in zip(torch_log_expected_density(self, fmu, fvar, y, alpha), want))
         mu, var, obs = fmu.contiguous(), fvar.contiguous(), y.contiguous()
@@ -232,6 +296,7 @@ class Likelihood:
         HIP tensors: one launch of ``mf_lik_pep_site_update_*``.  Returns None on either device: the cavity, which the kernel can
         write out and ``torch_pep_site_update`` returns, is ``PowerExpectationPropagation.compute_cavity``'s to report."""
         what = f"{type(self).__name__}.pep_site_update"
+        self._float_parameters("pep_site_update")
         self._check("pep_site_update", fmu, fvar=fvar, y=y)
         _lib.same_dtype_device(fmu, what, nat1=nat1, nat2=nat2, log_norm=log_norm)
         if any(t.numel() != fmu.numel() or not t.is_contiguous() for t in (nat1, nat2, log_norm)):
@@ -297,7 +362,7 @@ def torch_predict_log_density(lik: Likelihood, fmu: torch.Tensor, fvar: torch.Te
     ok = fvar > 0
     var = torch.where(ok, fvar, torch.ones_like(fvar))
     if isinstance(lik, Gaussian):
-        total = var + lik.variance
+        total = var + lik._theta_like(lik.variance, var)
         out = -0.5 * (math.log(2 * math.pi) + torch.log(total)) - 0.5 * (y - fmu) ** 2 / total
     else:
         x, _, logw = lik._rule(fmu)
@@ -364,34 +429,46 @@ def torch_pep_site_update(lik: Likelihood, fmu: torch.Tensor, fvar: torch.Tensor
     return torch.where(cavity, mc, nan), torch.where(cavity, vc, nan)
 
 
+def _log(x):
+    return torch.log(x) if isinstance(x, torch.Tensor) else math.log(x)
+
+
 class Gaussian(Likelihood):
-    """``p(y | f) = N(y | f, variance)``; ``variance`` is a plain float, not trainable."""
+    """``p(y | f) = N(y | f, variance)``.  ``variance``: a plain float, not trainable - or a tensor of shape ``()`` or of the
+    model's batch shape, which starts a trainable parameter: ``unconstrained_variance`` is the leaf and ``variance`` the constrained
+    tensor ``1e-6 + softplus(leaf)`` under the tape (gpflow's lower bound)."""
 
     _id = 0
 
-    def __init__(self, variance: float = 1.0, num_gauss_hermite_points: int = 20) -> None:
+    def __init__(self, variance=1.0, num_gauss_hermite_points: int = 20) -> None:
         super().__init__(num_gauss_hermite_points)
-        if not float(variance) > 0.0:
-            raise ValueError(f"Gaussian: variance must be positive, got {variance}")
-        self.variance = float(variance)
+        self._variance = self._init_theta(variance, 1e-6, "variance")
+
+    @property
+    def variance(self):
+        return self._variance if self._theta_leaf is None else self._theta()
+
+    @property
+    def unconstrained_variance(self) -> Optional[torch.Tensor]:
+        return self._theta_leaf
 
     def _params(self):
         return (self.variance,)
 
     def _log_prob_and_grad(self, f, y):
-        r = y - f
-        return -0.5 * (math.log(2 * math.pi) + math.log(self.variance)) - 0.5 * r * r / self.variance, r / self.variance
+        r, v = y - f, self._theta_like(self.variance, f)
+        return -0.5 * (math.log(2 * math.pi) + _log(v)) - 0.5 * r * r / v, r / v
 
     def _log_prob_second_derivative(self, f, y):
         return torch.full_like(f, -1.0 / self.variance)
 
     def _closed_expectations(self, mu, var, y):
-        r = y - mu
-        ve = -0.5 * (math.log(2 * math.pi) + math.log(self.variance)) - 0.5 * (r * r + var) / self.variance
-        return ve, r / self.variance, torch.full_like(mu, -0.5 / self.variance)
+        r, v = y - mu, self._theta_like(self.variance, mu)
+        ve = -0.5 * (math.log(2 * math.pi) + _log(v)) - 0.5 * (r * r + var) / v
+        return ve, r / v, (-0.5 / v).expand(mu.shape) if isinstance(v, torch.Tensor) else torch.full_like(mu, -0.5 / v)
 
     def predict_mean_and_var(self, fmu, fvar):
-        return fmu, fvar + self.variance
+        return fmu, fvar + self._theta_like(self.variance, fvar)
 
 
 class Bernoulli(Likelihood):
@@ -437,27 +514,45 @@ class Poisson(Likelihood):
 
 
 class StudentT(Likelihood):
-    """``p(y | f) = StudentT(y | df, loc = f, scale)``; ``scale`` and ``df`` are plain floats, not trainable.  Not log-concave: a CVI
-    step can drive a site precision negative, which the filter reports as a non-positive pivot."""
+    """``p(y | f) = StudentT(y | df, loc = f, scale)``.  ``df`` is a plain float, not trainable; ``scale`` is one too - or a tensor
+    of shape ``()`` or of the model's batch shape, which starts a trainable parameter: ``unconstrained_scale`` is the leaf and
+    ``scale`` the constrained tensor ``softplus(leaf)`` under the tape.  Not log-concave: a CVI step can drive a site precision
+    negative, which the filter reports as a non-positive pivot."""
 
     _id = 3
 
-    def __init__(self, scale: float = 1.0, df: float = 3.0, num_gauss_hermite_points: int = 20) -> None:
+    def __init__(self, scale=1.0, df: float = 3.0, num_gauss_hermite_points: int = 20) -> None:
         super().__init__(num_gauss_hermite_points)
-        if not float(scale) > 0.0 or not float(df) > 0.0:
+        if not float(df) > 0.0:
             raise ValueError(f"StudentT: scale and df must be positive, got scale={scale}, df={df}")
-        self.scale, self.df = float(scale), float(df)
-        # the part of log p(y | f) that does not depend on f, for the kernel
-        self._const = (math.lgamma(0.5 * (self.df + 1.0)) - math.lgamma(0.5 * self.df) - 0.5 * math.log(self.df * math.pi)
-                       - math.log(self.scale))
+        self.df = float(df)
+        self._scale = self._init_theta(scale, 0.0, "scale", df)
+        # the part of log p(y | f) that depends on neither f nor the scale, for the kernels
+        self._const0 = math.lgamma(0.5 * (self.df + 1.0)) - math.lgamma(0.5 * self.df) - 0.5 * math.log(self.df * math.pi)
+
+    @property
+    def scale(self):
+        return self._scale if self._theta_leaf is None else self._theta()
+
+    @property
+    def unconstrained_scale(self) -> Optional[torch.Tensor]:
+        return self._theta_leaf
+
+    @property
+    def _const(self):
+        """The part of ``log p(y | f)`` that does not depend on ``f``."""
+        return self._const0 - _log(self.scale)
 
     def _params(self):
         return (self.scale, self.df, self._const)
 
+    def _theta_params(self):
+        return (self.df, self._const0)
+
     def _log_prob_and_grad(self, f, y):
-        r = y - f
-        a = self.df * self.scale * self.scale
-        return self._const - 0.5 * (self.df + 1.0) * torch.log1p(r * r / a), (self.df + 1.0) * r / (a + r * r)
+        r, scale = y - f, self._theta_like(self.scale, f)
+        a = self.df * scale * scale
+        return self._const0 - _log(scale) - 0.5 * (self.df + 1.0) * torch.log1p(r * r / a), (self.df + 1.0) * r / (a + r * r)
 
     def _log_prob_second_derivative(self, f, y):
         r2 = (y - f) ** 2
@@ -467,7 +562,8 @@ class StudentT(Likelihood):
     def predict_mean_and_var(self, fmu, fvar):
         if not self.df > 2.0:
             raise ValueError("StudentT.predict_mean_and_var: the variance is finite only for df > 2")
-        return fmu, fvar + self.scale * self.scale * self.df / (self.df - 2.0)
+        scale = self._theta_like(self.scale, fvar)
+        return fmu, fvar + scale * scale * self.df / (self.df - 2.0)
 
 
 class MultiStageLikelihood(Likelihood):

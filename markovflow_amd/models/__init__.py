@@ -43,7 +43,7 @@ from .gpr import GaussianProcessRegression
 from .segmented_ops import (IW_SAMPLE_CHUNK, SPARSE_EXPECT_TILE, SPARSE_FACTOR_LATENTS, SPARSE_FACTOR_MAX_OUTPUTS, SPARSE_MVN_OUTPUTS,
                             SPARSE_SITE_MAX_TWO_D, _sparse_mvn_expectations_launch,
                             _iw_log_weights_launch, _segments_of, _sparse_expectations_launch, _sparse_factor_expectations_launch,
-                            _sparse_multi_expectations_launch, iw_log_likelihood, iw_log_likelihood_torch, iw_merged_time_points,
+                            _sparse_multi_expectations_launch, _sparse_theta_expectations_launch, iw_log_likelihood, iw_log_likelihood_torch, iw_merged_time_points,
                             pair_cavity, pair_cavity_hip, pair_cavity_torch, sparse_cvi_site_update_hip, sparse_cvi_site_update_torch, sparse_expectation_tiles,
                             sparse_expected_log_likelihood, sparse_expected_log_likelihood_torch,
                             sparse_factor_expected_log_likelihood, sparse_factor_expected_log_likelihood_torch,
@@ -52,7 +52,7 @@ from .segmented_ops import (IW_SAMPLE_CHUNK, SPARSE_EXPECT_TILE, SPARSE_FACTOR_L
                             sparse_full_site_projections, sparse_multi_site_projections, sparse_mvn_expected_log_likelihood,
                             sparse_mvn_expected_log_likelihood_torch, sparse_pep_site_update_hip, sparse_pep_site_update_torch,
                             sparse_site_projections, sparse_stack_expected_log_likelihood,
-                            sparse_stack_expected_log_likelihood_torch)
+                            sparse_stack_expected_log_likelihood_torch, sparse_theta_expected_log_likelihood)
 from .sites import CVIGaussianProcess, PowerExpectationPropagation
 from .sparse import (ImportanceWeightedVI, SparseCVIGaussianProcess, SparsePowerExpectationPropagation,
                      SparseVariationalGaussianProcess, _SparseSitesGaussianProcess)

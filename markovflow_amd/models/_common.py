@@ -21,10 +21,15 @@ def _refuse_non_stationary(kernel, who: str) -> None:
                                   "supported by GaussianProcessRegression alone")
 
 
-def _require_likelihood(likelihood, multi_latent: bool = False) -> None:
-    """``multi_latent``: the caller projects one marginal per latent function; every other model and fused op is written for ONE."""
+def _require_likelihood(likelihood, multi_latent: bool = False, tensor_parameter: bool = False) -> None:
+    """``multi_latent``: the caller projects one marginal per latent function; every other model and fused op is written for ONE.
+    ``tensor_parameter``: the caller reads a trainable parameter of the likelihood (``Gaussian(variance=tensor)``,
+    ``StudentT(scale=tensor)``) from device memory; every other model and fused op takes the parameters as host numbers."""
     if not isinstance(likelihood, Likelihood):
         raise TypeError("likelihood must be a markovflow_amd.likelihoods.Likelihood")
+    if likelihood._theta_leaf is not None and not tensor_parameter:
+        raise NotImplementedError(f"{type(likelihood).__name__} carries a tensor (trainable) parameter: only the single-output route of "
+                                  "SparseVariationalGaussianProcess supports it; construct the likelihood with a float")
     if (likelihood.latent_dim > 1 or getattr(likelihood, "_full_covariance", False)) and not multi_latent:
         raise NotImplementedError(f"{type(likelihood).__name__} has {likelihood.latent_dim} latent functions per observation: only "
                                   "SparseVariationalGaussianProcess supports a likelihood with latent_dim > 1")

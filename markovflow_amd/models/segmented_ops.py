@@ -12,6 +12,8 @@ forward launch wrote:
   * ``sparse_pep_site_update_{torch,hip}``: ``mf_lik_sparse_pep_site_update_*`` (tile-parallel kernel pair), and the cavity it
     takes, ``pair_cavity_{torch,hip}``: ``mf_pair_cavity_*`` (a group of lanes per pair, one launch);
   * ``sparse_expected_log_likelihood(_torch)``: ``mf_lik_sparse_expectations_*`` (two passes, tile-parallel), the SVGP data term;
+  * ``sparse_theta_expected_log_likelihood``: ``mf_lik_sparse_expectations_theta_*``, the same term with the likelihood's parameter
+    (``Gaussian``'s variance, ``StudentT``'s scale) read from device memory, per series, and the adjoint onto it;
   * ``sparse_multi_expected_log_likelihood(_torch)``: ``mf_lik_sparse_multi_expectations_*``, the same term for a likelihood with
     several latent functions per observation (``sparse_multi_site_projections``: one dense projection per latent);
   * ``sparse_stack_expected_log_likelihood(_torch)``: ``mf_lik_stack_expectations_*``, the same term on ``K`` STACKED chains
@@ -395,9 +397,87 @@ def sparse_expected_log_likelihood(likelihood: Likelihood, w: torch.Tensor, c: t
                                         likelihood, w, c, y, offsets, tiles)
 
 
+def _sparse_theta_expectations_launch(likelihood: Likelihood, theta, w, c, y, offsets, tiles, pair_mean, pair_cov, want_pair: bool,
+                                      want_theta: bool):
+    """ONE call of ``mf_lik_sparse_expectations_theta_*``: ``(ve_sum [.., S], g_mean [.., S, 2d] | None, g_cov [.., S, 2d, 2d] | None,
+    g_theta [.., S] | None)``.  ``theta``: ``()`` - stride 0, one value for all series - or the batch shape - stride 1."""
+    base = "mf_lik_sparse_expectations_theta"
+    dtype, dev = w.dtype, w.device
+    two_d, segs = w.shape[-1], offsets.shape[-1] - 1
+    num_tiles, tile_seg, seg_tile = tiles
+    new = _new_outputs(tuple(offsets.shape[:-1]), dtype, dev)
+    outs = (new(True, segs), new(want_pair, segs, two_d), new(want_pair, segs, two_d, two_d), new(want_theta, segs))
+    ws, ws_bytes = _workspace(getattr(_lib.load(), base + "_workspace_bytes"), dev, num_tiles, two_d, w.element_size())
+    _launch(base, dtype, dev, offsets.numel() // (segs + 1), w.shape[-2], segs, two_d, *likelihood._theta_kernel_args(), theta,
+            0 if theta.dim() == 0 else 1, offsets, w, c, y, pair_mean, pair_cov, num_tiles, tile_seg, seg_tile, ws, ws_bytes, *outs)
+    return outs
+
+
+class _ThetaExpectedLogLikelihood(torch.autograd.Function):
+    """The SVGP data term with the likelihood's parameter as a third differentiable input: value ``batch + [M + 1]``; the adjoints
+    onto the pair marginals AND onto the parameter come out of the same launch and wait for the backward."""
+
+    @staticmethod
+    def forward(ctx, pair_mean, pair_cov, theta, likelihood, w, c, y, offsets, tiles):
+        want_pair, want_theta = ctx.needs_input_grad[0] or ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        with torch.no_grad():
+            ve_sum, g_mean, g_cov, g_theta = _sparse_theta_expectations_launch(
+                likelihood, theta.detach(), w.detach(), c.detach(), y.detach(), offsets, tiles, pair_mean.detach(), pair_cov.detach(),
+                want_pair, want_theta)
+        ctx.save_for_backward(g_mean, g_cov, g_theta)
+        ctx.shared = theta.dim() == 0
+        return ve_sum
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        _differentiable_once("sparse_theta_expected_log_likelihood", "adjoints")
+        g_mean, g_cov, g_theta = ctx.saved_tensors
+        g_th = None
+        if ctx.needs_input_grad[2]:            # over the segments, and over the batch when every series shares the value
+            g_th = torch.sum(grad_out * g_theta) if ctx.shared else torch.sum(grad_out * g_theta, dim=-1)
+        return (grad_out[..., None] * g_mean if ctx.needs_input_grad[0] else None,
+                grad_out[..., None, None] * g_cov if ctx.needs_input_grad[1] else None, g_th) + (None,) * 6
+
+
+def sparse_theta_expected_log_likelihood(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor,
+                                         offsets: torch.Tensor, pair_mean: torch.Tensor, pair_cov: torch.Tensor,
+                                         theta: Optional[torch.Tensor] = None, tiles=None) -> torch.Tensor:
+    """``sparse_expected_log_likelihood`` for a likelihood whose parameter is a TENSOR (``Gaussian``: the variance, ``StudentT``: the
+    scale): ``theta``, of shape ``()`` or ``batch`` (one value per series), is read from device memory - no host read - by ONE call of
+    ``mf_lik_sparse_expectations_theta_*``, which leaves the adjoint onto it behind beside the pair adjoints.  Differentiable ONCE in
+    ``pair_mean``, ``pair_cov`` and ``theta``; there is no second launch.  ``theta`` defaults to the likelihood's own constrained
+    parameter under the tape (``likelihood.variance`` / ``likelihood.scale``), so that autograd chains through its softplus.  A
+    ``theta`` that is not positive and finite makes the values and adjoints of its series NaN; nothing checks it on the host."""
+    what = "sparse_theta_expected_log_likelihood"
+    _require_likelihood(likelihood, tensor_parameter=True)
+    if likelihood._id not in (0, 3):
+        raise NotImplementedError(f"{what}: {type(likelihood).__name__} has no trainable parameter; use sparse_expected_log_likelihood")
+    if theta is None:
+        if likelihood._theta_leaf is None:
+            raise ValueError(f"{what}: theta is required for a likelihood constructed with a float parameter")
+        theta = likelihood._theta()
+    two_d, segs = w.shape[-1], offsets.shape[-1] - 1
+    batch = tuple(offsets.shape[:-1])
+    if two_d > SPARSE_SITE_MAX_TWO_D or two_d % 2:
+        raise NotImplementedError(f"{what}: 2d = {two_d} is outside 2, 4, ..., {SPARSE_SITE_MAX_TWO_D}; use "
+                                  "sparse_expected_log_likelihood_torch")
+    _check_shapes(what, dict(w=(w, batch + (w.shape[-2], two_d)), c=(c, batch + (w.shape[-2],)), y=(y, batch + (w.shape[-2],)),
+                             pair_mean=(pair_mean, batch + (segs, two_d)), pair_cov=(pair_cov, batch + (segs, two_d, two_d))))
+    if tuple(theta.shape) not in ((), batch):
+        raise ValueError(f"{what}: theta has shape {tuple(theta.shape)}, expected () or {batch}")
+    _lib.same_dtype_device(w, what, c=c, y=y, pair_mean=pair_mean, pair_cov=pair_cov, theta=theta)
+    if torch.is_grad_enabled() and (w.requires_grad or c.requires_grad):
+        raise NotImplementedError(f"{what} has no adjoint onto w and c (a kernel hyper-parameter under the tape): use "
+                                  "sparse_expected_log_likelihood_torch")
+    if tiles is None:
+        tiles = sparse_expectation_tiles(offsets)
+    return _ThetaExpectedLogLikelihood.apply(pair_mean, pair_cov, theta, likelihood, w, c, y, offsets, tiles)
+
+
 def sparse_expected_log_likelihood_torch(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor,
                                          indices: torch.Tensor, pair_mean: torch.Tensor, pair_cov: torch.Tensor) -> torch.Tensor:
-    """The same quantity as a torch composition, differentiable by autograd in ``pair_mean``, ``pair_cov``, ``w`` and ``c``: gathers
+    """The same quantity as a torch composition, differentiable by autograd in ``pair_mean``, ``pair_cov``, ``w`` and ``c`` - and in a
+    tensor parameter of the likelihood, whose ``variational_expectations`` is then plain torch on either device: gathers
     of the pair marginals by the per-point pair index (``indices [.., N]``), ``likelihood.variational_expectations`` and
     ``index_add_`` over the segments.  It runs on CPU tensors, it is the models' route for ``2d > 18`` and for a kernel
     hyper-parameter under the tape, and it is what ``mf_lik_sparse_expectations_*`` is measured against."""

@@ -41,7 +41,8 @@ from .segmented_ops import (SPARSE_FACTOR_LATENTS, SPARSE_FACTOR_MAX_OUTPUTS, SP
                             sparse_multi_site_projections, sparse_mvn_expected_log_likelihood,
                             sparse_mvn_expected_log_likelihood_torch, sparse_pep_site_update_hip, sparse_pep_site_update_torch,
                             sparse_site_projections, sparse_stack_expected_log_likelihood,
-                            sparse_stack_expected_log_likelihood_torch, sparse_stack_instantiated)
+                            sparse_stack_expected_log_likelihood_torch, sparse_stack_instantiated,
+                            sparse_theta_expected_log_likelihood)
 
 
 class _SparseGaussianProcess(_PredictLogDensity):
@@ -50,6 +51,7 @@ class _SparseGaussianProcess(_PredictLogDensity):
 
     _multi_latent = False      # True in the one model that projects a marginal per latent function of the likelihood
     _multi_output = False      # True in the one model that takes one observed series per output of the kernel
+    _tensor_parameter = False  # True in the one model that trains a tensor parameter of the likelihood
 
     def __init__(self, kernel: SDEKernel, likelihood: Likelihood, inducing_points: torch.Tensor, min_inducing: int) -> None:
         if not isinstance(kernel, SDEKernel):
@@ -61,7 +63,7 @@ class _SparseGaussianProcess(_PredictLogDensity):
         elif isinstance(kernel, StackKernel) and not isinstance(kernel, IndependentMultiOutputStack):
             raise NotImplementedError(f"{type(self).__name__} takes a StackKernel with its multi-output emission only: use "
                                       "IndependentMultiOutputStack")
-        _require_likelihood(likelihood, multi_latent=self._multi_latent)
+        _require_likelihood(likelihood, multi_latent=self._multi_latent, tensor_parameter=self._tensor_parameter)
         if (likelihood.latent_dim > 1 or isinstance(likelihood, MultivariateGaussian)) and likelihood.latent_dim != kernel.output_dim:
             raise ValueError(f"the likelihood has latent_dim = {likelihood.latent_dim}, the kernel has output_dim = "
                              f"{kernel.output_dim}: a multi-latent likelihood needs one output of the kernel per latent function")
@@ -477,9 +479,17 @@ def _sorted_series(time_points: torch.Tensor) -> Tuple[Optional[torch.Tensor], t
 
 class SparseVariationalGaussianProcess(_SparseGaussianProcess):
     """GP prior, general likelihood, a free-form Gaussian posterior ``q(s(z))`` on the states at ``M`` inducing points held as a
-    trainable ``StateSpaceModel`` (markovflow/models/sparse_variational.py:31-270; zero mean function, plain float likelihood
-    parameters, a batch of series as leading dimensions).  The ELBO is ``scale sum_i E_q log p(y_i | f_i) - KL[q(s(z)) || p(s(z))]``;
+    trainable ``StateSpaceModel`` (markovflow/models/sparse_variational.py:31-270; zero mean function, a batch of series as leading
+    dimensions).  The ELBO is ``scale sum_i E_q log p(y_i | f_i) - KL[q(s(z)) || p(s(z))]``;
     ``q`` is trained with any torch optimiser on ``trainable_variables`` or with ``ssm_natgrad.SSMNaturalGradient`` on ``dist_q``.
+
+    ``Gaussian(variance=tensor)`` and ``StudentT(scale=tensor)`` - shape ``()`` or the batch shape, one value per series - train their
+    parameter with the model on single-output observations: the data term is then ONE call of ``mf_lik_sparse_expectations_theta_*``,
+    which reads the parameter from device memory (no host read per step) and leaves its adjoint behind beside the pair adjoints, under
+    the conditions of the float form (HIP tensors, ``2d <= 18``, no hyper-parameter of the kernel or the emission under the tape;
+    otherwise ``sparse_expected_log_likelihood_torch``, differentiable in the parameter by autograd).  ``SSMNaturalGradient`` on
+    ``dist_q`` alternates with a torch optimiser on ``likelihood.trainable_variables``; neither step invalidates the cached projections.
+    The stack and multi-output routes, and every other model, refuse a tensor parameter at construction.
 
     A likelihood with ``L = latent_dim > 1`` latent functions (``MultiStageLikelihood``) takes a kernel with ``output_dim = L``
     (``IndependentMultiOutput``): the observations stay ``batch + [N, 1]``, every point is projected once per latent
@@ -517,6 +527,7 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
 
     _multi_latent = True
     _multi_output = True
+    _tensor_parameter = True
 
     def __init__(self, kernel: SDEKernel, likelihood: Likelihood, inducing_points: torch.Tensor, num_data: Optional[int] = None,
                  initial_distribution: Optional[StateSpaceModel] = None) -> None:
@@ -527,6 +538,17 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
         """
         super().__init__(kernel, likelihood, inducing_points, min_inducing=2)
         self._route = "multi" if likelihood.latent_dim > 1 else "single"    # (``_data_route`` of the data last seen)
+        theta = likelihood._theta_leaf
+        if theta is not None:
+            if isinstance(kernel, StackKernel) or kernel.output_dim != 1:
+                raise NotImplementedError(f"{type(likelihood).__name__} carries a tensor (trainable) parameter: the stack and the "
+                                          "multi-output routes take the likelihood's parameters as host numbers; construct the "
+                                          "likelihood with a float")
+            if (theta.dtype != inducing_points.dtype or theta.device != inducing_points.device
+                    or tuple(theta.shape) not in ((), tuple(inducing_points.shape[:-1]))):
+                raise ValueError(f"the likelihood's tensor parameter must have the dtype and device of the inducing points and shape "
+                                 f"() or {tuple(inducing_points.shape[:-1])}, got {theta.dtype} on {theta.device}, "
+                                 f"{tuple(theta.shape)}")
         if isinstance(likelihood, MultivariateGaussian):
             if isinstance(kernel, StackKernel):
                 raise NotImplementedError("a MultivariateGaussian likelihood couples the outputs at every point through their joint "
@@ -750,6 +772,8 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
             if order is not None:
                 y = torch.gather(y, -1, order)
             fused = sparse_multi_expected_log_likelihood if multi else sparse_expected_log_likelihood
+            if self._likelihood._theta_leaf is not None:       # the parameter from device memory, its adjoint from the same launch
+                fused = sparse_theta_expected_log_likelihood
             return fused(self._likelihood, w, c, y, offsets, pair_mean, pair_cov, tiles=tiles)
         if self._kernel._needs_grad() or self._emission_needs_grad():
             # a hyper-parameter under the tape: w and c are part of the graph
@@ -820,7 +844,8 @@ class ImportanceWeightedVI(SparseVariationalGaussianProcess):
     the draw from ``q`` are ONE call of ``mf_lik_iw_log_weights_*``."""
 
     _multi_latent = False      # (the importance weights are written for one latent function ...
-    _multi_output = False      # ... and one observed series)
+    _multi_output = False      # ... and one observed series ...
+    _tensor_parameter = False  # ... and take the likelihood's parameters as host numbers)
 
     def __init__(self, kernel: SDEKernel, inducing_points: torch.Tensor, likelihood: Likelihood, num_importance_samples: int,
                  initial_distribution: Optional[StateSpaceModel] = None) -> None:
