@@ -28,10 +28,14 @@ forward launch wrote:
   * ``iw_log_likelihood(_torch)``: ``mf_lik_iw_log_weights_*`` (two passes, tile-parallel, no atomics), the data term of the
     importance weights with Matheron's correction assembled in the kernel.
 
-The four tile-parallel SVGP terms share their plumbing: ``_expectations_launch`` is the body of the four
-``_sparse_*_expectations_launch`` (outputs, workspace, ONE call), ``_ExpectedLogLikelihood`` the autograd function of the single,
-multi and stack terms (the factor term's sibling adds the ``mix`` adjoint), and the compositions are built from ``_gather_pairs``,
-``_flat_segments`` and ``_segment_sum``.
+The six tile-parallel SVGP terms share their plumbing.  ``_expectations_launch`` is the body of the six
+``_sparse_*_expectations_launch`` (outputs, workspace, ONE call; a launcher only names its entry point, its dimensions and its inputs).
+``_ExpectedLogLikelihood`` is the autograd function of all six: the pair marginals and an optional third differentiable input, whose
+cotangent the term supplies as a function of the extra output the launch wrote (``_theta_cotangent``, ``_mix_cotangent``,
+``_prec_cotangent``).  ``_expected_log_likelihood`` is the tail of the six public functions - ``w`` and ``c`` under the tape are
+refused, the tile table defaults - behind each one's own shape and range checks.  The compositions are built from ``_gather_pairs``,
+``_flat_segments`` and ``_segment_sum``.  The projection functions (``sparse_*_site_projections``) are plain torch on top of
+``conditional_statistics`` and differentiable when a hyper-parameter is under the tape; a model calls them under ``no_grad`` to cache.
 """
 from typing import Optional, Tuple
 
@@ -315,10 +319,11 @@ def pair_cavity_torch(pair_mean: torch.Tensor, pair_cov: torch.Tensor, nat1: tor
             (g_cav - g_marg).masked_fill(bad, nan))
 
 
-def _expectations_launch(base: str, likelihood: Likelihood, dims, inputs, offsets, tiles, pair_mean, pair_cov, want_grads: bool,
+def _expectations_launch(base: str, lik_args, dims, inputs, offsets, tiles, pair_mean, pair_cov, want_grads: bool,
                          chains=(), ws_dims=(), extra=None):
-    """ONE call of the tile-parallel SVGP entry point ``base``, the body of the four launchers below.  ``dims``: its dimension
-    arguments after the batch size; ``inputs``: its per-point tensors, the projection ``[.., 2d]`` first; ``chains``: the axes of the
+    """ONE call of the tile-parallel SVGP entry point ``base``, the body of the six launchers below.  ``lik_args``: the likelihood's
+    run of kernel arguments (``_kernel_args()``; the theta entry point's ends in the parameter and its stride); ``dims``: the dimension
+    arguments after the batch size; ``inputs``: the per-point tensors, the projection ``[.., 2d]`` first; ``chains``: the axes of the
     adjoints between the series and the segments (the stack's ``K``); ``ws_dims``: what ``base_workspace_bytes`` takes between ``2d``
     and the element size; ``extra``: ``(want, *shape)`` of a per-series output after ``g_cov``.  Returns ``(ve_sum [.., S],
     g_mean [.., chains, S, 2d] | None, g_cov [.., chains, S, 2d, 2d] | None)`` and the extra output, if any."""
@@ -332,41 +337,56 @@ def _expectations_launch(base: str, likelihood: Likelihood, dims, inputs, offset
     if extra is not None:
         outs += (new(*extra),)
     ws, ws_bytes = _workspace(getattr(_lib.load(), base + "_workspace_bytes"), dev, num_tiles, two_d, *ws_dims, first.element_size())
-    _launch(base, dtype, dev, offsets.numel() // (segs + 1), *dims, *likelihood._kernel_args(), offsets, *inputs, pair_mean, pair_cov,
-            num_tiles, tile_seg, seg_tile, ws, ws_bytes, *outs)
+    _launch(base, dtype, dev, offsets.numel() // (segs + 1), *dims, *lik_args, offsets, *inputs, pair_mean, pair_cov, num_tiles, tile_seg,
+            seg_tile, ws, ws_bytes, *outs)
     return outs
 
 
 def _sparse_expectations_launch(likelihood: Likelihood, w, c, y, offsets, tiles, pair_mean, pair_cov, want_grads: bool):
     """ONE call of ``mf_lik_sparse_expectations_*``: ``(ve_sum [.., S], g_mean [.., S, 2d] | None, g_cov [.., S, 2d, 2d] | None)``."""
-    return _expectations_launch("mf_lik_sparse_expectations", likelihood, (w.shape[-2], offsets.shape[-1] - 1, w.shape[-1]), (w, c, y),
-                                offsets, tiles, pair_mean, pair_cov, want_grads)
+    return _expectations_launch("mf_lik_sparse_expectations", likelihood._kernel_args(),
+                                (w.shape[-2], offsets.shape[-1] - 1, w.shape[-1]), (w, c, y), offsets, tiles, pair_mean, pair_cov, want_grads)
 
 
 class _ExpectedLogLikelihood(torch.autograd.Function):
-    """The single-latent, multi-latent and stacked SVGP data terms: value ``batch + [M + 1]``; the adjoints onto the pair marginals
-    come out of the same launch and wait for the backward.  ``launcher``: one of the ``_sparse_*_expectations_launch``; ``name``: the
-    public function, for the messages; ``chains``: the number of axes of the pair marginals between the series and the segments
-    (the stack's ``K``: 1), over which a segment's cotangent is broadcast."""
+    """Every tile-parallel SVGP data term: value ``batch + [M + 1]``; the adjoints onto the pair marginals and - when there is one and
+    it requires a gradient - onto a ``third`` differentiable input (``theta``, ``mix``, ``prec``) come out of the same launch and wait
+    for the backward.  ``launcher``: one of the ``_sparse_*_expectations_launch``, called with ``args`` (what it takes before the pair
+    marginals, ``offsets`` and ``tiles`` last, ``third`` at its place among them), the pair marginals, whether their adjoints are
+    wanted and, with a ``third``, whether its output is; ``cotangent``: ``(grad_out, that output, third, offsets)`` to the cotangent
+    of ``third``; ``name``: the public function, for the messages; ``chains``: the number of axes of the pair marginals between the
+    series and the segments (the stack's ``K``: 1), over which a segment's cotangent is broadcast."""
 
     @staticmethod
-    def forward(ctx, pair_mean, pair_cov, launcher, name, chains, likelihood, w, c, y, offsets, tiles):
-        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+    def forward(ctx, pair_mean, pair_cov, third, launcher, cotangent, name, chains, *args):
+        wants = (ctx.needs_input_grad[0] or ctx.needs_input_grad[1],) + (() if third is None else (ctx.needs_input_grad[2],))
         with torch.no_grad():
-            ve_sum, g_mean, g_cov = launcher(likelihood, w.detach(), c.detach(), y.detach(), offsets, tiles, pair_mean.detach(),
-                                             pair_cov.detach(), want)
-        if want:
-            ctx.save_for_backward(g_mean, g_cov)
-        ctx.name, ctx.chains = name, chains
+            ve_sum, g_mean, g_cov, *g_third = launcher(*(a.detach() if isinstance(a, torch.Tensor) else a for a in args),
+                                                       pair_mean.detach(), pair_cov.detach(), *wants)
+        ctx.save_for_backward(g_mean, g_cov, *g_third, third, args[-2])
+        ctx.cotangent, ctx.name, ctx.chains, ctx.num_args = cotangent, name, chains, len(args)
         return ve_sum
 
     @staticmethod
     def backward(ctx, grad_out):
         _differentiable_once(ctx.name, "adjoints")
-        g_mean, g_cov = ctx.saved_tensors
+        g_mean, g_cov, *g_third, third, offsets = ctx.saved_tensors
         g = grad_out[(Ellipsis,) + (None,) * ctx.chains + (slice(None),)]       # a segment's cotangent goes to every chain of it
         return (g[..., None] * g_mean if ctx.needs_input_grad[0] else None,
-                g[..., None, None] * g_cov if ctx.needs_input_grad[1] else None) + (None,) * 9
+                g[..., None, None] * g_cov if ctx.needs_input_grad[1] else None,
+                ctx.cotangent(grad_out, *g_third, third, offsets) if ctx.needs_input_grad[2] else None) + (None,) * (4 + ctx.num_args)
+
+
+def _expected_log_likelihood(what: str, launcher, args, w, c, pair_mean, pair_cov, third=None, cotangent=None, chains: int = 0,
+                             names: str = "w and c", cause: str = "a kernel hyper-parameter", composed: Optional[str] = None):
+    """The common tail of the public SVGP terms: the projections ``w``, ``c`` under the tape are refused (the message names them
+    ``names`` and points at ``composed``, ``what_torch`` by default), the tile table (``args[-1]``) defaults to that of the offsets
+    (``args[-2]``), and ``_ExpectedLogLikelihood`` is applied."""
+    if torch.is_grad_enabled() and (w.requires_grad or c.requires_grad):
+        raise NotImplementedError(f"{what} has no adjoint onto {names} ({cause} under the tape): use {composed or what + '_torch'}")
+    if args[-1] is None:
+        args = args[:-1] + (sparse_expectation_tiles(args[-2]),)
+    return _ExpectedLogLikelihood.apply(pair_mean, pair_cov, third, launcher, cotangent, what, chains, *args)
 
 
 def sparse_expected_log_likelihood(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor, offsets: torch.Tensor,
@@ -388,55 +408,23 @@ def sparse_expected_log_likelihood(likelihood: Likelihood, w: torch.Tensor, c: t
                   dict(w=(w, batch + (w.shape[-2], two_d)), c=(c, batch + (w.shape[-2],)), y=(y, batch + (w.shape[-2],)),
                        pair_mean=(pair_mean, batch + (segs, two_d)), pair_cov=(pair_cov, batch + (segs, two_d, two_d))))
     _lib.same_dtype_device(w, "sparse_expected_log_likelihood", c=c, y=y, pair_mean=pair_mean, pair_cov=pair_cov)
-    if torch.is_grad_enabled() and (w.requires_grad or c.requires_grad):
-        raise NotImplementedError("sparse_expected_log_likelihood has no adjoint onto w and c (a kernel hyper-parameter under the "
-                                  "tape): use sparse_expected_log_likelihood_torch")
-    if tiles is None:
-        tiles = sparse_expectation_tiles(offsets)
-    return _ExpectedLogLikelihood.apply(pair_mean, pair_cov, _sparse_expectations_launch, "sparse_expected_log_likelihood", 0,
-                                        likelihood, w, c, y, offsets, tiles)
+    return _expected_log_likelihood("sparse_expected_log_likelihood", _sparse_expectations_launch, (likelihood, w, c, y, offsets, tiles),
+                                    w, c, pair_mean, pair_cov)
 
 
 def _sparse_theta_expectations_launch(likelihood: Likelihood, theta, w, c, y, offsets, tiles, pair_mean, pair_cov, want_pair: bool,
                                       want_theta: bool):
     """ONE call of ``mf_lik_sparse_expectations_theta_*``: ``(ve_sum [.., S], g_mean [.., S, 2d] | None, g_cov [.., S, 2d, 2d] | None,
     g_theta [.., S] | None)``.  ``theta``: ``()`` - stride 0, one value for all series - or the batch shape - stride 1."""
-    base = "mf_lik_sparse_expectations_theta"
-    dtype, dev = w.dtype, w.device
-    two_d, segs = w.shape[-1], offsets.shape[-1] - 1
-    num_tiles, tile_seg, seg_tile = tiles
-    new = _new_outputs(tuple(offsets.shape[:-1]), dtype, dev)
-    outs = (new(True, segs), new(want_pair, segs, two_d), new(want_pair, segs, two_d, two_d), new(want_theta, segs))
-    ws, ws_bytes = _workspace(getattr(_lib.load(), base + "_workspace_bytes"), dev, num_tiles, two_d, w.element_size())
-    _launch(base, dtype, dev, offsets.numel() // (segs + 1), w.shape[-2], segs, two_d, *likelihood._theta_kernel_args(), theta,
-            0 if theta.dim() == 0 else 1, offsets, w, c, y, pair_mean, pair_cov, num_tiles, tile_seg, seg_tile, ws, ws_bytes, *outs)
-    return outs
+    segs = offsets.shape[-1] - 1
+    return _expectations_launch("mf_lik_sparse_expectations_theta", (*likelihood._theta_kernel_args(), theta, 0 if theta.dim() == 0 else 1),
+                                (w.shape[-2], segs, w.shape[-1]), (w, c, y), offsets, tiles, pair_mean, pair_cov, want_pair,
+                                extra=(want_theta, segs))
 
 
-class _ThetaExpectedLogLikelihood(torch.autograd.Function):
-    """The SVGP data term with the likelihood's parameter as a third differentiable input: value ``batch + [M + 1]``; the adjoints
-    onto the pair marginals AND onto the parameter come out of the same launch and wait for the backward."""
-
-    @staticmethod
-    def forward(ctx, pair_mean, pair_cov, theta, likelihood, w, c, y, offsets, tiles):
-        want_pair, want_theta = ctx.needs_input_grad[0] or ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        with torch.no_grad():
-            ve_sum, g_mean, g_cov, g_theta = _sparse_theta_expectations_launch(
-                likelihood, theta.detach(), w.detach(), c.detach(), y.detach(), offsets, tiles, pair_mean.detach(), pair_cov.detach(),
-                want_pair, want_theta)
-        ctx.save_for_backward(g_mean, g_cov, g_theta)
-        ctx.shared = theta.dim() == 0
-        return ve_sum
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        _differentiable_once("sparse_theta_expected_log_likelihood", "adjoints")
-        g_mean, g_cov, g_theta = ctx.saved_tensors
-        g_th = None
-        if ctx.needs_input_grad[2]:            # over the segments, and over the batch when every series shares the value
-            g_th = torch.sum(grad_out * g_theta) if ctx.shared else torch.sum(grad_out * g_theta, dim=-1)
-        return (grad_out[..., None] * g_mean if ctx.needs_input_grad[0] else None,
-                grad_out[..., None, None] * g_cov if ctx.needs_input_grad[1] else None, g_th) + (None,) * 6
+def _theta_cotangent(grad_out, g_theta, theta, offsets):
+    """Over the segments, and over the batch when every series shares the value."""
+    return torch.sum(grad_out * g_theta) if theta.dim() == 0 else torch.sum(grad_out * g_theta, dim=-1)
 
 
 def sparse_theta_expected_log_likelihood(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor,
@@ -466,12 +454,8 @@ def sparse_theta_expected_log_likelihood(likelihood: Likelihood, w: torch.Tensor
     if tuple(theta.shape) not in ((), batch):
         raise ValueError(f"{what}: theta has shape {tuple(theta.shape)}, expected () or {batch}")
     _lib.same_dtype_device(w, what, c=c, y=y, pair_mean=pair_mean, pair_cov=pair_cov, theta=theta)
-    if torch.is_grad_enabled() and (w.requires_grad or c.requires_grad):
-        raise NotImplementedError(f"{what} has no adjoint onto w and c (a kernel hyper-parameter under the tape): use "
-                                  "sparse_expected_log_likelihood_torch")
-    if tiles is None:
-        tiles = sparse_expectation_tiles(offsets)
-    return _ThetaExpectedLogLikelihood.apply(pair_mean, pair_cov, theta, likelihood, w, c, y, offsets, tiles)
+    return _expected_log_likelihood(what, _sparse_theta_expectations_launch, (likelihood, theta, w, c, y, offsets, tiles), w, c, pair_mean,
+                                    pair_cov, theta, _theta_cotangent, composed="sparse_expected_log_likelihood_torch")
 
 
 def sparse_expected_log_likelihood_torch(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor,
@@ -510,7 +494,7 @@ def _sparse_multi_point_marginals(w: torch.Tensor, c: torch.Tensor, indices: tor
 
 def _sparse_multi_expectations_launch(likelihood: Likelihood, w, c, y, offsets, tiles, pair_mean, pair_cov, want_grads: bool):
     """ONE call of ``mf_lik_sparse_multi_expectations_*``: ``(ve_sum [.., S], g_mean [.., S, 2d] | None, g_cov [.., S, 2d, 2d] | None)``."""
-    return _expectations_launch("mf_lik_sparse_multi_expectations", likelihood,
+    return _expectations_launch("mf_lik_sparse_multi_expectations", likelihood._kernel_args(),
                                 (w.shape[-3], offsets.shape[-1] - 1, w.shape[-1], w.shape[-2]), (w, c, y), offsets, tiles, pair_mean,
                                 pair_cov, want_grads)
 
@@ -538,13 +522,8 @@ def sparse_multi_expected_log_likelihood(likelihood: Likelihood, w: torch.Tensor
     _check_shapes(what, dict(w=(w, batch + (n, latents, two_d)), c=(c, batch + (n, latents)), y=(y, batch + (n,)),
                              pair_mean=(pair_mean, batch + (segs, two_d)), pair_cov=(pair_cov, batch + (segs, two_d, two_d))))
     _lib.same_dtype_device(w, what, c=c, y=y, pair_mean=pair_mean, pair_cov=pair_cov)
-    if torch.is_grad_enabled() and (w.requires_grad or c.requires_grad):
-        raise NotImplementedError(f"{what} has no adjoint onto w and c (a kernel hyper-parameter under the tape): use "
-                                  "sparse_multi_expected_log_likelihood_torch")
-    if tiles is None:
-        tiles = sparse_expectation_tiles(offsets)
-    return _ExpectedLogLikelihood.apply(pair_mean, pair_cov, _sparse_multi_expectations_launch, what, 0, likelihood, w, c, y, offsets,
-                                        tiles)
+    return _expected_log_likelihood(what, _sparse_multi_expectations_launch, (likelihood, w, c, y, offsets, tiles), w, c, pair_mean,
+                                    pair_cov)
 
 
 def sparse_multi_expected_log_likelihood_torch(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor,
@@ -590,7 +569,7 @@ def _sparse_stack_check(what: str, likelihood, w, c, y, lead, segs, pair_mean, p
 def _sparse_stack_expectations_launch(likelihood: Likelihood, w, c, y, offsets, tiles, pair_mean, pair_cov, want_grads: bool):
     """ONE call of ``mf_lik_stack_expectations_*``: ``(ve_sum [.., S], g_mean [.., K, S, 2d] | None, g_cov [.., K, S, 2d, 2d] | None)``."""
     latents = w.shape[-3]
-    return _expectations_launch("mf_lik_stack_expectations", likelihood, (latents, w.shape[-2], offsets.shape[-1] - 1, w.shape[-1]),
+    return _expectations_launch("mf_lik_stack_expectations", likelihood._kernel_args(), (latents, w.shape[-2], offsets.shape[-1] - 1, w.shape[-1]),
                                 (w, c, y), offsets, tiles, pair_mean, pair_cov, want_grads, chains=(latents,), ws_dims=(latents,))
 
 
@@ -615,13 +594,8 @@ def sparse_stack_expected_log_likelihood(likelihood: Likelihood, w: torch.Tensor
         raise NotImplementedError(f"{what}: K = {latents}, 2d = {two_d}, {type(likelihood).__name__} is outside the instantiated "
                                   f"signatures (2d even in 2 ... {SPARSE_SITE_MAX_TWO_D}; MultiStageLikelihood, "
                                   "HeteroscedasticGaussian); use sparse_stack_expected_log_likelihood_torch")
-    if torch.is_grad_enabled() and (w.requires_grad or c.requires_grad):
-        raise NotImplementedError(f"{what} has no adjoint onto w and c (a kernel hyper-parameter under the tape): use "
-                                  "sparse_stack_expected_log_likelihood_torch")
-    if tiles is None:
-        tiles = sparse_expectation_tiles(offsets)
-    return _ExpectedLogLikelihood.apply(pair_mean, pair_cov, _sparse_stack_expectations_launch, what, 1, likelihood, w, c, y, offsets,
-                                        tiles)
+    return _expected_log_likelihood(what, _sparse_stack_expectations_launch, (likelihood, w, c, y, offsets, tiles), w, c, pair_mean,
+                                    pair_cov, chains=1)
 
 
 def sparse_stack_expected_log_likelihood_torch(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor,
@@ -678,14 +652,14 @@ def sparse_factor_site_projections(kernel, time_points: torch.Tensor, inducing_p
                                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """``sparse_site_projections`` onto the LATENT processes of a ``FactorAnalysisKernel`` with ``L`` latents: ``wg [.., N, L, 2d] =
     H_inner P_k`` and the full ``cg [.., N, L, L] = H_inner T_k H_inner^T``, with the same ``indices`` and ``offsets``.  None of it
-    depends on the loading matrix or the weight function, so it is computed under ``no_grad`` and a model caches it."""
-    with torch.no_grad():
-        proj, cov, indices = conditionals._conditional_statistics(time_points, inducing_points, kernel)
-        h = kernel.latent_emission_model(time_points).emission_matrix                       # [.., N, L, d]
-        wg = h @ proj
-        cg = h @ cov @ h.transpose(-1, -2)
-        cg = 0.5 * (cg + cg.transpose(-1, -2))
-        return wg.contiguous(), cg.contiguous(), indices, _site_offsets(time_points, inducing_points)
+    depends on the loading matrix or the weight function: a model caches it.  Differentiable in the chain's hyper-parameters when
+    they are under the tape."""
+    proj, cov, indices = conditionals._conditional_statistics(time_points, inducing_points, kernel)
+    h = kernel.latent_emission_model(time_points).emission_matrix                           # [.., N, L, d]
+    wg = h @ proj
+    cg = h @ cov @ h.transpose(-1, -2)
+    cg = 0.5 * (cg + cg.transpose(-1, -2))
+    return wg.contiguous(), cg.contiguous(), indices, _site_offsets(time_points, inducing_points)
 
 
 def _sparse_factor_check(what: str, likelihood, wg, cg, mix, y, lead, segs, pair_mean, pair_cov) -> None:
@@ -705,41 +679,14 @@ def _sparse_factor_expectations_launch(likelihood: Likelihood, wg, cg, mix, y, o
     """ONE call of ``mf_lik_sparse_factor_expectations_*``: ``(ve_sum [.., S], g_mean [.., S, 2d] | None, g_cov [.., S, 2d, 2d] | None,
     g_w [.., N, P, L] | None)``."""
     n, latents, outputs = wg.shape[-3], wg.shape[-2], mix.shape[-2]
-    return _expectations_launch("mf_lik_sparse_factor_expectations", likelihood,
+    return _expectations_launch("mf_lik_sparse_factor_expectations", likelihood._kernel_args(),
                                 (n, offsets.shape[-1] - 1, wg.shape[-1], latents, outputs), (wg, cg, mix, y), offsets, tiles,
                                 pair_mean, pair_cov, want_grads, extra=(want_g_w, n, outputs, latents))
 
 
-class _SparseFactorExpectedLogLikelihood(torch.autograd.Function):
-    """Value ``batch + [M + 1]``; the adjoints onto the pair marginals and - when ``mix`` requires a gradient - onto the mixing weights
-    come out of the same launch and wait for the backward."""
-
-    @staticmethod
-    def forward(ctx, pair_mean, pair_cov, mix, likelihood, wg, cg, y, offsets, tiles):
-        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        want_w = ctx.needs_input_grad[2]
-        with torch.no_grad():
-            ve_sum, g_mean, g_cov, g_w = _sparse_factor_expectations_launch(likelihood, wg.detach(), cg.detach(), mix.detach(), y.detach(),
-                                                                            offsets, tiles, pair_mean.detach(), pair_cov.detach(), want,
-                                                                            want_w)
-        ctx.want, ctx.want_w = want, want_w
-        saved = ((g_mean, g_cov) if want else ()) + ((g_w, _segments_of(offsets, wg.shape[-3])) if want_w else ())
-        ctx.save_for_backward(*saved)
-        return ve_sum
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        _differentiable_once("sparse_factor_expected_log_likelihood", "adjoints")
-        saved = list(ctx.saved_tensors)
-        g_mean = g_cov = g_mix = None
-        if ctx.want:
-            g_mean, g_cov = saved[:2]
-            saved = saved[2:]
-        if ctx.want_w:
-            g_w, segment = saved
-            g_mix = torch.gather(grad_out, -1, segment)[..., None, None] * g_w       # every point takes its segment's cotangent
-        return (grad_out[..., None] * g_mean if ctx.needs_input_grad[0] else None,
-                grad_out[..., None, None] * g_cov if ctx.needs_input_grad[1] else None, g_mix, None, None, None, None, None, None)
+def _mix_cotangent(grad_out, g_w, mix, offsets):
+    """Every point takes its segment's cotangent."""
+    return torch.gather(grad_out, -1, _segments_of(offsets, mix.shape[-3]))[..., None, None] * g_w
 
 
 def sparse_factor_expected_log_likelihood(likelihood: Likelihood, wg: torch.Tensor, cg: torch.Tensor, mix: torch.Tensor,
@@ -762,12 +709,8 @@ def sparse_factor_expected_log_likelihood(likelihood: Likelihood, wg: torch.Tens
         raise NotImplementedError(f"{what}: L = {latents}, 2d = {two_d}, P = {outputs} is outside L in {SPARSE_FACTOR_LATENTS}, 2d even "
                                   f"in 2L ... {SPARSE_SITE_MAX_TWO_D}, 1 <= P <= {SPARSE_FACTOR_MAX_OUTPUTS}; use "
                                   "sparse_factor_expected_log_likelihood_torch")
-    if torch.is_grad_enabled() and (wg.requires_grad or cg.requires_grad):
-        raise NotImplementedError(f"{what} has no adjoint onto wg and cg (a hyper-parameter of the chain under the tape): use "
-                                  "sparse_factor_expected_log_likelihood_torch")
-    if tiles is None:
-        tiles = sparse_expectation_tiles(offsets)
-    return _SparseFactorExpectedLogLikelihood.apply(pair_mean, pair_cov, mix, likelihood, wg, cg, y, offsets, tiles)
+    return _expected_log_likelihood(what, _sparse_factor_expectations_launch, (likelihood, wg, cg, mix, y, offsets, tiles), wg, cg,
+                                    pair_mean, pair_cov, mix, _mix_cotangent, names="wg and cg", cause="a hyper-parameter of the chain")
 
 
 def sparse_factor_expected_log_likelihood_torch(likelihood: Likelihood, wg: torch.Tensor, cg: torch.Tensor, mix: torch.Tensor,
@@ -798,14 +741,14 @@ def sparse_full_site_projections(kernel: SDEKernel, time_points: torch.Tensor, i
                                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """``sparse_site_projections`` for a kernel with ``P = kernel.output_dim`` outputs whose likelihood needs their joint marginal:
     ``w [.., N, P, 2d] = H P_k`` and the FULL ``c [.., N, P, P] = H T_k H^T`` (symmetric bit for bit), with the same ``indices`` and
-    ``offsets``; the kernel's own emission (a ``FactorAnalysisKernel``'s composed one), under ``no_grad``: a model caches it."""
-    with torch.no_grad():
-        proj, cov, indices = conditionals._conditional_statistics(time_points, inducing_points, kernel)
-        h = kernel.generate_emission_model(time_points).emission_matrix                     # [.., N, P, d]
-        w = h @ proj
-        c = h @ cov @ h.transpose(-1, -2)
-        c = 0.5 * (c + c.transpose(-1, -2))
-        return w.contiguous(), c.contiguous(), indices, _site_offsets(time_points, inducing_points)
+    ``offsets``; the kernel's own emission (a ``FactorAnalysisKernel``'s composed one).  Differentiable in the hyper-parameters of
+    the chain and of the emission when they are under the tape."""
+    proj, cov, indices = conditionals._conditional_statistics(time_points, inducing_points, kernel)
+    h = kernel.generate_emission_model(time_points).emission_matrix                         # [.., N, P, d]
+    w = h @ proj
+    c = h @ cov @ h.transpose(-1, -2)
+    c = 0.5 * (c + c.transpose(-1, -2))
+    return w.contiguous(), c.contiguous(), indices, _site_offsets(time_points, inducing_points)
 
 
 def _sparse_mvn_check(what: str, likelihood, w, c, y, lead, segs, pair_mean, pair_cov) -> None:
@@ -826,37 +769,13 @@ def _sparse_mvn_expectations_launch(likelihood: Likelihood, w, c, y, prec, offse
     """ONE call of ``mf_lik_sparse_mvn_expectations_*``: ``(quad_sum [.., S], g_mean [.., S, 2d] | None, g_cov [.., S, 2d, 2d] | None,
     m_sum [.., S, P, P] | None)``."""
     n, outputs, segs = w.shape[-3], w.shape[-2], offsets.shape[-1] - 1
-    return _expectations_launch("mf_lik_sparse_mvn_expectations", likelihood, (n, segs, w.shape[-1], outputs), (w, c, y, prec), offsets,
+    return _expectations_launch("mf_lik_sparse_mvn_expectations", likelihood._kernel_args(), (n, segs, w.shape[-1], outputs), (w, c, y, prec), offsets,
                                 tiles, pair_mean, pair_cov, want_grads, ws_dims=(outputs,), extra=(want_m_sum, segs, outputs, outputs))
 
 
-class _SparseMvnQuadraticTerm(torch.autograd.Function):
-    """``-quad_sum / 2``, ``batch + [M + 1]``: the part of the data term that depends on the pair marginals and on the precision.  Its
-    adjoints onto the pair marginals and - when ``prec`` requires a gradient - onto the precision come out of the same launch and wait
-    for the backward."""
-
-    @staticmethod
-    def forward(ctx, pair_mean, pair_cov, prec, likelihood, w, c, y, offsets, tiles):
-        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        want_m = ctx.needs_input_grad[2]
-        with torch.no_grad():
-            quad_sum, g_mean, g_cov, m_sum = _sparse_mvn_expectations_launch(likelihood, w.detach(), c.detach(), y.detach(), prec.detach(),
-                                                                             offsets, tiles, pair_mean.detach(), pair_cov.detach(), want,
-                                                                             want_m)
-        ctx.want, ctx.want_m = want, want_m
-        ctx.save_for_backward(*(((g_mean, g_cov) if want else ()) + ((m_sum,) if want_m else ())))
-        return -0.5 * quad_sum
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        _differentiable_once("sparse_mvn_expected_log_likelihood", "adjoints")
-        saved = list(ctx.saved_tensors)
-        g_prec = None
-        if ctx.want_m:
-            m_sum = saved.pop()
-            g_prec = torch.sum((grad_out[..., None, None] * (-0.5 * m_sum)).reshape((-1,) + tuple(m_sum.shape[-2:])), dim=0)
-        return (grad_out[..., None] * saved[0] if ctx.needs_input_grad[0] else None,
-                grad_out[..., None, None] * saved[1] if ctx.needs_input_grad[1] else None, g_prec, None, None, None, None, None, None)
+def _prec_cotangent(grad_out, m_sum, prec, offsets):
+    """``-m_sum / 2`` over the batch and the segments: one precision for all of them."""
+    return torch.sum((grad_out[..., None, None] * (-0.5 * m_sum)).reshape((-1,) + tuple(m_sum.shape[-2:])), dim=0)
 
 
 def sparse_mvn_expected_log_likelihood(likelihood: Likelihood, w: torch.Tensor, c: torch.Tensor, y: torch.Tensor, offsets: torch.Tensor,
@@ -877,13 +796,15 @@ def sparse_mvn_expected_log_likelihood(likelihood: Likelihood, w: torch.Tensor, 
     if outputs not in SPARSE_MVN_OUTPUTS or two_d > SPARSE_SITE_MAX_TWO_D or two_d % 2:
         raise NotImplementedError(f"{what}: P = {outputs}, 2d = {two_d} is outside P in {SPARSE_MVN_OUTPUTS}, 2d even in 2 ... "
                                   f"{SPARSE_SITE_MAX_TWO_D}; use sparse_mvn_expected_log_likelihood_torch")
-    if torch.is_grad_enabled() and (w.requires_grad or c.requires_grad):
-        raise NotImplementedError(f"{what} has no adjoint onto w and c (a hyper-parameter of the kernel under the tape): use "
-                                  "sparse_mvn_expected_log_likelihood_torch")
-    if tiles is None:
-        tiles = sparse_expectation_tiles(offsets)
+
+    def quadratic_term(*args):      # -quad_sum / 2: the part of the data term whose adjoints the launch writes
+        quad_sum, *adjoints = _sparse_mvn_expectations_launch(*args)
+        return (-0.5 * quad_sum, *adjoints)
+
+    prec = likelihood.precision(w)
+    quad = _expected_log_likelihood(what, quadratic_term, (likelihood, w, c, y, prec, offsets, tiles), w, c, pair_mean, pair_cov, prec,
+                                    _prec_cotangent, cause="a hyper-parameter of the kernel")
     counts = (offsets[..., 1:] - offsets[..., :-1]).to(w.dtype)
-    quad = _SparseMvnQuadraticTerm.apply(pair_mean, pair_cov, likelihood.precision(w), likelihood, w, c, y, offsets, tiles)
     return quad - 0.5 * counts * likelihood.log_normaliser(w)
 
 

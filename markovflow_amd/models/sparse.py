@@ -16,7 +16,7 @@ ONE call of ``mf_lik_sparse_expectations_*``, the KL term is ``StateSpaceModel.k
 Matheron's rule, whose assembly from one prior draw, the ``K`` evaluations of ``log p(y_n | f_n)`` at every data point and the adjoint
 onto the draw from ``q`` are ONE call of ``mf_lik_iw_log_weights_*``.
 """
-from typing import Optional, Tuple
+from typing import Callable, NamedTuple, Optional, Tuple
 
 import math
 
@@ -477,6 +477,95 @@ def _sorted_series(time_points: torch.Tensor) -> Tuple[Optional[torch.Tensor], t
     return order, torch.gather(time_points, -1, order)
 
 
+def _in_order(values: torch.Tensor, order: Optional[torch.Tensor], dim: int = -1) -> torch.Tensor:
+    """``values`` (``[.., N]``, or ``[.., N, P]`` with ``dim = -2``) in the sorted order of ``_sorted_series``."""
+    if order is None:
+        return values
+    return torch.gather(values, dim, order if dim == -1 else order[..., None].expand(values.shape))
+
+
+class _Route(NamedTuple):
+    """One data route of ``SparseVariationalGaussianProcess``: a row of ``_ROUTES``.  The functions of ``segmented_ops.py`` are held
+    by NAME and looked up in this module when they are called, so that what a test replaces here is what runs."""
+    project: str                    # (kernel, sorted time points, inducing points) -> (w, c, indices, offsets)
+    points: Callable                # (kernel, time_points, observations, order) -> what the two ops take between c and the
+    #                                 segmentation: the kernel's y in the sorted order, behind whatever else every call evaluates
+    fused: Optional[str]            # (likelihood, w, c, *points, offsets, pair_mean, pair_cov, tiles=tiles) -> batch + [M + 1]
+    composed: str                   # (likelihood, w, c, *points, indices, pair_mean, pair_cov) -> the same, by autograd
+    fusable: Callable               # (model, time_points) -> the fused condition beyond "HIP tensors, 2d <= 18, no kernel
+    #                                 hyper-parameter under the tape"
+    loading_cached: bool = True     # a FactorAnalysisKernel's loading matrix is a source of the projections (and of their cache)
+    one_segmentation: bool = False  # the fused op wants the chains of a series on ONE segmentation: read back with the projections
+
+
+def _column(kernel, time_points, observations, order):              # [N, 1] -> y [N]
+    return (_in_order(observations[..., 0], order),)
+
+
+def _rows(kernel, time_points, observations, order):                # [N, P] as it is
+    return (_in_order(observations, order, -2),)
+
+
+def _mixed_rows(kernel, time_points, observations, order):
+    # ... behind the mixing weights: on every call, under the tape of the loading matrix and the weight function
+    return (kernel.mixing_weights(_in_order(time_points, order)), _in_order(observations, order, -2))
+
+
+def _chain_rows(kernel, time_points, observations, order):          # [N, K] -> y [K, N]: one series per chain
+    return (_in_order(observations.transpose(-1, -2), order).contiguous(),)
+
+
+def _coupled_column(kernel, time_points, observations, order):
+    # [N, 1] -> y [N] in the DATA's order and the chains' orders beside it: every chain is sorted on its own time points
+    return observations[..., 0], order
+
+
+def _stack_fused(likelihood, w, c, y, order, offsets, pair_mean, pair_cov, tiles):
+    """The coupled term on chains that share one segmentation: chain 0's order and offsets are every chain's."""
+    return sparse_stack_expected_log_likelihood(likelihood, w, c, y if order is None else _in_order(y, order[..., 0, :]),
+                                                offsets[..., 0, :].contiguous(), pair_mean, pair_cov, tiles=tiles)
+
+
+def _stack_composed(likelihood, w, c, y, order, indices, pair_mean, pair_cov):
+    return sparse_stack_expected_log_likelihood_torch(likelihood, w, c, y, indices, pair_mean, pair_cov, orders=order)
+
+
+def _emission_fixed(model, time_points) -> bool:        # (the loading matrix under the tape: w and c are part of the graph)
+    return not model._emission_needs_grad()
+
+
+_ROUTES = {
+    # observations [N, 1], a likelihood with one latent function
+    "single": _Route("sparse_site_projections", _column, "sparse_expected_log_likelihood", "sparse_expected_log_likelihood_torch",
+                     _emission_fixed),
+    # ... whose parameter is a tensor: read from device memory, its adjoint from the same launch
+    "theta": _Route("sparse_site_projections", _column, "sparse_theta_expected_log_likelihood", "sparse_expected_log_likelihood_torch",
+                    _emission_fixed),
+    # [N, 1], a likelihood with L latent functions on a kernel with L outputs
+    "multi": _Route("sparse_multi_site_projections", _column, "sparse_multi_expected_log_likelihood",
+                    "sparse_multi_expected_log_likelihood_torch", lambda model, x: 2 * model._kernel.state_dim >= SPARSE_MULTI_MIN_TWO_D),
+    # [N, P], one series per output of a kernel that is not a FactorAnalysisKernel: no fused term
+    "outputs": _Route("sparse_multi_site_projections", _rows, None, "sparse_multi_output_expected_log_likelihood_torch",
+                      lambda model, x: False),
+    # [N, P] on a FactorAnalysisKernel: the projections onto the latents do not depend on the loading matrix, a step on it keeps them
+    "factor": _Route("sparse_factor_site_projections", _mixed_rows, "sparse_factor_expected_log_likelihood",
+                     "sparse_factor_expected_log_likelihood_torch",
+                     lambda model, x: (model._kernel.latent_dim in SPARSE_FACTOR_LATENTS
+                                       and model._kernel.state_dim >= model._kernel.latent_dim
+                                       and model._kernel.output_dim <= SPARSE_FACTOR_MAX_OUTPUTS), loading_cached=False),
+    # [N, P] under a MultivariateGaussian likelihood, whatever the kernel: the full P x P marginal per point
+    "mvn": _Route("sparse_full_site_projections", _rows, "sparse_mvn_expected_log_likelihood", "sparse_mvn_expected_log_likelihood_torch",
+                  lambda model, x: model._likelihood.obs_dim in SPARSE_MVN_OUTPUTS and _emission_fixed(model, x)),
+    # a stack kernel, [N, 1] under a K-latent likelihood: the chains are coupled at every point
+    "stack": _Route("sparse_site_projections", _coupled_column, "_stack_fused", "_stack_composed",
+                    lambda model, x: (sparse_stack_instantiated(model._likelihood, model._kernel.num_kernels, 2 * model._kernel.state_dim)
+                                      and model._projections(x)[6]), one_segmentation=True),
+    # a stack kernel, [N, K] under a one-latent likelihood: K decoupled chains, the single-latent term on the batch lead + [K]
+    "stack_outputs": _Route("sparse_site_projections", _chain_rows, "sparse_expected_log_likelihood",
+                            "sparse_expected_log_likelihood_torch", lambda model, x: True),
+}
+
+
 class SparseVariationalGaussianProcess(_SparseGaussianProcess):
     """GP prior, general likelihood, a free-form Gaussian posterior ``q(s(z))`` on the states at ``M`` inducing points held as a
     trainable ``StateSpaceModel`` (markovflow/models/sparse_variational.py:31-270; zero mean function, a batch of series as leading
@@ -537,7 +626,6 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
         :param initial_distribution: the initial ``q`` on the inducing points; the prior by default.
         """
         super().__init__(kernel, likelihood, inducing_points, min_inducing=2)
-        self._route = "multi" if likelihood.latent_dim > 1 else "single"    # (``_data_route`` of the data last seen)
         theta = likelihood._theta_leaf
         if theta is not None:
             if isinstance(kernel, StackKernel) or kernel.output_dim != 1:
@@ -549,13 +637,10 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
                 raise ValueError(f"the likelihood's tensor parameter must have the dtype and device of the inducing points and shape "
                                  f"() or {tuple(inducing_points.shape[:-1])}, got {theta.dtype} on {theta.device}, "
                                  f"{tuple(theta.shape)}")
-        if isinstance(likelihood, MultivariateGaussian):
-            if isinstance(kernel, StackKernel):
-                raise NotImplementedError("a MultivariateGaussian likelihood couples the outputs at every point through their joint "
-                                          "marginal: a stack kernel keeps one independent chain per output; use IndependentMultiOutput")
-            self._route = "mvn"
-        elif isinstance(kernel, StackKernel):
-            self._route = "stack" if likelihood.latent_dim > 1 else "stack_outputs"
+        if isinstance(likelihood, MultivariateGaussian) and isinstance(kernel, StackKernel):
+            raise NotImplementedError("a MultivariateGaussian likelihood couples the outputs at every point through their joint "
+                                      "marginal: a stack kernel keeps one independent chain per output; use IndependentMultiOutput")
+        self._route = self._data_route()           # (of the data last seen: the cached projections are this route's)
         if num_data is not None and not num_data > 0:
             raise ValueError(f"num_data must be positive, got {num_data}")
         self.num_data = num_data
@@ -596,157 +681,57 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
         return self._dist_q.trainable_variables
 
     # ---- data --------------------------------------------------------------------------------------------------------------------
-    @property
-    def _multi(self) -> bool:
-        """A likelihood with several latent functions: the multi-latent projections and data term."""
-        return self._likelihood.latent_dim > 1
-
-    def _data_route(self, observations: torch.Tensor) -> str:
-        """What the observations' last dimension selects: ``"single"`` (``[N, 1]``, one latent), ``"multi"`` (``[N, 1]``, a
-        multi-latent likelihood), ``"factor"`` (``[N, P]`` on a ``FactorAnalysisKernel``) or ``"outputs"`` (``[N, P]`` on any other
-        kernel with ``P`` outputs); ``"mvn"`` whatever the observations under a ``MultivariateGaussian`` likelihood."""
-        if isinstance(self._likelihood, MultivariateGaussian):
-            return "mvn"
+    def _data_route(self, columns: int = 1) -> _Route:
+        """The row of ``_ROUTES`` that the likelihood, the kernel and the observations' last dimension select."""
+        lik, multi = self._likelihood, self._likelihood.latent_dim > 1
+        if isinstance(lik, MultivariateGaussian):
+            return _ROUTES["mvn"]
         if isinstance(self._kernel, StackKernel):
-            return "stack" if self._multi else "stack_outputs"
-        if observations.shape[-1] == 1:
-            return "multi" if self._multi else "single"
-        return "factor" if isinstance(self._kernel, FactorAnalysisKernel) else "outputs"
+            return _ROUTES["stack" if multi else "stack_outputs"]
+        if columns == 1:
+            return _ROUTES["multi" if multi else "single" if lik._theta_leaf is None else "theta"]
+        return _ROUTES["factor" if isinstance(self._kernel, FactorAnalysisKernel) else "outputs"]
 
     def _emission_needs_grad(self) -> bool:
         """A hyper-parameter of the emission under the tape (the loading matrix of a ``FactorAnalysisKernel``)."""
         return torch.is_grad_enabled() and any(x.requires_grad for x in super()._emission_sources())
 
     def _emission_sources(self) -> Tuple[torch.Tensor, ...]:
-        # (the projections onto the latents of a FactorAnalysisKernel do not depend on its loading matrix: a step on it keeps them)
-        return () if self._route == "factor" else super()._emission_sources()
+        return super()._emission_sources() if self._route.loading_cached else ()
 
     def _fused(self, time_points: torch.Tensor) -> bool:
-        two_d = 2 * self._kernel.state_dim
-        if not (time_points.is_cuda and two_d <= SPARSE_SITE_MAX_TWO_D and not self._kernel._needs_grad()):
-            return False
-        if self._route == "factor":
-            latents = self._kernel.latent_dim
-            return latents in SPARSE_FACTOR_LATENTS and two_d >= 2 * latents and self._kernel.output_dim <= SPARSE_FACTOR_MAX_OUTPUTS
-        if self._route == "outputs":           # (no fused multi-output term for a kernel that is not a FactorAnalysisKernel)
-            return False
-        if self._route == "mvn":               # the loading matrix under the tape: w and c are part of the graph
-            return self._likelihood.obs_dim in SPARSE_MVN_OUTPUTS and not self._emission_needs_grad()
-        if self._route == "single":            # the loading matrix under the tape: w and c are part of the graph
-            return not self._emission_needs_grad()
-        return two_d >= SPARSE_MULTI_MIN_TWO_D
+        return (time_points.is_cuda and 2 * self._kernel.state_dim <= SPARSE_SITE_MAX_TWO_D and not self._kernel._needs_grad()
+                and bool(self._route.fusable(self, time_points)))
+
+    def _sorted_projections(self, time_points: torch.Tensor):
+        """``(order | None, w, c, indices, offsets)``: the permutation that sorts each series (None for sorted data) and the route's
+        projection function on the sorted points - under the tape, if the caller has one."""
+        order, time_points = _sorted_series(time_points)
+        return (order,) + globals()[self._route.project](self._kernel, time_points, self.inducing_inputs)
 
     def _compute_projections(self, time_points: torch.Tensor):
-        """``(order | None, w, c, indices, offsets, tiles)`` of the data: the permutation that sorts each series (None for sorted
-        data), ``sparse_site_projections`` of the sorted points (``sparse_multi_site_projections`` for a multi-latent likelihood or
-        multi-output observations: ``w`` and ``c`` carry one row per latent or output; ``sparse_factor_site_projections`` for a
-        ``FactorAnalysisKernel`` with multi-output observations: ``wg``, ``cg`` of the latents; ``sparse_full_site_projections`` under a
-        ``MultivariateGaussian`` likelihood: ``c`` is the full ``P x P`` block) and the tile table."""
-        if self._route in ("stack", "stack_outputs"):
-            return self._compute_stack_projections(time_points)
-        order, time_points = _sorted_series(time_points)
-        project = {"single": sparse_site_projections, "multi": sparse_multi_site_projections,
-                   "outputs": sparse_multi_site_projections, "factor": sparse_factor_site_projections,
-                   "mvn": sparse_full_site_projections}[self._route]
-        w, c, indices, offsets = project(self._kernel, time_points, self.inducing_inputs)
-        tiles = sparse_expectation_tiles(offsets) if time_points.is_cuda else None
-        return order, w, c, indices, offsets, tiles
-
-    def _compute_stack_projections(self, time_points: torch.Tensor):
-        """``(order | None, w, c, indices, offsets, tiles, shared)`` of data ``lead + [K, N]`` on a stack kernel:
-        ``sparse_site_projections`` on the stacked batch (every chain sorted on its own time points), ``w [.., K, N, 2d]``,
-        ``c [.., K, N]``.  ``shared``: the ``K`` chains of every series have equal inducing points, equal data times and one sorting
-        permutation, so they share ONE segmentation (one read-back, kept with the projections) - the coupled route's tile table is
-        then that of chain 0's offsets; the per-output route's is that of the batch of chains."""
-        order, x = _sorted_series(time_points)
-        w, c, indices, offsets = sparse_site_projections(self._kernel, x, self.inducing_inputs)
-        shared, tiles = False, None
-        if self._route == "stack":
-            z = self.inducing_inputs
+        """``_sorted_projections`` of the data and the tile table, ``(order | None, w, c, indices, offsets, tiles)``; on a stack kernel
+        (data ``lead + [K, N]``, every chain sorted on its own time points, ``w [.., K, N, 2d]``) a seventh entry ``shared``: the route
+        couples the chains, and those of every series have equal inducing points, equal data times and one sorting permutation, so
+        they share ONE segmentation (one read-back) - the tile table is then that of chain 0's offsets, otherwise there is none."""
+        order, w, c, indices, offsets = self._sorted_projections(time_points)
+        segmentation, shared = offsets, False
+        if self._route.one_segmentation:
+            z, x = self.inducing_inputs, _in_order(time_points, order)
             same = (z == z[..., :1, :]).all() & (x == x[..., :1, :]).all()
             if order is not None:
                 same = same & (order == order[..., :1, :]).all()
             shared = bool(same)
-            if shared and time_points.is_cuda:
-                tiles = sparse_expectation_tiles(offsets[..., 0, :].contiguous())
-        elif time_points.is_cuda:
-            tiles = sparse_expectation_tiles(offsets)
-        return order, w, c, indices, offsets, tiles, shared
+            segmentation = offsets[..., 0, :].contiguous() if shared else None
+        tiles = sparse_expectation_tiles(segmentation) if time_points.is_cuda and segmentation is not None else None
+        return (order, w, c, indices, offsets, tiles) + ((shared,) if isinstance(self._kernel, StackKernel) else ())
 
-    def _stack_expected_log_likelihood(self, time_points: torch.Tensor, observations: torch.Tensor, pair_mean, pair_cov
-                                       ) -> torch.Tensor:
-        """The data term on a stack kernel, ``lead + [M + 1]`` (coupled) or ``lead + [K, M + 1]`` (one series per output)."""
-        kernel, lik = self._kernel, self._likelihood
-        two_d = 2 * kernel.state_dim
-        on_device = time_points.is_cuda and two_d <= SPARSE_SITE_MAX_TWO_D and not kernel._needs_grad()
-        if kernel._needs_grad():
-            # a hyper-parameter under the tape: w and c are part of the graph
-            order, x = _sorted_series(time_points)
-            proj, cov, indices = conditionals._conditional_statistics(x, self.inducing_inputs, kernel)
-            h = kernel.generate_emission_model(x).emission_matrix
-            w, c = (h @ proj)[..., 0, :], (h @ cov @ h.transpose(-1, -2))[..., 0, 0]
-            offsets = tiles = None
-            shared = False
-        else:
-            order, w, c, indices, offsets, tiles, shared = self._projections(time_points)
-        if self._route == "stack_outputs":
-            # K decoupled chains: the single-latent term on the batch lead + [K]
-            y = observations.transpose(-1, -2)
-            if order is not None:
-                y = torch.gather(y, -1, order)
-            if on_device:
-                return sparse_expected_log_likelihood(lik, w, c, y.contiguous(), offsets, pair_mean, pair_cov, tiles=tiles)
-            return sparse_expected_log_likelihood_torch(lik, w, c, y, indices, pair_mean, pair_cov)
-        y = observations[..., 0]
-        if on_device and shared and sparse_stack_instantiated(lik, kernel.num_kernels, two_d):
-            if order is not None:
-                y = torch.gather(y, -1, order[..., 0, :])
-            return sparse_stack_expected_log_likelihood(lik, w, c, y, offsets[..., 0, :].contiguous(), pair_mean, pair_cov, tiles=tiles)
-        return sparse_stack_expected_log_likelihood_torch(lik, w, c, y, indices, pair_mean, pair_cov, orders=order)
-
-    def _multi_output_expected_log_likelihood(self, time_points: torch.Tensor, observations: torch.Tensor, pair_mean, pair_cov
-                                              ) -> torch.Tensor:
-        """The data term for observations ``batch + [N, P]``, ``P`` the kernel's output dimension."""
-        kernel, factor = self._kernel, self._route == "factor"
-        fused = self._fused(time_points)
-        if not fused and kernel._needs_grad():
-            # a hyper-parameter of the chain under the tape: the projections are part of the graph
-            order, x = _sorted_series(time_points)
-            proj, cov, indices = conditionals._conditional_statistics(x, self.inducing_inputs, kernel)
-            h = (kernel.latent_emission_model(x) if factor else kernel.generate_emission_model(x)).emission_matrix
-            w, c = h @ proj, (h @ cov @ h.transpose(-1, -2) if factor else torch.sum((h @ cov) * h, dim=-1))
-        else:
-            order, w, c, indices, offsets, tiles = self._projections(time_points)
-            x = time_points if order is None else torch.gather(time_points, -1, order)
-        y = observations
-        if order is not None:
-            y = torch.gather(y, -2, order[..., None].expand(y.shape))
-        if not factor:
-            return sparse_multi_output_expected_log_likelihood_torch(self._likelihood, w, c, y, indices, pair_mean, pair_cov)
-        mix = kernel.mixing_weights(x)             # on every call, under the tape of the loading matrix and the weight function
-        if fused:
-            return sparse_factor_expected_log_likelihood(self._likelihood, w, c, mix, y, offsets, pair_mean, pair_cov, tiles=tiles)
-        return sparse_factor_expected_log_likelihood_torch(self._likelihood, w, c, mix, y, indices, pair_mean, pair_cov)
-
-    def _mvn_expected_log_likelihood(self, time_points: torch.Tensor, observations: torch.Tensor, pair_mean, pair_cov) -> torch.Tensor:
-        """The data term under a ``MultivariateGaussian`` likelihood, observations ``batch + [N, P]``.  Neither route's projections
-        depend on the likelihood's Cholesky factor: a step on it keeps the cache."""
-        kernel = self._kernel
-        fused = self._fused(time_points)
-        if not fused and (kernel._needs_grad() or self._emission_needs_grad()):
-            # a hyper-parameter of the chain or of the emission under the tape: the projections are part of the graph
-            order, x = _sorted_series(time_points)
-            proj, cov, indices = conditionals._conditional_statistics(x, self.inducing_inputs, kernel)
-            h = kernel.generate_emission_model(x).emission_matrix
-            w, c = h @ proj, h @ cov @ h.transpose(-1, -2)
-        else:
-            order, w, c, indices, offsets, tiles = self._projections(time_points)
-        y = observations
-        if order is not None:
-            y = torch.gather(y, -2, order[..., None].expand(y.shape))
-        if fused:
-            return sparse_mvn_expected_log_likelihood(self._likelihood, w, c, y, offsets, pair_mean, pair_cov, tiles=tiles)
-        return sparse_mvn_expected_log_likelihood_torch(self._likelihood, w, c, y, indices, pair_mean, pair_cov)
+    def _site_projections(self, time_points: torch.Tensor, fused: bool):
+        """``(order | None, w, c, indices, offsets, tiles)``: the cached projections - or, off the fused path with a hyper-parameter of
+        the chain or of the emission under the tape, the same call under the tape: ``w`` and ``c`` are part of the graph."""
+        if fused or not (self._kernel._needs_grad() or (self._route.loading_cached and self._emission_needs_grad())):
+            return self._projections(time_points)[:6]
+        return self._sorted_projections(time_points) + (None,)
 
     def _pair_marginals(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """``(m_pair [.., M+1, 2d], S_pair [.., M+1, 2d, 2d])`` of ``dist_q`` - under the tape when its leaves require a gradient -
@@ -754,43 +739,18 @@ class SparseVariationalGaussianProcess(_SparseGaussianProcess):
         return conditionals.pairwise_marginals(self._dist_q, *self._stationary_prior())
 
     def _expected_log_likelihood(self, time_points: torch.Tensor, observations: torch.Tensor) -> torch.Tensor:
-        """``sum_i E_q log p(y_i | f_i)`` per pair, ``batch + [M + 1]``."""
+        """``sum_i E_q log p(y_i | f_i)`` per pair, ``batch + [M + 1]`` (one series per output on a stack kernel: ``lead + [K, M + 1]``):
+        the route's fused op on the cached projections, or its torch composition."""
         pair_mean, pair_cov = self._pair_marginals()
-        multi = self._multi
-        route = self._data_route(observations)
-        if route != self._route:                   # the cached projections are the other route's
+        route = self._data_route(observations.shape[-1])
+        if route is not self._route:               # the cached projections are the other route's
             self._route, self._projection_cache = route, None
-        if route in ("stack", "stack_outputs"):
-            return self._stack_expected_log_likelihood(time_points, observations, pair_mean, pair_cov)
-        if route in ("factor", "outputs"):
-            return self._multi_output_expected_log_likelihood(time_points, observations, pair_mean, pair_cov)
-        if route == "mvn":
-            return self._mvn_expected_log_likelihood(time_points, observations, pair_mean, pair_cov)
-        if self._fused(time_points):
-            order, w, c, _, offsets, tiles = self._projections(time_points)
-            y = observations[..., 0]
-            if order is not None:
-                y = torch.gather(y, -1, order)
-            fused = sparse_multi_expected_log_likelihood if multi else sparse_expected_log_likelihood
-            if self._likelihood._theta_leaf is not None:       # the parameter from device memory, its adjoint from the same launch
-                fused = sparse_theta_expected_log_likelihood
-            return fused(self._likelihood, w, c, y, offsets, pair_mean, pair_cov, tiles=tiles)
-        if self._kernel._needs_grad() or self._emission_needs_grad():
-            # a hyper-parameter under the tape: w and c are part of the graph
-            order, time_points = _sorted_series(time_points)
-            proj, cov, indices = conditionals._conditional_statistics(time_points, self.inducing_inputs, self._kernel)
-            h = self._kernel.generate_emission_model(time_points).emission_matrix
-            if multi:
-                w, c = h @ proj, torch.sum((h @ cov) * h, dim=-1)
-            else:
-                w, c = (h @ proj)[..., 0, :], (h @ cov @ h.transpose(-1, -2))[..., 0, 0]
-        else:
-            order, w, c, indices, _, _ = self._projections(time_points)
-        y = observations[..., 0]
-        if order is not None:
-            y = torch.gather(y, -1, order)
-        composed = sparse_multi_expected_log_likelihood_torch if multi else sparse_expected_log_likelihood_torch
-        return composed(self._likelihood, w, c, y, indices, pair_mean, pair_cov)
+        fused = self._fused(time_points)
+        order, w, c, indices, offsets, tiles = self._site_projections(time_points, fused)
+        points = route.points(self._kernel, time_points, observations, order)
+        if fused:
+            return globals()[route.fused](self._likelihood, w, c, *points, offsets, pair_mean, pair_cov, tiles=tiles)
+        return globals()[route.composed](self._likelihood, w, c, *points, indices, pair_mean, pair_cov)
 
     # ---- inference ---------------------------------------------------------------------------------------------------------------
     def elbo(self, input_data: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
@@ -870,8 +830,7 @@ class ImportanceWeightedVI(SparseVariationalGaussianProcess):
             return cached[1]
         order, offsets = projections[0], projections[4]
         with torch.no_grad():
-            x = time_points if order is None else torch.gather(time_points, -1, order)
-            merged = iw_merged_time_points(x, self.inducing_inputs, offsets)
+            merged = iw_merged_time_points(_in_order(time_points, order), self.inducing_inputs, offsets)
         self._merged_cache = (projections, merged)
         return merged
 
@@ -883,18 +842,12 @@ class ImportanceWeightedVI(SparseVariationalGaussianProcess):
         time_points, observations = self._check_data(input_data, what)
         k = self._posterior.num_importance_samples
         projections = self._projections(time_points)
-        order, w, _, indices, offsets, tiles = projections
+        order, _, _, _, offsets, tiles = projections
         merged = self._merged(projections, time_points)
-        y = observations[..., 0]
-        if order is not None:
-            y = torch.gather(y, -1, order)
+        y = _in_order(observations[..., 0], order)
         h = self._kernel.generate_emission_model(merged[..., :1]).emission_matrix.reshape(-1, self._kernel.state_dim)[0]
         fused = self._fused(time_points)
-        if not fused and self._kernel._needs_grad():
-            # a hyper-parameter under the tape: w is part of the graph
-            x = time_points if order is None else torch.gather(time_points, -1, order)
-            proj, _, indices = conditionals._conditional_statistics(x, self.inducing_inputs, self._kernel)
-            w = (self._kernel.generate_emission_model(x).emission_matrix @ proj)[..., 0, :]
+        _, w, _, indices, _, _ = self._site_projections(time_points, fused)      # (a hyper-parameter under the tape: w is part of the graph)
         prior = self._kernel.state_space_model(merged).sample((k,))
         u_post = self._dist_q.sample((k,))
         if fused:
