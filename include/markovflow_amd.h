@@ -240,6 +240,31 @@ int mf_ssm_marginal_means_f32(int64_t Bl, int64_t Br, int64_t T, int d, const fl
                               float* out, void* ws, size_t ws_bytes, void* stream);
 
 /*
+ * StateSpaceModel.sample  (state_space_model.py:298-324) in ONE call on the chain's own leaves (csrc/mf_sample.hip):
+ *   x_0 = mu0 + cholP0 eps_0,   x_k = A_{k-1} x_{k-1} + b_{k-1} + cholQ_{k-1} eps_k,   k = 1 ... T - 1,
+ * with the FULL stored d x d blocks of cholP0 / cholQ multiplied (a stored factor that is not triangular gives what the batched
+ * product of the torch route gives).  mu0 [B,d], cholP0 [B,d,d], A [B,T-1,d,d], b [B,T-1,d], cholQ [B,T-1,d,d]; eps and out
+ * [S,B,T,d]: trajectory r = s B + series uses the chain of series r % B (the convention of mf_ssm_marginal_means).  eps and out
+ * need the alignment of their scalar only.  The samples of a series are the lanes of a group: the chain is read once per
+ * (series, chunk), eps and out move through LDS tiles in 16-byte pieces of one trajectory.
+ * chunks: 0 automatic, 1 one sweep per trajectory (no workspace), >= 2 that many partitions in time per trajectory, clamped to T
+ * (chunks of ceil(T / chunks) steps; the last may be shorter): a summary pass (the chunk's transition product and every sample's
+ * zero-start end state), a scan over the chunk ends, and an emitting pass restarted at every chunk - eps and the chain are read
+ * twice, out is written once.  The result is deterministic for a given partition.  ws: mf_ssm_sample_workspace_bytes for the same
+ * shape and `chunks` (0 for the sweep); a NULL or short workspace selects the sweep, never an error.
+ * T = 1 is legal (A, b, cholQ may be NULL); B = 0 or S = 0 returns 0 without a launch.  State dimension 1..9.
+ * Returns 0, -(position of the offending argument: 1 B, 2 S, 3 T < 1, 4 d < 1, 5 ... 11 a NULL or misaligned array, 14 chunks < 0),
+ * -100 for d > 9, or -1000 (launch failed).
+ */
+size_t mf_ssm_sample_workspace_bytes(int64_t B, int64_t S, int64_t T, int d, int elem_size, int64_t chunks);
+int mf_ssm_sample_f64(int64_t B, int64_t S, int64_t T, int d, const double* mu0, const double* cholP0, const double* A,
+                      const double* b, const double* cholQ, const double* eps, double* out, void* ws, size_t ws_bytes,
+                      int64_t chunks, void* stream);
+int mf_ssm_sample_f32(int64_t B, int64_t S, int64_t T, int d, const float* mu0, const float* cholP0, const float* A,
+                      const float* b, const float* cholQ, const float* eps, float* out, void* ws, size_t ws_bytes,
+                      int64_t chunks, void* stream);
+
+/*
  * Block-wise d x d products out[s,k] = X[s,k] Y[s,k] over [B, n] blocks; x_stride / y_stride = blocks per series in
  * the allocations of X / Y (>= n: a leading slice of a longer chain needs no copy).  Replaces the batched tf.matmul of
  * StateSpaceModel.subsequent_covariances (state_space_model.py:326-341), Cov(x_{k+1}, x_k) = A_k P_k.

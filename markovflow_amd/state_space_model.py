@@ -246,6 +246,24 @@ class StateSpaceModel(GaussMarkovDistribution):
             sample_shape = (sample_shape,)
         full = tuple(sample_shape) + tuple(self.batch_shape) + self.event_shape
         eps = torch.randn(full + (1,), dtype=self._A_s.dtype, device=self._A_s.device)
+        d = self.state_dim
+        if eps.numel() == 0 or not eps.is_cuda or self._needs_grad() or d > _lib.load().mf_max_state_dim():
+            return self._sample_composed(eps)
+        # outside the tape: ONE kernel on the chain's own leaves (csrc/mf_sample.hip) - no concatenated copies of the chain, no
+        # [.., T, d] intermediates; few long trajectories are partitioned in time (chunks = 0: the library's rule)
+        mu0, cp0, a_f, b_f, cq = self._flat_params()
+        bsz, n = a_f.shape[0], self.num_transitions + 1
+        num_samples = eps.numel() // (bsz * n * d)
+        out = torch.empty(full, dtype=eps.dtype, device=eps.device)
+        ws_bytes = int(_lib.load().mf_ssm_sample_workspace_bytes(bsz, num_samples, n, d, eps.element_size(), 0))
+        ws = _lib.workspace(ws_bytes, eps.device)
+        _lib.call("mf_ssm_sample", eps.dtype, bsz, num_samples, n, d, _lib.ptr(mu0), _lib.ptr(cp0), _lib.ptr(a_f), _lib.ptr(b_f),
+                  _lib.ptr(cq), _lib.ptr(eps), _lib.ptr(out), _lib.ptr(ws), ws_bytes, 0, _lib.stream_ptr(eps.device))
+        return out
+
+    def _sample_composed(self, eps: torch.Tensor) -> torch.Tensor:
+        """The draw from ``eps`` (``sample_shape + batch_shape + event_shape + [1]``) as a composition of torch operators around the
+        mean recursion: chains under the tape, state dimensions beyond the register kernels and empty shapes."""
         z = torch.matmul(self.concatenated_cholesky_process_covariance, eps)[..., 0]
         cond = self.concatenated_state_offsets + z
         if cond.numel() == 0:
