@@ -265,6 +265,48 @@ int mf_ssm_sample_f32(int64_t B, int64_t S, int64_t T, int d, const float* mu0, 
                       int64_t chunks, void* stream);
 
 /*
+ * StateSpaceModel.log_pdf  (state_space_model.py:485-526) and its adjoints in ONE call each on the chain's own leaves
+ * (csrc/mf_logpdf.hip).  states [S,B,T,d], trajectory r = s B + series on the chain of series r % B (mf_ssm_sample's layout); with
+ *   r_0 = x_0 - mu0,   r_k = x_k - A_{k-1} x_{k-1} - b_{k-1},   z_k = L_k^-1 r_k,   u_k = L_k^-T z_k,
+ * L_k the LOWER TRIANGLE of cholP0 (k = 0) / cholQ_{k-1} - nothing above the diagonal is read, unlike mf_ssm_sample -
+ *   out[s,b] = sum_k ( -1/2 |z_k|^2 - sum_i log|L_k,ii| ) - 1/2 T d log 2 pi,
+ * and for a cotangent g [S,B]:  g_states_k = -g (u_k - A_k^T u_{k+1}),  g_mu0 / g_b_{k-1} = sum_s g u_k,  g_A_{k-1} = sum_s g u_k x_{k-1}^T,
+ * g_cholP0 / g_cholQ_{k-1} = tril(sum_s g u_k z_k^T) - diag((sum_s g) / L_k,ii), zeros written above the diagonal.
+ * A group of 16 (S <= 16) or 64 lanes holds samples of one (series, chunk of steps); states and g_states need the alignment of
+ * their scalar only and move through LDS tiles.  chunks: 0 automatic, >= 1 that many partitions in time, clamped to T (chunks of
+ * ceil(T / chunks) steps; the last may be shorter).  The value adds a trajectory's steps in ascending order inside a chunk and the
+ * chunks in ascending order: it depends on `chunks` and on nothing else.  The parameter adjoints add the samples in ascending order
+ * inside a block of 16 / 64 and the blocks in ascending order: no atomics, the same bits on every launch, for every `chunks`, for
+ * a series alone or in a batch.  ws: the matching *_workspace_bytes for the same shape and `chunks` (value: a partial per
+ * (trajectory, chunk) when there is more than one chunk; adjoints: a slab of the five parameter adjoints per block of samples when
+ * there is more than one block); a NULL, misaligned or short workspace that is needed is an error.
+ * In the grad call g_states is wanted (non-NULL) or not on its own; the five parameter adjoints are wanted all or none (T = 1: g_A, g_b
+ * and g_cholQ have no elements and may be NULL); each output has the same bits whichever of the others is asked for.
+ * A zero or non-finite diagonal entry of cholP0 / cholQ is NOT checked on the host: it makes the outputs of the (sample, series)
+ * pairs that read it (and the parameter adjoints of that series' step) non-finite and touches nothing else.
+ * T = 1 is legal (A, b, cholQ may be NULL); B = 0, S = 0 or no output asked for returns 0 without a launch.  State dimension 1..9.
+ * Returns 0, -(position of the offending argument: 1 B, 2 S, 3 T < 1, 4 d < 1, 5 ... 10 a NULL or misaligned array; value: 12 / 13 the
+ * workspace / its size, 14 chunks < 0; grad: 11 g, 12 g_states misaligned, 13 ... 17 a parameter adjoint missing among wanted ones,
+ * 18 / 19 the workspace / its size, 20 chunks < 0), -100 for d > 9, or -1000 (launch failed).
+ */
+size_t mf_ssm_log_pdf_workspace_bytes(int64_t B, int64_t S, int64_t T, int d, int elem_size, int64_t chunks);
+int mf_ssm_log_pdf_f64(int64_t B, int64_t S, int64_t T, int d, const double* mu0, const double* cholP0, const double* A,
+                       const double* b, const double* cholQ, const double* states, double* out, void* ws, size_t ws_bytes,
+                       int64_t chunks, void* stream);
+int mf_ssm_log_pdf_f32(int64_t B, int64_t S, int64_t T, int d, const float* mu0, const float* cholP0, const float* A,
+                       const float* b, const float* cholQ, const float* states, float* out, void* ws, size_t ws_bytes,
+                       int64_t chunks, void* stream);
+size_t mf_ssm_log_pdf_grad_workspace_bytes(int64_t B, int64_t S, int64_t T, int d, int elem_size, int64_t chunks);
+int mf_ssm_log_pdf_grad_f64(int64_t B, int64_t S, int64_t T, int d, const double* mu0, const double* cholP0, const double* A,
+                            const double* b, const double* cholQ, const double* states, const double* g, double* g_states,
+                            double* g_mu0, double* g_cholP0, double* g_A, double* g_b, double* g_cholQ, void* ws, size_t ws_bytes,
+                            int64_t chunks, void* stream);
+int mf_ssm_log_pdf_grad_f32(int64_t B, int64_t S, int64_t T, int d, const float* mu0, const float* cholP0, const float* A,
+                            const float* b, const float* cholQ, const float* states, const float* g, float* g_states,
+                            float* g_mu0, float* g_cholP0, float* g_A, float* g_b, float* g_cholQ, void* ws, size_t ws_bytes,
+                            int64_t chunks, void* stream);
+
+/*
  * Block-wise d x d products out[s,k] = X[s,k] Y[s,k] over [B, n] blocks; x_stride / y_stride = blocks per series in
  * the allocations of X / Y (>= n: a leading slice of a longer chain needs no copy).  Replaces the batched tf.matmul of
  * StateSpaceModel.subsequent_covariances (state_space_model.py:326-341), Cov(x_{k+1}, x_k) = A_k P_k.

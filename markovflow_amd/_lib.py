@@ -32,6 +32,8 @@ _SIGS = {
                                 "Tp", "Tp", "Tp", _vp]),
     "mf_ssm_marginal_means": (_int, [_i64, _i64, _i64, _int, "Tp", "Tp", "Tp", _vp, _sz, _vp]),
     "mf_ssm_sample": (_int, [_i64, _i64, _i64, _int] + ["Tp"] * 7 + [_vp, _sz, _i64, _vp]),
+    "mf_ssm_log_pdf": (_int, [_i64, _i64, _i64, _int] + ["Tp"] * 7 + [_vp, _sz, _i64, _vp]),
+    "mf_ssm_log_pdf_grad": (_int, [_i64, _i64, _i64, _int] + ["Tp"] * 13 + [_vp, _sz, _i64, _vp]),
     "mf_ssm_marginals": (_int, [_i64, _i64, _int] + ["Tp"] * 8 + [_vp, _sz, _vp]),
     "mf_ssm_kl_from_moments": (_int, [_i64, _i64, _int, "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", "Tp", _vp, _sz, _vp]),
     "mf_block_matmul": (_int, [_i64, _i64, _int, "Tp", _i64, "Tp", _i64, "Tp", _vp]),
@@ -159,6 +161,8 @@ _PLAIN = {
     "mf_lik_st_cvi_site_update_workspace_bytes": (_sz, [_i64, _int, _int, _int]),
     "mf_nlsde_drift_difference_workspace_bytes": (_sz, [_i64, _i64]),
     "mf_ssm_sample_workspace_bytes": (_sz, [_i64, _i64, _i64, _int, _int, _i64]),
+    "mf_ssm_log_pdf_workspace_bytes": (_sz, [_i64, _i64, _i64, _int, _int, _i64]),
+    "mf_ssm_log_pdf_grad_workspace_bytes": (_sz, [_i64, _i64, _i64, _int, _int, _i64]),
 }
 
 _lib = None

@@ -387,7 +387,20 @@ class StateSpaceModel(GaussMarkovDistribution):
         return torch.cat([init[..., None], rest], dim=-1)
 
     def log_pdf(self, states) -> torch.Tensor:
-        """``log p(x)`` (state_space_model.py:515-526)."""
+        """``log p(x)`` (state_space_model.py:515-526).  HIP states of the chain's dtype whose trailing dimensions are exactly
+        ``batch_shape + event_shape`` (leading sample dimensions of any rank, or none) take ONE kernel call on the chain's own leaves,
+        and one more in ``backward()`` for the states and the five leaves (``_LogPdf``, csrc/mf_logpdf.hip); CPU tensors, state
+        dimensions beyond the register kernels, shapes that only broadcast and empty shapes take the composition."""
+        tail = tuple(self.batch_shape) + self.event_shape
+        if (isinstance(states, torch.Tensor) and states.is_cuda and states.dtype == self._A_s.dtype and states.device == self._A_s.device
+                and states.dim() >= len(tail) and tuple(states.shape[states.dim() - len(tail):]) == tail and states.numel() > 0
+                and self.state_dim <= _lib.load().mf_max_state_dim()):
+            lead = tuple(states.shape[:states.dim() - len(tail)])
+            return _LogPdf.apply(states, *self._flat_params()).reshape(lead + tuple(self.batch_shape))
+        return self._log_pdf_composed(states)
+
+    def _log_pdf_composed(self, states) -> torch.Tensor:
+        """``log p(x)`` as the sum of ``_log_pdf_factors``: a composition of torch operators, differentiated by autograd."""
         return torch.sum(self._log_pdf_factors(states), dim=-1)
 
     def kl_divergence(self, dist: GaussMarkovDistribution) -> torch.Tensor:
@@ -616,6 +629,47 @@ class _KLDivergence(torch.autograd.Function):
                       _lib.stream_ptr(dev))
             _lib.raise_on_info(info, "kl_divergence (backward)", dev)
         return (*g1, *g2)
+
+
+class _LogPdf(torch.autograd.Function):
+    """
+    ``log p(x)`` per (sample, series) as a differentiable function of the states ``sample_shape + [B, T, d]`` (flattened to
+    ``[S, B, T, d]``) and the flat chain parameters.  Forward: one ``mf_ssm_log_pdf_*`` call.  Backward: one
+    ``mf_ssm_log_pdf_grad_*`` call that asks for the states' adjoint and / or the five parameter adjoints, whichever
+    ``needs_input_grad`` wants (csrc/mf_logpdf.hip).  The reference differentiates state_space_model.py:485-526 through TensorFlow.
+    """
+
+    @staticmethod
+    def forward(ctx, states, mu0, cp0, a_s, b_s, cq):
+        bsz, nt, d = a_s.shape[0], a_s.shape[1], a_s.shape[-1]
+        x = states.detach().reshape(-1, bsz, nt + 1, d).contiguous()
+        num = x.shape[0]
+        out = torch.empty((num, bsz), dtype=x.dtype, device=x.device)
+        ws_bytes = int(_lib.load().mf_ssm_log_pdf_workspace_bytes(bsz, num, nt + 1, d, x.element_size(), 0))
+        ws = _lib.workspace(ws_bytes, x.device)
+        _lib.call("mf_ssm_log_pdf", x.dtype, bsz, num, nt + 1, d, _lib.ptr(mu0.detach()), _lib.ptr(cp0.detach()), _lib.ptr(a_s.detach()),
+                  _lib.ptr(b_s.detach()), _lib.ptr(cq.detach()), _lib.ptr(x), _lib.ptr(out), _lib.ptr(ws), ws_bytes, 0,
+                  _lib.stream_ptr(x.device))
+        ctx.save_for_backward(x, mu0, cp0, a_s, b_s, cq)
+        ctx.states_shape = states.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from .models._common import _differentiable_once
+        _differentiable_once("StateSpaceModel.log_pdf", "states and chain saved, detached,")
+        x, mu0, cp0, a_s, b_s, cq = ctx.saved_tensors
+        num, bsz, n, d = x.shape
+        want_x, want_p = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:])
+        g = grad_out.reshape(num, bsz).contiguous()
+        g_x = torch.empty_like(x) if want_x else None
+        g_p = [torch.empty_like(t) for t in (mu0, cp0, a_s, b_s, cq)] if want_p else [None] * 5
+        ws_bytes = int(_lib.load().mf_ssm_log_pdf_grad_workspace_bytes(bsz, num, n, d, x.element_size(), 0)) if want_p else 0
+        ws = _lib.workspace(ws_bytes, x.device)
+        _lib.call("mf_ssm_log_pdf_grad", x.dtype, bsz, num, n, d, _lib.ptr(mu0), _lib.ptr(cp0), _lib.ptr(a_s), _lib.ptr(b_s), _lib.ptr(cq),
+                  _lib.ptr(x), _lib.ptr(g), _lib.ptr(g_x), *[_lib.ptr(t) for t in g_p], _lib.ptr(ws), ws_bytes, 0,
+                  _lib.stream_ptr(x.device))
+        return (g_x.reshape(ctx.states_shape) if want_x else None, *[t if need else None for t, need in zip(g_p, ctx.needs_input_grad[1:])])
 
 
 class _Marginals(torch.autograd.Function):
